@@ -17,7 +17,11 @@ when the timed region starts -- and a step ends with the keypoints + descriptors
 returns) and, for N > 1, the gathered lists in rank 0's host memory.  `--contexts` contexts (streams) per GPU are
 pipelined.
 
-Added to the contract's JSON line (rank 0; N = 1 unless noted):
+A plain run sets up, warms up, times the K steps and prints the contract's line; `--dump-outputs DIR` also writes what the
+last timed step delivered (dump_outputs below).  Everything else this file measures or checks -- the entries below --
+runs only with `--full` (the `--no-*` options then leave single legs out).
+
+Added to the contract's JSON line by `--full` (rank 0; N = 1 unless noted):
   value_host_to_host  the same steps starting from pinned HOST pixels (hess_submit_host: one asynchronous transfer per
                       batch, pipelined over the contexts) -- SURVEY 8(d)'s definition of the metric, PCIe included
   value_device_resident   = value, under its own name
@@ -70,7 +74,12 @@ def main():
                     "Round 5, same call, the driver's --steps 20 --warmup 5 / 200 steady steps, Gpix/s: 3: 18.4 - 20.0 / 21.8, 4: 18.9 - 19.2 / 20.6, "
                     "5: 19.7 - 19.8 / 21.9, 6: 20.5 / 21.3 - 22.4, 7: 20.2 - 20.4 / 22.5, 8: 19.7 / 20.4 - 21.0, 9: 20.2 - 20.4 / 22.0, 11: 19.9 - 20.5 / 22.3 "
                     "(the streams share four hardware queues).  N > 1: five contexts per rank keep a node of eight ranks at 40 copier "
-                    "threads / 40 streams and the node-shared result buffers near 1.2 GB for 3 % of one GPU's steady rate")
+                    "threads / 40 streams and the node-shared result buffers near 1.2 GB for 3 %% of one GPU's steady rate")
+    ap.add_argument("--full", action="store_true", help="also run every leg after the timed region (steady state, roofline, host "
+                    "and API legs, configs[4], real images, matcher, parity with the CPU oracle, CPU baseline); the --no-* options "
+                    "below leave single legs out of a full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the keypoints and descriptors of the last timed step as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel hipEvents")
     ap.add_argument("--no-host-leg", action="store_true", help="skip the host-to-host and single-image legs")
@@ -94,6 +103,9 @@ def main():
                     "takes the N > 1 code path: process group, helper-thread gather; HESS_BENCH_FORCE_DIST=1)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds after which a self-launched job is ended (exit code 124)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline figure alone
+        args.no_steady = args.no_profile = args.no_host_leg = args.no_api_leg = True
+        args.no_configs4 = args.no_real_images = args.no_matcher = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         # No launcher around us: be the launcher.  This process makes no GPU call (it never imports torch); the ranks are
@@ -355,19 +367,23 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         dt = float(t.item())
     last = ctxs[(args.steps - 1) % nctx]          # context that ran the last timed step: its results are still there
-    timed_k0, timed_d0 = last.fetch(0)            # image 0 of the timed run (parity_checked below)
-    timed_keys = [last.fetch(b)[0] for b in range(B)]
-    # N > 1: image 0 of every other rank out of the gathered lists of the last timed step (rank 0 checks them below)
-    gathered_first = {}
-    if use_dist and rank == 0 and gathered:
+    timed = [last.fetch(b) for b in range(B)]
+    timed_k0, timed_d0 = timed[0]                 # image 0 of the timed run (parity_checked below)
+    timed_keys = [k for k, _ in timed]
+    # N > 1: the other ranks' lists of the last timed step, as rank 0 holds them (it checks image 0 of each below)
+    others = {}
+    if use_dist and rank == 0 and gathered and (args.dump_outputs or not args.no_cpu_baseline):
         for r in range(1, world):
-            n0 = gathered["counts"][r][0]
             if "host" in gathered:   # the node-shared host buffers are what rank 0 would hand on: check those
                 hk, hd = gathered["host"][r]
-                gathered_first[r] = (hk[:n0].copy(), hd[:n0].copy())
+                others[r] = (hk.copy(), hd.copy())
             else:
-                gathered_first[r] = (gathered["keys"][r][:n0].cpu().numpy().copy(),
-                                     gathered["desc"][r][:n0].cpu().numpy().copy())
+                others[r] = (gathered["keys"][r].cpu().numpy().copy(), gathered["desc"][r].cpu().numpy().copy())
+    gathered_first = {r: (k[:gathered["counts"][r][0]], d[:gathered["counts"][r][0]]) for r, (k, d) in others.items()}
+    if rank == 0 and args.dump_outputs:
+        parts = [([len(k) for k, _ in timed], np.concatenate(timed_keys), np.concatenate([d for _, d in timed]))]
+        parts += [(gathered["counts"][r], np.frombuffer(k.tobytes(), dtype=_abi.KEYPOINT_DTYPE), d) for r, (k, d) in sorted(others.items())]
+        dump_outputs(args.dump_outputs, parts)
 
     # The contract's region holds the pipeline's fill and drain (the fences empty it on both sides): at the driver's 20
     # steps that is about 2 ms of 21.  The steady-state rate of the same pipeline is reported beside it, from a leg of
@@ -550,6 +566,35 @@ def main():
         worker.close()
         tdist.barrier()
         tdist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, parts, limit=DUMP_LIMIT_BYTES):
+    """What the last timed step delivered to its caller, as out_dir/<name>.npy:
+      counts.npy       float64 [images]: features per image, in the order of the global batch
+      keypoints.npy    float32 [features, 7]: x, y, s, o, response, level, type (the images' lists back to back)
+      descriptors.npy  float32 [features, dim]
+    parts: one (counts per image, keypoints structured [n], descriptors [n, dim]) per rank, in rank order.  When the three
+    arrays would exceed `limit` bytes, keypoints and descriptors hold the same fixed seeded sample of rows instead, in
+    order, and sample_rows.npy (float64) says which."""
+    import numpy as np
+
+    counts = np.array([c for p in parts for c in p[0]], dtype=np.float64)
+    keys = np.concatenate([p[1] for p in parts])
+    kp = np.stack([keys[f].astype(np.float32) for f in keys.dtype.names], axis=1)
+    desc = np.concatenate([p[2] for p in parts]).astype(np.float32, copy=False)
+    out = {"counts": counts, "keypoints": kp, "descriptors": desc}
+    row_bytes = kp.shape[1] * 4 + desc.shape[1] * 4
+    headers = 4 * 256   # (the .npy header of each file: 128 bytes for these shapes)
+    if headers + counts.nbytes + len(kp) * row_bytes > limit:
+        keep = (limit - headers - counts.nbytes) // (row_bytes + 8)   # (+ 8: the row's entry in sample_rows)
+        rows = np.sort(np.random.default_rng(0).choice(len(kp), size=keep, replace=False))
+        out.update(keypoints=kp[rows], descriptors=desc[rows], sample_rows=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_legs(ctxs, nctx, imgs, B, args, run_steps, fence, torch):

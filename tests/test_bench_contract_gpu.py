@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline)."""
+"""bench.py prints ONE JSON line with the contract's keys (driver contract; with --full also roofline + cpu_baseline)."""
 import json
 import os
 import subprocess
@@ -25,7 +25,7 @@ def _fracs(node, path=""):
 
 def test_bench_json_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--batch", "3"], capture_output=True, text=True, timeout=900)
+                        "--batch", "3", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -99,7 +99,7 @@ def test_driver_command_is_close_to_steady_state():
     runs (tools/r06/driver_outliers.sh) and is not what this test is about."""
     over = []
     for attempt in range(2):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
                             "--no-configs4", "--no-api-leg", "--no-host-leg", "--no-cpu-baseline", "--no-real-images", "--no-matcher"],
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -112,7 +112,7 @@ def test_driver_command_is_close_to_steady_state():
 
 
 @pytest.mark.parametrize("dest", ["shm", "file", "host"])
-def test_two_rank_control_flow_on_one_gpu(dest, tmp_path):
+def test_two_rank_control_flow_on_one_gpu(dest, tmp_path, tmp_path_factory):
     """The N > 1 path of bench.py rehearsed with two ranks that share the one GPU (gloo instead of RCCL, which cannot
     form a group of ranks on the same device): count exchange, gather, and image 0 of BOTH ranks compared with the
     oracle out of what rank 0 holds at the end of a step -- for each of the three places the other rank's lists can
@@ -120,6 +120,8 @@ def test_two_rank_control_flow_on_one_gpu(dest, tmp_path):
       shm   rank 0 reads them in place from the node-shared result buffers in /dev/shm (sized by need);
       file  the same with the buffers in files (what the library does when /dev/shm has no room: forced here);
       host  no shared buffers at all (a name the library refuses): rank 0 copies the gathered lists out of its HBM."""
+    import numpy as np
+
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HESS_BENCH_BACKEND="gloo", HESS_BENCH_SAME_GPU="1")
@@ -128,7 +130,9 @@ def test_two_rank_control_flow_on_one_gpu(dest, tmp_path):
         env.update(HESS_SHARE_FORCE_FILE="1", HESS_SHARE_DIR=str(tmp_path), HESS_LIB=hessgpu_amd.DEV_LIB_PATH)
     if dest == "host":
         env["HESS_BENCH_SHM_PREFIX"] = "no/such"
-    bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--contexts", "2", "--batch", "3", "--no-profile"]
+    bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--contexts", "2", "--batch", "3", "--full", "--no-profile"]
+    dump = tmp_path_factory.mktemp("dump")   # (not tmp_path: the file variant checks that its share directory ends empty)
+    bench += ["--dump-outputs", str(dump)]
     if dest == "shm":   # the BARE command, as the driver runs N = 1: bench.py starts its own two ranks (hessgpu_amd/launch.py)
         cmd = [sys.executable] + bench
         env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
@@ -155,6 +159,54 @@ def test_two_rank_control_flow_on_one_gpu(dest, tmp_path):
         assert "gather destination of every rank: host" in r.stderr
     assert not [f for f in os.listdir("/dev/shm") if f.startswith("hessbench_")]
     assert not list(tmp_path.iterdir())          # the files are gone with their contexts
+    # --dump-outputs on rank 0: both ranks' lists of the last timed step, images in the order of the global batch
+    out = {n: np.load(dump / f"{n}.npy") for n in ("counts", "keypoints", "descriptors")}
+    assert out["counts"].shape == (6,) and out["counts"].min() > 1000
+    assert out["keypoints"].shape == (int(out["counts"].sum()), 7) and out["descriptors"].shape == (len(out["keypoints"]), 128)
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """The plain command (no --full) prints the contract's line without the legs that follow the timed region, and
+    --dump-outputs writes what the last timed step delivered: the same arrays from every run of the same command, and
+    image 0's features bit for bit those of the CPU oracle on the same pixels."""
+    import numpy as np
+
+    import fixtures
+    from hessgpu_amd import _abi
+    from oracle_lib import OracleSession
+
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "2", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and abs(d["value"] - 2 * 3 * 1920 * 1080 / (d["ms_per_step"] * 3 * 1e-3) / 1e6) / d["value"] < 0.01
+        for k in ("value_steady_state", "roofline", "kernel_ms_per_step", "value_host_to_host", "value_siftgpu_api_1thread",
+                  "configs4", "real_images", "matcher", "parity_checked", "cpu_baseline"):
+            assert k not in d, k
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["counts.npy", "descriptors.npy", "keypoints.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        outs.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+    a, b = outs
+    for k in a:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    counts = a["counts"]
+    assert counts.dtype == np.float64 and counts.shape == (2,) and counts.min() > 1000
+    assert a["keypoints"].dtype == np.float32 and a["keypoints"].shape == (int(counts.sum()), 7)
+    n0 = int(counts[0])
+    o = OracleSession(threads=4, keep_levels=False, truncate_method=_abi.TRUNC_TOPK, feature_count_threshold=4096)
+    o.run(fixtures.synthetic_blobs(1920, 1080, 0)[None])
+    ok, od = o.fetch(0)
+    o.close()
+    assert len(ok) == n0
+    for i, f in enumerate(_abi.KEYPOINT_DTYPE.names):
+        assert np.array_equal(a["keypoints"][:n0, i], ok[f].astype(np.float32)), f
+    assert np.array_equal(a["descriptors"][:n0].view(np.uint32), od.view(np.uint32))
 
 
 def _bare_env(**extra):

@@ -3,6 +3,7 @@
 # --variant NAME flags...`) on the GPU box:  tools/ab_bench.sh TAG "pytest args or -" variant...   ("cur" = in-tree lib)
 # Runs the given GPU tests first with the in-tree library; benches only if pytest did not crash (rc 0 or 1).
 TAG=$1; TESTS=$2; shift 2
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # (kernel_ms_per_step is an entry of a full run)
 mkdir -p gpurun_out
 if [ "$TESTS" != "-" ]; then
   timeout -k 10 600 python -m pytest $TESTS -m gpu -x -q > gpurun_out/${TAG}_tests.log 2>&1

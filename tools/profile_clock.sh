@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_clk -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-host-leg --contexts 1 "$@" > /dev/null 2> $OUT/pmc_clk.err
+rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_clk -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-host-leg --contexts 1 "$@" > /dev/null 2> $OUT/pmc_clk.err
 python3 - $OUT <<'PY'
 import csv, glob, sys, collections, re
 out = sys.argv[1]

@@ -9,12 +9,12 @@ mkdir -p $OUT
 # what is being measured: the hash of the kernel sources of THIS snapshot (bench.py compares it with the sources it runs)
 (cd $R && python3 -c "import json, time; from hessgpu_amd import build; print(json.dumps({'kernel_sources_sha16': build.sources_digest(), 'measured_utc': time.strftime('%Y-%m-%dT%H:%M:%SZ', time.gmtime())}))" > $OUT/provenance.json)
 # 0. the driver's own command, first thing on the fresh box (what BENCH_rNN.json will hold)
-(cd $R && python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err)
+(cd $R && python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err)
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel statistics, single stream (averages comparable with bench.py's hipEvent roofline leg)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_ctx1 -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher --contexts 1 > $OUT/bench_ctx1.json 2> $OUT/bench_ctx1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_ctx1 -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher --contexts 1 > $OUT/bench_ctx1.json 2> $OUT/bench_ctx1.err
 # 2. kernel statistics, default pipelined contexts (six)
-rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/stats_default -- python3 $R/bench.py --steps 30 --warmup 4 --no-cpu-baseline --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher > $OUT/bench_ctxd.json 2> $OUT/bench_ctxd.err
+rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/stats_default -- python3 $R/bench.py --full --steps 30 --warmup 4 --no-cpu-baseline --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher > $OUT/bench_ctxd.json 2> $OUT/bench_ctxd.err
 # 2b. the pipelined steps ALONE under the lightest trace (no statistics, no copy trace, no single-stream legs in the run):
 #     what the overlap / idle summary is taken from (round 5: with the roofline leg's single-stream steps in the same trace
 #     the "idle share" read 15 %; the pipelined part alone is 1 % idle)
@@ -46,8 +46,8 @@ python3 $R/tools/trace_overlap.py $OUT/stats_ctx1 > $OUT/overlap_ctx1.txt 2>&1 |
 python3 $R/tools/trace_overlap.py $OUT/trace_pipelined > $OUT/overlap_default.txt 2>&1 || true
 # unprofiled bench lines on the same box: the default line and batches of 16
 cd $R
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python3 bench.py --batch 16 --no-cpu-baseline --no-api-leg --no-configs4 --no-real-images --no-matcher > $OUT/bench_batch16.json 2> $OUT/bench_batch16.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --batch 16 --no-cpu-baseline --no-api-leg --no-configs4 --no-real-images --no-matcher > $OUT/bench_batch16.json 2> $OUT/bench_batch16.err
 python3 tools/bench_host_path.py > $OUT/host_path.json 2> $OUT/host_path.err
 # keep only the small summaries (the traces are large)
 find $OUT -name '*kernel_trace.csv' -delete

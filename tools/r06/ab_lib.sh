@@ -2,6 +2,7 @@
 # Same-call A/B of library builds (tools/_variants/<name>/libhessgpu.so, "cur" = the in-tree one):
 #   tools/r06/ab_lib.sh TAG lib lib ...    bench.py --steps 200 without the side legs, twice per library, alternating
 TAG=$1; shift
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # (kernel_ms_per_step and parity_checked are entries of a full run)
 R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p gpurun_out
 for rnd in 1 2; do

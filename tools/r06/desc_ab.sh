@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   OUT=$R/gpurun_out/$TAG/$v; mkdir -p $OUT
   if [ "$v" = "cur" ]; then unset HESS_LIB; else export HESS_LIB=$R/tools/_variants/$v/libhessgpu.so; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher --contexts 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -3 $OUT/bench.err; exit 3; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --no-real-images --no-matcher --contexts 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -3 $OUT/bench.err; exit 3; }
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats4 -- python3 $R/tools/r06/cfg4_probe.py --quick --runs 10 --delivery dma > $OUT/cfg4.json 2> $OUT/cfg4.err || { tail -3 $OUT/cfg4.err; exit 4; }
   find $OUT -name '*kernel_trace.csv' -delete; find $OUT -name '*agent_info.csv' -delete
   python3 - $OUT $v <<'PY'

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   OUT=$R/gpurun_out/$TAG/$v; mkdir -p $OUT
   if [ "$v" = "cur" ]; then unset HESS_LIB; else export HESS_LIB=$R/tools/_variants/$v/libhessgpu.so; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --contexts 1 > $OUT/bench.json 2> $OUT/bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-steady --no-host-leg --no-api-leg --no-configs4 --contexts 1 > $OUT/bench.json 2> $OUT/bench.err
   find $OUT -name '*kernel_trace.csv' -delete; find $OUT -name '*agent_info.csv' -delete
   python3 - $OUT $v "$PAT" <<'PY'
 import csv,glob,sys

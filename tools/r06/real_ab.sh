@@ -1,13 +1,14 @@
 #!/bin/bash
 # real-image leg of bench.py for library variants: tools/r06/real_ab.sh TAG lib lib ...
 TAG=$1; shift
+OUT=${OUT:-results}   # where the bench lines and logs go
 R=${GRAFT_REPO_ROOT:-$PWD}
-mkdir -p gpurun_out/$TAG
+mkdir -p $OUT/$TAG
 for rnd in 1 2; do
 for v in "$@"; do
   if [ "$v" = "cur" ]; then unset HESS_LIB; else export HESS_LIB=$R/tools/_variants/$v/libhessgpu.so; fi
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-api-leg --no-host-leg --no-configs4 --no-matcher --no-profile --no-steady > gpurun_out/$TAG/${v}_$rnd.json 2> gpurun_out/$TAG/${v}_$rnd.err || { echo "bench $v failed"; tail -5 gpurun_out/$TAG/${v}_$rnd.err; exit 9; }
-  python - "$v" gpurun_out/$TAG/${v}_$rnd.json <<'PY'
+  timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-api-leg --no-host-leg --no-configs4 --no-matcher --no-profile --no-steady > $OUT/$TAG/${v}_$rnd.json 2> $OUT/$TAG/${v}_$rnd.err || { echo "bench $v failed"; tail -5 $OUT/$TAG/${v}_$rnd.err; exit 9; }
+  python - "$v" $OUT/$TAG/${v}_$rnd.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])["real_images"]
 for k,v in d.items():
