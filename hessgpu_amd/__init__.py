@@ -61,7 +61,8 @@ def default_params(**overrides):
 
 class HessContext(Session):
     """One hess_ctx on one HIP device (reference: one SiftGPU instance per device).  dev_switches=True: a context of
-    the developer build, which reads the HESS_* schedule switches and test hooks from the environment."""
+    the developer build, which reads the HESS_* schedule switches and test hooks from the environment.  The overrides are
+    hess_params fields, e.g. detector=_abi.DETECTOR_DOG for the difference-of-Gaussians detector (default: Hessian)."""
 
     def __init__(self, device=0, dev_switches=False, **overrides):
         lib, fns = _load(bool(dev_switches))

@@ -7,7 +7,7 @@ CPU oracle's `hess_cpu_` entry points with the same table so both sides read ali
 """
 import ctypes as C
 
-HESS_ABI_VERSION = 4
+HESS_ABI_VERSION = 5
 
 HESS_OK = 0
 HESS_ERR_ARG = -1
@@ -23,6 +23,7 @@ DESC_ORDER_INTERLEAVED, DESC_ORDER_SEQUENTIAL, DESC_ORDER_PIXEL = 0, 1, 2
 FMT_LUM, FMT_LUM_ALPHA, FMT_RGB, FMT_RGBA, FMT_BGR, FMT_BGRA = 1, 2, 3, 4, 5, 6
 PIX_U8, PIX_U16, PIX_F32 = 1, 2, 3
 DBG_GAUSS, DBG_DETH, DBG_GOT = 0, 1, 2
+DETECTOR_HESSIAN, DETECTOR_DOG = 0, 1
 (T_LOAD, T_ALLOC, T_PYRAMID, T_DETECT, T_LIST, T_ORIENT, T_MULTI_ORIENT, T_DOWNLOAD,
  T_DESCRIPTOR, T_VBO, T_REDUCTION, T_TOTAL, T_COUNT) = range(13)
 (K_GAUSS, K_DOWNSAMPLE, K_HESSIAN, K_EXTREMA, K_TOPK, K_ORIENT, K_DESCRIPTOR, K_INPUT,
@@ -31,7 +32,19 @@ KERNEL_NAMES = ["gauss", "downsample", "hessian", "extrema", "topk", "orient", "
                 "input", "gauss_octave0"]  # gauss_octave0 repeats the octave-0 launches counted in gauss
 
 
+class _ReservedWords(C.Structure):
+    _fields_ = [("detector", C.c_int32),        # DETECTOR_* (word 0 of reserved; the test oracle's detector switch too)
+                ("reserved_tail", C.c_int32 * 5)]
+
+
+class _Reserved(C.Union):
+    _anonymous_ = ("_words",)
+    _fields_ = [("reserved", C.c_int32 * 6),    # words 1..5 must be zero for the product
+                ("_words", _ReservedWords)]
+
+
 class HessParams(C.Structure):
+    _anonymous_ = ("_reserved",)
     _fields_ = [
         ("abi_version", C.c_int32),
         ("dog_level_num", C.c_int32),
@@ -59,7 +72,7 @@ class HessParams(C.Structure):
         ("verbose", C.c_int32),
         ("dynamic_indexing", C.c_int32),
         ("descriptor_order", C.c_int32),   # DESC_ORDER_*
-        ("reserved", C.c_int32 * 6),   # must be zero for the product (word 0: the test oracle's detector switch)
+        ("_reserved", _Reserved),      # union { reserved[6]; { detector; reserved_tail[5]; } }
     ]
 
 

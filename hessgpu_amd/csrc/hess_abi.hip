@@ -30,12 +30,16 @@ hess_ctx* hess_create(int device, const hess_params* params) {
   if (!c) return nullptr;
   if (params) c->p = *params; else default_params(&c->p);
   bool reserved_nonzero = false;
-  for (int r : c->p.reserved) reserved_nonzero = reserved_nonzero || r != 0;
-  // version-2 / -3 structs: same layout; 0 in the order word is what they ask for (the interleaved order, their default)
-  if ((c->p.abi_version == 2 && c->p.descriptor_order == 0) || (c->p.abi_version == 3 && c->p.descriptor_order <= HESS_DESC_ORDER_SEQUENTIAL))
+  for (int r : c->p.reserved_tail) reserved_nonzero = reserved_nonzero || r != 0;
+  // version-2 / -3 structs: same layout; 0 in the order word is what they ask for (the interleaved order, their default);
+  // version-2 .. -4 structs leave the detector word (then reserved[0]) zero: the Hessian detector
+  if (c->p.detector == HESS_DETECTOR_HESSIAN &&
+      ((c->p.abi_version == 2 && c->p.descriptor_order == 0) || (c->p.abi_version == 3 && c->p.descriptor_order <= HESS_DESC_ORDER_SEQUENTIAL) ||
+       c->p.abi_version == 4))
     c->p.abi_version = HESS_ABI_VERSION;
   if (c->p.abi_version != HESS_ABI_VERSION || c->p.dog_level_num < 0 || c->p.dog_level_num > kMaxDog ||
-      c->p.descriptor_order < 0 || c->p.descriptor_order > HESS_DESC_ORDER_PIXEL || reserved_nonzero) {        // reserved words must be zero (word 0 is the test oracle's detector switch: not a product option)
+      c->p.descriptor_order < 0 || c->p.descriptor_order > HESS_DESC_ORDER_PIXEL || reserved_nonzero ||  // words 1..5 must be zero
+      (c->p.detector != HESS_DETECTOR_HESSIAN && c->p.detector != HESS_DETECTOR_DOG)) {
     fprintf(stderr, "hessgpu: bad hess_params (abi_version %d)\n", c->p.abi_version);
     delete c;
     return nullptr;

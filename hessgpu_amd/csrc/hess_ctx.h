@@ -44,6 +44,7 @@ namespace hess {
 
 
 struct Schedule {
+  int detector;                // HESS_DETECTOR_*: levels 0..dog+1 (Hessian) or 0..dog+2 (DoG) per octave
   int dog, level_max, level_num, level_ds;
   float sigma[kMaxLev];        // inter-level blur (SiftGPU.cpp:547-552)
   float level_sigma[kMaxLev];  // GetLevelSigma (SiftGPU.cpp:1422-1425)

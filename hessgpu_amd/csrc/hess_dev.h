@@ -3,7 +3,8 @@
 // det-Hessian (the reference's "dog" slot), got = (gradient, theta), key, feature list.
 //
 // HBM layout (one context, batch capacity B, SURVEY.md section 8 "Array sizes"):
-//   gauss, deth : float planes  [octave][level 0..dog+1][image][h_o][wa_o]
+//   gauss, deth : float planes  [octave][level 0..dog+1][image][h_o][wa_o]  (0..dog+2 with the DoG detector: deth then
+//                 holds D_l = G_l - G_(l-1) from level 1 on)
 //   got         : float2 planes [octave][level 1..dog  ][image][h_o][wa_o]
 //   per image   : row bit-masks / row counts of the extrema scan, raw detection list,
 //                 selected list, feature records, output keypoints + descriptors.
@@ -17,7 +18,7 @@ namespace hess {
 
 constexpr int kMaxOct = 16;
 constexpr int kMaxDog = 10;
-constexpr int kMaxLev = kMaxDog + 2;
+constexpr int kMaxLev = kMaxDog + 3;  // Gaussian levels 0..dog+2 of the difference-of-Gaussians detector
 constexpr int kMaxTaps = 33;  // KERNEL_MAX_WIDTH, ProgramCU.cu:42
 // streaming extrema scan (k_detect.hip): owned columns per strip, rows per wavefront segment
 #ifndef HESS_STREAM_NC
@@ -121,12 +122,14 @@ struct OrientParams {
   int num_orientation;  // 0 (-ofix), 1 (-m 1), >1 multi
   int subpixel, half_sift;
   int existing;         // 1: user keypoints -- position/scale from the packed record, only .w is written
+  int two_peaks;        // HESS_DETECTOR_DOG with num_orientation > 1: the two strongest peaks as 16-bit angles, 65535 = none
+                        // (ProgramCU.cu:1493-1548) instead of up to four as 8-bit angles (:1424-1489)
   float level_sigma[kMaxLev];
 };
 
 struct DescParams {
   float window_factor;  // 3.0
-  int half_sift, normalize, multi;
+  int half_sift, normalize, multi;  // multi: 0 one float angle in FRec::w, 1 four 8-bit angles, 2 two 16-bit angles (DoG)
   int lowe_origin;
   float octave_sigma;   // 2^ds (PyramidCU.cpp:746-748)
   int dog;
@@ -227,6 +230,9 @@ void launch_downsample(hipStream_t st, const float* src, int sw, int splane, flo
 void launch_hessian(hipStream_t st, const Geom& g, int octave, const float* gauss, float* deth,
                     float* got, const float* norms /* host: sigma^4 per level */, int batch,
                     int level_first, int level_last);
+// Difference-of-Gaussians detector: D_l = G_l - G_(l-1) into the det-H planes of levels 1..level_max of every octave, one
+// launch (ComputeDOG_Kernel, ProgramCU.cu:598-637, without its gradient part: the Gaussian launches emit that)
+void launch_dog_planes(hipStream_t st, const Geom& g, const float* gauss, float* deth, int level_max, int batch);
 // det-H of level `level` of every octave, one launch (no gradient plane); also clears `zero_bytes` (a multiple of 16)
 // at `zero` if given: the buffers the detection stages expect zeroed
 void launch_hessian_level(hipStream_t st, const Geom& g, const float* gauss, float* deth, int level, float norm,
@@ -250,8 +256,11 @@ int extrema_tasks(const Geom& g);  // scan tasks per image for this geometry (de
 // Extrema scan (ComputeKEY_Kernel, ProgramCU.cu:657-882): every accepted pixel as a complete RawKey in the image's
 // unordered store, its bit in the row's mask words, its row's count, and -- ds.hist != null -- the top-K key histogram.
 // rowmask, rowcnt, ds.spill_count, ds.hist arrive zeroed.
+// dog_mode: the scan of the difference-of-Gaussians detector -- list level l is sought in planes l, l+1, l+2 (centre l+1),
+// without sign conditions, type = sign of the extremum (ProgramCU.cu:680-699, 853-854); `gauss` is not read.
 void launch_extrema_mark(hipStream_t st, const Geom& g, const DetectParams& dp, const float* gauss,
-                         const float* deth, uint64_t* rowmask, int* rowcnt, const DetectStore& ds, int batch);
+                         const float* deth, uint64_t* rowmask, int* rowcnt, const DetectStore& ds, int batch,
+                         bool dog_mode = false);
 bool extrema_streams(const Geom& g);  // the streaming scan applies to this geometry
 // List order (ListGen_Kernel, ProgramCU.cu:924-1051, made deterministic): row counts -> exclusive offsets in list order
 // (level totals, -tc level truncation: GenerateFeatureList / LimitFeatureCount, PyramidCU.cpp:1283-1368,

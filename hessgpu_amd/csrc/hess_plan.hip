@@ -99,18 +99,37 @@ void resolve(hess_ctx* c) {
   if (p.max_orientation < 1) p.max_orientation = 1;  // SiftGPU.cpp:1047
   if (p.max_orientation > 4) p.max_orientation = 4;
   Schedule& s = c->sch;
+  s.detector = p.detector;
   s.dog = p.dog_level_num;
-  s.level_max = s.dog + 1;
-  s.level_num = s.level_max + 1;
-  s.level_ds = s.dog;
   const float sigmak = powf(2.0f, 1.0f / p.dog_level_num);
-  const float dsigma0 = p.sigma0 * sqrtf(sigmak * sigmak - 1.0f);
-  for (int i = 1; i <= s.level_max; i++) {
-    s.sigma[i - 1] = dsigma0 * powf(sigmak, (float)(i - 1));
-    make_taps(p, s.sigma[i - 1], &s.taps[i]);
+  if (s.detector == HESS_DETECTOR_DOG) {
+    // The build WITHOUT GPU_HESSIAN (SiftGPU.cpp:466-556, #else branches): levels _level_min = -1 .. _level_max = dog + 1
+    // with _sigma0 = 1.6 * 2^(1/dog); level j here is that build's level j - 1, so levels 0 .. dog + 2 carry the Hessian
+    // build's sigmas plus one more on top (the arithmetic is that build's: the bits of the taps follow it).  p.sigma0 keeps
+    // the Hessian convention (sigma of level 0).
+    s.level_max = s.dog + 2;
+    s.level_num = s.level_max + 1;
+    s.level_ds = s.dog;                                                      // _level_min + _dog_level_num, + 1 here
+    const float sigma0 = p.sigma0 * powf(2.0f, 1.0f / p.dog_level_num);     // :503
+    const float dsigma0 = sigma0 * sqrtf(1.0f - 1.0f / (sigmak * sigmak));  // :531
+    for (int i = 0; i <= s.level_max - 1; i++) {                            // :544-555
+      s.sigma[i] = dsigma0 * powf(sigmak, (float)i);
+      make_taps(p, s.sigma[i], &s.taps[i + 1]);
+    }
+    for (int l = 0; l <= s.level_max; l++)  // GetLevelSigma(level = l - 1), :1422-1425
+      s.level_sigma[l] = sigma0 * powf(2.0f, (float)(l - 1) / (float)p.dog_level_num);
+  } else {
+    s.level_max = s.dog + 1;
+    s.level_num = s.level_max + 1;
+    s.level_ds = s.dog;
+    const float dsigma0 = p.sigma0 * sqrtf(sigmak * sigmak - 1.0f);
+    for (int i = 1; i <= s.level_max; i++) {
+      s.sigma[i - 1] = dsigma0 * powf(sigmak, (float)(i - 1));
+      make_taps(p, s.sigma[i - 1], &s.taps[i]);
+    }
+    for (int l = 0; l <= s.level_max; l++) s.level_sigma[l] = p.sigma0 * powf(2.0f, (float)l / (float)p.dog_level_num);
   }
   for (int l = 0; l <= s.level_max; l++) {
-    s.level_sigma[l] = p.sigma0 * powf(2.0f, (float)l / (float)p.dog_level_num);
     const float ls = s.level_sigma[l] * 1.0f;  // octaveSigma = 1 (PyramidCU.cpp:1574-1585)
     const float n2 = ls * ls;                  // passed by DetectKeypointsEX
     s.norm[l] = n2 * n2;                       // squared again by ProgramCU::ComputeHessian (:592)
@@ -122,7 +141,10 @@ void resolve(hess_ctx* c) {
 }
 
 float initial_smooth_sigma(const hess_ctx* c, int octave_min) {  // SiftGPU.cpp:482-489
-  const float sa = c->p.sigma0 * powf(2.0f, 0.0f / (float)c->p.dog_level_num);
+  // sa = _sigma0 * 2^(_level_min / dog): _level_min = 0 (Hessian), or _sigma0 = 1.6 * 2^(1/dog) and _level_min = -1 (DoG)
+  const float sa = c->sch.detector == HESS_DETECTOR_DOG
+                       ? (c->p.sigma0 * powf(2.0f, 1.0f / c->p.dog_level_num)) * powf(2.0f, -1.0f / (float)c->p.dog_level_num)
+                       : c->p.sigma0 * powf(2.0f, 0.0f / (float)c->p.dog_level_num);
   const float sb = c->p.sigman / powf(2.0f, (float)octave_min);
   return (sa > sb + 0.001) ? sqrtf(sa * sa - sb * sb) : 0.0f;
 }

@@ -243,13 +243,15 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
     if (o == 0 && direct_u8 && c->has_taps0 && !c->no_first_fusion && s.level_max >= 2 && s.level_ds != 1 && chain_from != 0 &&
         gauss_first_available(c->taps0, s.taps[1])) {  // (decided BEFORE the profile scope: a refused launch must not book bytes)
       // u8 pixels -> level 0 (LDS) -> level 1, det-H of level 0: the level-0 plane is nobody's input but level 1's
+      // (and, with the DoG detector, D_1's: the level is stored then)
       const GaussJob j1 = level_job(0, 1);
-      ProfScope ps(c, HESS_K_GAUSS, (double)batch * og.plane * (1.0 + 4.0 + 4.0), HESS_K_GAUSS_OCT0,
-                   c->keep_levels ? 0.0 : (double)batch * og.plane * 8.0);
+      const bool store0 = c->keep_levels || s.detector == HESS_DETECTOR_DOG;
+      ProfScope ps(c, HESS_K_GAUSS, (double)batch * og.plane * (1.0 + 4.0 + 4.0 + (s.detector == HESS_DETECTOR_DOG ? 4.0 : 0.0)),
+                   HESS_K_GAUSS_OCT0, store0 ? 0.0 : (double)batch * og.plane * 8.0);
       first_fused = launch_gauss_first(st, (const uint8_t*)dev, pitch, (long long)image_stride, c->taps0, j1,
-                                       c->keep_levels ? plane_ptr(gauss, 0, 0) : nullptr, batch);
+                                       store0 ? plane_ptr(gauss, 0, 0) : nullptr, batch);
     }
-    if (o == 0) c->level0_in_lds = first_fused && !c->keep_levels;
+    if (o == 0) c->level0_in_lds = first_fused && !c->keep_levels && s.detector != HESS_DETECTOR_DOG;
     if (o == 0 && first_fused) {
       // (nothing: level 1 exists, the loop below starts at level 2)
     } else if (o == 0) {
@@ -333,6 +335,16 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
       c->zero_filled = !user_mode;
     }
   }
+  if (s.detector == HESS_DETECTOR_DOG) {
+    // ---- difference of Gaussians (ComputeDOG_Kernel): D_l = G_l - G_(l-1), levels 1..dog+2, over the det-H planes the
+    // launches above wrote (level 0 keeps its det-H, as in the test oracle).  The DoG schedule is the Hessian one with one
+    // more level per octave and no top-level fusion (top_fused is false: level dog+2 is stored, its det-H comes from
+    // hessian_rows4 with the fill of the detection buffers) and no level chain (it needs level_max == level_ds + 1).
+    double px = 0;
+    for (int o = 0; o < g.noct; o++) px += g.o[o].plane;
+    ProfScope ps(c, HESS_K_HESSIAN, (double)batch * px * 12.0 * s.level_max);
+    launch_dog_planes(st, g, gauss, deth, s.level_max, batch);
+  }
   }  // !(user_mode && on_current)
   if (user_mode) return enqueue_user(c);
   // ---- extrema + ordered list (DetectKeypointsEX part 2 + GenerateFeatureList) ----
@@ -355,7 +367,8 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
     double det_bytes = 0;
     for (int o = 0; o < g.noct; o++) det_bytes += 4.0 * s.level_num * g.o[o].plane;
     ProfScope ps(c, HESS_K_EXTREMA, det_bytes * batch);
-    launch_extrema_mark(st, gx, dp, gauss, deth, (uint64_t*)c->rowmask.p, (int*)c->rowcnt.p, dstore, batch);
+    launch_extrema_mark(st, gx, dp, gauss, deth, (uint64_t*)c->rowmask.p, (int*)c->rowcnt.p, dstore, batch,
+                        s.detector == HESS_DETECTOR_DOG);
   }
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[2], st));
   {
@@ -390,6 +403,7 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
   op.subpixel = p.subpixel;
   op.half_sift = p.half_sift;
   op.existing = 0;
+  op.two_peaks = s.detector == HESS_DETECTOR_DOG && op.num_orientation > 1;
   for (int l = 0; l < kMaxLev; l++) op.level_sigma[l] = l <= s.level_max ? s.level_sigma[l] : 0.0f;
   {
     ProfScope ps(c, HESS_K_ORIENT, 0.0);
@@ -406,7 +420,7 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
   dsp.window_factor = p.desc_window_factor;
   dsp.half_sift = p.half_sift;
   dsp.normalize = p.normalize;
-  dsp.multi = c->multi ? 1 : 0;
+  dsp.multi = c->multi ? (s.detector == HESS_DETECTOR_DOG ? 2 : 1) : 0;
   dsp.lowe_origin = p.lowe_origin;
   dsp.octave_sigma = first_octave_sigma(c);  // PyramidCU.cpp:746-748
   dsp.dog = g.dog;

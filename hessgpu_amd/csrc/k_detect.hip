@@ -131,6 +131,26 @@ __global__ __launch_bounds__(256) void hessian_rows4_kernel(Geom g, const float*
   }
 }
 
+// Difference-of-Gaussian planes (the detector built without GPU_HESSIAN): D_l = G_l - G_(l-1), one plain float subtraction
+// per pixel (ComputeDOG_Kernel, ProgramCU.cu:598-637; its gradient half comes out of the Gaussian launches), levels
+// 1..blockIdx.y / batch + 1 of every octave in one launch; 4 px per thread (wa is a multiple of 4, so is every plane).
+__global__ __launch_bounds__(256) void dog_planes_kernel(Geom g, const float* gauss, float* deth, int batch) {
+  int blk = blockIdx.x, o = 0;  // block -> octave: octaves back to back, whole blocks each (uniform scalar walk)
+  for (; o < g.noct - 1; o++) {
+    const int nb = ((g.o[o].plane >> 2) + 255) >> 8;
+    if (blk < nb) break;
+    blk -= nb;
+  }
+  const OctGeom& og = g.o[o];
+  const int i = (blk * 256 + threadIdx.x) << 2;
+  if (i >= og.plane) return;
+  const int l = 1 + (int)blockIdx.y / batch, b = (int)blockIdx.y % batch;
+  const long long at = og.lvl_off + ((long long)l * g.B + b) * og.plane + i;
+  const float4 hi = *reinterpret_cast<const float4*>(gauss + at);
+  const float4 lo = *reinterpret_cast<const float4*>(gauss + at - (long long)g.B * og.plane);
+  store_stream_f4(deth + at, hi.x - lo.x, hi.y - lo.y, hi.z - lo.z, hi.w - lo.w);
+}
+
 // =============================== extrema test ================================================
 
 struct KeyVal {
@@ -148,11 +168,25 @@ struct KeyVal {
     if ((response > nmin) || (response > 0)) return false;                       \
   }
 
+// READ_CMP_DOG_DATA as compiled without GPU_HESSIAN (ProgramCU.cu:680-699): no sign conditions.
+#define HESS_READ_CMP_DOG(d0, d1, d2, tex, i)                                    \
+  d0 = tex[(i) - 1]; d1 = tex[(i)]; d2 = tex[(i) + 1];                           \
+  if (response > nmax) {                                                         \
+    nmax = fmaxf(nmax, d0); nmax = fmaxf(nmax, d1); nmax = fmaxf(nmax, d2);      \
+    if (response < nmax) return false;                                           \
+  } else {                                                                       \
+    nmin = fminf(nmin, d0); nmin = fminf(nmin, d1); nmin = fminf(nmin, d2);      \
+    if (response > nmin) return false;                                           \
+  }
+#define HESS_READ_ANY(d0, d1, d2, tex, i) \
+  if (DM) { HESS_READ_CMP_DOG(d0, d1, d2, tex, i) } else { HESS_READ_CMP(d0, d1, d2, tex, i) }
+
 // ComputeKEY_Kernel body for one interior pixel (ProgramCU.cu:725-857).  The comparison macro
 // re-selects its branch per triple with the running nmax exactly as READ_CMP_DOG_DATA does.
 // PRE = true stops after the 26-neighbour and edge tests (everything before the sub-pixel solve) and
 // reports whether the pixel is still a candidate; the arithmetic is the same code either way.
-template <bool PRE = false>
+// DM = true: the difference-of-Gaussians build (no sign conditions; type = sign of the extremum, texG unread).
+template <bool PRE = false, bool DM = false>
 __device__ __forceinline__ bool key_eval(const float* texC, const float* texP, const float* texN,
                                          const float* texG, int width, int index, const DetectParams& dp,
                                          KeyVal* out, long long gindex = -1) {
@@ -171,8 +205,8 @@ __device__ __forceinline__ bool key_eval(const float* texC, const float* texP, c
   nmax = fmaxf(d10, d12);
   nmin = fminf(d10, d12);
   if ((response <= nmax) && (response >= nmin)) return false;
-  HESS_READ_CMP(d00, d01, d02, texC, i0);
-  HESS_READ_CMP(d20, d21, d22, texC, i2);
+  HESS_READ_ANY(d00, d01, d02, texC, i0);
+  HESS_READ_ANY(d20, d21, d22, texC, i2);
 
   const float vx2 = response * 2.0f;
   const float fxx = d10 + d12 - vx2;
@@ -182,12 +216,12 @@ __device__ __forceinline__ bool key_eval(const float* texC, const float* texP, c
   const float temp2 = (fxx + fyy) * (fxx + fyy);
   if ((temp1 <= 0) || (temp2 > dp.edge * temp1)) return false;
 
-  HESS_READ_CMP(p00, p01, p02, texP, i0);
-  HESS_READ_CMP(p10, p11, p12, texP, i1);
-  HESS_READ_CMP(p20, p21, p22, texP, i2);
-  HESS_READ_CMP(n00, n01, n02, texN, i0);
-  HESS_READ_CMP(n10, n11, n12, texN, i1);
-  HESS_READ_CMP(n20, n21, n22, texN, i2);
+  HESS_READ_ANY(p00, p01, p02, texP, i0);
+  HESS_READ_ANY(p10, p11, p12, texP, i1);
+  HESS_READ_ANY(p20, p21, p22, texP, i2);
+  HESS_READ_ANY(n00, n01, n02, texN, i0);
+  HESS_READ_ANY(n10, n11, n12, texN, i1);
+  HESS_READ_ANY(n20, n21, n22, texN, i2);
   (void)p00; (void)p02; (void)p20; (void)p22; (void)n00; (void)n02; (void)n20; (void)n22;
   if (PRE) return true;
 
@@ -226,7 +260,8 @@ __device__ __forceinline__ bool key_eval(const float* texC, const float* texP, c
   if (!offset_test_passed) return false;
   if (out) {
     uint32_t type;  // ProgramCU.cu:828-851
-    if (response < 0) type = 2u;
+    if (DM) type = (response > nmax) ? 1u : 0u;  // result = +-1, ProgramCU.cu:853-854
+    else if (response < 0) type = 2u;
     else {
       const long long gi = gindex >= 0 ? gindex : (long long)i1;  // (texG may have its own pitch: the LDS-tiled scan)
       const float g0 = texG[gi - 1], g1 = texG[gi], g2 = texG[gi + 1];
@@ -321,6 +356,8 @@ __device__ __forceinline__ RowTask decode_row(const Geom& g, int wave, int batch
 // by the scatter pass is independent of the order candidates were queued in.
 constexpr int EX_TR = 4, EX_TC = 128, EX_STRIDE = EX_TC + 8 + 4;  // cols x0-4 .. x0+260, +4 pad
 
+// DM: the difference-of-Gaussians detector -- the planes staged are D_1 .. D_(dog+2) (one level up), key_eval<.., true>.
+template <bool DM>
 __global__ __launch_bounds__(256) void extrema_mark_kernel(Geom g, DetectParams dp, const float* gauss, const float* deth,
                                                            uint64_t* rowmask, int* rowcnt, DetectStore ds) {
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [dog+2][EX_TR+2][EX_STRIDE]
@@ -357,7 +394,7 @@ __global__ __launch_bounds__(256) void extrema_mark_kernel(Geom g, DetectParams 
         dst[u] = (l * ROWS + r) * EX_STRIDE + gx * 4;
         const bool ok = (y >= 0 && y < og.h && x >= 0 && x < og.wa);
         const int yc = ok ? y : 0, xc = ok ? x : 0;  // branch-free: always load, select afterwards
-        const float4 q = *reinterpret_cast<const float4*>(deth + og.lvl_off + ((long long)l * g.B + b) * og.plane + (long long)yc * og.wa + xc);
+        const float4 q = *reinterpret_cast<const float4*>(deth + og.lvl_off + ((long long)(l + (DM ? 1 : 0)) * g.B + b) * og.plane + (long long)yc * og.wa + xc);
         if (ok) v[u] = q;
       }
     }
@@ -424,7 +461,7 @@ __global__ __launch_bounds__(256) void extrema_mark_kernel(Geom g, DetectParams 
       const int rl_ = code >> 8, cl = code & 255;
       const int row = y0 + rl_, col = x0 + cl;
       KeyVal kv;
-      const bool ok = i < nc && key_eval<false>(C, P, N, G, EX_STRIDE, (rl_ + 1) * EX_STRIDE + (cl + 4), dp, &kv,
+      const bool ok = i < nc && key_eval<false, DM>(C, P, N, G, EX_STRIDE, (rl_ + 1) * EX_STRIDE + (cl + 4), dp, &kv,
                                                 (long long)row * og.wa + col);
       const uint64_t m = __builtin_amdgcn_ballot_w64(ok);
       int before = 0;
@@ -461,7 +498,7 @@ constexpr int SX_PITCH = kStreamPitch, SX_QCAP = 128;  // (rows per segment: Geo
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ float min3f(float a, float b, float c) { return fminf(fminf(a, b), c); }
 
-template <int DOG>
+template <int DOG, bool DM = false>
 __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParams dp, const float* gauss, const float* deth,
                                                              unsigned long long* rowmask, int* rowcnt, DetectStore ds) {
   constexpr int NLV = DOG + 2;
@@ -487,7 +524,7 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
   const bool col_in = cx >= 0 && cx < og.wa;         // (wa is a multiple of 4: a lane's columns are all in or all out)
   const int wa = og.wa, h = og.h;
   const long long lstep = (long long)g.B * og.plane;
-  const float* base = deth + og.lvl_off + (long long)b * og.plane;  // level l at base + l*lstep
+  const float* base = deth + og.lvl_off + (long long)b * og.plane + (DM ? lstep : 0);  // level l at base + l*lstep (DM: D_(l+1))
   // a pixel is tested if it is interior (ProgramCU.cu:700-705) and owned by this lane
   const bool own = lane >= 1 && lane <= 62;
   bool cv[NC];
@@ -523,7 +560,7 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
     const int l = e >> 28, row = (e >> 14) & 0x3FFF, col = e & 0x3FFF;
     const float* C = base + l * lstep;
     KeyVal kv;
-    const bool ok = active && key_eval<false>(C, C - lstep, C + lstep, gbase + l * lstep, wa, row * wa + col, dp, &kv);
+    const bool ok = active && key_eval<false, DM>(C, C - lstep, C + lstep, gbase + l * lstep, wa, row * wa + col, dp, &kv);
     const uint64_t m = __builtin_amdgcn_ballot_w64(ok);
     post_detections(sk, nfound, ok, m, kv, o * g.dog + (l - 1), row, col, og.mask_base + ((l - 1) * h + row) * og.w64 + (col >> 6),
                     og.row_base + (l - 1) * h + row);
@@ -1126,18 +1163,28 @@ void launch_hessian_level(hipStream_t st, const Geom& g, const float* gauss, flo
                      reinterpret_cast<uint4*>(zero), (long long)(zero_bytes / 16));
 }
 
+void launch_dog_planes(hipStream_t st, const Geom& g, const float* gauss, float* deth, int level_max, int batch) {
+  int blocks = 0;
+  for (int o = 0; o < g.noct; o++) blocks += ((g.o[o].plane >> 2) + 255) >> 8;
+  hipLaunchKernelGGL(dog_planes_kernel, dim3(blocks, level_max * batch), dim3(256), 0, st, g, gauss, deth, batch);
+}
+
 bool extrema_streams(const Geom& g) { return g.dog <= 5 && g.o[0].wa < (1 << 14) && g.o[0].h < (1 << 14); }
 
 int extrema_tasks(const Geom& g) { return extrema_streams(g) ? g.nstream * 4 : g.ntiles; }
 
 void launch_extrema_mark(hipStream_t st, const Geom& g, const DetectParams& dp, const float* gauss,
-                         const float* deth, uint64_t* rowmask, int* rowcnt, const DetectStore& ds, int batch) {
+                         const float* deth, uint64_t* rowmask, int* rowcnt, const DetectStore& ds, int batch, bool dog_mode) {
   // rowcnt, rowmask, ds.spill_count and ds.hist arrive zeroed (one fill per batch in enqueue(), hess_schedule.hip)
   // streaming scan; its candidate queue packs row and column in 14 bits each
   if (extrema_streams(g)) {
     unsigned long long* rm = reinterpret_cast<unsigned long long*>(rowmask);
     const dim3 grid(g.nstream, batch), blk(256);
-#define HESS_STREAM_LAUNCH(D) hipLaunchKernelGGL(extrema_stream_kernel<D>, grid, blk, 0, st, g, dp, gauss, deth, rm, rowcnt, ds)
+#define HESS_STREAM_LAUNCH(D)                                                                                             \
+  do {                                                                                                                    \
+    if (dog_mode) hipLaunchKernelGGL((extrema_stream_kernel<D, true>), grid, blk, 0, st, g, dp, gauss, deth, rm, rowcnt, ds); \
+    else hipLaunchKernelGGL(extrema_stream_kernel<D>, grid, blk, 0, st, g, dp, gauss, deth, rm, rowcnt, ds);             \
+  } while (0)
     switch (g.dog) {
       case 1: HESS_STREAM_LAUNCH(1); break;
       case 2: HESS_STREAM_LAUNCH(2); break;
@@ -1151,13 +1198,17 @@ void launch_extrema_mark(hipStream_t st, const Geom& g, const DetectParams& dp, 
   // more than 5 detection levels per octave, or planes of 16384 px and more: LDS-tiled scan (level count
   // and plane size are run-time values there)
   const size_t lds = (size_t)(g.dog + 2) * (EX_TR + 2) * EX_STRIDE * sizeof(float);
-  static size_t lds_allowed = 0;  // dog >= 4 needs more than the default 64 KB of dynamic LDS
-  if (lds > lds_allowed) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(extrema_mark_kernel),
+  static size_t lds_allowed[2] = {0, 0};  // dog >= 4 needs more than the default 64 KB of dynamic LDS
+  if (lds > lds_allowed[dog_mode]) {
+    (void)hipFuncSetAttribute(dog_mode ? reinterpret_cast<const void*>(extrema_mark_kernel<true>)
+                                       : reinterpret_cast<const void*>(extrema_mark_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    lds_allowed = lds;
+    lds_allowed[dog_mode] = lds;
   }
-  hipLaunchKernelGGL(extrema_mark_kernel, dim3(g.ntiles, batch), dim3(256), lds, st, g, dp, gauss, deth, rowmask, rowcnt, ds);
+  if (dog_mode)
+    hipLaunchKernelGGL(extrema_mark_kernel<true>, dim3(g.ntiles, batch), dim3(256), lds, st, g, dp, gauss, deth, rowmask, rowcnt, ds);
+  else
+    hipLaunchKernelGGL(extrema_mark_kernel<false>, dim3(g.ntiles, batch), dim3(256), lds, st, g, dp, gauss, deth, rowmask, rowcnt, ds);
 }
 
 void launch_extrema_place(hipStream_t st, const Geom& g, const LimitParams& lp, const DetectStore& ds, const uint64_t* rowmask,

@@ -398,6 +398,35 @@ __global__ __launch_bounds__(256) void orientation_kernel(Geom g, OrientParams o
         const float off = 0.5f * ((n0 - p0) / (weight + weight - n0 - p0));
         const float kw = radius_per_ten_degrees * ((float)index_max + 0.5f + off);
         kw_bits = __float_as_uint(kw);
+      } else if (op.two_peaks) {  // the build without GPU_HESSIAN, ProgramCU.cu:1493-1548: two peaks, 16-bit angles
+        const float vote_threshold = mx * 0.8f;
+        const bool peak = (lane < 36) && (vote > vote_threshold) && (vote > pre) && (vote > nxt);
+        const float di = 0.5f * ((nxt - pre) / (vote + vote - nxt - pre));
+        const float rot = (float)lane + di + 0.5f;
+        uint64_t pm = __ballot(peak);
+        float mv0 = 0, mv1 = 0, mr0 = 0, mr1 = 0;
+        int found = 0;  // the reference's orientation counter: peaks that entered the top two
+        while (pm) {
+          const int j = __builtin_ctzll(pm);
+          pm &= pm - 1;
+          const float cw = rl(vote, j), cr = rl(rot, j);
+          if (cw > mv1) {
+            if (cw > mv0) { mv1 = mv0; mr1 = mr0; mv0 = cw; mr0 = cr; }
+            else { mv1 = cw; mr1 = cr; }
+            found++;
+          }
+        }
+        float fr1 = mr0 / 36.0f;
+        if (fr1 < 0) fr1 += 1.0f;
+        const uint32_t us1 = (found == 0) ? 65535u : (uint32_t)(unsigned short)floorf(fr1 * 65535.0f);
+        uint32_t us2 = 65535u;
+        if (found > 1) {
+          float fr2 = mr1 / 36.0f;
+          if (fr2 < 0) fr2 += 1.0f;
+          us2 = (uint32_t)(unsigned short)floorf(fr2 * 65535.0f);
+        }
+        kw_bits = (us2 << 16) | us1;
+        ocnt = (us1 != 65535u) + (us2 != 65535u);  // what ReshapeFeatureListCPU expands (PyramidCU.cpp:800-820)
       } else {  // ProgramCU.cu:1424-1489
         const float vote_threshold = mx * 0.8f;
         const bool peak = (lane < 36) && (vote > vote_threshold) && (vote > pre) && (vote > nxt);
@@ -503,6 +532,13 @@ __device__ __forceinline__ void quad_fma(float& acc, float coef, float w) {
   acc = fmaf(coef, wb, acc);
 }
 
+// Angle k of a multi-orientation record (PyramidCU.cpp:763-767): four 8-bit angles (multi = 1), or two 16-bit angles of the
+// difference-of-Gaussians build (multi = 2).
+__device__ __forceinline__ float multi_angle(int multi, uint32_t w, int k) {
+  return multi == 2 ? (float)((2.0 * kPI / 65535.0) * (double)((w >> (16 * k)) & 0xFFFFu))
+                    : (float)((2.0 * kPI / 255.0) * (double)((w >> (8 * k)) & 0xFFu));
+}
+
 // A launch that does only a part of one image's features (a single large image delivered in parts: the copier's DMA copy
 // of part k crosses the host link while part k + 1 is computed): the image's list narrowed to features
 // [n part / den, n (part + 1) / den) -- in list order, which is the order of the packed output, so a part is one contiguous
@@ -532,7 +568,7 @@ __device__ __forceinline__ void keypoint_records(const DescParams& dp, uint32_t*
       const int i = src >> 2, k = src & 3;
       const FRec rec = recs[(long long)b * cap_list + i];
       const int li = list[(long long)b * cap_list + i].level_index;
-      const float kw = dp.multi ? (float)((2.0 * kPI / 255.0) * (double)((rec.w >> (8 * k)) & 0xFFu))
+      const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
                                 : __uint_as_float(rec.w);
       const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
       const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
@@ -685,7 +721,7 @@ __global__ __launch_bounds__(256) void descriptor_kernel(Geom g, DescParams dp, 
     const int width = og.wa, height = og.h;
 
     // un-mirrored orientation handed to the kernel (PyramidCU.cpp:764,791; A.1 of SURVEY)
-    const float kw = dp.multi ? (float)((2.0 * kPI / 255.0) * (double)((rec.w >> (8 * k)) & 0xFFu))
+    const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
                               : __uint_as_float(rec.w);
     const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
     const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
@@ -989,7 +1025,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, P
         (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
     const int width = og.wa, height = og.h;
 
-    const float kw = dp.multi ? (float)((2.0 * kPI / 255.0) * (double)((rec.w >> (8 * k)) & 0xFFu))
+    const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
                               : __uint_as_float(rec.w);
     const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
     const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;

@@ -468,6 +468,8 @@ void SiftGPU::PrintUsage() {
                "-m [n] -s [n] -ofix -ofix-not -loweo     orientations, sub-pixel, fixed orientation, Lowe origin\n"
                "-topk <n> -tc/-tc1/-tc2/-tc3 <n>         limit the number of features\n"
                "-half -sd -b -bvlf -ads -maxd <n> -p WxH -tight -cuda <dev> -v <0..4>\n"
+               "-dog                                     difference-of-Gaussians detector (classic SiftGPU, the reference built\n"
+               "                                         without GPU_HESSIAN; default: determinant of the Hessian)\n"
                "-dseq                                    descriptor bins summed in the reference's sequential order\n"
                "-dint                                    ... as four interleaved partial sums (equal to -dseq within 1e-6)\n"
                "                                         default: one pass over the pixels, fixed-point sums -- within 3e-5 of -dseq\n"
@@ -520,6 +522,7 @@ void SiftGPU::ParseParam(int argc, char** argv) {  // SiftGPU.cpp:855-1380
     if (k == "di") { p.dynamic_indexing = 1; continue; }  // SiftGPU.cpp:1030-1032
     if (k == "dseq") { p.descriptor_order = HESS_DESC_ORDER_SEQUENTIAL; continue; }  // this build only: hess_abi.h
     if (k == "dint") { p.descriptor_order = HESS_DESC_ORDER_INTERLEAVED; continue; }
+    if (k == "dog") { p.detector = HESS_DETECTOR_DOG; continue; }  // this build only: hess_abi.h (the reference compiles it in)
     if (k == "sd") { if (!_initialized) p.compute_descriptors = 0; continue; }
     if (k == "b") { im->binary_sift = 1; continue; }
     if (k == "ads") { p.auto_downscale = 1; continue; }

@@ -33,8 +33,18 @@ extern "C" {
  *    instead of handing out the results of the run before.
  * 4: HESS_DESC_ORDER_PIXEL, the order hess_default_params now chooses (a version-3 struct keeps what it asks for: 0 is
  *    the interleaved order); hess_debug_keep_levels (the top Gaussian level of an octave is no longer written to HBM
- *    unless asked for); a context whose DMA copy was lost refuses further runs (HESS_ERR_DEVICE, "poisoned"). */
-#define HESS_ABI_VERSION 4
+ *    unless asked for); a context whose DMA copy was lost refuses further runs (HESS_ERR_DEVICE, "poisoned").
+ * 5: hess_params.detector (word 0 of reserved[], which a version-2, -3 or -4 struct leaves zero: the Hessian detector):
+ *    HESS_DETECTOR_DOG runs the difference-of-Gaussians detector of the reference's build without GPU_HESSIAN. */
+#define HESS_ABI_VERSION 5
+
+/* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
+ *   HESSIAN  determinant of the Hessian * sigma^4 of levels 1..dog, extrema with sign conditions (the default)
+ *   DOG      differences of adjacent Gaussian levels D_l = G_l - G_(l-1) (levels 0..dog+2, sigma0 * 2^(1/dog) per the
+ *            reference's _level_min = -1), extrema without sign conditions, type = sign of the extremum, and with
+ *            max_orientation > 1 the two strongest histogram peaks as 16-bit angles (ProgramCU.cu:598-637, 680-699,
+ *            853-854, 1493-1548; SiftGPU.cpp:466-556) -- classic SiftGPU. */
+enum { HESS_DETECTOR_HESSIAN = 0, HESS_DETECTOR_DOG = 1 };
 
 typedef enum hess_status {
   HESS_OK = 0,
@@ -126,8 +136,14 @@ typedef struct hess_params {
                                    ProgramCU.cu:1755-1771): a sample whose bin coordinate rounds up to
                                    exactly 8.0 is then added to bin 8 (folded into bin 0), not dropped */
   int32_t descriptor_order;     /* HESS_DESC_ORDER_*: how a descriptor bin's samples are added up (see the enum)  */
-  int32_t reserved[6];          /* must be zero: hess_create refuses anything else (word 0 is where the test
-                                   oracle keeps its detector switch, oracle/hess_oracle.h -- not a product option) */
+  union {
+    int32_t reserved[6];        /* words 1..5 must be zero: hess_create refuses anything else                     */
+    struct {
+      int32_t detector;         /* HESS_DETECTOR_* (word 0 of reserved[]; also the test oracle's detector switch,
+                                   oracle/hess_oracle.h, whose values 0 and 1 are these two)                      */
+      int32_t reserved_tail[5];
+    };
+  };
 } hess_params;
 
 /* Binary-identical to SiftGPU::SiftKeypoint (SiftGPU.h:108-116): 24 bytes. */
@@ -145,7 +161,9 @@ enum { HESS_T_LOAD = 0, HESS_T_ALLOC, HESS_T_PYRAMID, HESS_T_DETECT, HESS_T_LIST
 
 /* Stage dumps for the parity tests (hess_debug_level `what`). */
 enum { HESS_DBG_GAUSS = 0,  /* Gaussian level, wa*h floats                                   */
-       HESS_DBG_DETH = 1,   /* det-Hessian * sigma^4, wa*h floats                            */
+       HESS_DBG_DETH = 1,   /* the detector's response plane, wa*h floats: det-Hessian * sigma^4 (levels
+                               0..dog+1), or with HESS_DETECTOR_DOG G_l - G_(l-1) (levels 1..dog+2; level 0
+                               holds det-H * sigma^4 of G_0, as in the test oracle)               */
        HESS_DBG_GOT = 2     /* (|grad|/2, theta) interleaved, 2*wa*h floats, levels 1..dog   */ };
 
 /* One raw detection (before top-K / orientation), for hess_debug_list. 32 bytes. */
@@ -252,7 +270,8 @@ int hess_debug_regrown(hess_ctx* ctx);
 /* Parity hook: the top Gaussian level of every octave (level dog+1) is nobody's input -- the launch that produces it
  * computes its det-Hessian from the output tile and does NOT write the level to HBM (the reference materialises it,
  * PyramidCU.cpp:1486-1558, and reads it back once, :1576-1591).  on != 0: the following runs of this context store it
- * as well, so that hess_debug_level(HESS_DBG_GAUSS, level dog+1) can return it (HESS_ERR_STATE otherwise). */
+ * as well, so that hess_debug_level(HESS_DBG_GAUSS, level dog+1) can return it (HESS_ERR_STATE otherwise).  With
+ * HESS_DETECTOR_DOG the top level is dog+2 and the same rule applies to it. */
 int hess_debug_keep_levels(hess_ctx* ctx, int on);
 
 /* Multi-process jobs on one node (one process per GPU): keep this context's pinned host result buffers in

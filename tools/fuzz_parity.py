@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU: random image sizes, contents and parameters, every stage compared bit for bit
-with the CPU oracle (the comparison of tests/test_gpu_parity.py).  Not part of the test suite (run time grows with
+with the CPU oracle (the comparison of tests/test_gpu_parity.py; for the difference-of-Gaussians detector, drawn for half
+the cases, that of tests/test_dog_detector_gpu.py: levels 0..dog+2).  Not part of the test suite (run time grows with
 the number of cases):   python tools/fuzz_parity.py [cases=40] [seed=1]"""
 import os
 import sys
@@ -14,6 +15,7 @@ import fixtures
 import hessgpu_amd
 from hessgpu_amd import _abi
 from oracle_lib import OracleSession
+from test_dog_detector_gpu import _compare as _compare_dog
 from test_gpu_parity import _compare_all
 
 
@@ -56,10 +58,13 @@ def main():
             kw["dynamic_indexing"] = 1
         if rng.rand() < 0.15:
             kw["normalize"] = 0
+        if rng.rand() < 0.5:
+            kw["detector"] = _abi.DETECTOR_DOG   # the oracle's detector word 1 is the same detector
         g = hessgpu_amd.HessContext(0, **kw)
         o = OracleSession(threads=16, **kw)
         try:
-            n = _compare_all(g, o, img, f"case {k}: {w}x{h}x{batch} {kind} {kw}", stages=True)
+            compare = _compare_dog if kw.get("detector") else _compare_all
+            n = compare(g, o, img, f"case {k}: {w}x{h}x{batch} {kind} {kw}", stages=True)
         finally:
             g.close()
             o.close()
