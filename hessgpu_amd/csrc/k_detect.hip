@@ -479,20 +479,24 @@ __global__ __launch_bounds__(256) void extrema_mark_kernel(Geom g, DetectParams 
 
 // ---- streaming extrema scan (pass 1, default for dog <= 5): registers instead of an LDS tile ----
 // One wavefront marches down a strip of 124 owned columns (lane j holds columns x0-2+2j, x0-1+2j of
-// every det-H level; lanes 0 and 63 only supply the halo column) over Geom::stream_rows rows (24; 12 for batches of one or two images).  (Columns per lane =
-// kStreamCols, hess_dev.h: with one column per lane the kernel needs 116 instead of 168 registers and runs four
-// instead of three wavefronts per SIMD, but spends 43 % more instructions per pixel on the neighbour exchange:
-// same time)  Per new row and
-// level it forms the horizontal 3-max / 3-min (neighbours from the adjacent lanes by DPP wave shifts)
-// and keeps them for the last three rows, so the 26-neighbour maximum of a pixel is
+// every streamed level; lanes 0 and 63 only supply the halo column) over Geom::stream_rows rows (24; 12 for batches of one or two images).  (Columns per lane =
+// kStreamCols, hess_dev.h: when all dog+2 levels were streamed, one column per lane needed 116 instead of 168 registers
+// and ran four instead of three wavefronts per SIMD, but spent 43 % more instructions per pixel on the neighbour exchange:
+// same time, DESIGN.md section 6.  Streaming levels 1..dog only, two columns per lane need 120 at dog 3: four wavefronts.)
+// Only the detection levels 1..dog are streamed.  Per new row and level it forms the horizontal 3-max / 3-min (neighbours from the adjacent lanes
+// by DPP wave shifts) and keeps them for the last three rows, so the maximum over a pixel's neighbours is
 //   max3( max over 3 rows of the level below, same of the level above,
 //         max3(row above, row below, left/right) of its own level )
-// -- about 65 VALU operations per pixel for all levels together, every level-pixel loaded from HBM
-// once per strip segment, no LDS traffic and no barriers.  The necessary condition "beyond the first
-// threshold and >= all 26 neighbours or <= all of them" is the same superset filter as in
-// extrema_mark_kernel; survivors are queued (64 per batch, all lanes busy) for the exact
-// order-dependent test key_eval, which sets positional mask bits and row counts with atomics (the
-// masks are zeroed before the launch).
+// -- every streamed level-pixel loaded from HBM once per strip segment, no LDS traffic and no barriers.  The necessary
+// condition "beyond the first threshold and >= all its neighbours or <= all of them" is the superset filter of
+// extrema_mark_kernel, over the 26 neighbours for levels 2..dog-1 and over the 17 of its own and the inner adjacent
+// level for levels 1 and dog: the outer levels 0 and dog+1 are only ever the P / N neighbours of those two, and
+// key_eval, which the survivors are queued for anyway (64 per batch, all lanes busy), reads the nine P / N values it
+// needs from memory.  So of the outer planes only the lines around the queued pixels are fetched: 28 % / 41 % of levels
+// 0 / dog+1 on synthetic blobs, 10 % / 8 % on the reference's photographs, against the 8 B per octave-pixel every pixel
+// loaded before (tools/scan_line_demand.py).  key_eval is the exact, order-dependent test; it sets
+// positional mask bits and row counts with atomics (the masks are zeroed before the launch), so what the filter lets
+// through changes work, not results.
 constexpr int SX_PITCH = kStreamPitch, SX_QCAP = 128;  // (rows per segment: Geom::stream_rows)
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -501,7 +505,7 @@ __device__ __forceinline__ float min3f(float a, float b, float c) { return fminf
 template <int DOG, bool DM = false>
 __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParams dp, const float* gauss, const float* deth,
                                                              unsigned long long* rowmask, int* rowcnt, DetectStore ds) {
-  constexpr int NLV = DOG + 2;
+  constexpr int NLV = DOG;  // streamed levels: the detection levels 1..dog (plane l + 1 at ring index l)
   constexpr int NC = kStreamCols;  // columns per lane
   __shared__ uint32_t queue[4][SX_QCAP];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -525,6 +529,7 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
   const int wa = og.wa, h = og.h;
   const long long lstep = (long long)g.B * og.plane;
   const float* base = deth + og.lvl_off + (long long)b * og.plane + (DM ? lstep : 0);  // level l at base + l*lstep (DM: D_(l+1))
+  const float* sbase = base + lstep;  // the first streamed level
   // a pixel is tested if it is interior (ProgramCU.cu:700-705) and owned by this lane
   const bool own = lane >= 1 && lane <= 62;
   bool cv[NC];
@@ -542,11 +547,11 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
 #pragma unroll
     for (int l = 0; l < NLV; l++) {
       if (NC == 2) {
-        const float2 t = *reinterpret_cast<const float2*>(base + l * lstep + off);
+        const float2 t = *reinterpret_cast<const float2*>(sbase + l * lstep + off);
         dst[l].v[0] = t.x; dst[l].v[NC - 1] = t.y;
       } else {
 #pragma unroll
-        for (int c = 0; c < NC; c++) dst[l].v[c] = base[l * lstep + off + c];
+        for (int c = 0; c < NC; c++) dst[l].v[c] = sbase[l * lstep + off + c];
       }
     }
   };
@@ -567,8 +572,8 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
     nfound += __popcll(m);
   };
 
-  // ring of the last three rows: horizontal 3-max/3-min of every level (centre included) and the raw centre values of
-  // the detection levels.  The 27-point maximum INCLUDING the pixel itself is all the test needs: r >= max(26
+  // ring of the last three rows: horizontal 3-max/3-min of every streamed level (centre included) and its raw centre
+  // values.  The 27-point maximum INCLUDING the pixel itself is all the test needs: r >= max(26
   // neighbours) <=> r >= max(27 values), the pixel being one of them -- so no left/right or above/below maxima that leave
   // the centre out (rounds 1-3 kept those: 24 more instructions per row and 36 more registers).
   float hmx[NLV][3][NC], hmn[NLV][3][NC];
@@ -584,7 +589,7 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
         const float a = cur[l].v[c];
         hmx[l][slot][c] = max3f(left, a, right);
         hmn[l][slot][c] = min3f(left, a, right);
-        if (l >= 1 && l <= DOG) rc[l - 1][slot][c] = a;
+        rc[l][slot][c] = a;
       }
     }
   };
@@ -624,10 +629,12 @@ __global__ __launch_bounds__(256) void extrema_stream_kernel(Geom g, DetectParam
           for (int li = 0; li < DOG; li++)
 #pragma unroll
             for (int c = 0; c < NC; c++) {
-              const int l = li + 1;
+              // the streamed levels among li - 1 .. li + 1 (r itself among the values: it is never NaN here, so neither
+              // is the maximum, and a maximum over fewer of the 27 values can only be smaller)
+              const int lo = li > 0 ? li - 1 : li, hi = li < DOG - 1 ? li + 1 : li;
               const float r = rc[li][sc][c];
-              const float nx = max3f(m9x[l - 1][c], m9x[l][c], m9x[l + 1][c]);  // over all 27, r itself among them
-              const float nn = min3f(m9n[l - 1][c], m9n[l][c], m9n[l + 1][c]);
+              const float nx = max3f(m9x[lo][c], m9x[li][c], m9x[hi][c]);
+              const float nn = min3f(m9n[lo][c], m9n[li][c], m9n[hi][c]);
               const bool f = cv[c] & (fabsf(r) > dp.thr0) & ((r >= nx) | (r <= nn));
               cand |= f ? (1u << (li * NC + c)) : 0u;
             }
