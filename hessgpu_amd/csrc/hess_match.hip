@@ -16,8 +16,14 @@
 //   match_dot_kernel       64x64 tile of the dot-product matrix per workgroup, descriptor panels in LDS,
 //                          v_dot4_u32_u8, gates per pair, score matrix written for
 //   match_row_kernel       one wavefront per row over the matrix (same tie order), and match_col_kernel.
+// Many pairs of a bank per call (hess_matcher_match_pairs, no reference counterpart) --
+//   bank_build_kernel      sets padded to 256-row blocks, float sources quantised, score offsets from the byte sums;
+//   match_pairs_*          match_mfma_kernel's tile code and match_finish_kernel's merges over every pair of a chunk from
+//                          work tables, and the compaction of each pair's matches on the device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -270,18 +276,19 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
   return d;
 }
 
+// The work of one workgroup: row block `rb` of set 1 against column segment `sg` of set 2.  match_mfma_kernel runs it
+// for one pair (rb, sg = blockIdx), match_pairs_mfma_kernel for every pair of a chunk from a work table.
 template <bool COLS>
-__global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* des1, int num1, const uint8_t* des2, int num2,
-                                                         const int* rfix, const int* cfix, int nseg, int supers_per_seg,
-                                                         int nsuper, int3* cpart, int3* rstate) {
+__device__ __forceinline__ void mfma_block(const uint8_t* des1, int num1, const uint8_t* des2, int num2, const int* rfix,
+                                           const int* cfix, int nseg, int supers_per_seg, int nsuper, int3* cpart,
+                                           int3* rstate, unsigned rb, int sg) {
   __shared__ __attribute__((aligned(16))) uint8_t bufB[2][MM_SUPER * MM_PITCH];
   __shared__ int bufC[2][MM_SUPER];
   __shared__ int3 cp[2][4][MM_SUPER];  // the four wavefronts' column partials of a super tile, merged after its barrier
   static_assert(sizeof(bufB) >= 4 * 32 * MM_RS_PITCH * 8, "the row-state exchange reuses the descriptor buffers");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int sg = blockIdx.y;
-  const int i0 = blockIdx.x * MM_ROWS + wv * 64;  // this wavefront's first row
+  const int i0 = rb * MM_ROWS + wv * 64;  // this wavefront's first row
   const int s0 = sg * supers_per_seg, s1 = min(s0 + supers_per_seg, nsuper);
   v4i a[2][4];
   v16i ra[2];
@@ -384,7 +391,7 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* des1, in
 #pragma unroll
       for (int w = 1; w < 4; w++) col_merge(t, cp[cur][w][tid]);
       const int j = sup * MM_SUPER + tid;
-      if (j < num2) cpart[(size_t)blockIdx.x * num2 + j] = t;
+      if (j < num2) cpart[(size_t)rb * num2 + j] = t;
     }
   }
   // ---- the 32 classes of every row -> one state per row and segment, through LDS (the descriptor buffers are free) ----
@@ -422,18 +429,19 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* des1, in
   }
 }
 
+template <bool COLS>
+__global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* des1, int num1, const uint8_t* des2, int num2,
+                                                         const int* rfix, const int* cfix, int nseg, int supers_per_seg,
+                                                         int nsuper, int3* cpart, int3* rstate) {
+  mfma_block<COLS>(des1, num1, des2, num2, rfix, cfix, nseg, supers_per_seg, nsuper, cpart, rstate, blockIdx.x, blockIdx.y);
+}
+
 // Rows: merge the per-segment states in the reference's order -- largest score; equal scores: the lower thread class
 // (column mod 32: the tree keeps the lower thread), then the lower column (a thread keeps its first maximum).
 // ... and, in the same launch, the columns (match_col_block) -- workgroups [0, row_blocks) take rows, the rest columns
 // (a launch of its own for either costs more than its work: 5 us each at 8192 x 8192).
-__global__ __launch_bounds__(256) void match_finish_kernel(const int3* rstate, int num1, int nseg, int row_blocks,
-                                                           const int3* cpart, int ntile, int num2, float distmax,
-                                                           float ratiomax, int* rowm, int* colm) {
-  if ((int)blockIdx.x >= row_blocks) {  // (workgroup-uniform)
-    match_col_block(blockIdx.x - row_blocks, cpart, ntile, num2, distmax, ratiomax, colm);
-    return;
-  }
-  const int row = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void finish_row(const int3* rstate, int num1, int nseg, int row, float distmax, float ratiomax,
+                                           int* rowm) {
   if (row >= num1) return;
   const int3* p = rstate + (size_t)row * nseg;
   int3 s = p[0];
@@ -445,6 +453,125 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const int3* rstate, i
     if (take) { s.x = u.x; s.z = u.z; }
   }
   rowm[row] = decide(s.x, s.y, s.z, distmax, ratiomax);
+}
+
+__global__ __launch_bounds__(256) void match_finish_kernel(const int3* rstate, int num1, int nseg, int row_blocks,
+                                                           const int3* cpart, int ntile, int num2, float distmax,
+                                                           float ratiomax, int* rowm, int* colm) {
+  if ((int)blockIdx.x >= row_blocks) {  // (workgroup-uniform)
+    match_col_block(blockIdx.x - row_blocks, cpart, ntile, num2, distmax, ratiomax, colm);
+    return;
+  }
+  finish_row(rstate, num1, nseg, blockIdx.x * 256 + threadIdx.x, distmax, ratiomax, rowm);
+}
+
+// ---- many pairs of a bank per call (hess_matcher_match_pairs) ------------------------------------------------------
+// A bank holds N descriptor sets back to back on the device, each padded with zero descriptors to whole 256-row blocks,
+// with the score offsets of both sides.  The pairs of a call run in chunks; a chunk is three launches: the multiply of
+// every (pair, row block, column segment) from one work table, the row and column decisions of every pair from a second,
+// and the compaction of every pair's matches.
+
+// Bank build: 8 descriptors per workgroup, 32 lanes x 4 bytes each.  sets[s] = (first padded row, first source row, rows)
+// in ascending padded rows; padded rows past a set's count are zero.  Float sources are quantised as the host does,
+// (unsigned char)(int)(512 * d + 0.5) -- the product in float, the sum in double, truncation, the low byte.
+template <bool F32>
+__global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const int3* sets, int nsets, int total,
+                                                         uint8_t* bank, int* rfix, int* cfix) {
+  const int g = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
+  if (g >= total) return;  // (uniform over the 32 lanes of a descriptor)
+  int lo = 0, hi = nsets - 1;  // the last set starting at or before g (empty sets share their successor's start)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sets[mid].x <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  const int3 S = sets[lo];
+  const int r = g - S.x;
+  uint32_t v = 0;
+  if (r < S.z) {
+    const size_t e = ((size_t)S.y + r) * KD + 4 * l;
+    if (F32) {
+      const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(src) + e);
+      const float q[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) v |= ((uint32_t)(int)((double)(512.0f * q[k]) + 0.5) & 255u) << (8 * k);
+    } else {
+      v = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + e);
+    }
+  }
+  *reinterpret_cast<uint32_t*>(bank + (size_t)g * KD + 4 * l) = v;
+  int sum = (int)(v & 255) + (int)((v >> 8) & 255) + (int)((v >> 16) & 255) + (int)(v >> 24);
+#pragma unroll
+  for (int d = 16; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 32);
+  if (l == 0) {  // score offsets of match_mfma_kernel: rows 128*sum - 128^2*128, columns 128*sum
+    cfix[g] = 128 * sum;
+    rfix[g] = 128 * sum - 128 * 128 * KD;
+  }
+}
+
+// One pair of a chunk.  a, b: first bank row of set 1 / set 2; rs, cp, rm, cm: offsets of its row states, column partials,
+// row and column decisions in the chunk's scratch.
+struct PairJob {
+  int a, b, n1, n2;
+  int nrb, nsuper, nseg, sps;
+  int rs, cp, rm, cm;
+  int pad[4];
+};
+
+// work[k] = (pair of the chunk, row block | segment << 16)
+template <bool COLS>
+__global__ __launch_bounds__(256) void match_pairs_mfma_kernel(const uint8_t* bank, const int* rfix, const int* cfix,
+                                                               const PairJob* jobs, const int2* work, int3* cpart,
+                                                               int3* rstate) {
+  const int2 w = work[blockIdx.x];
+  const PairJob& J = jobs[w.x];
+  mfma_block<COLS>(bank + (size_t)J.a * KD, J.n1, bank + (size_t)J.b * KD, J.n2, rfix + J.a, cfix + J.b, J.nseg, J.sps,
+                   J.nsuper, COLS ? cpart + J.cp : nullptr, rstate + J.rs, (unsigned)(w.y & 0xffff), w.y >> 16);
+}
+
+// work[k] = (pair of the chunk, block): blocks [0, row blocks of the pair) take its rows, the rest its columns
+__global__ __launch_bounds__(256) void match_pairs_finish_kernel(const PairJob* jobs, const int2* work,
+                                                                 const int3* rstate, const int3* cpart, float distmax,
+                                                                 float ratiomax, int* rowm, int* colm) {
+  const int2 w = work[blockIdx.x];
+  const PairJob& J = jobs[w.x];
+  const int row_blocks = (J.n1 + 255) / 256;
+  if (w.y >= row_blocks) {  // (workgroup-uniform)
+    match_col_block(w.y - row_blocks, cpart + J.cp, J.nrb, J.n2, distmax, ratiomax, colm + J.cm);
+    return;
+  }
+  finish_row(rstate + J.rs, J.n1, J.nseg, w.y * 256 + threadIdx.x, distmax, ratiomax, rowm + J.rm);
+}
+
+// One workgroup per pair: the rows i in ascending order with rowm[i] >= 0 (and, for mutual best, colm[rowm[i]] == i),
+// the first max_match of them.  out: [MP_PAIRS] counts, then [pair][max_match][2].
+__global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob* jobs, const int* rowm, const int* colm,
+                                                                  int mutual_best, int max_match, int* counts,
+                                                                  int* pairs) {
+  __shared__ int wsum[4];
+  const PairJob& J = jobs[blockIdx.x];
+  const int* rm = rowm + J.rm;
+  const int* cm = colm + J.cm;
+  int* out = pairs + (size_t)blockIdx.x * max_match * 2;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int n = 0;
+  for (int base = 0; base < J.n1 && n < max_match; base += 256) {
+    const int i = base + tid;
+    int j = -1;
+    if (i < J.n1) {
+      j = rm[i];
+      if (j >= J.n2 || (j >= 0 && mutual_best && cm[j] != i)) j = -1;
+    }
+    const unsigned long long bal = __ballot(j >= 0);
+    if (lane == 0) wsum[wv] = __popcll(bal);
+    __syncthreads();
+    int pos = n + __popcll(bal & ((1ull << lane) - 1));
+    for (int k = 0; k < wv; k++) pos += wsum[k];
+    if (j >= 0 && pos < max_match) { out[2 * pos] = i; out[2 * pos + 1] = j; }
+    n += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+  }
+  if (tid == 0) counts[blockIdx.x] = min(n, max_match);
 }
 
 }  // namespace
@@ -467,7 +594,26 @@ struct hess_matcher {
   std::string err;
   float last_ms = 0.0f;
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  // bank (hess_matcher_bank_*): sets back to back, each padded to whole 256-row blocks; score offsets of both sides
+  uint8_t* bank = nullptr;
+  int *bank_rfix = nullptr, *bank_cfix = nullptr;
+  std::vector<int> bank_off, bank_num;  // first padded row and stored descriptors of each set
+  // match_pairs: per-chunk scratch on the device, the chunk's plan and results through two pinned host slots
+  int3 *mp_rstate = nullptr, *mp_cpart = nullptr;
+  int *mp_rowm = nullptr, *mp_colm = nullptr, *mp_out = nullptr;
+  uint8_t* mp_plan = nullptr;
+  size_t mp_rs_cap = 0, mp_cp_cap = 0, mp_rm_cap = 0, mp_cm_cap = 0, mp_out_cap = 0, mp_plan_cap = 0;
+  uint8_t* mp_hplan[2] = {nullptr, nullptr};
+  int* mp_hout[2] = {nullptr, nullptr};
+  size_t mp_hplan_cap = 0, mp_hout_cap = 0;
+  hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
 };
+
+// Pairs of one match_pairs chunk, and the device scratch one chunk may use (row states n1 x nseg and, for mutual best,
+// column partials nrb x n2 per pair, then row and column decisions).  A pair whose scratch alone exceeds the budget is
+// a chunk of its own.
+constexpr int MP_PAIRS = 64;
+constexpr size_t MP_SCRATCH = (size_t)256 << 20;
 
 #define M_TRY(m, expr)                                                                       \
   do {                                                                                       \
@@ -505,6 +651,14 @@ void hess_matcher_destroy(hess_matcher* m) {
   for (int k = 0; k < 2; k++) { (void)hipFree(m->des[k]); (void)hipFree(m->loc[k]); }
   (void)hipFree(m->cpart); (void)hipFree(m->dotm); (void)hipFree(m->rowm); (void)hipFree(m->colm);
   (void)hipFree(m->fix[0]); (void)hipFree(m->fix[1]); (void)hipFree(m->cpart2); (void)hipFree(m->rstate);
+  (void)hipFree(m->bank); (void)hipFree(m->bank_rfix);
+  (void)hipFree(m->mp_rstate); (void)hipFree(m->mp_cpart); (void)hipFree(m->mp_rowm); (void)hipFree(m->mp_colm);
+  (void)hipFree(m->mp_out); (void)hipFree(m->mp_plan);
+  for (int k = 0; k < 2; k++) {
+    (void)hipHostFree(m->mp_hplan[k]); (void)hipHostFree(m->mp_hout[k]);
+    for (int q = 0; q < 3; q++)
+      if (m->mp_ev[k][q]) (void)hipEventDestroy(m->mp_ev[k][q]);
+  }
   if (m->e0) (void)hipEventDestroy(m->e0);
   if (m->e1) (void)hipEventDestroy(m->e1);
   if (m->st) (void)hipStreamDestroy(m->st);
@@ -671,6 +825,379 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
     }
   }
   return nmatch;
+}
+
+// ---- bank of descriptor sets, many pairs per call --------------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+template <class T>
+hipError_t grow_device(T*& p, size_t& cap, size_t n) {
+  if (n <= cap) return hipSuccess;
+  (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const hipError_t e = hipMalloc(&p, n * sizeof(T));
+  if (e == hipSuccess) cap = n;
+  return e;
+}
+
+template <class T>
+hipError_t grow_pinned(T* (&p)[2], size_t& cap, size_t n) {
+  if (n <= cap) return hipSuccess;
+  for (int k = 0; k < 2; k++) { (void)hipHostFree(p[k]); p[k] = nullptr; }
+  cap = 0;
+  for (int k = 0; k < 2; k++) {
+    const hipError_t e = hipHostMalloc(&p[k], n * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) return e;
+  }
+  cap = n;
+  return hipSuccess;
+}
+
+void bank_clear(hess_matcher* m) {
+  (void)hipFree(m->bank);
+  (void)hipFree(m->bank_rfix);
+  m->bank = nullptr;
+  m->bank_rfix = m->bank_cfix = nullptr;
+  m->bank_off.clear();
+  m->bank_num.clear();
+}
+
+// The bank from `src` (device memory, u8 or f32 [sum of counts][128]): set s is counts[s] rows, of which the first
+// max_sift are kept (SetDescriptors).  Returns after the bank is built.
+int bank_build(hess_matcher* m, int nsets, const int* counts, const void* src, bool f32) {
+  std::vector<int3> sets((size_t)nsets);
+  std::vector<int> off((size_t)nsets), num((size_t)nsets);
+  size_t padded = 0, srow = 0;
+  for (int s = 0; s < nsets; s++) {
+    const int n = counts[s] > m->max_sift ? m->max_sift : counts[s];
+    off[s] = (int)padded;
+    num[s] = n;
+    sets[s] = make_int3((int)padded, (int)srow, n);
+    padded += ((size_t)n + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+    srow += (size_t)counts[s];
+    if (padded > (size_t)INT32_MAX / KD || srow > (size_t)INT32_MAX) {
+      m->err = "bank too large";
+      return HESS_ERR_TOO_BIG;
+    }
+  }
+  if (padded) {
+    M_TRY(m, hipMalloc(&m->bank, padded * KD));
+    M_TRY(m, hipMalloc(&m->bank_rfix, 2 * padded * sizeof(int)));
+    m->bank_cfix = m->bank_rfix + padded;
+    int3* dsets = nullptr;
+    M_TRY(m, hipMalloc(&dsets, sets.size() * sizeof(int3)));
+    hipError_t e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
+    if (e == hipSuccess) {
+      const dim3 grid((unsigned)((padded + 7) / 8));
+      if (f32)
+        hipLaunchKernelGGL(bank_build_kernel<true>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, m->bank,
+                           m->bank_rfix, m->bank_cfix);
+      else
+        hipLaunchKernelGGL(bank_build_kernel<false>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, m->bank,
+                           m->bank_rfix, m->bank_cfix);
+      e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(m->st);
+    (void)hipFree(dsets);
+    M_TRY(m, e);
+    M_TRY(m, es);
+  }
+  m->bank_off.swap(off);
+  m->bank_num.swap(num);
+  return 0;
+}
+
+int bank_args(hess_matcher* m, int nsets, const int* counts, const void* des, size_t* rows) {
+  if (!m) return HESS_ERR_ARG;
+  if (nsets < 0 || (nsets > 0 && !counts)) { m->err = "bank: nsets < 0 or counts NULL"; return HESS_ERR_ARG; }
+  size_t t = 0;
+  for (int s = 0; s < nsets; s++) {
+    if (counts[s] < 0) { m->err = "bank: negative count for set " + std::to_string(s); return HESS_ERR_ARG; }
+    t += (size_t)counts[s];
+  }
+  if (t && !des) { m->err = "bank: descriptors NULL"; return HESS_ERR_ARG; }
+  *rows = t;
+  return 0;
+}
+
+// One chunk of a match_pairs call: pairs [p0, p1), the segment length of its multiply, its scratch and work tables.
+struct MpChunk {
+  int p0, p1, sps;
+  size_t rs, cp, rm, cm, nwg, nfin;
+};
+
+}  // namespace
+
+extern "C" {
+
+int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const unsigned char* des) {
+  size_t rows = 0;
+  if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  bank_clear(m);
+  uint8_t* staging = nullptr;
+  if (rows) {
+    M_TRY(m, hipMalloc(&staging, rows * KD));
+    const hipError_t e = hipMemcpy(staging, des, rows * KD, hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)hipFree(staging);
+    M_TRY(m, e);
+  }
+  const int rc = bank_build(m, nsets, counts, staging, false);
+  (void)hipFree(staging);
+  if (rc) bank_clear(m);
+  return rc;
+}
+
+// Host floats: quantised on the host as hess_matcher_set_descriptors_f32 does, then the byte path.
+int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, const float* des) {
+  size_t rows = 0;
+  if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
+  std::vector<int> kept((size_t)nsets);
+  size_t nk = 0;
+  for (int s = 0; s < nsets; s++) nk += (size_t)(kept[s] = counts[s] > m->max_sift ? m->max_sift : counts[s]);
+  std::vector<unsigned char> q(nk * KD);
+  size_t src = 0, dst = 0;
+  for (int s = 0; s < nsets; s++) {
+    for (size_t i = 0; i < (size_t)kept[s] * KD; ++i) q[dst + i] = (unsigned char)(int)(512 * des[src + i] + 0.5);
+    src += (size_t)counts[s] * KD;
+    dst += (size_t)kept[s] * KD;
+  }
+  return hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
+}
+
+int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, const float* dev_desc) {
+  size_t rows = 0;
+  if (const int rc = bank_args(m, nsets, counts, dev_desc, &rows)) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  if (rows) {
+    if ((uintptr_t)dev_desc % 16) { m->err = "bank_set_device: the descriptors must be 16-byte aligned"; return HESS_ERR_ARG; }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, dev_desc);
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != m->device) {
+      (void)hipGetLastError();
+      m->err = "bank_set_device: the descriptors are not device memory of device " + std::to_string(m->device);
+      return HESS_ERR_ARG;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_desc) != hipSuccess ||
+        (const char*)dev_desc + rows * KD * sizeof(float) > (const char*)base + size) {
+      (void)hipGetLastError();
+      m->err = "bank_set_device: the counts reach past the end of the descriptors' allocation";
+      return HESS_ERR_ARG;
+    }
+    (void)hipGetLastError();
+  }
+  bank_clear(m);
+  const int rc = bank_build(m, nsets, counts, dev_desc, true);
+  if (rc) bank_clear(m);
+  return rc;
+}
+
+int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
+  if (!m) return HESS_ERR_ARG;
+  if (set < 0 || set >= (int)m->bank_num.size()) {
+    m->err = "bank_read: no set " + std::to_string(set) + " in a bank of " + std::to_string(m->bank_num.size());
+    return HESS_ERR_ARG;
+  }
+  const int n = m->bank_num[set];
+  if (out && n) {
+    M_TRY(m, hipSetDevice(m->device));
+    M_TRY(m, hipMemcpy(out, m->bank + (size_t)m->bank_off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
+  }
+  return n;
+}
+
+int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
+                             int* out_counts, float distmax, float ratiomax, int mutual_best) {
+  if (!m) return HESS_ERR_ARG;
+  if (npairs < 0 || max_match < 0 || (npairs > 0 && (!pairs_ab || !out_counts || (max_match > 0 && !out_pairs)))) {
+    m->err = "match_pairs: npairs or max_match < 0, or an array is NULL";
+    return HESS_ERR_ARG;
+  }
+  const int nsets = (int)m->bank_num.size();
+  for (int p = 0; p < npairs; p++)
+    if (pairs_ab[2 * p] < 0 || pairs_ab[2 * p] >= nsets || pairs_ab[2 * p + 1] < 0 || pairs_ab[2 * p + 1] >= nsets) {
+      m->err = "match_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
+      return HESS_ERR_ARG;
+    }
+  m->last_ms = 0.0f;
+  if (npairs == 0) return 0;
+  M_TRY(m, hipSetDevice(m->device));
+  mutual_best = mutual_best ? 1 : 0;
+
+  // a pair with an empty side has no work and no matches
+  auto sides = [&](int p, int& n1, int& n2) {
+    n1 = m->bank_num[pairs_ab[2 * p]];
+    n2 = m->bank_num[pairs_ab[2 * p + 1]];
+    if (n1 == 0 || n2 == 0) n1 = n2 = 0;
+  };
+  // Segments per pair from the whole chunk's grid: whole rounds of workgroups over the 256 CUs as in hess_matcher_match
+  // (two per CU when that leaves each at least four super tiles), at most MM_MAX_TILES / 4 super tiles per segment.
+  auto chunk_sps = [](size_t work) {
+    const size_t target = work >= 512 * 4 ? 512 : 256;
+    const size_t sps = (work + target - 1) / target;
+    return sps < 1 ? 1 : (sps > MM_MAX_TILES / 4 ? MM_MAX_TILES / 4 : (int)sps);
+  };
+  auto pair_seg = [](int nsuper, int sps, int& nseg, int& psps) {
+    nseg = (nsuper + sps - 1) / sps;
+    psps = (nsuper + nseg - 1) / nseg;
+    nseg = (nsuper + psps - 1) / psps;
+  };
+  auto measure = [&](MpChunk& c) {
+    c.rs = c.cp = c.rm = c.cm = c.nwg = c.nfin = 0;
+    for (int p = c.p0; p < c.p1; p++) {
+      int n1, n2;
+      sides(p, n1, n2);
+      if (!n1) continue;
+      const int nrb = (n1 + MM_ROWS - 1) / MM_ROWS, nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
+      int nseg, psps;
+      pair_seg(nsuper, c.sps, nseg, psps);
+      c.rs += (size_t)n1 * nseg;
+      c.cp += mutual_best ? (size_t)nrb * n2 : 0;
+      c.rm += n1;
+      c.cm += mutual_best ? n2 : 0;
+      c.nwg += (size_t)nrb * nseg;
+      c.nfin += (n1 + 255) / 256 + (mutual_best ? (n2 + 31) / 32 : 0);
+    }
+    return sizeof(int3) * (c.rs + c.cp) + sizeof(int) * (c.rm + c.cm);
+  };
+  std::vector<MpChunk> chunks;
+  int mm = 0;  // matches kept per pair: max_match, at most the rows of its set 1
+  for (int p0 = 0; p0 < npairs;) {
+    MpChunk c{p0, p0, 1, 0, 0, 0, 0, 0, 0};
+    size_t work = 0;
+    while (c.p1 < npairs && c.p1 - p0 < MP_PAIRS) {
+      int n1, n2;
+      sides(c.p1, n1, n2);
+      const size_t w = n1 ? (size_t)((n1 + MM_ROWS - 1) / MM_ROWS) * ((n2 + MM_SUPER - 1) / MM_SUPER) : 0;
+      MpChunk t = c;
+      t.p1++;
+      t.sps = chunk_sps(work + w);
+      if (c.p1 > p0 && measure(t) > MP_SCRATCH) break;
+      c = t;
+      work += w;
+      mm = std::max(mm, std::min(n1, max_match));
+    }
+    measure(c);
+    if (c.rs + c.cp > (size_t)INT32_MAX || c.nwg > (size_t)INT32_MAX) {
+      m->err = "match_pairs: a pair needs more scratch than one launch can address";
+      return HESS_ERR_TOO_BIG;
+    }
+    chunks.push_back(c);
+    p0 = c.p1;
+  }
+  size_t rs = 1, cp = 1, rm = 1, cm = 1, plan = 0, outn = 0;
+  for (const MpChunk& c : chunks) {
+    rs = std::max(rs, c.rs); cp = std::max(cp, c.cp); rm = std::max(rm, c.rm); cm = std::max(cm, c.cm);
+    plan = std::max(plan, (size_t)(c.p1 - c.p0) * sizeof(PairJob) + (c.nwg + c.nfin) * sizeof(int2));
+    outn = std::max(outn, (size_t)MP_PAIRS + (size_t)(c.p1 - c.p0) * mm * 2);
+  }
+  M_TRY(m, grow_device(m->mp_rstate, m->mp_rs_cap, rs));
+  M_TRY(m, grow_device(m->mp_cpart, m->mp_cp_cap, cp));
+  M_TRY(m, grow_device(m->mp_rowm, m->mp_rm_cap, rm));
+  M_TRY(m, grow_device(m->mp_colm, m->mp_cm_cap, cm));
+  M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, outn));
+  M_TRY(m, grow_device(m->mp_plan, m->mp_plan_cap, plan));
+  M_TRY(m, grow_pinned(m->mp_hplan, m->mp_hplan_cap, plan));
+  M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, outn));
+  for (int k = 0; k < 2; k++)
+    for (int q = 0; q < 3; q++)
+      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
+
+  // chunk k is enqueued into slot k & 1; its results are read on the host while chunk k + 1 runs
+  float total_ms = 0.0f;
+  auto collect = [&](size_t k) -> hipError_t {
+    const MpChunk& c = chunks[k];
+    hipEvent_t* ev = m->mp_ev[k & 1];
+    hipError_t e = hipEventSynchronize(ev[2]);
+    if (e != hipSuccess) return e;
+    float ms = 0.0f;
+    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e != hipSuccess) return e;
+    total_ms += ms;
+    const int* h = m->mp_hout[k & 1];
+    for (int p = c.p0; p < c.p1; p++) {
+      const int n = h[p - c.p0];
+      out_counts[p] = n;
+      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - c.p0) * mm * 2, (size_t)n * 2 * sizeof(int));
+    }
+    return hipSuccess;
+  };
+  hipError_t err = hipSuccess;
+  for (size_t k = 0; k < chunks.size() && err == hipSuccess; k++) {
+    const MpChunk& c = chunks[k];
+    const int np = c.p1 - c.p0;
+    // the plan: jobs, then the multiply's work table, then the finish's
+    uint8_t* hp = m->mp_hplan[k & 1];
+    PairJob* jobs = reinterpret_cast<PairJob*>(hp);
+    int2* work = reinterpret_cast<int2*>(hp + np * sizeof(PairJob));
+    int2* fin = work + c.nwg;
+    size_t o_rs = 0, o_cp = 0, o_rm = 0, o_cm = 0, iw = 0, jf = 0;
+    for (int p = c.p0; p < c.p1; p++) {
+      PairJob& J = jobs[p - c.p0];
+      memset(&J, 0, sizeof(J));
+      int n1, n2;
+      sides(p, n1, n2);
+      J.a = m->bank_off[pairs_ab[2 * p]];
+      J.b = m->bank_off[pairs_ab[2 * p + 1]];
+      J.n1 = n1;
+      J.n2 = n2;
+      if (!n1) continue;
+      J.nrb = (n1 + MM_ROWS - 1) / MM_ROWS;
+      J.nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
+      pair_seg(J.nsuper, c.sps, J.nseg, J.sps);
+      J.rs = (int)o_rs; J.cp = (int)o_cp; J.rm = (int)o_rm; J.cm = (int)o_cm;
+      o_rs += (size_t)n1 * J.nseg;
+      o_cp += mutual_best ? (size_t)J.nrb * n2 : 0;
+      o_rm += n1;
+      o_cm += mutual_best ? n2 : 0;
+      for (int sg = 0; sg < J.nseg; sg++)
+        for (int rb = 0; rb < J.nrb; rb++) work[iw++] = make_int2(p - c.p0, rb | sg << 16);
+      const int nfb = (n1 + 255) / 256 + (mutual_best ? (n2 + 31) / 32 : 0);
+      for (int b = 0; b < nfb; b++) fin[jf++] = make_int2(p - c.p0, b);
+    }
+    const size_t plan_bytes = np * sizeof(PairJob) + (c.nwg + c.nfin) * sizeof(int2);
+    const PairJob* djobs = reinterpret_cast<const PairJob*>(m->mp_plan);
+    const int2* dwork = reinterpret_cast<const int2*>(m->mp_plan + np * sizeof(PairJob));
+    hipEvent_t* ev = m->mp_ev[k & 1];
+    err = hipMemcpyAsync(m->mp_plan, hp, plan_bytes, hipMemcpyHostToDevice, m->st);
+    if (err != hipSuccess) break;
+    (void)hipEventRecord(ev[0], m->st);
+    if (c.nwg) {
+      if (mutual_best)
+        hipLaunchKernelGGL(match_pairs_mfma_kernel<true>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, m->bank, m->bank_rfix,
+                           m->bank_cfix, djobs, dwork, m->mp_cpart, m->mp_rstate);
+      else
+        hipLaunchKernelGGL(match_pairs_mfma_kernel<false>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, m->bank,
+                           m->bank_rfix, m->bank_cfix, djobs, dwork, m->mp_cpart, m->mp_rstate);
+      hipLaunchKernelGGL(match_pairs_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, dwork + c.nwg,
+                         m->mp_rstate, m->mp_cpart, distmax, ratiomax, m->mp_rowm, m->mp_colm);
+    }
+    hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, djobs, m->mp_rowm, m->mp_colm,
+                       mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    (void)hipEventRecord(ev[1], m->st);
+    err = hipGetLastError();
+    if (err != hipSuccess) break;
+    err = hipMemcpyAsync(m->mp_hout[k & 1], m->mp_out, (MP_PAIRS + (size_t)np * mm * 2) * sizeof(int), hipMemcpyDeviceToHost,
+                         m->st);
+    if (err != hipSuccess) break;
+    (void)hipEventRecord(ev[2], m->st);
+    if (k > 0) err = collect(k - 1);
+  }
+  if (err == hipSuccess) err = collect(chunks.size() - 1);
+  if (err != hipSuccess) {
+    (void)hipStreamSynchronize(m->st);
+    m->err = std::string("match_pairs: ") + hipGetErrorString(err);
+    return HESS_ERR_DEVICE;
+  }
+  m->last_ms = total_ms;
+  return 0;
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }

@@ -24,12 +24,44 @@ def _lib():
         L.hess_matcher_set_locations.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.hess_matcher_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                          C.c_float, C.c_float, C.c_float, C.c_int]
+        L.hess_matcher_bank_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hess_matcher_bank_set_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hess_matcher_bank_set_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hess_matcher_bank_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.hess_matcher_match_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_float, C.c_float, C.c_int]
         L.hess_matcher_last_ms.restype = C.c_float
         L.hess_matcher_last_ms.argtypes = [C.c_void_p]
         L.hess_matcher_last_error.restype = C.c_char_p
         L.hess_matcher_last_error.argtypes = [C.c_void_p]
         _bound = True
     return L
+
+
+def all_pairs(n):
+    """Every pair (i, j), i < j, of n sets: [n (n - 1) / 2, 2] int32."""
+    i, j = np.triu_indices(int(n), 1)
+    return np.stack([i, j], 1).astype(np.int32)
+
+
+def window_pairs(n, w):
+    """Every pair (i, j) of n sets with i < j <= i + w (a sequence matched against its w successors)."""
+    out = [(i, j) for i in range(int(n)) for j in range(i + 1, min(int(n), i + int(w) + 1))]
+    return np.array(out, dtype=np.int32).reshape(-1, 2)
+
+
+def check_pairs(pairs):
+    """-> C-contiguous int32 [n, 2] of (a, b) bank indices; ValueError for a wrong shape or dtype or a negative index."""
+    a = np.asarray(pairs)
+    if a.size == 0 and a.ndim <= 2 and (a.ndim < 2 or a.shape[1] in (0, 2)):
+        return np.zeros((0, 2), dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"pairs must have shape [n, 2], not {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"pairs must be integers, not {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() > np.iinfo(np.int32).max):
+        raise ValueError("pair indices must lie in 0 .. 2^31 - 1")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 class Matcher:
@@ -80,3 +112,59 @@ class Matcher:
 
     def last_ms(self):
         return float(self.L.hess_matcher_last_ms(self.h))
+
+    # ---- bank of descriptor sets on the device, many pairs per call ----
+    def set_bank(self, sets):
+        """sets: a list of [n_i, 128] arrays, all u8 (stored as they are) or all float (quantised like
+        set_descriptors)."""
+        sets = [np.asarray(d) for d in sets]
+        for d in sets:
+            if d.ndim != 2 or d.shape[1] != 128:
+                raise ValueError(f"a bank set must be [n, 128], not {d.shape}")
+        counts = np.array([len(d) for d in sets], dtype=np.int32)
+        u8 = all(d.dtype == np.uint8 for d in sets)
+        dt = np.uint8 if u8 else np.float32
+        flat = np.ascontiguousarray(np.concatenate(sets).astype(dt, copy=False) if sets else np.zeros((0, 128), dt))
+        fn = self.L.hess_matcher_bank_set if u8 else self.L.hess_matcher_bank_set_f32
+        self._check(fn(self.h, len(counts), counts.ctypes.data, flat.ctypes.data if flat.size else None))
+        self._bank_sets = len(counts)
+
+    def set_bank_device(self, ptr, counts):
+        """ptr: device address of float [sum(counts)][128] on the matcher's device (quantised on the device).  The
+        producer must have finished writing it."""
+        c = np.ascontiguousarray(counts, dtype=np.int32)
+        self._check(self.L.hess_matcher_bank_set_device(self.h, len(c), c.ctypes.data, ptr))
+        self._bank_sets = len(c)
+
+    def set_bank_from_session(self, session):
+        """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,
+        without leaving the device."""
+        dim = session.desc_dim()
+        if dim != 128:
+            raise ValueError(f"the matcher takes 128-d descriptors; this context's are {dim}-d (-half / -sd)")
+        _, desc, total = session.device_results()
+        counts = [session.count(i) for i in range(session._batch)]
+        if sum(counts) != total:
+            raise ValueError(f"the context's counts ({sum(counts)}) do not cover its device results ({total})")
+        self.set_bank_device(desc, counts)
+
+    def bank(self, i):
+        """The stored bytes of set i: [n, 128] u8."""
+        n = self._check(self.L.hess_matcher_bank_read(self.h, int(i), None))
+        out = np.zeros((n, 128), dtype=np.uint8)
+        if n:
+            self._check(self.L.hess_matcher_bank_read(self.h, int(i), out.ctypes.data))
+        return out
+
+    def match_pairs(self, pairs, max_match=4096, distmax=0.7, ratiomax=0.8, mutual_best=True):
+        """Unguided match of bank[a] against bank[b] for every (a, b) in pairs -> list of [k, 2] int32 arrays, each what
+        set_descriptors(0, bank[a]), set_descriptors(1, bank[b]), match(max_match, ...) returns."""
+        p = check_pairs(pairs)
+        if max_match < 0:
+            raise ValueError("max_match must be >= 0")
+        n = len(p)
+        out = np.zeros((n, max(max_match, 1), 2), dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.L.hess_matcher_match_pairs(self.h, n, p.ctypes.data, max_match, out.ctypes.data, cnt.ctypes.data,
+                                                    distmax, ratiomax, int(mutual_best)))
+        return [out[k, :cnt[k]].copy() for k in range(n)]

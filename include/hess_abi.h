@@ -35,7 +35,9 @@ extern "C" {
  *    the interleaved order); hess_debug_keep_levels (the top Gaussian level of an octave is no longer written to HBM
  *    unless asked for); a context whose DMA copy was lost refuses further runs (HESS_ERR_DEVICE, "poisoned").
  * 5: hess_params.detector (word 0 of reserved[], which a version-2, -3 or -4 struct leaves zero: the Hessian detector):
- *    HESS_DETECTOR_DOG runs the difference-of-Gaussians detector of the reference's build without GPU_HESSIAN. */
+ *    HESS_DETECTOR_DOG runs the difference-of-Gaussians detector of the reference's build without GPU_HESSIAN.
+ *    hess_matcher_bank_set / _set_f32 / _set_device / _read and hess_matcher_match_pairs (added during version 5
+ *    without a bump). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -322,6 +324,27 @@ int hess_matcher_set_locations(hess_matcher* m, int index, const float* location
 /* GetSiftMatch (H = F = NULL) / GetGuidedSiftMatch; pairs: max_match x 2 ints; returns #matches. */
 int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* H, const float* F,
                        float distmax, float ratiomax, float hdistmax, float fdistmax, int mutual_best);
+
+/* Batched matching (no reference counterpart): a BANK of descriptor sets stays on the device and one call matches a
+ * list of (a, b) pairs of it.  Independent of the two single-pair slots above.  Loading a bank replaces the previous
+ * one; each set is truncated to max_sift as hess_matcher_set_descriptors does (at load time).  128-d descriptors only.
+ * counts[s]: descriptors of set s; the sets lie back to back in `des` (u8 or host floats, quantised as _f32 does). */
+int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const unsigned char* des);
+int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, const float* des);
+/* dev_desc: float [sum of counts][128] in device memory of the matcher's device -- e.g. what hess_device_results hands
+ * out, with counts from hess_count.  Quantised on the device, bit-identical to the host conversion.  The caller must have
+ * waited for the run that produced the descriptors (hess_wait / hess_run_*); the call returns when the bank is built,
+ * so the context's next run may start at once.  A pointer that is not device memory of that device: HESS_ERR_ARG. */
+int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, const float* dev_desc);
+/* The stored bytes of set `set` (its count x 128; out may be NULL).  Returns the count. */
+int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out);
+/* Unguided GetSiftMatch for every pair p: set 1 = bank[pairs_ab[2p]], set 2 = bank[pairs_ab[2p+1]].  Pair p's result is
+ * what hess_matcher_match(max_match, H = F = NULL, distmax, ratiomax, mutual_best) returns for those two sets:
+ * out_counts[p] matches in out_pairs[p][0 .. out_counts[p]) of the caller's [npairs][max_match][2] ints.  Pairs may
+ * repeat, be reversed or (a, a).  A set index outside the bank: HESS_ERR_ARG, nothing launched.  Returns 0 or a
+ * negative hess_status; hess_matcher_last_ms: device time of all the call's kernels. */
+int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
+                             int* out_counts, float distmax, float ratiomax, int mutual_best);
 float hess_matcher_last_ms(hess_matcher* m);   /* device time of the last match's kernels */
 const char* hess_matcher_last_error(hess_matcher* m);
 
