@@ -3,23 +3,24 @@
 // Replaces SiftMatchCU (SiftMatchCU.cpp:71-176) and its kernels MultiplyDescriptor(_G)_Kernel,
 // RowMatch_Kernel, ColMatch_Kernel (ProgramCU.cu:3455-3843).  Integer work: results are bit-exact.
 //
-// Unguided match (GetSiftMatch): matrix cores, no score matrix in memory --
-//   match_mfma_kernel      one workgroup per (256-row block, column segment): the segment's descriptors of set 2 pass
-//                          through LDS once for its four wavefronts, each of which holds 64 rows of set 1 in registers and
-//                          folds the v_mfma_i32_32x32x32_i8 tiles into RowMatch_Kernel's per-thread states and the column
-//                          partials as packed 32-bit keys; see the comment at the kernel;
-//   match_finish_kernel    merges a row's per-segment states (largest score, then the reference's tie order: lower
-//                          thread class, lower column), acos distance + ratio;
-//                          and, in the same launch, the per-row-block (max, index, second) column partials in ascending
-//                          row order (match_col_kernel: the same for the small / guided path).
-// Guided match (GetGuidedSiftMatch: per-pair homography / fundamental-matrix gates, per-8-row-block rule) --
+// Descriptor sets (the user's bank, the two single-pair slots) --
+//   bank_build_kernel      sets padded to 256-row blocks, float sources quantised, score offsets from the byte sums.
+// Unguided match (GetSiftMatch), one pair or many pairs of a bank per call (hess_matcher_match_pairs, no reference
+// counterpart): matrix cores, no score matrix in memory --
+//   match_mfma_kernel      one workgroup per (pair, 256-row block, column segment) of a work table: the segment's
+//                          descriptors of set 2 pass through LDS once for its four wavefronts, each of which holds 64 rows
+//                          of set 1 in registers and folds the v_mfma_i32_32x32x32_i8 tiles into RowMatch_Kernel's
+//                          per-thread states and the column partials as packed 32-bit keys; see the comment at the kernel;
+//   match_finish_kernel    per (pair, block) of a second table: merges a row's per-segment states (largest score, then
+//                          the reference's tie order: lower thread class, lower column), acos distance + ratio; and, in
+//                          the same launch, the per-row-block (max, index, second) column partials in ascending row order
+//                          (match_col_kernel: the same for the small / guided path);
+//   match_pairs_compact_kernel  each pair's matches compacted on the device (a single pair is compacted on the host).
+// Small unguided match and guided match (GetGuidedSiftMatch: per-pair homography / fundamental-matrix gates,
+// per-8-row-block rule) --
 //   match_dot_kernel       64x64 tile of the dot-product matrix per workgroup, descriptor panels in LDS,
 //                          v_dot4_u32_u8, gates per pair, score matrix written for
 //   match_row_kernel       one wavefront per row over the matrix (same tie order), and match_col_kernel.
-// Many pairs of a bank per call (hess_matcher_match_pairs, no reference counterpart) --
-//   bank_build_kernel      sets padded to 256-row blocks, float sources quantised, score offsets from the byte sums;
-//   match_pairs_*          match_mfma_kernel's tile code and match_finish_kernel's merges over every pair of a chunk from
-//                          work tables, and the compaction of each pair's matches on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -276,20 +277,41 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
   return d;
 }
 
-// The work of one workgroup: row block `rb` of set 1 against column segment `sg` of set 2.  match_mfma_kernel runs it
-// for one pair (rb, sg = blockIdx), match_pairs_mfma_kernel for every pair of a chunk from a work table.
+// One pair of a launch.  a, b: first row of set 1 in the rows (and rfix) passed as set 1, of set 2 in those passed as set 2
+// -- the bank twice for a bank pair, the two single-pair slots (a = b = 0) for hess_matcher_match; rs, cp, rm, cm: offsets
+// of its row states, column partials, row and column decisions in the scratch.
+struct PairJob {
+  int a, b, n1, n2;
+  int nrb, nsuper, nseg, sps;
+  int rs, cp, rm, cm;
+  int pad[4];
+};
+
+// The work of one workgroup: work[blockIdx.x] = (job, rb | sg << 16), row block rb of the job's set 1 against its column
+// segment sg of set 2.
 template <bool COLS>
-__device__ __forceinline__ void mfma_block(const uint8_t* des1, int num1, const uint8_t* des2, int num2, const int* rfix,
-                                           const int* cfix, int nseg, int supers_per_seg, int nsuper, int3* cpart,
-                                           int3* rstate, unsigned rb, int sg) {
+__global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, const int* rfix, const uint8_t* rows2,
+                                                         const int* cfix, const PairJob* jobs, const int2* work,
+                                                         int3* cpart, int3* rstate) {
   __shared__ __attribute__((aligned(16))) uint8_t bufB[2][MM_SUPER * MM_PITCH];
   __shared__ int bufC[2][MM_SUPER];
   __shared__ int3 cp[2][4][MM_SUPER];  // the four wavefronts' column partials of a super tile, merged after its barrier
   static_assert(sizeof(bufB) >= 4 * 32 * MM_RS_PITCH * 8, "the row-state exchange reuses the descriptor buffers");
+  const int2 w = work[blockIdx.x];
+  const PairJob& J = jobs[w.x];
+  const unsigned rb = w.y & 0xffff;
+  const int sg = w.y >> 16;
+  const uint8_t* const des1 = rows1 + (size_t)J.a * KD;
+  const uint8_t* const des2 = rows2 + (size_t)J.b * KD;
+  const int num1 = J.n1, num2 = J.n2, nseg = J.nseg, nsuper = J.nsuper;
+  rfix += J.a;
+  cfix += J.b;
+  cpart += J.cp;
+  rstate += J.rs;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int i0 = rb * MM_ROWS + wv * 64;  // this wavefront's first row
-  const int s0 = sg * supers_per_seg, s1 = min(s0 + supers_per_seg, nsuper);
+  const int s0 = sg * J.sps, s1 = min(s0 + J.sps, nsuper);
   v4i a[2][4];
   v16i ra[2];
   {
@@ -429,51 +451,38 @@ __device__ __forceinline__ void mfma_block(const uint8_t* des1, int num1, const 
   }
 }
 
-template <bool COLS>
-__global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* des1, int num1, const uint8_t* des2, int num2,
-                                                         const int* rfix, const int* cfix, int nseg, int supers_per_seg,
-                                                         int nsuper, int3* cpart, int3* rstate) {
-  mfma_block<COLS>(des1, num1, des2, num2, rfix, cfix, nseg, supers_per_seg, nsuper, cpart, rstate, blockIdx.x, blockIdx.y);
-}
-
-// Rows: merge the per-segment states in the reference's order -- largest score; equal scores: the lower thread class
-// (column mod 32: the tree keeps the lower thread), then the lower column (a thread keeps its first maximum).
-// ... and, in the same launch, the columns (match_col_block) -- workgroups [0, row_blocks) take rows, the rest columns
-// (a launch of its own for either costs more than its work: 5 us each at 8192 x 8192).
-__device__ __forceinline__ void finish_row(const int3* rstate, int num1, int nseg, int row, float distmax, float ratiomax,
-                                           int* rowm) {
-  if (row >= num1) return;
-  const int3* p = rstate + (size_t)row * nseg;
+// Rows and columns of every pair of a launch: work[blockIdx.x] = (job, block); blocks [0, row blocks of the job) take its
+// rows, the rest its columns (match_col_block) -- a launch of its own for either costs more than its work: 5 us each at
+// 8192 x 8192.  Rows: merge the per-segment states in the reference's order -- largest score; equal scores: the lower
+// thread class (column mod 32: the tree keeps the lower thread), then the lower column (a thread keeps its first maximum).
+__global__ __launch_bounds__(256) void match_finish_kernel(const PairJob* jobs, const int2* work, const int3* rstate,
+                                                           const int3* cpart, float distmax, float ratiomax, int* rowm,
+                                                           int* colm) {
+  const int2 w = work[blockIdx.x];
+  const PairJob& J = jobs[w.x];
+  const int row_blocks = (J.n1 + 255) / 256;
+  if (w.y >= row_blocks) {  // (workgroup-uniform)
+    match_col_block(w.y - row_blocks, cpart + J.cp, J.nrb, J.n2, distmax, ratiomax, colm + J.cm);
+    return;
+  }
+  const int row = w.y * 256 + threadIdx.x;
+  if (row >= J.n1) return;
+  const int3* p = rstate + J.rs + (size_t)row * J.nseg;
   int3 s = p[0];
-  for (int q = 1; q < nseg; q++) {
+  for (int q = 1; q < J.nseg; q++) {
     const int3 u = p[q];
     const bool take = u.x > s.x || (u.x == s.x && u.z >= 0 &&
                                     (s.z < 0 || (u.z & 31) < (s.z & 31) || ((u.z & 31) == (s.z & 31) && u.z < s.z)));
     s.y = u.x > s.x ? max(s.x, u.y) : max(s.y, u.x);
     if (take) { s.x = u.x; s.z = u.z; }
   }
-  rowm[row] = decide(s.x, s.y, s.z, distmax, ratiomax);
+  rowm[J.rm + row] = decide(s.x, s.y, s.z, distmax, ratiomax);
 }
 
-__global__ __launch_bounds__(256) void match_finish_kernel(const int3* rstate, int num1, int nseg, int row_blocks,
-                                                           const int3* cpart, int ntile, int num2, float distmax,
-                                                           float ratiomax, int* rowm, int* colm) {
-  if ((int)blockIdx.x >= row_blocks) {  // (workgroup-uniform)
-    match_col_block(blockIdx.x - row_blocks, cpart, ntile, num2, distmax, ratiomax, colm);
-    return;
-  }
-  finish_row(rstate, num1, nseg, blockIdx.x * 256 + threadIdx.x, distmax, ratiomax, rowm);
-}
-
-// ---- many pairs of a bank per call (hess_matcher_match_pairs) ------------------------------------------------------
-// A bank holds N descriptor sets back to back on the device, each padded with zero descriptors to whole 256-row blocks,
-// with the score offsets of both sides.  The pairs of a call run in chunks; a chunk is three launches: the multiply of
-// every (pair, row block, column segment) from one work table, the row and column decisions of every pair from a second,
-// and the compaction of every pair's matches.
-
-// Bank build: 8 descriptors per workgroup, 32 lanes x 4 bytes each.  sets[s] = (first padded row, first source row, rows)
-// in ascending padded rows; padded rows past a set's count are zero.  Float sources are quantised as the host does,
-// (unsigned char)(int)(512 * d + 0.5) -- the product in float, the sum in double, truncation, the low byte.
+// Descriptor sets: back to back on the device, each padded with zero descriptors to whole 256-row blocks, with the score
+// offsets of both sides.  Build: 8 descriptors per workgroup, 32 lanes x 4 bytes each.  sets[s] = (first padded row, first
+// source row, rows) in ascending padded rows; padded rows past a set's count are zero.  Float sources are quantised as the
+// host does, (unsigned char)(int)(512 * d + 0.5) -- the product in float, the sum in double, truncation, the low byte.
 template <bool F32>
 __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const int3* sets, int nsets, int total,
                                                          uint8_t* bank, int* rfix, int* cfix) {
@@ -509,40 +518,6 @@ __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const 
   }
 }
 
-// One pair of a chunk.  a, b: first bank row of set 1 / set 2; rs, cp, rm, cm: offsets of its row states, column partials,
-// row and column decisions in the chunk's scratch.
-struct PairJob {
-  int a, b, n1, n2;
-  int nrb, nsuper, nseg, sps;
-  int rs, cp, rm, cm;
-  int pad[4];
-};
-
-// work[k] = (pair of the chunk, row block | segment << 16)
-template <bool COLS>
-__global__ __launch_bounds__(256) void match_pairs_mfma_kernel(const uint8_t* bank, const int* rfix, const int* cfix,
-                                                               const PairJob* jobs, const int2* work, int3* cpart,
-                                                               int3* rstate) {
-  const int2 w = work[blockIdx.x];
-  const PairJob& J = jobs[w.x];
-  mfma_block<COLS>(bank + (size_t)J.a * KD, J.n1, bank + (size_t)J.b * KD, J.n2, rfix + J.a, cfix + J.b, J.nseg, J.sps,
-                   J.nsuper, COLS ? cpart + J.cp : nullptr, rstate + J.rs, (unsigned)(w.y & 0xffff), w.y >> 16);
-}
-
-// work[k] = (pair of the chunk, block): blocks [0, row blocks of the pair) take its rows, the rest its columns
-__global__ __launch_bounds__(256) void match_pairs_finish_kernel(const PairJob* jobs, const int2* work,
-                                                                 const int3* rstate, const int3* cpart, float distmax,
-                                                                 float ratiomax, int* rowm, int* colm) {
-  const int2 w = work[blockIdx.x];
-  const PairJob& J = jobs[w.x];
-  const int row_blocks = (J.n1 + 255) / 256;
-  if (w.y >= row_blocks) {  // (workgroup-uniform)
-    match_col_block(w.y - row_blocks, cpart + J.cp, J.nrb, J.n2, distmax, ratiomax, colm + J.cm);
-    return;
-  }
-  finish_row(rstate + J.rs, J.n1, J.nseg, w.y * 256 + threadIdx.x, distmax, ratiomax, rowm + J.rm);
-}
-
 // One workgroup per pair: the rows i in ascending order with rowm[i] >= 0 (and, for mutual best, colm[rowm[i]] == i),
 // the first max_match of them.  out: [MP_PAIRS] counts, then [pair][max_match][2].
 __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob* jobs, const int* rowm, const int* colm,
@@ -574,38 +549,43 @@ __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob*
   if (tid == 0) counts[blockIdx.x] = min(n, max_match);
 }
 
+// Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.
+struct DescSets {
+  uint8_t* rows = nullptr;
+  int *rfix = nullptr, *cfix = nullptr;  // one allocation: cfix = rfix + padded rows
+  std::vector<int> off, num;             // first padded row and stored descriptors of each set
+  int count(int s) const { return s < (int)num.size() ? num[s] : 0; }
+};
+
 }  // namespace
 
 struct hess_matcher {
   int device = 0, max_sift = 4096;
   hipStream_t st = nullptr;
-  uint8_t* des[2] = {nullptr, nullptr};
+  DescSets bank, slot[2];  // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
   float2* loc[2] = {nullptr, nullptr};
-  int num[2] = {0, 0}, have_loc[2] = {0, 0};
+  int have_loc[2] = {0, 0};
+  // small / guided path: score matrix and column partials per 64-row tile
   int3* cpart = nullptr;
-  int *dotm = nullptr, *rowm = nullptr, *colm = nullptr;
+  int* dotm = nullptr;
   size_t mat_cap = 0;
-  // matrix-core path (unguided): per-descriptor byte sums turned into score offsets, per-segment row states
-  int* fix[2] = {nullptr, nullptr};
-  int3 *cpart2 = nullptr, *rstate = nullptr;
-  size_t cpart2_cap = 0, rstate_cap = 0;
-  int rc_cap = 0;
+  // matrix-core path: row states, column partials per 256-row block, the plan (jobs, work tables) on the device and in two
+  // pinned host slots
+  int3 *mm_rstate = nullptr, *mm_cpart = nullptr;
+  uint8_t* plan = nullptr;
+  uint8_t* hplan[2] = {nullptr, nullptr};
+  size_t mm_rs_cap = 0, mm_cp_cap = 0, plan_cap = 0, hplan_cap = 0;
+  // row and column decisions of both paths
+  int *rowm = nullptr, *colm = nullptr;
+  size_t rowm_cap = 0, colm_cap = 0;
   std::vector<int> hrow, hcol;
   std::string err;
   float last_ms = 0.0f;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // bank (hess_matcher_bank_*): sets back to back, each padded to whole 256-row blocks; score offsets of both sides
-  uint8_t* bank = nullptr;
-  int *bank_rfix = nullptr, *bank_cfix = nullptr;
-  std::vector<int> bank_off, bank_num;  // first padded row and stored descriptors of each set
-  // match_pairs: per-chunk scratch on the device, the chunk's plan and results through two pinned host slots
-  int3 *mp_rstate = nullptr, *mp_cpart = nullptr;
-  int *mp_rowm = nullptr, *mp_colm = nullptr, *mp_out = nullptr;
-  uint8_t* mp_plan = nullptr;
-  size_t mp_rs_cap = 0, mp_cp_cap = 0, mp_rm_cap = 0, mp_cm_cap = 0, mp_out_cap = 0, mp_plan_cap = 0;
-  uint8_t* mp_hplan[2] = {nullptr, nullptr};
+  // match_pairs: compacted results on the device and through two pinned host slots
+  int* mp_out = nullptr;
   int* mp_hout[2] = {nullptr, nullptr};
-  size_t mp_hplan_cap = 0, mp_hout_cap = 0;
+  size_t mp_out_cap = 0, mp_hout_cap = 0;
   hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
 };
 
@@ -623,213 +603,6 @@ constexpr size_t MP_SCRATCH = (size_t)256 << 20;
       return HESS_ERR_DEVICE;                                                                \
     }                                                                                        \
   } while (0)
-
-extern "C" {
-
-hess_matcher* hess_matcher_create(int device, int max_sift) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    fprintf(stderr, "hessgpu: no usable HIP device %d (found %d)\n", device, ndev);
-    return nullptr;
-  }
-  hess_matcher* m = new (std::nothrow) hess_matcher();
-  if (!m) return nullptr;
-  m->device = device;
-  m->max_sift = max_sift > 0 ? max_sift : 4096;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess) {
-    delete m;
-    return nullptr;
-  }
-  (void)hipEventCreate(&m->e0);
-  (void)hipEventCreate(&m->e1);
-  return m;
-}
-
-void hess_matcher_destroy(hess_matcher* m) {
-  if (!m) return;
-  (void)hipSetDevice(m->device);
-  for (int k = 0; k < 2; k++) { (void)hipFree(m->des[k]); (void)hipFree(m->loc[k]); }
-  (void)hipFree(m->cpart); (void)hipFree(m->dotm); (void)hipFree(m->rowm); (void)hipFree(m->colm);
-  (void)hipFree(m->fix[0]); (void)hipFree(m->fix[1]); (void)hipFree(m->cpart2); (void)hipFree(m->rstate);
-  (void)hipFree(m->bank); (void)hipFree(m->bank_rfix);
-  (void)hipFree(m->mp_rstate); (void)hipFree(m->mp_cpart); (void)hipFree(m->mp_rowm); (void)hipFree(m->mp_colm);
-  (void)hipFree(m->mp_out); (void)hipFree(m->mp_plan);
-  for (int k = 0; k < 2; k++) {
-    (void)hipHostFree(m->mp_hplan[k]); (void)hipHostFree(m->mp_hout[k]);
-    for (int q = 0; q < 3; q++)
-      if (m->mp_ev[k][q]) (void)hipEventDestroy(m->mp_ev[k][q]);
-  }
-  if (m->e0) (void)hipEventDestroy(m->e0);
-  if (m->e1) (void)hipEventDestroy(m->e1);
-  if (m->st) (void)hipStreamDestroy(m->st);
-  delete m;
-}
-
-int hess_matcher_set_max(hess_matcher* m, int max_sift) {
-  if (!m || max_sift <= 0) return HESS_ERR_ARG;
-  m->max_sift = max_sift;
-  return 0;
-}
-
-// SiftMatchCU::SetDescriptors(index, num, const unsigned char*), SiftMatchCU.cpp:71-85.
-int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsigned char* des) {
-  if (!m || !des || num < 0) return HESS_ERR_ARG;
-  index = index > 1 ? 1 : (index < 0 ? 0 : index);
-  M_TRY(m, hipSetDevice(m->device));
-  if (num > m->max_sift) num = m->max_sift;
-  m->have_loc[index] = 0;
-  (void)hipFree(m->des[index]);
-  m->des[index] = nullptr;
-  m->num[index] = num;
-  (void)hipFree(m->fix[index]);
-  m->fix[index] = nullptr;
-  if (num) {
-    // padded with zero descriptors to whole blocks of the matrix-core path (256 rows / 128 columns, match_mfma_kernel):
-    // their exact score is 0, which is never a maximum
-    const size_t padded = ((size_t)num + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
-    M_TRY(m, hipMalloc(&m->des[index], padded * KD));
-    M_TRY(m, hipMemcpy(m->des[index], des, (size_t)num * KD, hipMemcpyHostToDevice));
-    if (padded > (size_t)num) M_TRY(m, hipMemset(m->des[index] + (size_t)num * KD, 0, (padded - num) * KD));
-    // score offsets of the matrix-core path: rows 128*sum - 128^2*128, columns 128*sum (see match_mfma_kernel)
-    std::vector<int> f(padded);
-    for (size_t i = 0; i < padded; i++) {
-      int sum = 0;
-      if (i < (size_t)num)
-        for (int k = 0; k < KD; k++) sum += des[i * KD + k];
-      f[i] = 128 * sum - (index == 0 ? 128 * 128 * KD : 0);
-    }
-    M_TRY(m, hipMalloc(&m->fix[index], padded * sizeof(int)));
-    M_TRY(m, hipMemcpy(m->fix[index], f.data(), padded * sizeof(int), hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
-// Float descriptors are quantised as the reference does: int(512*d + 0.5) into a byte (SiftMatchCU.cpp:88-100).
-int hess_matcher_set_descriptors_f32(hess_matcher* m, int index, int num, const float* des) {
-  if (!m || !des || num < 0) return HESS_ERR_ARG;
-  if (num > m->max_sift) num = m->max_sift;
-  std::vector<unsigned char> q((size_t)num * KD);
-  for (size_t i = 0; i < q.size(); ++i) q[i] = (unsigned char)(int)(512 * des[i] + 0.5);
-  return hess_matcher_set_descriptors(m, index, num, q.data());
-}
-
-// SiftMatchCU::SetFeautreLocation, SiftMatchCU.cpp:103-123: (x, y) pairs, `gap` floats skipped after each.
-int hess_matcher_set_locations(hess_matcher* m, int index, const float* locations, int gap) {
-  if (!m || !locations || index < 0 || index > 1) return HESS_ERR_ARG;
-  const int n = m->num[index];
-  if (n <= 0) return 0;
-  M_TRY(m, hipSetDevice(m->device));
-  std::vector<float2> h((size_t)n);
-  for (int i = 0; i < n; i++) { h[i].x = locations[0]; h[i].y = locations[1]; locations += 2 + gap; }
-  (void)hipFree(m->loc[index]);
-  M_TRY(m, hipMalloc(&m->loc[index], (size_t)n * sizeof(float2)));
-  M_TRY(m, hipMemcpy(m->loc[index], h.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
-  m->have_loc[index] = 1;
-  return 0;
-}
-
-// SiftMatchCU::GetSiftMatch / GetGuidedSiftMatch + GetBestMatch (SiftMatchCU.cpp:125-173).
-// H, F: 3x3 row-major, both NULL for the unguided match.  Returns the number of matches (>= 0) or a
-// negative hess_status.
-int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* H, const float* F, float distmax,
-                       float ratiomax, float hdistmax, float fdistmax, int mutual_best) {
-  if (!m || !pairs || max_match < 0) return HESS_ERR_ARG;
-  const int n1 = m->num[0], n2 = m->num[1];
-  if (n1 <= 0 || n2 <= 0) return 0;
-  const bool guided = (H != nullptr) || (F != nullptr);
-  if (guided && (!H || !F)) { m->err = "guided matching needs both H and F"; return HESS_ERR_ARG; }
-  if (guided && (!m->have_loc[0] || !m->have_loc[1])) return 0;  // SiftMatchCU.cpp:131
-  M_TRY(m, hipSetDevice(m->device));
-  if (m->rc_cap < m->max_sift) {
-    (void)hipFree(m->rowm); (void)hipFree(m->colm);
-    m->rowm = m->colm = nullptr;
-    M_TRY(m, hipMalloc(&m->rowm, (size_t)m->max_sift * sizeof(int) + 4));
-    M_TRY(m, hipMalloc(&m->colm, (size_t)m->max_sift * sizeof(int) + 4));
-    m->rc_cap = m->max_sift;
-  }
-  // small problems (three launches of latency) stay on the one-pass dot kernel: 1024 x 1024 0.026 vs 0.033 ms
-  if (!guided && (size_t)n1 * n2 > ((size_t)3 << 20)) {
-    // matrix-core path: (256-row block, column segment) workgroups, at least two per CU where the problem allows;
-    // a segment is whole super tiles of 128 columns, at most 15 of them (the tile index shares six key bits)
-    const int nrb = (n1 + MM_ROWS - 1) / MM_ROWS, nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
-    // Workgroups: whole rounds over the 256 CUs -- two per CU (what the registers allow) when that leaves a workgroup at
-    // least four super tiles, else one per CU with twice the tiles (its prologue and the merge of the row states at its
-    // end cost about as much as two super tiles).  Same call, 4096^2 / 8192^2, TMAC/s: 256 workgroups 91 / 193, 384:
-    // 91 / 176, 512: 81 / 211, 768: 81 / 180 (profiles/r06_experiments/matcher.txt).
-    const int target_wgs = (long long)nrb * nsuper >= 512 * 4 ? 512 : 256;
-    int nseg = (target_wgs + nrb - 1) / nrb;
-    nseg = nseg < 1 ? 1 : (nseg > nsuper ? nsuper : nseg);
-    int sps = (nsuper + nseg - 1) / nseg;
-    if (sps > MM_MAX_TILES / 4) sps = MM_MAX_TILES / 4;
-    nseg = (nsuper + sps - 1) / sps;
-    const size_t need_rs = (size_t)n1 * nseg, need_cp = (size_t)nrb * n2;  // column partials per 256-row workgroup
-    if (need_rs > m->rstate_cap) {
-      (void)hipFree(m->rstate); m->rstate = nullptr;
-      M_TRY(m, hipMalloc(&m->rstate, need_rs * sizeof(int3)));
-      m->rstate_cap = need_rs;
-    }
-    if (mutual_best && need_cp > m->cpart2_cap) {
-      (void)hipFree(m->cpart2); m->cpart2 = nullptr;
-      M_TRY(m, hipMalloc(&m->cpart2, need_cp * sizeof(int3)));
-      m->cpart2_cap = need_cp;
-    }
-    (void)hipEventRecord(m->e0, m->st);
-    if (mutual_best)
-      hipLaunchKernelGGL(match_mfma_kernel<true>, dim3(nrb, nseg), dim3(256), 0, m->st, m->des[0], n1, m->des[1], n2, m->fix[0],
-                         m->fix[1], nseg, sps, nsuper, m->cpart2, m->rstate);
-    else
-      hipLaunchKernelGGL(match_mfma_kernel<false>, dim3(nrb, nseg), dim3(256), 0, m->st, m->des[0], n1, m->des[1], n2, m->fix[0],
-                         m->fix[1], nseg, sps, nsuper, nullptr, m->rstate);
-    // rows and -- for mutual best -- columns in one launch (the partials of row blocks past num1 hold the neutral
-    // (0, -1, 0) of their zero rows)
-    const int row_blocks = (n1 + 255) / 256;
-    hipLaunchKernelGGL(match_finish_kernel, dim3(row_blocks + (mutual_best ? (n2 + 31) / 32 : 0)), dim3(256), 0, m->st, m->rstate,
-                       n1, nseg, row_blocks, m->cpart2, nrb, n2, distmax, ratiomax, m->rowm, m->colm);
-  } else {
-  const size_t need = (size_t)n1 * n2;
-  if (need > m->mat_cap) {
-    (void)hipFree(m->cpart); (void)hipFree(m->dotm);
-    m->cpart = nullptr;
-    m->dotm = nullptr;
-    M_TRY(m, hipMalloc(&m->cpart, (size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift * sizeof(int3)));
-    M_TRY(m, hipMalloc(&m->dotm, need * sizeof(int)));
-    m->mat_cap = need;
-  }
-  GeoParams gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.guided = guided ? 1 : 0;
-  if (guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
-  (void)hipEventRecord(m->e0, m->st);
-  hipLaunchKernelGGL(match_dot_kernel, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM), dim3(256), 0, m->st, m->des[0], n1,
-                     m->des[1], n2, m->loc[0], m->loc[1], gp, mutual_best ? m->cpart : nullptr, m->dotm);
-  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
-                     m->rowm);
-  if (mutual_best)
-    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart, (n1 + TM - 1) / TM, n2,
-                       distmax, ratiomax, m->colm);
-  }
-  (void)hipEventRecord(m->e1, m->st);
-  m->hrow.resize(n1);
-  m->hcol.resize(n2);
-  M_TRY(m, hipMemcpyAsync(m->hrow.data(), m->rowm, (size_t)n1 * 4, hipMemcpyDeviceToHost, m->st));
-  if (mutual_best) M_TRY(m, hipMemcpyAsync(m->hcol.data(), m->colm, (size_t)n2 * 4, hipMemcpyDeviceToHost, m->st));
-  M_TRY(m, hipStreamSynchronize(m->st));
-  (void)hipEventElapsedTime(&m->last_ms, m->e0, m->e1);
-  int nmatch = 0;
-  for (int i = 0; i < n1 && nmatch < max_match; ++i) {
-    const int j = m->hrow[i];
-    if (j >= 0 && (!mutual_best || m->hcol[j] == i)) {
-      pairs[2 * nmatch] = i;
-      pairs[2 * nmatch + 1] = j;
-      nmatch++;
-    }
-  }
-  return nmatch;
-}
-
-// ---- bank of descriptor sets, many pairs per call --------------------------------------------------------------------
-
-}  // extern "C"
 
 namespace {
 
@@ -857,48 +630,48 @@ hipError_t grow_pinned(T* (&p)[2], size_t& cap, size_t n) {
   return hipSuccess;
 }
 
-void bank_clear(hess_matcher* m) {
-  (void)hipFree(m->bank);
-  (void)hipFree(m->bank_rfix);
-  m->bank = nullptr;
-  m->bank_rfix = m->bank_cfix = nullptr;
-  m->bank_off.clear();
-  m->bank_num.clear();
+void sets_clear(DescSets& s) {
+  (void)hipFree(s.rows);
+  (void)hipFree(s.rfix);
+  s.rows = nullptr;
+  s.rfix = s.cfix = nullptr;
+  s.off.clear();
+  s.num.clear();
 }
 
-// The bank from `src` (device memory, u8 or f32 [sum of counts][128]): set s is counts[s] rows, of which the first
-// max_sift are kept (SetDescriptors).  Returns after the bank is built.
-int bank_build(hess_matcher* m, int nsets, const int* counts, const void* src, bool f32) {
+// `s` (cleared) from `src` (device memory, u8 or f32 [sum of counts][128]): set k is counts[k] rows, of which the first
+// max_sift are kept (SetDescriptors).  Returns after the sets are built.
+int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const void* src, bool f32) {
   std::vector<int3> sets((size_t)nsets);
   std::vector<int> off((size_t)nsets), num((size_t)nsets);
   size_t padded = 0, srow = 0;
-  for (int s = 0; s < nsets; s++) {
-    const int n = counts[s] > m->max_sift ? m->max_sift : counts[s];
-    off[s] = (int)padded;
-    num[s] = n;
-    sets[s] = make_int3((int)padded, (int)srow, n);
+  for (int k = 0; k < nsets; k++) {
+    const int n = counts[k] > m->max_sift ? m->max_sift : counts[k];
+    off[k] = (int)padded;
+    num[k] = n;
+    sets[k] = make_int3((int)padded, (int)srow, n);
     padded += ((size_t)n + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
-    srow += (size_t)counts[s];
+    srow += (size_t)counts[k];
     if (padded > (size_t)INT32_MAX / KD || srow > (size_t)INT32_MAX) {
       m->err = "bank too large";
       return HESS_ERR_TOO_BIG;
     }
   }
   if (padded) {
-    M_TRY(m, hipMalloc(&m->bank, padded * KD));
-    M_TRY(m, hipMalloc(&m->bank_rfix, 2 * padded * sizeof(int)));
-    m->bank_cfix = m->bank_rfix + padded;
+    M_TRY(m, hipMalloc(&s.rows, padded * KD));
+    M_TRY(m, hipMalloc(&s.rfix, 2 * padded * sizeof(int)));
+    s.cfix = s.rfix + padded;
     int3* dsets = nullptr;
     M_TRY(m, hipMalloc(&dsets, sets.size() * sizeof(int3)));
     hipError_t e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
     if (e == hipSuccess) {
       const dim3 grid((unsigned)((padded + 7) / 8));
       if (f32)
-        hipLaunchKernelGGL(bank_build_kernel<true>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, m->bank,
-                           m->bank_rfix, m->bank_cfix);
+        hipLaunchKernelGGL(bank_build_kernel<true>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, s.rows,
+                           s.rfix, s.cfix);
       else
-        hipLaunchKernelGGL(bank_build_kernel<false>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, m->bank,
-                           m->bank_rfix, m->bank_cfix);
+        hipLaunchKernelGGL(bank_build_kernel<false>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, s.rows,
+                           s.rfix, s.cfix);
       e = hipGetLastError();
     }
     const hipError_t es = hipStreamSynchronize(m->st);
@@ -906,9 +679,40 @@ int bank_build(hess_matcher* m, int nsets, const int* counts, const void* src, b
     M_TRY(m, e);
     M_TRY(m, es);
   }
-  m->bank_off.swap(off);
-  m->bank_num.swap(num);
+  s.off.swap(off);
+  s.num.swap(num);
   return 0;
+}
+
+// `s` from host bytes: `rows` (the sum of counts) staged on the device, then sets_build.  On failure `s` is empty.
+int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const unsigned char* des, size_t rows) {
+  sets_clear(s);
+  uint8_t* staging = nullptr;
+  if (rows) {
+    M_TRY(m, hipMalloc(&staging, rows * KD));
+    const hipError_t e = hipMemcpy(staging, des, rows * KD, hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)hipFree(staging);
+    M_TRY(m, e);
+  }
+  const int rc = sets_build(m, s, nsets, counts, staging, false);
+  (void)hipFree(staging);
+  if (rc) sets_clear(s);
+  return rc;
+}
+
+// Host floats quantised as the reference does, int(512*d + 0.5) into a byte (SiftMatchCU.cpp:88-100): set k is counts[k]
+// rows, of which the first max_sift (kept[k]) are kept.
+std::vector<unsigned char> quantise(const float* des, int nsets, const int* counts, int max_sift, int* kept) {
+  size_t nk = 0;
+  for (int k = 0; k < nsets; k++) nk += (size_t)(kept[k] = counts[k] > max_sift ? max_sift : counts[k]);
+  std::vector<unsigned char> q(nk * KD);
+  size_t src = 0, dst = 0;
+  for (int k = 0; k < nsets; k++) {
+    for (size_t i = 0; i < (size_t)kept[k] * KD; ++i) q[dst + i] = (unsigned char)(int)(512 * des[src + i] + 0.5);
+    src += (size_t)counts[k] * KD;
+    dst += (size_t)kept[k] * KD;
+  }
+  return q;
 }
 
 int bank_args(hess_matcher* m, int nsets, const int* counts, const void* des, size_t* rows) {
@@ -924,32 +728,245 @@ int bank_args(hess_matcher* m, int nsets, const int* counts, const void* des, si
   return 0;
 }
 
-// One chunk of a match_pairs call: pairs [p0, p1), the segment length of its multiply, its scratch and work tables.
-struct MpChunk {
+// Segments of a pair of nsuper super tiles: at most sps super tiles each (the tile index shares six key bits, so
+// sps <= MM_MAX_TILES / 4), as many as that needs, balanced: psps <= sps.
+void pair_seg(int nsuper, int sps, int& nseg, int& psps) {
+  nseg = (nsuper + sps - 1) / sps;
+  psps = (nsuper + nseg - 1) / nseg;
+  nseg = (nsuper + psps - 1) / psps;
+}
+
+// Jobs [p0, p1) of one multiply and one finish launch, with segments of at most sps super tiles; the scratch they use (row
+// states, column partials, row and column decisions) and the entries of the two work tables.
+struct Chunk {
   int p0, p1, sps;
   size_t rs, cp, rm, cm, nwg, nfin;
+  size_t plan_bytes() const { return (size_t)(p1 - p0) * sizeof(PairJob) + (nwg + nfin) * sizeof(int2); }
 };
+
+// Plans c's jobs (a, b, n1, n2 given, n1 = n2 = 0 for a pair without work): shapes, segments and offsets into the scratch;
+// and c's totals.  Returns the scratch bytes.
+size_t plan_chunk(PairJob* jobs, Chunk& c, int mutual_best) {
+  c.rs = c.cp = c.rm = c.cm = c.nwg = c.nfin = 0;
+  for (int p = c.p0; p < c.p1; p++) {
+    PairJob& J = jobs[p];
+    if (!J.n1) continue;
+    J.nrb = (J.n1 + MM_ROWS - 1) / MM_ROWS;
+    J.nsuper = (J.n2 + MM_SUPER - 1) / MM_SUPER;
+    pair_seg(J.nsuper, c.sps, J.nseg, J.sps);
+    J.rs = (int)c.rs; J.cp = (int)c.cp; J.rm = (int)c.rm; J.cm = (int)c.cm;
+    c.rs += (size_t)J.n1 * J.nseg;
+    c.cp += mutual_best ? (size_t)J.nrb * J.n2 : 0;
+    c.rm += J.n1;
+    c.cm += mutual_best ? J.n2 : 0;
+    c.nwg += (size_t)J.nrb * J.nseg;
+    c.nfin += (J.n1 + 255) / 256 + (mutual_best ? (J.n2 + 31) / 32 : 0);
+  }
+  return sizeof(int3) * (c.rs + c.cp) + sizeof(int) * (c.rm + c.cm);
+}
+
+// Enqueues planned chunk c on m->st: its jobs and work tables (multiply: (job, row block | segment << 16); finish: (job,
+// block)) into the pinned slot hp and up to m->plan, then `start`, the multiply and the finish.  s1, s2: the sets the
+// jobs' a, b index.  The caller has grown every buffer to c's size.
+hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Chunk& c,
+                     uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax) {
+  const int np = c.p1 - c.p0;
+  memcpy(hp, jobs + c.p0, np * sizeof(PairJob));
+  int2* const work = reinterpret_cast<int2*>(hp + np * sizeof(PairJob));
+  int2* const fin = work + c.nwg;
+  size_t iw = 0, jf = 0;
+  for (int q = 0; q < np; q++) {
+    const PairJob& J = jobs[c.p0 + q];
+    if (!J.n1) continue;
+    for (int sg = 0; sg < J.nseg; sg++)
+      for (int rb = 0; rb < J.nrb; rb++) work[iw++] = make_int2(q, rb | sg << 16);
+    const int nfb = (J.n1 + 255) / 256 + (mutual_best ? (J.n2 + 31) / 32 : 0);
+    for (int b = 0; b < nfb; b++) fin[jf++] = make_int2(q, b);
+  }
+  const PairJob* djobs = reinterpret_cast<const PairJob*>(m->plan);
+  const int2* dwork = reinterpret_cast<const int2*>(m->plan + np * sizeof(PairJob));
+  const hipError_t e = hipMemcpyAsync(m->plan, hp, c.plan_bytes(), hipMemcpyHostToDevice, m->st);
+  if (e != hipSuccess) return e;
+  (void)hipEventRecord(start, m->st);
+  if (c.nwg) {
+    if (mutual_best)
+      hipLaunchKernelGGL(match_mfma_kernel<true>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows,
+                         s2.cfix, djobs, dwork, m->mm_cpart, m->mm_rstate);
+    else
+      hipLaunchKernelGGL(match_mfma_kernel<false>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows,
+                         s2.cfix, djobs, dwork, m->mm_cpart, m->mm_rstate);
+    hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, dwork + c.nwg,
+                       m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
+  }
+  return hipGetLastError();
+}
 
 }  // namespace
 
 extern "C" {
 
+hess_matcher* hess_matcher_create(int device, int max_sift) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    fprintf(stderr, "hessgpu: no usable HIP device %d (found %d)\n", device, ndev);
+    return nullptr;
+  }
+  hess_matcher* m = new (std::nothrow) hess_matcher();
+  if (!m) return nullptr;
+  m->device = device;
+  m->max_sift = max_sift > 0 ? max_sift : 4096;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess) {
+    delete m;
+    return nullptr;
+  }
+  (void)hipEventCreate(&m->e0);
+  (void)hipEventCreate(&m->e1);
+  return m;
+}
+
+void hess_matcher_destroy(hess_matcher* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  sets_clear(m->bank);
+  for (int k = 0; k < 2; k++) { sets_clear(m->slot[k]); (void)hipFree(m->loc[k]); }
+  (void)hipFree(m->cpart); (void)hipFree(m->dotm);
+  (void)hipFree(m->mm_rstate); (void)hipFree(m->mm_cpart); (void)hipFree(m->plan);
+  (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out);
+  for (int k = 0; k < 2; k++) {
+    (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]);
+    for (int q = 0; q < 3; q++)
+      if (m->mp_ev[k][q]) (void)hipEventDestroy(m->mp_ev[k][q]);
+  }
+  if (m->e0) (void)hipEventDestroy(m->e0);
+  if (m->e1) (void)hipEventDestroy(m->e1);
+  if (m->st) (void)hipStreamDestroy(m->st);
+  delete m;
+}
+
+int hess_matcher_set_max(hess_matcher* m, int max_sift) {
+  if (!m || max_sift <= 0) return HESS_ERR_ARG;
+  m->max_sift = max_sift;
+  return 0;
+}
+
+// SiftMatchCU::SetDescriptors(index, num, const unsigned char*), SiftMatchCU.cpp:71-85: slot `index` becomes a one-set bank.
+int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsigned char* des) {
+  if (!m || !des || num < 0) return HESS_ERR_ARG;
+  index = index > 1 ? 1 : (index < 0 ? 0 : index);
+  M_TRY(m, hipSetDevice(m->device));
+  if (num > m->max_sift) num = m->max_sift;
+  m->have_loc[index] = 0;
+  return sets_load(m, m->slot[index], 1, &num, des, (size_t)num);
+}
+
+// Float descriptors are quantised as the reference does (SiftMatchCU.cpp:88-100).
+int hess_matcher_set_descriptors_f32(hess_matcher* m, int index, int num, const float* des) {
+  if (!m || !des || num < 0) return HESS_ERR_ARG;
+  int kept = 0;
+  std::vector<unsigned char> q = quantise(des, 1, &num, m->max_sift, &kept);
+  return hess_matcher_set_descriptors(m, index, kept, q.data());
+}
+
+// SiftMatchCU::SetFeautreLocation, SiftMatchCU.cpp:103-123: (x, y) pairs, `gap` floats skipped after each.
+int hess_matcher_set_locations(hess_matcher* m, int index, const float* locations, int gap) {
+  if (!m || !locations || index < 0 || index > 1) return HESS_ERR_ARG;
+  const int n = m->slot[index].count(0);
+  if (n <= 0) return 0;
+  M_TRY(m, hipSetDevice(m->device));
+  std::vector<float2> h((size_t)n);
+  for (int i = 0; i < n; i++) { h[i].x = locations[0]; h[i].y = locations[1]; locations += 2 + gap; }
+  (void)hipFree(m->loc[index]);
+  M_TRY(m, hipMalloc(&m->loc[index], (size_t)n * sizeof(float2)));
+  M_TRY(m, hipMemcpy(m->loc[index], h.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
+  m->have_loc[index] = 1;
+  return 0;
+}
+
+// SiftMatchCU::GetSiftMatch / GetGuidedSiftMatch + GetBestMatch (SiftMatchCU.cpp:125-173).
+// H, F: 3x3 row-major, both NULL for the unguided match.  Returns the number of matches (>= 0) or a
+// negative hess_status.
+int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* H, const float* F, float distmax,
+                       float ratiomax, float hdistmax, float fdistmax, int mutual_best) {
+  if (!m || !pairs || max_match < 0) return HESS_ERR_ARG;
+  const int n1 = m->slot[0].count(0), n2 = m->slot[1].count(0);
+  if (n1 <= 0 || n2 <= 0) return 0;
+  const bool guided = (H != nullptr) || (F != nullptr);
+  if (guided && (!H || !F)) { m->err = "guided matching needs both H and F"; return HESS_ERR_ARG; }
+  if (guided && (!m->have_loc[0] || !m->have_loc[1])) return 0;  // SiftMatchCU.cpp:131
+  M_TRY(m, hipSetDevice(m->device));
+  M_TRY(m, grow_device(m->rowm, m->rowm_cap, (size_t)n1));
+  M_TRY(m, grow_device(m->colm, m->colm_cap, (size_t)n2));
+  // small problems (three launches of latency) stay on the one-pass dot kernel: 1024 x 1024 0.026 vs 0.033 ms
+  if (!guided && (size_t)n1 * n2 > ((size_t)3 << 20)) {
+    // matrix-core path, the pair as a chunk of one job: (256-row block, column segment) workgroups, at least two per CU
+    // where the problem allows.  Workgroups: whole rounds over the 256 CUs -- two per CU (what the registers allow) when
+    // that leaves a workgroup at least four super tiles, else one per CU with twice the tiles (its prologue and the merge
+    // of the row states at its end cost about as much as two super tiles).  Same call, 4096^2 / 8192^2, TMAC/s: 256
+    // workgroups 91 / 193, 384: 91 / 176, 512: 81 / 211, 768: 81 / 180 (profiles/r06_experiments/matcher.txt).
+    const int nrb = (n1 + MM_ROWS - 1) / MM_ROWS, nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
+    const int target_wgs = (long long)nrb * nsuper >= 512 * 4 ? 512 : 256;
+    int nseg = (target_wgs + nrb - 1) / nrb;
+    nseg = nseg < 1 ? 1 : (nseg > nsuper ? nsuper : nseg);
+    const int sps = std::min((nsuper + nseg - 1) / nseg, MM_MAX_TILES / 4);
+    PairJob job{};
+    job.n1 = n1;
+    job.n2 = n2;
+    Chunk c{0, 1, sps, 0, 0, 0, 0, 0, 0};
+    plan_chunk(&job, c, mutual_best);
+    M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, c.rs));
+    M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, c.cp));
+    M_TRY(m, grow_device(m->plan, m->plan_cap, c.plan_bytes()));
+    M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, c.plan_bytes()));
+    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], &job, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax));
+  } else {
+  const size_t need = (size_t)n1 * n2;
+  if (need > m->mat_cap) {
+    (void)hipFree(m->cpart); (void)hipFree(m->dotm);
+    m->cpart = nullptr;
+    m->dotm = nullptr;
+    M_TRY(m, hipMalloc(&m->cpart, (size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift * sizeof(int3)));
+    M_TRY(m, hipMalloc(&m->dotm, need * sizeof(int)));
+    m->mat_cap = need;
+  }
+  GeoParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.guided = guided ? 1 : 0;
+  if (guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
+  (void)hipEventRecord(m->e0, m->st);
+  hipLaunchKernelGGL(match_dot_kernel, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM), dim3(256), 0, m->st, m->slot[0].rows,
+                     n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp, mutual_best ? m->cpart : nullptr, m->dotm);
+  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
+                     m->rowm);
+  if (mutual_best)
+    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart, (n1 + TM - 1) / TM, n2,
+                       distmax, ratiomax, m->colm);
+  }
+  (void)hipEventRecord(m->e1, m->st);
+  m->hrow.resize(n1);
+  m->hcol.resize(n2);
+  M_TRY(m, hipMemcpyAsync(m->hrow.data(), m->rowm, (size_t)n1 * 4, hipMemcpyDeviceToHost, m->st));
+  if (mutual_best) M_TRY(m, hipMemcpyAsync(m->hcol.data(), m->colm, (size_t)n2 * 4, hipMemcpyDeviceToHost, m->st));
+  M_TRY(m, hipStreamSynchronize(m->st));
+  (void)hipEventElapsedTime(&m->last_ms, m->e0, m->e1);
+  int nmatch = 0;
+  for (int i = 0; i < n1 && nmatch < max_match; ++i) {
+    const int j = m->hrow[i];
+    if (j >= 0 && (!mutual_best || m->hcol[j] == i)) {
+      pairs[2 * nmatch] = i;
+      pairs[2 * nmatch + 1] = j;
+      nmatch++;
+    }
+  }
+  return nmatch;
+}
+
+// ---- bank of descriptor sets, many pairs per call --------------------------------------------------------------------
+
 int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const unsigned char* des) {
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   M_TRY(m, hipSetDevice(m->device));
-  bank_clear(m);
-  uint8_t* staging = nullptr;
-  if (rows) {
-    M_TRY(m, hipMalloc(&staging, rows * KD));
-    const hipError_t e = hipMemcpy(staging, des, rows * KD, hipMemcpyHostToDevice);
-    if (e != hipSuccess) (void)hipFree(staging);
-    M_TRY(m, e);
-  }
-  const int rc = bank_build(m, nsets, counts, staging, false);
-  (void)hipFree(staging);
-  if (rc) bank_clear(m);
-  return rc;
+  return sets_load(m, m->bank, nsets, counts, des, rows);
 }
 
 // Host floats: quantised on the host as hess_matcher_set_descriptors_f32 does, then the byte path.
@@ -957,15 +974,7 @@ int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, con
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   std::vector<int> kept((size_t)nsets);
-  size_t nk = 0;
-  for (int s = 0; s < nsets; s++) nk += (size_t)(kept[s] = counts[s] > m->max_sift ? m->max_sift : counts[s]);
-  std::vector<unsigned char> q(nk * KD);
-  size_t src = 0, dst = 0;
-  for (int s = 0; s < nsets; s++) {
-    for (size_t i = 0; i < (size_t)kept[s] * KD; ++i) q[dst + i] = (unsigned char)(int)(512 * des[src + i] + 0.5);
-    src += (size_t)counts[s] * KD;
-    dst += (size_t)kept[s] * KD;
-  }
+  std::vector<unsigned char> q = quantise(des, nsets, counts, m->max_sift, kept.data());
   return hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
 }
 
@@ -993,22 +1002,22 @@ int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, 
     }
     (void)hipGetLastError();
   }
-  bank_clear(m);
-  const int rc = bank_build(m, nsets, counts, dev_desc, true);
-  if (rc) bank_clear(m);
+  sets_clear(m->bank);
+  const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, true);
+  if (rc) sets_clear(m->bank);
   return rc;
 }
 
 int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
   if (!m) return HESS_ERR_ARG;
-  if (set < 0 || set >= (int)m->bank_num.size()) {
-    m->err = "bank_read: no set " + std::to_string(set) + " in a bank of " + std::to_string(m->bank_num.size());
+  if (set < 0 || set >= (int)m->bank.num.size()) {
+    m->err = "bank_read: no set " + std::to_string(set) + " in a bank of " + std::to_string(m->bank.num.size());
     return HESS_ERR_ARG;
   }
-  const int n = m->bank_num[set];
+  const int n = m->bank.num[set];
   if (out && n) {
     M_TRY(m, hipSetDevice(m->device));
-    M_TRY(m, hipMemcpy(out, m->bank + (size_t)m->bank_off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
+    M_TRY(m, hipMemcpy(out, m->bank.rows + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
   }
   return n;
 }
@@ -1020,7 +1029,7 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
     m->err = "match_pairs: npairs or max_match < 0, or an array is NULL";
     return HESS_ERR_ARG;
   }
-  const int nsets = (int)m->bank_num.size();
+  const int nsets = (int)m->bank.num.size();
   for (int p = 0; p < npairs; p++)
     if (pairs_ab[2 * p] < 0 || pairs_ab[2 * p] >= nsets || pairs_ab[2 * p + 1] < 0 || pairs_ab[2 * p + 1] >= nsets) {
       m->err = "match_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
@@ -1031,12 +1040,15 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
   M_TRY(m, hipSetDevice(m->device));
   mutual_best = mutual_best ? 1 : 0;
 
-  // a pair with an empty side has no work and no matches
-  auto sides = [&](int p, int& n1, int& n2) {
-    n1 = m->bank_num[pairs_ab[2 * p]];
-    n2 = m->bank_num[pairs_ab[2 * p + 1]];
-    if (n1 == 0 || n2 == 0) n1 = n2 = 0;
-  };
+  std::vector<PairJob> jobs((size_t)npairs);
+  for (int p = 0; p < npairs; p++) {
+    PairJob& J = jobs[p];
+    J.a = m->bank.off[pairs_ab[2 * p]];
+    J.b = m->bank.off[pairs_ab[2 * p + 1]];
+    J.n1 = m->bank.num[pairs_ab[2 * p]];
+    J.n2 = m->bank.num[pairs_ab[2 * p + 1]];
+    if (J.n1 == 0 || J.n2 == 0) J.n1 = J.n2 = 0;  // a pair with an empty side has no work and no matches
+  }
   // Segments per pair from the whole chunk's grid: whole rounds of workgroups over the 256 CUs as in hess_matcher_match
   // (two per CU when that leaves each at least four super tiles), at most MM_MAX_TILES / 4 super tiles per segment.
   auto chunk_sps = [](size_t work) {
@@ -1044,47 +1056,23 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
     const size_t sps = (work + target - 1) / target;
     return sps < 1 ? 1 : (sps > MM_MAX_TILES / 4 ? MM_MAX_TILES / 4 : (int)sps);
   };
-  auto pair_seg = [](int nsuper, int sps, int& nseg, int& psps) {
-    nseg = (nsuper + sps - 1) / sps;
-    psps = (nsuper + nseg - 1) / nseg;
-    nseg = (nsuper + psps - 1) / psps;
-  };
-  auto measure = [&](MpChunk& c) {
-    c.rs = c.cp = c.rm = c.cm = c.nwg = c.nfin = 0;
-    for (int p = c.p0; p < c.p1; p++) {
-      int n1, n2;
-      sides(p, n1, n2);
-      if (!n1) continue;
-      const int nrb = (n1 + MM_ROWS - 1) / MM_ROWS, nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
-      int nseg, psps;
-      pair_seg(nsuper, c.sps, nseg, psps);
-      c.rs += (size_t)n1 * nseg;
-      c.cp += mutual_best ? (size_t)nrb * n2 : 0;
-      c.rm += n1;
-      c.cm += mutual_best ? n2 : 0;
-      c.nwg += (size_t)nrb * nseg;
-      c.nfin += (n1 + 255) / 256 + (mutual_best ? (n2 + 31) / 32 : 0);
-    }
-    return sizeof(int3) * (c.rs + c.cp) + sizeof(int) * (c.rm + c.cm);
-  };
-  std::vector<MpChunk> chunks;
+  std::vector<Chunk> chunks;
   int mm = 0;  // matches kept per pair: max_match, at most the rows of its set 1
   for (int p0 = 0; p0 < npairs;) {
-    MpChunk c{p0, p0, 1, 0, 0, 0, 0, 0, 0};
+    Chunk c{p0, p0, 1, 0, 0, 0, 0, 0, 0};
     size_t work = 0;
     while (c.p1 < npairs && c.p1 - p0 < MP_PAIRS) {
-      int n1, n2;
-      sides(c.p1, n1, n2);
+      const int n1 = jobs[c.p1].n1, n2 = jobs[c.p1].n2;
       const size_t w = n1 ? (size_t)((n1 + MM_ROWS - 1) / MM_ROWS) * ((n2 + MM_SUPER - 1) / MM_SUPER) : 0;
-      MpChunk t = c;
+      Chunk t = c;
       t.p1++;
       t.sps = chunk_sps(work + w);
-      if (c.p1 > p0 && measure(t) > MP_SCRATCH) break;
+      if (c.p1 > p0 && plan_chunk(jobs.data(), t, mutual_best) > MP_SCRATCH) break;
       c = t;
       work += w;
       mm = std::max(mm, std::min(n1, max_match));
     }
-    measure(c);
+    plan_chunk(jobs.data(), c, mutual_best);  // (the plan of the chunk as it ends)
     if (c.rs + c.cp > (size_t)INT32_MAX || c.nwg > (size_t)INT32_MAX) {
       m->err = "match_pairs: a pair needs more scratch than one launch can address";
       return HESS_ERR_TOO_BIG;
@@ -1093,18 +1081,18 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
     p0 = c.p1;
   }
   size_t rs = 1, cp = 1, rm = 1, cm = 1, plan = 0, outn = 0;
-  for (const MpChunk& c : chunks) {
+  for (const Chunk& c : chunks) {
     rs = std::max(rs, c.rs); cp = std::max(cp, c.cp); rm = std::max(rm, c.rm); cm = std::max(cm, c.cm);
-    plan = std::max(plan, (size_t)(c.p1 - c.p0) * sizeof(PairJob) + (c.nwg + c.nfin) * sizeof(int2));
+    plan = std::max(plan, c.plan_bytes());
     outn = std::max(outn, (size_t)MP_PAIRS + (size_t)(c.p1 - c.p0) * mm * 2);
   }
-  M_TRY(m, grow_device(m->mp_rstate, m->mp_rs_cap, rs));
-  M_TRY(m, grow_device(m->mp_cpart, m->mp_cp_cap, cp));
-  M_TRY(m, grow_device(m->mp_rowm, m->mp_rm_cap, rm));
-  M_TRY(m, grow_device(m->mp_colm, m->mp_cm_cap, cm));
+  M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, rs));
+  M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, cp));
+  M_TRY(m, grow_device(m->rowm, m->rowm_cap, rm));
+  M_TRY(m, grow_device(m->colm, m->colm_cap, cm));
   M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, outn));
-  M_TRY(m, grow_device(m->mp_plan, m->mp_plan_cap, plan));
-  M_TRY(m, grow_pinned(m->mp_hplan, m->mp_hplan_cap, plan));
+  M_TRY(m, grow_device(m->plan, m->plan_cap, plan));
+  M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, plan));
   M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, outn));
   for (int k = 0; k < 2; k++)
     for (int q = 0; q < 3; q++)
@@ -1113,7 +1101,7 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
   // chunk k is enqueued into slot k & 1; its results are read on the host while chunk k + 1 runs
   float total_ms = 0.0f;
   auto collect = [&](size_t k) -> hipError_t {
-    const MpChunk& c = chunks[k];
+    const Chunk& c = chunks[k];
     hipEvent_t* ev = m->mp_ev[k & 1];
     hipError_t e = hipEventSynchronize(ev[2]);
     if (e != hipSuccess) return e;
@@ -1131,56 +1119,13 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
   };
   hipError_t err = hipSuccess;
   for (size_t k = 0; k < chunks.size() && err == hipSuccess; k++) {
-    const MpChunk& c = chunks[k];
+    const Chunk& c = chunks[k];
     const int np = c.p1 - c.p0;
-    // the plan: jobs, then the multiply's work table, then the finish's
-    uint8_t* hp = m->mp_hplan[k & 1];
-    PairJob* jobs = reinterpret_cast<PairJob*>(hp);
-    int2* work = reinterpret_cast<int2*>(hp + np * sizeof(PairJob));
-    int2* fin = work + c.nwg;
-    size_t o_rs = 0, o_cp = 0, o_rm = 0, o_cm = 0, iw = 0, jf = 0;
-    for (int p = c.p0; p < c.p1; p++) {
-      PairJob& J = jobs[p - c.p0];
-      memset(&J, 0, sizeof(J));
-      int n1, n2;
-      sides(p, n1, n2);
-      J.a = m->bank_off[pairs_ab[2 * p]];
-      J.b = m->bank_off[pairs_ab[2 * p + 1]];
-      J.n1 = n1;
-      J.n2 = n2;
-      if (!n1) continue;
-      J.nrb = (n1 + MM_ROWS - 1) / MM_ROWS;
-      J.nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
-      pair_seg(J.nsuper, c.sps, J.nseg, J.sps);
-      J.rs = (int)o_rs; J.cp = (int)o_cp; J.rm = (int)o_rm; J.cm = (int)o_cm;
-      o_rs += (size_t)n1 * J.nseg;
-      o_cp += mutual_best ? (size_t)J.nrb * n2 : 0;
-      o_rm += n1;
-      o_cm += mutual_best ? n2 : 0;
-      for (int sg = 0; sg < J.nseg; sg++)
-        for (int rb = 0; rb < J.nrb; rb++) work[iw++] = make_int2(p - c.p0, rb | sg << 16);
-      const int nfb = (n1 + 255) / 256 + (mutual_best ? (n2 + 31) / 32 : 0);
-      for (int b = 0; b < nfb; b++) fin[jf++] = make_int2(p - c.p0, b);
-    }
-    const size_t plan_bytes = np * sizeof(PairJob) + (c.nwg + c.nfin) * sizeof(int2);
-    const PairJob* djobs = reinterpret_cast<const PairJob*>(m->mp_plan);
-    const int2* dwork = reinterpret_cast<const int2*>(m->mp_plan + np * sizeof(PairJob));
     hipEvent_t* ev = m->mp_ev[k & 1];
-    err = hipMemcpyAsync(m->mp_plan, hp, plan_bytes, hipMemcpyHostToDevice, m->st);
+    err = run_chunk(m, m->bank, m->bank, jobs.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax);
     if (err != hipSuccess) break;
-    (void)hipEventRecord(ev[0], m->st);
-    if (c.nwg) {
-      if (mutual_best)
-        hipLaunchKernelGGL(match_pairs_mfma_kernel<true>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, m->bank, m->bank_rfix,
-                           m->bank_cfix, djobs, dwork, m->mp_cpart, m->mp_rstate);
-      else
-        hipLaunchKernelGGL(match_pairs_mfma_kernel<false>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, m->bank,
-                           m->bank_rfix, m->bank_cfix, djobs, dwork, m->mp_cpart, m->mp_rstate);
-      hipLaunchKernelGGL(match_pairs_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, dwork + c.nwg,
-                         m->mp_rstate, m->mp_cpart, distmax, ratiomax, m->mp_rowm, m->mp_colm);
-    }
-    hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, djobs, m->mp_rowm, m->mp_colm,
-                       mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
+                       m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
     (void)hipEventRecord(ev[1], m->st);
     err = hipGetLastError();
     if (err != hipSuccess) break;
