@@ -12,7 +12,7 @@
 //                          of set 1 in registers and folds the v_mfma_i32_32x32x32_i8 tiles into RowMatch_Kernel's
 //                          per-thread states and the column partials as packed 32-bit keys; see the comment at the kernel;
 //   match_finish_kernel    per (pair, block) of a second table: merges a row's per-segment states (largest score, then
-//                          the reference's tie order: lower thread class, lower column), acos distance + ratio; and, in
+//                          the reference's tie order: the tree's thread class, lower column), acos distance + ratio; and, in
 //                          the same launch, the per-row-block (max, index, second) column partials in ascending row order
 //                          (match_col_kernel: the same for the small / guided path);
 //   match_pairs_compact_kernel  each pair's matches compacted on the device (a single pair is compacted on the host).
@@ -162,7 +162,10 @@ __device__ __forceinline__ int decide(int best, int second, int idx, float distm
 
 // RowMatch_Kernel semantics: lane = (class c = j mod 32, half); strict '>' per lane keeps its first
 // maximum; the two lanes of a class merge towards the lower j, then the classes merge with the
-// reference's own tree (partner 16, 8, 4, 2, 1 away; a tie keeps the lower class of the pair).
+// reference's own tree (partner 16, 8, 4, 2, 1 away; a tie keeps the lower class of the pair).  Among equal
+// maxima the tree does NOT keep the lowest class: the last step (partner 1 away) decides bit 0 of the class, the
+// one before bit 1, ..., so it keeps the class whose BIT-REVERSED number is smallest (class 16 beats class 1, class 2
+// beats class 1).  match_mfma_kernel and match_finish_kernel restate that order without the tree.
 __global__ __launch_bounds__(256) void match_row_kernel(const int* dotm, int num1, int num2, float distmax,
                                                         float ratiomax, int* rowm) {
   const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(256) void match_row_kernel(const int* dotm, int num
     ix = t ? j : ix;
     mx = t ? v : mx;
   }
-  // merge: first the two lanes of a class (lower j wins ties), then classes 16,8,4,2,1 apart (lower class wins)
+  // merge: first the two lanes of a class (lower j wins ties), then classes 16,8,4,2,1 apart (the lower class of each pair wins)
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     const int omx = __shfl_down(mx, d), onx = __shfl_down(nx, d), oix = __shfl_down(ix, d);
@@ -253,9 +256,9 @@ __global__ __launch_bounds__(256) void match_col_kernel(const int3* cpart, int n
 // the (max, second, index) triple took seven.  63 in the low bits = "none yet" (a score of 0 forms a key below it).
 // Column partials (max, row, second over the wavefront's rows in ascending order, ColMatch's rule, ProgramCU.cu:3510-3519)
 // the same way with key = score << 6 | (62 - row in the lane's half), formed from the row key by one add of a scalar.
-// At the end of the segment the 32 classes of a row are merged through LDS (one lane per row walks them in ascending
-// class order: the reference's tree keeps the lower thread on ties, ProgramCU.cu:3766-3780) and ONE (best, second,
-// column) per row and segment is stored.
+// At the end of the segment the 32 classes of a row are merged through LDS (one lane per row and half walks 16 of them in
+// the order in which the reference's tree prefers them on ties -- ascending BIT-REVERSED class, see match_row_kernel and
+// ProgramCU.cu:3776-3787) and ONE (best, second, column) per row and segment is stored.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
@@ -424,18 +427,21 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
     for (int reg = 0; reg < 16; reg++) rs[(reg + 16 * h) * MM_RS_PITCH + r] = make_int2(rmx[blk][reg], rnx[blk][reg]);
     __builtin_amdgcn_wave_barrier();  // (one wavefront's LDS operations complete in order)
     {
-      // lane (row r, half hh) walks the 16 classes 16 hh .. 16 hh + 15 of its row in ascending order ('>' on the score: the
-      // lower class keeps a tie); then the two halves of a row are combined the same way (the lower classes' half wins a tie)
-      const int2* const row = rs + r * MM_RS_PITCH + 16 * h;
+      // the tree's order of preference among equal scores is ascending bit-reversed class: position k = c2 + 16 hh of that
+      // order is class brev5(k) = 2 brev4(c2) + hh.  Lane (row r, half hh) walks its 16 classes (the even ones for hh = 0, the
+      // odd ones for hh = 1) in that order ('>' on the score: the earlier position keeps a tie); then the two halves of a
+      // row are combined the same way (half 0, positions 0..15, wins a tie)
+      const int2* const row = rs + r * MM_RS_PITCH + h;
       int2 s = row[0];
-      int cls = 16 * h;
+      int cls = h;
 #pragma unroll 5
       for (int c2 = 1; c2 < 16; c2++) {
-        const int2 u = row[c2];
+        const int c = 2 * (int)(__brev((unsigned)c2) >> 28);  // (uniform: scalar)
+        const int2 u = row[c];
         const bool take = (u.x >> 6) > (s.x >> 6);
         s.y = take ? max(s.x, u.y) : max(s.y, u.x);
         s.x = take ? u.x : s.x;
-        cls = take ? 16 * h + c2 : cls;
+        cls = take ? c + h : cls;
       }
       const int ox = __shfl_xor(s.x, 32), oy = __shfl_xor(s.y, 32), ocls = __shfl_xor(cls, 32);
       const bool take = (ox >> 6) > (s.x >> 6);   // (meaningful in the lanes of half 0, which store)
@@ -453,8 +459,9 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
 
 // Rows and columns of every pair of a launch: work[blockIdx.x] = (job, block); blocks [0, row blocks of the job) take its
 // rows, the rest its columns (match_col_block) -- a launch of its own for either costs more than its work: 5 us each at
-// 8192 x 8192.  Rows: merge the per-segment states in the reference's order -- largest score; equal scores: the lower
-// thread class (column mod 32: the tree keeps the lower thread), then the lower column (a thread keeps its first maximum).
+// 8192 x 8192.  Rows: merge the per-segment states in the reference's order -- largest score; equal scores: the thread
+// class (column mod 32) the tree prefers, i.e. the smaller bit-reversed class (see match_row_kernel), then the lower column
+// (a thread keeps its first maximum).
 __global__ __launch_bounds__(256) void match_finish_kernel(const PairJob* jobs, const int2* work, const int3* rstate,
                                                            const int3* cpart, float distmax, float ratiomax, int* rowm,
                                                            int* colm) {
@@ -471,8 +478,8 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const PairJob* jobs, 
   int3 s = p[0];
   for (int q = 1; q < J.nseg; q++) {
     const int3 u = p[q];
-    const bool take = u.x > s.x || (u.x == s.x && u.z >= 0 &&
-                                    (s.z < 0 || (u.z & 31) < (s.z & 31) || ((u.z & 31) == (s.z & 31) && u.z < s.z)));
+    const unsigned bu = __brev((unsigned)u.z) >> 27, bs = __brev((unsigned)s.z) >> 27;  // bit-reversed classes
+    const bool take = u.x > s.x || (u.x == s.x && u.z >= 0 && (s.z < 0 || bu < bs || (bu == bs && u.z < s.z)));
     s.y = u.x > s.x ? max(s.x, u.y) : max(s.y, u.x);
     if (take) { s.x = u.x; s.z = u.z; }
   }

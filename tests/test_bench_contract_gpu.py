@@ -125,6 +125,11 @@ def test_two_rank_control_flow_on_one_gpu(dest, tmp_path, tmp_path_factory):
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HESS_BENCH_BACKEND="gloo", HESS_BENCH_SAME_GPU="1")
+    # A prefix of this run's own for its shared memory objects: /dev/shm belongs to the node, and hessbench_* objects of
+    # another job -- or of an earlier one whose ranks were killed and could not unlink theirs -- are not this run's doing.
+    prefix = f"hessbench_t{os.getpid()}_{port}"
+    env["HESS_BENCH_SHM_PREFIX"] = prefix
+    before = set(os.listdir("/dev/shm"))
     if dest == "file":   # (HESS_SHARE_FORCE_FILE is a test hook of the developer build: the ranks load that library)
         import hessgpu_amd
         env.update(HESS_SHARE_FORCE_FILE="1", HESS_SHARE_DIR=str(tmp_path), HESS_LIB=hessgpu_amd.DEV_LIB_PATH)
@@ -157,7 +162,8 @@ def test_two_rank_control_flow_on_one_gpu(dest, tmp_path, tmp_path_factory):
         assert "node-shared result buffers:" in r.stderr
     else:
         assert "gather destination of every rank: host" in r.stderr
-    assert not [f for f in os.listdir("/dev/shm") if f.startswith("hessbench_")]
+    # nothing of this run is left: no object of its prefix (shm, file) and no new hessbench_* object at all (host)
+    assert not [f for f in os.listdir("/dev/shm") if f.startswith(prefix) or (f.startswith("hessbench_") and f not in before)]
     assert not list(tmp_path.iterdir())          # the files are gone with their contexts
     # --dump-outputs on rank 0: both ranks' lists of the last timed step, images in the order of the global batch
     out = {n: np.load(dump / f"{n}.npy") for n in ("counts", "keypoints", "descriptors")}
@@ -220,9 +226,18 @@ def test_a_rank_that_dies_mid_run_ends_the_self_launched_job():
     the exchange of that step.  The parent ends it and reports 17 -- within seconds, not after the backend's timeout."""
     import time
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1",
-                        "--contexts", "2", "--batch", "2", "--no-profile", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
-                       env=_bare_env(HESS_BENCH_BACKEND="gloo", HESS_BENCH_SAME_GPU="1", HESS_BENCH_TEST_EXIT="1:2:17"))
+    prefix = f"hessbench_dies{os.getpid()}"
+    try:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1",
+                            "--contexts", "2", "--batch", "2", "--no-profile", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+                           env=_bare_env(HESS_BENCH_BACKEND="gloo", HESS_BENCH_SAME_GPU="1", HESS_BENCH_TEST_EXIT="1:2:17",
+                                         HESS_BENCH_SHM_PREFIX=prefix))
+    finally:
+        # ranks that leave through _exit or are ended by a signal cannot unlink their shared result buffers: the test removes
+        # what its job left, so that the node is as it found it (test_two_rank_control_flow_on_one_gpu looks at /dev/shm)
+        for f in os.listdir("/dev/shm"):
+            if f.startswith(prefix):
+                os.unlink(os.path.join("/dev/shm", f))
     assert r.returncode == 17, (r.returncode, r.stderr[-2000:])
     assert "rank(s) ended non-zero" in r.stderr and "(1, 17)" in r.stderr   # (rank 0 may fail on the broken connection in the same poll)
     assert not [l for l in r.stdout.splitlines() if l.strip().startswith("{")]      # no result line from a broken job

@@ -36,8 +36,10 @@ def _single_all(m, bank, pairs, cfg):
 
 
 def _synthetic_sets(sizes, seed):
-    """Full byte range; sets drawn from one pool with noise so that different sets match; duplicated rows inside and
-    across sets (ties on rows and on columns)."""
+    """Full byte range; sets drawn from one pool with noise; duplicated rows inside and across sets.  Uniformly random bytes
+    put every dot product far above the clamp of the score, so NO pair of these sets has a match in any configuration: they
+    check sizes, chunking and that nothing overflows into a false match.  The bank cases that match, ties included, are in
+    test_matcher_ties_gpu.py."""
     rng = np.random.RandomState(seed)
     pool = rng.randint(0, 256, size=(6000, 128)).astype(np.int32)
     out = []

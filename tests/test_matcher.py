@@ -120,9 +120,11 @@ def test_gpu_matcher_bit_exact_vs_oracle():
 
 @pytest.mark.gpu
 def test_gpu_matcher_full_byte_range_sizes_and_ties():
-    """The unguided match runs on the matrix cores with signed bytes (bias 128 + exact correction), 32-row
-    blocks and column segments: full-range unsigned bytes, sizes around the block/segment boundaries and
-    heavy ties (duplicated descriptors in different segments and strided-thread classes)."""
+    """Full-range unsigned bytes on both paths (the matrix cores multiply signed bytes: bias 128 + exact correction), sizes
+    around the block/segment boundaries.  What this checks is that nothing overflows into a false match: uniformly random
+    bytes give dot products of about 2 M, eight times the 2^18 at which the score is clamped, so best and second are both at
+    distance 0 and the expected result of every case is EMPTY, duplicated rows or not.  It does not test ties; the cases
+    that match are in test_matcher_ties_gpu.py."""
     from hessgpu_amd.matcher import Matcher
 
     rng = np.random.RandomState(7)
@@ -142,6 +144,7 @@ def test_gpu_matcher_full_byte_range_sizes_and_ties():
             for dm, rm in ((2.0, 2.0), (0.9, 0.9)):
                 got = m.match(distmax=dm, ratiomax=rm, mutual_best=mutual)
                 ref = oracle_match(a, b, distmax=dm, ratiomax=rm, mutual_best=mutual)
+                assert len(ref) == 0
                 assert np.array_equal(got, ref), (n1, n2, mutual, dm, rm)
     m.close()
 
@@ -171,7 +174,9 @@ def test_siftmatchgpu_class_through_the_c_mirror():
 @pytest.mark.gpu
 def test_matrix_core_path_is_the_same_every_time():
     """The unguided match is the same every time: 300 matches of each size (ragged against the 256-row / 128-column blocks,
-    one far wider than tall), mutual best and not, every one equal to the first, which equals the oracle's.  (Written for a
+    one far wider than tall), mutual best and not, every one equal to the first, which equals the oracle's.  The inputs are
+    full-range random bytes, whose dot products all exceed the clamp: every one of these results is EMPTY (asserted); the
+    same test on inputs that match is in test_matcher_ties_gpu.py.  (Written for a
     form that finished inside the multiply launch -- the workgroup that happened to finish last merged what the others wrote --
     which was correct and 60 % slower, profiles/r06_experiments/matcher.txt; the test is what stays.)"""
     from hessgpu_amd.matcher import Matcher
@@ -187,6 +192,7 @@ def test_matrix_core_path_is_the_same_every_time():
         m.set_descriptors(1, b)
         for mutual in (True, False):
             first = m.match(max_match=max(n1, n2), mutual_best=mutual)
+            assert len(first) == 0
             if n1 * n2 < 12_000_000:
                 assert np.array_equal(first, oracle_match(a, b, max_match=max(n1, n2), mutual_best=mutual))
             for k in range(300):
