@@ -989,6 +989,15 @@ void siftmatch_set_descriptors_f32(SiftMatchGPU* m, int index, int num, const fl
 int siftmatch_get_match(SiftMatchGPU* m, int max_match, int* buf, float distmax, float ratiomax, int mbm) {
   return m->GetSiftMatch(max_match, reinterpret_cast<int(*)[2]>(buf), distmax, ratiomax, mbm);
 }
+void siftmatch_set_locations(SiftMatchGPU* m, int index, const float* loc, int gap) { m->SetFeautreLocation(index, loc, gap); }
+int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const float* H, const float* F, float distmax,
+                               float ratiomax, float hdistmax, float fdistmax, int mbm) {
+  float h[3][3], f[3][3];  // the class takes non-const arrays
+  if (H) memcpy(h, H, sizeof(h));
+  if (F) memcpy(f, F, sizeof(f));
+  return m->GetGuidedSiftMatch(max_match, reinterpret_cast<int(*)[2]>(buf), H ? h : nullptr, F ? f : nullptr, distmax,
+                               ratiomax, hdistmax, fdistmax, mbm);
+}
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { return s->RunSIFT(num, keys, have_orientation); }
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { s->SetKeypointList(num, keys, have_orientation); }
 

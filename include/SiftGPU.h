@@ -185,6 +185,10 @@ SiftMatchGPU* siftmatch_create(int max_sift);
 void siftmatch_destroy(SiftMatchGPU* m);
 void siftmatch_set_descriptors_f32(SiftMatchGPU* m, int index, int num, const float* d);
 int siftmatch_get_match(SiftMatchGPU* m, int max_match, int* buf, float distmax, float ratiomax, int mbm);
+void siftmatch_set_locations(SiftMatchGPU* m, int index, const float* loc, int gap);
+// H, F: 3x3 row-major or NULL (GetGuidedSiftMatch's rule for a missing matrix)
+int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const float* H, const float* F, float distmax,
+                               float ratiomax, float hdistmax, float fdistmax, int mbm);
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 // The resolved hess_params of the instance (what ParseParam did), for tests.
