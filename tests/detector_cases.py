@@ -1,0 +1,447 @@
+"""Inputs for the detector tests and the one checker both callers use (a plain helper module, no tests in it).
+
+check_against_model(session, case) runs a case on any Session -- the CPU oracle (tests/test_detector_model.py) or the
+product context (tests/test_detector_model_gpu.py) -- and compares it stage by stage with np_restatement.DetectorModel,
+every stage computed by the model FROM THE SESSION'S OWN PREVIOUS STAGE, so that errors do not accumulate and a failure
+names the stage and the rule:
+
+  geometry      octave sizes (decimation / up-sampling on input, -ads stepping, octave_num)                       exact
+  gauss         level 0 from the pixels (conversion, decimation, up-sampling, first blur or its skip), level l from
+                the session's level l - 1, level 0 of the next octave from the session's level `dog`               TOL_GAUSS
+  det-H, grad, theta   from the session's Gaussian level                                                            TOL_*
+  detect        the raw list from the session's det-H planes: positions, order, type; list reduction and top-K     exact *
+                offsets and response                                                                                2e-3, 1e-3
+  orient        per raw item from the session's gradient planes: number of orientations, second truncation pass    exact *
+                exported position / scale from the session's own offsets                                            one quantum
+                orientation                                                                                         one quantum
+  descriptor    a sample of <= 40, at the session's own quantised key                                               1e-4
+  (*) except at items the model flags as uncertain (np_restatement.key_test_ex, orientations_ex): either answer passes.
+
+Images come from seeds; nothing here reads a file.
+"""
+import functools
+import math
+from types import SimpleNamespace
+
+import numpy as np
+
+import fixtures
+import np_restatement as R
+from hessgpu_amd import _abi
+
+# dense planes: the bounds of tests/test_oracle_vs_numpy.py
+TOL_GAUSS = 2e-6
+TOL_DETH = 1e-5          # x max(1, max |det-H|)
+TOL_GRAD = 1e-6
+TOL_THETA = 1e-5         # where the gradient is > 1e-6
+TOL_OFFSET = 2e-3
+TOL_RESP = 1e-3          # relative
+QUANTUM = 2 * R.PI / 255.0
+TOL_DESC = 1e-4
+MAX_DESC = 40
+MAX_UNCERTAIN_SHARE = 0.01
+
+NOISE_KW = dict(dog_threshold=0.0005, edge_threshold=50.0)
+
+
+def noise(w, h, seed=None):
+    rng = np.random.RandomState(w * 131 + h if seed is None else seed)
+    return (rng.rand(h, w) * 255).astype(np.uint8)
+
+
+def blobs_noise(w=96, h=80, seed=5, amp=6.0):
+    """fixtures.synthetic_blobs plus uniform noise of +-amp grey levels: blobs for the higher octaves, noise for many
+    detections in the lower ones."""
+    rng = np.random.RandomState(1000 + seed)
+    img = fixtures.synthetic_blobs(w, h, seed).astype(np.float64) + (rng.rand(h, w) * 2 - 1) * amp
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+GRID_LAYERS = ((7, 1.9, 0.4), (15, 4.0, 0.5), (31, 8.0, 0.6))     # (period, sigma of the dots, gain)
+
+
+def dot_grid(w=160, h=120, seed=7, layers=GRID_LAYERS):
+    """Alternating bright / dark Gaussian dots on grids of three periods: a blob per dot and saddles between them, on
+    several levels of several octaves.  The amplitudes come from a set of four, so that many detections share their
+    half-precision response."""
+    rng = np.random.RandomState(seed)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    img = np.full((h, w), 0.5)
+    for period, sigma, gain in layers:
+        for cy in range(period // 2, h, period):
+            for cx in range(period // 2, w, period):
+                a = gain * (0.20 + 0.05 * rng.randint(0, 4)) * (1 if ((cx // period + cy // period) & 1) else -1)
+                img += a * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * sigma * sigma))
+    return np.clip(np.rint(img * 255), 0, 255).astype(np.uint8)
+
+
+def colour(w=96, h=80, seed=3, bright=True):
+    """u8 RGB with three different channels; bright: a third of the pixels near white (the 16-bit numerator wraps above
+    2^31 / 65535 = 32768.5 grey levels of 65535, i.e. above half of full scale)."""
+    chans = [blobs_noise(w, h, seed + i).astype(np.float64) for i in range(3)]
+    img = np.stack(chans, axis=-1)
+    if bright:
+        img[:, w // 3: 2 * w // 3] = 128 + img[:, w // 3: 2 * w // 3] / 2
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def _user_keys(w, h, seed=2):
+    """Keys inside, on and beyond the border, scales inside every level's bin, clear of the bins' ends, and beyond the
+    first and the last level."""
+    rng = np.random.RandomState(seed)
+    pts = []
+    for x in (0.0, 1.4, w / 2.0, w - 1.4, float(w)):
+        for y in (0.0, 1.6, h / 2.0, h - 0.7, float(h)):
+            pts.append((x, y, 1.7 + 3.0 * rng.rand()))
+    for s in (0.5, 1.2, 1.6, 2.0, 2.6, 3.2, 4.1, 5.0, 6.3, 8.2, 10.0, 13.0, 17.0, 40.0, 90.0):
+        pts.append((w * (0.3 + 0.4 * rng.rand()), h * (0.3 + 0.4 * rng.rand()), s))
+    keys = np.zeros(len(pts), dtype=_abi.KEYPOINT_DTYPE)
+    keys["x"], keys["y"], keys["s"] = (np.array(v, dtype=np.float32) for v in zip(*pts))
+    keys["o"] = ((keys["x"] * 0.37 + keys["y"] * 0.11 + keys["s"]) % 6.28).astype(np.float32)
+    return keys
+
+
+def _case(name, image, fmt=None, keys=None, have_orientation=1, min_features=1, **kw):
+    return SimpleNamespace(name=name, image=image, fmt=fmt, keys=keys, have_orientation=have_orientation,
+                           min_features=min_features, kw=kw)
+
+
+@functools.lru_cache(maxsize=None)
+def cases():
+    """-> {name: case}.  kw are hess_params overrides; the image is built on first use."""
+    out = []
+    for w, h in ((132, 25), (260, 49), (324, 223)):
+        out.append(_case(f"noise {w}x{h}", noise(w, h), **NOISE_KW))
+    b = blobs_noise()
+    out.append(_case("first_octave -1", b, first_octave=-1))
+    out.append(_case("first_octave -2", b, first_octave=-2))
+    out.append(_case("first_octave -5 ads", b, first_octave=-5, auto_downscale=1, tex_max_dim=200))
+    out.append(_case("first_octave 1", noise(324, 223), first_octave=1, **NOISE_KW))
+    for dog in (1, 2, 4, 5, 6):
+        out.append(_case(f"dog_level_num {dog}", b, dog_level_num=dog, dog_threshold=0.002))
+    out.append(_case("sigman 1.56", b, sigman=1.56))                       # first blur of sigma 0.36: 3 taps, clamped to 5
+    out.append(_case("factors", b, filter_width_factor=5.0, orient_window_factor=1.5, orient_gaussian_factor=1.2,
+                     desc_window_factor=2.5))
+    out.append(_case("subpixel 0", b, subpixel=0))
+    out.append(_case("half_sift", b, half_sift=1))
+    out.append(_case("max_orientation 1", b, max_orientation=1))
+    out.append(_case("half_sift max_orientation 1", b, half_sift=1, max_orientation=1))
+    out.append(_case("fixed_orientation", b, fixed_orientation=1))
+    out.append(_case("lowe_origin", b, lowe_origin=1, dog_threshold=0.004, edge_threshold=5.0))
+    out.append(_case("octave_num 2", b, octave_num=2))
+    out.append(_case("octave_num 9", b, octave_num=9))
+    out.append(_case("normalize 0", b, normalize=0))
+    out.append(_case("dynamic_indexing", b, dynamic_indexing=1))
+    g = dot_grid()
+    gk = GRID_KW
+    for name, method, thr in (("highest0", _abi.TRUNC_HIGHEST_0, GRID_THRESHOLD), ("highest1", _abi.TRUNC_HIGHEST_1, GRID_THRESHOLD),
+                              ("lowest", _abi.TRUNC_LOWEST, GRID_THRESHOLD_LOWEST)):
+        out.append(_case(f"truncate {name}", g, truncate_method=method, feature_count_threshold=thr, **gk))
+    out.append(_case("top-K", g, truncate_method=_abi.TRUNC_TOPK, feature_count_threshold=GRID_TOPK, **gk))
+    out.append(_case("top-K above the count", g, truncate_method=_abi.TRUNC_TOPK, feature_count_threshold=100000, **gk))
+    c = colour()
+    ck = COLOUR_KW
+    alpha = np.full(c.shape[:2] + (1,), 255, np.uint8)
+    out.append(_case("u8 rgb", c, **ck))
+    out.append(_case("u8 lum", c[..., 1].copy(), **ck))
+    out.append(_case("u16 rgb", c.astype(np.uint16) * 257, **ck))
+    out.append(_case("u16 lum", c[..., 1].astype(np.uint16) * 257, **ck))
+    out.append(_case("f32 lum", (c[..., 1] / 255.0).astype(np.float32), **ck))
+    out.append(_case("f32 rgb", (c / 255.0).astype(np.float32), **ck))
+    out.append(_case("f32 bgr", (c[..., ::-1] / 255.0).astype(np.float32), fmt=_abi.FMT_BGR, **ck))
+    out.append(_case("u8 rgba", np.concatenate([c, alpha], axis=2), **ck))
+    out.append(_case("u8 bgr", np.ascontiguousarray(c[..., ::-1]), fmt=_abi.FMT_BGR, **ck))
+    out.append(_case("u8 bgra", np.concatenate([c[..., ::-1], alpha], axis=2), fmt=_abi.FMT_BGRA, **ck))
+    keys = _user_keys(96, 80)
+    for ho in (1, 0):
+        out.append(_case(f"keypoint list orient={ho}", b, keys=keys, have_orientation=ho))
+        out.append(_case(f"keypoint list orient={ho} first_octave -1 lowe", b, keys=keys, have_orientation=ho, first_octave=-1,
+                         lowe_origin=1))
+    out.append(_case("keypoint list half_sift", b, keys=keys, have_orientation=0, half_sift=1))
+    out.append(_case("keypoint list max_orientation 1", b, keys=keys, have_orientation=0, max_orientation=1))
+    out.append(_case("keypoint list fixed_orientation", b, keys=keys, have_orientation=0, fixed_orientation=1))
+    return {c.name: c for c in out}
+
+
+# The dot grid has [345, 219, 34, 1, 50, 10, 2, 7] detections and [381, 282, 43, 1, 59, 14, 3, 22] features per level
+# (tests/test_detector_model.py::test_grid_thresholds_fall_inside_a_level asserts it).  120 lies inside level 1 counted from
+# the top (104 detections above it, 323 with it): the first pass keeps level 1, the second, on the 424 features, drops it
+# (424 - 282 = 142 > 120).  400 lies inside level 1 counted from the bottom.  192: the detections ranked 191, 192 and 193 by
+# abs(half(response)) are equal, so the top-K cut separates equals.
+#
+# 'truncate highest0' and 'truncate highest1' give the same features here, and at every threshold: method 1 stops generating
+# lists, walking downwards, once the levels above hold more than the threshold (PyramidCU.cpp:1314-1319), and method 0's
+# LimitFeatureCount drops a level, walking upwards, while the levels above it hold more than the threshold
+# (SiftPyramid.cpp:224-277) -- one condition, stated twice.  They differ in the work done, not in the result, so no
+# case can tell a product that mixed the two up; the pair of cases pins that both reach the common result.
+GRID_KW = dict(dog_threshold=0.0004, edge_threshold=60.0)
+# The mean of three channels, and the bright band at half contrast, leave little above the default thresholds.
+COLOUR_KW = dict(dog_threshold=0.0015, edge_threshold=20.0)
+GRID_THRESHOLD = 120
+GRID_THRESHOLD_LOWEST = 400
+GRID_TOPK = 192
+
+
+def _circ(a, b):
+    d = abs(a - b) % (2 * R.PI)
+    return min(d, 2 * R.PI - d)
+
+
+def _half(packed):
+    return float(np.array([int(packed) >> 16], dtype=np.uint16).view(np.float16)[0])
+
+
+class Mismatch(AssertionError):
+    """A stage of the session does not follow the model: .stage names it."""
+
+    def __init__(self, stage, msg):
+        super().__init__(f"[{stage}] {msg}")
+        self.stage = stage
+
+
+def _need(cond, stage, msg):
+    if not cond:
+        raise Mismatch(stage, msg() if callable(msg) else msg)
+
+
+def check_against_model(session, case, model=None, dense=True, log=None):
+    """Run `case` on `session` and compare every stage with the model (default: the right rules for session.params).
+    -> statistics: candidates, uncertain (detection), detections, features, orient_uncertain, descriptors checked and the
+    largest deviation per stage.  Raises Mismatch."""
+    m = model or R.DetectorModel(session.params)
+    img = np.asarray(case.image)
+    h, w = img.shape[:2]
+    st = dict(candidates=0, uncertain=0, orient_uncertain=0, gauss=0.0, deth=0.0, grad=0.0, theta=0.0, desc=0.0)
+    session.keep_levels(True)
+    counts = session.run(img[None], fmt=case.fmt)
+    ds, omin, geo, scales = m.plan(w, h)
+    _need(session.geometry() == geo, "geometry", lambda: f"{session.geometry()} != {geo}")
+    dog, nlev = m.dog, m.dog + 2
+
+    # ---- dense planes
+    G = [[session.level(0, oc, l, _abi.DBG_GAUSS) for l in range(nlev)] for oc in range(len(geo))]
+    D = [[session.level(0, oc, l, _abi.DBG_DETH) for l in range(nlev)] for oc in range(len(geo))]
+    GOT = [[session.level(0, oc, l, _abi.DBG_GOT).astype(np.float64) if 1 <= l <= dog else None for l in range(nlev)]
+           for oc in range(len(geo))]
+    if dense:
+        base, taps0 = m.base_plane(img, case.fmt)
+        for oc, (wa, hh) in enumerate(geo):
+            for l in range(nlev):
+                a = G[oc][l].astype(np.float64)
+                if l == 0 and oc == 0:
+                    want = base if taps0 is None else R.gaussian(base, taps0)
+                elif l == 0:
+                    want = R.downsample(G[oc - 1][dog].astype(np.float64), wa, hh)
+                else:
+                    want = R.gaussian(G[oc][l - 1].astype(np.float64), m.level_taps(l))
+                _need(a.shape == want.shape, "gauss", lambda: f"octave {oc} level {l}: shape {a.shape} != {want.shape}")
+                d = float(np.abs(a - want).max())
+                st["gauss"] = max(st["gauss"], d)
+                _need(d < TOL_GAUSS, "gauss", lambda: f"octave {oc} level {l}: max |d| {d:.3g}")
+                deth, grad, theta = R.hessian_planes(a, m.level_sigma(l))
+                d = float(np.abs(D[oc][l] - deth).max()) / max(1.0, float(np.abs(deth).max()))
+                st["deth"] = max(st["deth"], d)
+                _need(d < TOL_DETH, "det-H", lambda: f"octave {oc} level {l}: {d:.3g} of the plane's maximum")
+                if 1 <= l <= dog:
+                    got = GOT[oc][l]
+                    d = float(np.abs(got[..., 0] - grad).max())
+                    st["grad"] = max(st["grad"], d)
+                    _need(d < TOL_GRAD, "gradient", lambda: f"octave {oc} level {l}: {d:.3g}")
+                    dang = np.abs(np.angle(np.exp(1j * (got[..., 1] - theta))))
+                    sel = grad > 1e-6
+                    d = float(dang[sel].max()) if sel.any() else 0.0
+                    st["theta"] = max(st["theta"], d)
+                    _need(d < TOL_THETA, "theta", lambda: f"octave {oc} level {l}: {d:.3g}")
+
+    if case.keys is not None:
+        _check_keypoint_list(session, case, m, GOT, scales, st)
+        return st
+
+    # ---- detection from the session's det-H planes
+    raw = session.rawlist(0)
+    found, unsure = [], []
+    for oc in range(len(geo)):
+        for l in range(1, dog + 1):
+            f, u, n = m.scan(D[oc][l], D[oc][l - 1], D[oc][l + 1], G[oc][l])
+            found.append(f)
+            unsure.append(u)
+            st["candidates"] += n
+            st["uncertain"] += len(u)
+    reducing = m.fct > 0
+    full_counts = [len(f) for f in found]
+    kept = m.reduce_first(full_counts)
+    expect = [sorted(f) if k else [] for f, k in zip(found, kept)]
+    if m.method == R.TRUNC_TOPK and reducing:
+        flat = [(li, pos) for li, lst in enumerate(expect) for pos in lst]
+        resp = [found[li][pos][0] for li, pos in flat]
+        keep = m.topk(resp)
+        if len(keep) < len(flat):
+            key = sorted((abs(R.f2h(r)) for r in resp), reverse=True)
+            cut_in, cut_out = key[m.fct - 1], key[m.fct]
+            st["topk_tie_at_cut"] = int(cut_in == cut_out)
+            # a response at a rounding boundary of binary16 next to the cut would make the cut depend on float32 rounding
+            for r in resp:
+                lo, hi = abs(R.f2h(abs(r) * (1 - 32 * R.U))), abs(R.f2h(abs(r) * (1 + 32 * R.U)))
+                _need(lo == hi or hi < cut_out or lo > cut_in, "detect", f"response {r!r} decides the top-K cut by rounding")
+        expect = [[] for _ in expect]
+        for i in keep:
+            expect[flat[i][0]].append(flat[i][1])
+    if reducing:
+        _need(not any(unsure), "detect", lambda: f"uncertain detections in a case that reduces the list: {unsure}")
+    for li in range(len(expect)):
+        sel = raw[raw["level_index"] == li]
+        got = [(int(k["row"]), int(k["col"])) for k in sel]
+        bad = (set(got) ^ set(expect[li])) - unsure[li]
+        _need(not bad, "detect", lambda: f"level {li}: {len(got)} detections, model {len(expect[li])}; differ at (row, col) "
+                                         f"{sorted(bad)[:8]}")
+        _need(got == sorted(got), "detect", f"level {li}: the list is not in row-major order")
+        for k in sel:
+            pos = (int(k["row"]), int(k["col"]))
+            if pos not in found[li]:
+                continue
+            resp, typ, dx, dy, dsc = found[li][pos]
+            pk = int(k["packed"])
+            _need(pk & 4 and (pk & 3 == typ or pos in unsure[li]), "detect", f"level {li} {pos}: type {pk & 3}, model {typ}")
+            _need(abs(_half(pk) - resp) <= abs(resp) * TOL_RESP + 1e-7, "detect", f"level {li} {pos}: response {_half(pk)} model {resp}")
+            _need(max(abs(k["dx"] - dx), abs(k["dy"] - dy), abs(k["ds"] - dsc)) < TOL_OFFSET, "detect",
+                  f"level {li} {pos}: offsets {(k['dx'], k['dy'], k['ds'])} model {(dx, dy, dsc)}")
+    _need(len(raw) == sum(len(raw[raw["level_index"] == li]) for li in range(len(expect))), "detect", "level index out of range")
+    st["detections"] = len(raw)
+
+    # ---- orientation per raw item, from the session's gradient planes
+    keys, desc = session.fetch(0)
+    groups = []                                   # runs of equal (level, x, y, s): the orientations of one location
+    for i, k in enumerate(keys):
+        ident = (int(k["level"]), float(k["x"]), float(k["y"]), float(k["s"]))
+        if groups and groups[-1][0] == ident:
+            groups[-1][1].append(i)
+        else:
+            groups.append((ident, [i]))
+    items = []
+    for rk in raw:
+        li = int(rk["level_index"])
+        oc, l = li // dog, li % dog + 1
+        x, y, s = m.key_geometry(l, int(rk["row"]), int(rk["col"]), float(rk["dx"]), float(rk["dy"]), float(rk["ds"]))
+        angles, unc = m.rotations(GOT[oc][l][..., 0], GOT[oc][l][..., 1], x, y, s)
+        items.append((li, oc, l, x, y, s, angles, unc, rk))
+        st["orient_uncertain"] += int(unc)
+    multi = [0] * len(expect)
+    for it in items:
+        multi[it[0]] += len(it[6])
+    kept2 = m.reduce_second(multi) if reducing else multi
+    if reducing and m.method != R.TRUNC_TOPK:
+        _need(st["orient_uncertain"] == 0, "orient", "an uncertain orientation count in a case that truncates on the counts")
+    items = [it for it in items if kept2[it[0]] > 0 and (it[6] or it[7])]
+    _need(len(groups) == len(items), "orient", lambda: f"{len(groups)} locations among the features, model {len(items)} "
+                                                       f"(features per level {np.bincount(keys['level'], minlength=len(multi)).tolist()}, model {kept2})")
+    off = 0.0 if m.lowe_origin else 0.5
+    todo = []
+    for (ident, idx), (li, oc, l, x, y, s, angles, unc, rk) in zip(groups, items):
+        sc = scales[oc]
+        ex, ey, es = m.export(x, y, s, sc)
+        k0 = keys[idx[0]]
+        _need(ident[0] == li, "orient", f"feature {idx[0]}: level {ident[0]}, raw list {li}")
+        _need(abs(k0["x"] - ex) <= sc / 1024 * 1.01 + 1e-6 * abs(ex) and abs(k0["y"] - ey) <= sc / 1024 * 1.01 + 1e-6 * abs(ey),
+              "export", f"feature {idx[0]} level {li}: position {(k0['x'], k0['y'])}, model {(ex, ey)}")
+        _need(abs(k0["s"] - es) <= sc / 256 * 1.01, "export", f"feature {idx[0]}: scale {k0['s']}, model {es}")
+        _need(int(k0["type"]) == int(rk["packed"]) & 3 and float(k0["response"]) == _half(rk["packed"]), "export",
+              f"feature {idx[0]}: type / response differ from the raw list")
+        _need(len(idx) == len(angles) or unc, "orient", f"location {(li, int(rk['row']), int(rk['col']))}: {len(idx)} orientations, "
+                                                        f"model {len(angles)}")
+        if len(idx) == len(angles):
+            for j, a in zip(idx, angles):
+                d = _circ(float(keys[j]["o"]), m.mirrored(a))
+                _need(d <= QUANTUM + 1e-5 or unc, "orient", f"feature {j} level {li}: orientation {keys[j]['o']}, model {m.mirrored(a)}")
+        for j in idx:
+            todo.append((j, oc, l, sc))
+    st["features"] = len(keys)
+
+    # ---- descriptors: a sample, at the session's own key
+    if desc.size:
+        clipped = [t for t in todo if _clipped(keys[t[0]], t[3], m.dwf, geo[t[1]], off)]
+        pick = {t[0]: t for t in clipped[:: max(1, len(clipped) // 10)][:10]}
+        for t in todo[:: max(1, len(todo) // (MAX_DESC - len(pick)))]:
+            if len(pick) < MAX_DESC:
+                pick.setdefault(t[0], t)
+        for j, oc, l, sc in pick.values():
+            k = keys[j]
+            ang = (2 * R.PI - float(k["o"])) % (2 * R.PI)
+            d = m.descriptor(GOT[oc][l][..., 0], GOT[oc][l][..., 1], (float(k["x"]) - off) / sc + 0.5, (float(k["y"]) - off) / sc + 0.5,
+                             float(k["s"]) / sc, ang)
+            dev = float(np.abs(d - desc[j]).max())
+            st["desc"] = max(st["desc"], dev)
+            _need(dev < TOL_DESC, "descriptor", f"feature {j} level {int(k['level'])}: max |d| {dev:.3g}")
+        st["descriptors"] = len(pick)
+        st["clipped"] = len([j for j in pick if any(j == t[0] for t in clipped)])
+    return st
+
+
+def check_statistics(st, case):
+    """What both callers ask of check_against_model's statistics: the case is not empty, and the items at which either
+    answer passed -- detection and orientation decisions together -- are at most 1 % of the candidates that pass the exact
+    neighbour comparisons.  A keypoint list has no candidates: no orientation may be flagged there."""
+    assert st["features"] >= case.min_features, "the case is empty: it would prove nothing"
+    if case.keys is not None:
+        assert st["orient_uncertain"] == 0, st
+        return
+    assert st["detections"] >= 8, st
+    assert st["uncertain"] + st["orient_uncertain"] <= MAX_UNCERTAIN_SHARE * st["candidates"], st
+    assert st["descriptors"] >= min(30, st["features"]) and st["clipped"] >= 5, st
+
+
+def _clipped(k, sc, dwf, geo, off):
+    """The descriptor's footprint (half-diagonal 2 sqrt(2) x window) leaves the octave's plane."""
+    x, y, r = (float(k["x"]) - off) / sc + 0.5, (float(k["y"]) - off) / sc + 0.5, 2 * math.sqrt(2) * dwf * float(k["s"]) / sc
+    return x - r < 1.5 or y - r < 1.5 or x + r > geo[0] - 1.5 or y + r > geo[1] - 1.5
+
+
+def _check_keypoint_list(session, case, m, GOT, scales, st):
+    """RunSIFT(num, keys, flag) on the current image: level binning, fixed-point position and scale, the strongest
+    orientation only or the caller's own, descriptors -- all of it shows in the descriptor (which level's planes, where, at
+    which angle) and, without given orientations, in the returned angle."""
+    keys = case.keys
+    n = session.run_keypoints(keys, case.have_orientation)
+    _need(n == len(keys), "keylist", f"{n} features for {len(keys)} keys")
+    out, desc = session.fetch(0)
+    # -m 1 and -ofix download the list again after the orientation pass (SiftPyramid.cpp:165-172): position and scale come
+    # back through the fixed-point record, with the level; otherwise the caller's keys are returned as they came and only
+    # the descriptor shows the orientation that was found
+    downloaded = not case.have_orientation and (m.single or m.fixed_orientation)
+    worst = 0.0
+    for i, k in enumerate(keys):
+        hits = m.bin_key(k["s"], scales)
+        # a defect of the case, not of the session: no Mismatch, so that no wrong-rule test can be satisfied by it
+        assert len(hits) == 1, f"key {i} (scale {k['s']}) is on {len(hits)} levels in the model: choose another scale"
+        oc, l = hits[0] // m.dog, hits[0] % m.dog + 1
+        sc = scales[oc]
+        fx, fy, fs = m.user_key(float(k["x"]), float(k["y"]), float(k["s"]), sc)
+        grad, theta = GOT[oc][l][..., 0], GOT[oc][l][..., 1]
+        unc = False
+        if case.have_orientation:
+            ang = math.fmod(2 * R.PI - float(k["o"]), 2 * R.PI)
+        else:
+            (ang,), unc = m.rotations(grad, theta, fx, fy, fs, user=True)
+            st["orient_uncertain"] += int(unc)
+        if downloaded:
+            ex, ey, es = m.export(fx, fy, fs, sc)
+            _need(int(out[i]["level"]) == hits[0], "keylist", f"key {i} (scale {k['s']}): level {out[i]['level']}, model {hits[0]}")
+            _need(max(abs(out[i]["x"] - ex), abs(out[i]["y"] - ey)) <= 1e-6 * (1 + abs(ex) + abs(ey)) and abs(out[i]["s"] - es) <= 1e-6 * es,
+                  "keylist", f"key {i}: {(out[i]['x'], out[i]['y'], out[i]['s'])}, model {(ex, ey, es)}")
+            d = _circ(float(out[i]["o"]), m.mirrored(ang))
+            _need(d <= QUANTUM + 1e-5 or unc, "keylist", f"key {i} (level {hits[0]}): orientation {out[i]['o']}, model {m.mirrored(ang)}")
+            ang = (2 * R.PI - float(out[i]["o"])) % (2 * R.PI)
+        else:
+            _need(out[i].tobytes() == k.tobytes(), "keylist", f"key {i}: the caller's key changed")
+        if unc:
+            continue                      # (an empty window: no strongest orientation)
+        if fs == 0:
+            continue                      # a scale below 1 / 512 of a pixel: the window is empty
+        d = m.descriptor(grad, theta, fx, fy, fs, ang)
+        if not np.isfinite(d).all():      # nothing under the window: 0 / 0 in the normalisation on both sides
+            _need(not np.isfinite(desc[i]).all() or not desc[i].any(), "keylist", f"key {i}: descriptor of an empty window")
+            continue
+        dev = float(np.abs(d - desc[i]).max())
+        worst = max(worst, dev)
+        _need(dev < TOL_DESC, "keylist", f"key {i} (level {hits[0]}, scale {k['s']}): descriptor max |d| {dev:.3g}")
+    st["desc"] = worst
+    st["features"] = st["descriptors"] = len(keys)

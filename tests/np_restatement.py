@@ -25,9 +25,12 @@ def schedule(dog=3, sigma0=1.6, sigman=0.5, first_octave_ds=0):
 
 
 # ---- ProgramCU::CreateFilterKernel, ProgramCU.cu:423-453 ------------------------------------------
-def filter_taps(sigma, factor=4.0):
+def filter_taps(sigma, factor=4.0, clamp33=True):
+    """clamp33: the truncation to KERNEL_MAX_WIDTH = 33 (ProgramCU.cu:428-433), a switch for DetectorModel."""
     sz = int(math.ceil(factor * sigma - 0.5))
-    width = min(max(2 * sz + 1, 5), 33)
+    width = max(2 * sz + 1, 5)
+    if clamp33:
+        width = min(width, 33)
     sz = width // 2
     i = np.arange(-sz, sz + 1, dtype=np.float64)
     k = np.exp(-0.5 * i * i / (sigma * sigma))
@@ -120,50 +123,170 @@ def hessian_planes(g, sigma):
 
 # ---- ComputeKEY_Kernel, ProgramCU.cu:702-882 (pure Python, one pixel) -----------------------------
 def key_test(C, P, N, G, row, col, T, edge=10.0, subpixel=True):
-    """-> None or (response, type, dx, dy, ds).  C/P/N: det-H of the level / previous / next."""
-    thr0 = (0.8 if subpixel else 1.0) * T
+    """-> None or (response, type, dx, dy, ds).  C/P/N: det-H of the level / previous / next.  The rule itself is stated
+    once, in key_test_ex below, which also says how close each gate came to its threshold."""
+    return key_test_ex(C, P, N, G, row, col, T, edge, subpixel)[0]
+
+
+# ---- ComputeOrientation_Kernel, ProgramCU.cu:1221-1605 (multi-orientation branch) -----------------
+def orientations(grad, theta, x, y, s, half=False, gaussian_factor=1.5, window_factor=2.0):
+    """-> list of up to 4 rotations in bin units (rot in [0,36)), strongest first.  Stated once, in orientations_ex."""
+    return orientations_ex(grad, theta, x, y, s, half, gaussian_factor, window_factor)[0]
+
+
+# ---- ComputeDescriptor_Kernel + NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054 -----------------
+def descriptor(grad, theta, x, y, s, angle, half=False, window_factor=3.0):
+    """Stated once, in descriptor_ex."""
+    return descriptor_ex(grad, theta, x, y, s, angle, half, window_factor)
+
+
+# =====================================================================================================================
+# DetectorModel: every option of the Hessian detector, end to end on a small image, in float64.
+#
+# Written from the reference source (lines cited per rule) and SURVEY.md section 8.  A rule marked PROJECT is the
+# project's own: the reference does not state it (or cannot reach it).  Keyword switches of DetectorModel state
+# plausible WRONG rules with the same code (WRONG_RULES); tests/test_detector_model.py shows that each one is caught.
+# =====================================================================================================================
+U = 2.0 ** -24                      # unit round-off of binary32
+TEN_DEG = 5.7295779513082320876798154814105
+TRUNC_HIGHEST_0, TRUNC_HIGHEST_1, TRUNC_LOWEST, TRUNC_TOPK = 0, 1, 2, 3   # GlobalUtil.h TRUNCATE_METHOD_*
+FMT_LUM, FMT_RGB, FMT_RGBA, FMT_BGR, FMT_BGRA = 1, 3, 4, 5, 6
+
+WRONG_RULES = {
+    "top-K ties go to the higher index": dict(topk_tie_high=True),
+    "top-K keyed on the float response": dict(topk_float_key=True),
+    "second truncation pass omitted": dict(no_second_pass=True),
+    "up-sample row end clamps": dict(upsample_clamp=True),
+    "first blur not skipped": dict(no_skip=True),
+    "33-tap clamp omitted": dict(no_clamp33=True),
+    "half fold refreshes the 37th slot": dict(fold_refresh=True),
+    "single peak takes the last maximum": dict(single_last=True),
+    "subpixel=0 keeps the 0.8 factor": dict(keep08=True),
+    "16-bit RGB does not wrap": dict(no_wrap=True),
+    "level binning rounds at whole steps": dict(whole_step=True),
+    "lowe_origin offset before the octave scale": dict(lowe_before_scale=True),
+}
+
+
+def f2h(v):
+    """binary32 -> binary16 -> float, round to nearest even (__float2half_rn / half2float, GlobalUtil.cpp:588-621)."""
+    return float(np.float32(v).astype(np.float16))
+
+
+def fixed(v, bits):
+    """FLOAT_TO_FIXED_POINT, config.h:73-74: (int)(v * 2^bits + 0.5), evaluated in double."""
+    return int(v * (1 << bits) + 0.5)
+
+
+# ---- input conversion with decimation, GLTexImage.cpp:802-916 (DownSamplePixelDataI2F / F) ------------------------
+def input_plane(img, fmt=None, ds=0, no_wrap=False):
+    """-> float64 [H >> ds, (W >> ds) & ~3]: every 2^ds-th pixel of every 2^ds-th row (ws = width/ds - skip with skip the
+    columns TruncateWidthCU drops, :998-1016).  Integer types: the numerator 19595 R + 38470 G + 7471 B is an `int`
+    expression (:842), so it wraps modulo 2^32 for bright 16-bit pixels."""
+    a = np.asarray(img)
+    step = 1 << ds
+    h, w = a.shape[0] >> ds, (a.shape[1] >> ds) & ~3
+    a = a[:h * step:step, :w * step:step]
+    if a.ndim == 2:
+        if a.dtype == np.uint8:
+            return a.astype(np.float64) / 255.0
+        if a.dtype == np.uint16:
+            return a.astype(np.float64) / 65535.0
+        return a.astype(np.float64)
+    c = (2, 1, 0) if fmt in (FMT_BGR, FMT_BGRA) else (0, 1, 2)
+    if a.dtype in (np.uint8, np.uint16):
+        r, g, b = (a[..., i].astype(np.int64) for i in c)
+        num = 19595 * r + 38470 * g + 7471 * b
+        if not no_wrap:
+            num = (num + (1 << 31)) % (1 << 32) - (1 << 31)      # two's-complement int32
+        return num.astype(np.float64) / (65535.0 * (255.0 if a.dtype == np.uint8 else 65535.0))
+    r, g, b = (a[..., i].astype(np.float64) for i in c)
+    return float(np.float32(0.299)) * r + float(np.float32(0.587)) * g + float(np.float32(0.114)) * b   # :894,906
+
+
+# ---- UpsampleKernel, ProgramCU.cu:233-285: bilinear by 2^k, the source fetched by 1-D index -----------------------
+def upsample(src, k, clamp=False):
+    """Source pixel (row, col) yields 2^k output pixels of every output row dst_row >> k == row.  Its right and lower
+    neighbours are index + 1 and index + width of the FLAT plane: at the end of a row that is the next row's first
+    pixel, past the plane a texture fetch returns 0.  clamp: the WRONG rule (replicated border)."""
+    h, w = src.shape
+    S = 1 << k
+    if clamp:
+        p = np.pad(src, ((0, 1), (0, 1)), mode="edge")
+        v11, v12, v21, v22 = p[:h, :w], p[:h, 1:], p[1:, :w], p[1:, 1:]
+    else:
+        flat = np.concatenate([src.ravel(), np.zeros(w + 2)])
+        idx = np.arange(h * w).reshape(h, w)
+        v11, v12, v21, v22 = flat[idx], flat[idx + 1], flat[idx + w], flat[idx + w + 1]
+    out = np.zeros((h * S, w * S))
+    for helper in range(S):
+        w1 = helper / S
+        v1 = v21 * w1 + (1.0 - w1) * v11 if helper else v11
+        v2 = v22 * w1 + (1.0 - w1) * v12 if helper else v12
+        for i in range(S):
+            out[helper::S, i::S] = v1 * (1.0 - i / S) + v2 * (i / S) if i else v1
+    return out
+
+
+# ---- ComputeKEY_Kernel with rounding margins ------------------------------------------------------------------------
+def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False):
+    """ComputeKEY_Kernel, ProgramCU.cu:702-882 (pure Python, one pixel) -> (result, uncertain); result is None or
+    (response, type, dx, dy, ds).  uncertain: a gate value lies within 8 x a first-order bound of the
+    binary32 evaluation's error of its threshold, so the float32 implementation may decide either way (the comparisons
+    of r with its neighbours are exact on float32 planes and never flagged)."""
+    T = float(T)
+    thr0 = (0.8 if (subpixel or keep08) else 1.0) * T
     edge_t = (edge + 1.0) ** 2 / edge
-    r = C[row, col]
+    r = float(C[row, col])
+    unc = abs(abs(r) - thr0) <= 8 * U * thr0
     if abs(r) <= thr0:
-        return None
-    left, right = C[row, col - 1], C[row, col + 1]
+        return None, unc
+    left, right = float(C[row, col - 1]), float(C[row, col + 1])
     nmax, nmin = max(left, right), min(left, right)
     if nmin <= r <= nmax:
-        return None
-    state = {"nmax": nmax, "nmin": nmin}
+        return None, False
+    state = [nmax, nmin]
 
     def triple(plane, rr):
-        vals = [plane[rr, col - 1], plane[rr, col], plane[rr, col + 1]]
-        if r > state["nmax"]:
-            state["nmax"] = max([state["nmax"]] + vals)
-            return not (r < state["nmax"] or r < 0)
-        state["nmin"] = min([state["nmin"]] + vals)
-        return not (r > state["nmin"] or r > 0)
+        vals = [float(plane[rr, col - 1]), float(plane[rr, col]), float(plane[rr, col + 1])]
+        if r > state[0]:
+            state[0] = max([state[0]] + vals)
+            return not (r < state[0] or r < 0)
+        state[1] = min([state[1]] + vals)
+        return not (r > state[1] or r > 0)
 
     if not triple(C, row - 1) or not triple(C, row + 1):
-        return None
-    fxx = left + right - 2 * r
-    fyy = C[row - 1, col] + C[row + 1, col] - 2 * r
-    fxy = 0.25 * (C[row + 1, col + 1] + C[row - 1, col - 1] - C[row + 1, col - 1] - C[row - 1, col + 1])
+        return None, False
+    up, dn = float(C[row - 1, col]), float(C[row + 1, col])
+    c4 = [float(C[row + 1, col + 1]), float(C[row - 1, col - 1]), float(C[row + 1, col - 1]), float(C[row - 1, col + 1])]
+    fxx, exx = left + right - 2 * r, 3 * U * (abs(left) + abs(right) + 2 * abs(r))
+    fyy, eyy = up + dn - 2 * r, 3 * U * (abs(up) + abs(dn) + 2 * abs(r))
+    fxy, exy = 0.25 * (c4[0] + c4[1] - c4[2] - c4[3]), U * sum(abs(v) for v in c4)
     det = fxx * fyy - fxy * fxy
-    if det <= 0 or (fxx + fyy) ** 2 > edge_t * det:
-        return None
+    edet = abs(fyy) * exx + abs(fxx) * eyy + 2 * abs(fxy) * exy + 2 * U * (abs(fxx * fyy) + fxy * fxy)
+    tr = fxx + fyy
+    g = tr * tr - edge_t * det
+    eg = 2 * abs(tr) * (exx + eyy + U * abs(tr)) + U * tr * tr + edge_t * edet + 2 * U * edge_t * abs(det)
+    unc = unc or abs(det) <= 8 * edet or abs(g) <= 8 * eg
+    if det <= 0 or g > 0:
+        return None, unc
     for plane in (P, N):
         for rr in (row - 1, row, row + 1):
             if not triple(plane, rr):
-                return None
+                return None, False
     dx = dy = ds = 0.0
     resp = r
     if subpixel:
-        fx = 0.5 * (right - left)
-        fy = 0.5 * (C[row + 1, col] - C[row - 1, col])
-        fs = 0.5 * (N[row, col] - P[row, col])
-        fss = N[row, col] + P[row, col] - 2 * r
-        fxs = 0.25 * (N[row, col + 1] + P[row, col - 1] - N[row, col - 1] - P[row, col + 1])
-        fys = 0.25 * (N[row + 1, col] + P[row - 1, col] - N[row - 1, col] - P[row + 1, col])
+        pc, nc = float(P[row, col]), float(N[row, col])
+        fx, fy, fs = 0.5 * (right - left), 0.5 * (dn - up), 0.5 * (nc - pc)
+        fss = nc + pc - 2 * r
+        fxs = 0.25 * (float(N[row, col + 1]) + float(P[row, col - 1]) - float(N[row, col - 1]) - float(P[row, col + 1]))
+        fys = 0.25 * (float(N[row + 1, col]) + float(P[row - 1, col]) - float(N[row - 1, col]) - float(P[row + 1, col]))
         rows = [[fxx, fxy, fxs, -fx], [fxy, fyy, fys, -fy], [fxs, fys, fss, -fs]]
         rows = [rw if rw[0] > 0 else [-v for v in rw] for rw in rows]
         maxa = max(rw[0] for rw in rows)
+        solved = False
+        piv = [maxa]
         if maxa >= 1e-10:
             if maxa == rows[1][0]:
                 rows[0], rows[1] = rows[1], rows[0]
@@ -174,68 +297,150 @@ def key_test(C, P, N, G, row, col, T, edge=10.0, subpixel=True):
             a2 = [rows[2][0]] + [rows[2][j] - rows[2][0] * a0[j] for j in (1, 2, 3)]
             if abs(a2[1]) > abs(a1[1]):
                 a1, a2 = a2, a1
+            piv.append(abs(a1[1]))
             if abs(a1[1]) >= 1e-10:
                 a1 = a1[:2] + [a1[2] / a1[1], a1[3] / a1[1]]
                 a2 = a2[:2] + [a2[2] - a2[1] * a1[2], a2[3] - a2[1] * a1[3]]
+                piv.append(abs(a2[2]))
                 if abs(a2[2]) >= 1e-10:
+                    solved = True
                     ds = a2[3] / a2[2]
                     dy = a1[3] - ds * a1[2]
                     dx = a0[3] - ds * a0[2] - dy * a0[1]
                     resp = r + 0.5 * (dx * fx + dy * fy + ds * fs)
-                    if not (abs(resp) > T and abs(ds) < 1 and abs(dx) < 1 and abs(dy) < 1):
-                        return None
+        unc = unc or any(abs(p - 1e-10) <= 1e-11 for p in piv)       # a pivot at its guard
+        if solved:
+            A = np.array([[fxx, fxy, fxs], [fxy, fyy, fys], [fxs, fys, fss]])
+            # the solution of a 3 x 3 system in binary32: relative error <= c u cond(A), c = 8 covers the elimination
+            eoff = 8 * U * float(np.linalg.cond(A)) * max(abs(dx), abs(dy), abs(ds))
+            eresp = 2 * U * (abs(r) + abs(dx * fx) + abs(dy * fy) + abs(ds * fs)) + 0.5 * eoff * (abs(fx) + abs(fy) + abs(fs))
+            unc = unc or any(abs(abs(v) - 1.0) <= 8 * eoff for v in (dx, dy, ds)) or abs(abs(resp) - T) <= 8 * eresp
+            if not (abs(resp) > T and abs(ds) < 1 and abs(dx) < 1 and abs(dy) < 1):
+                return None, unc
     if resp < 0:
         typ = 2
     else:
-        typ = 0 if (G[row, col - 1] - 2 * G[row, col] + G[row, col + 1]) > 0 else 1
-    return resp, typ, dx, dy, ds
+        gl, gc, gr = float(G[row, col - 1]), float(G[row, col]), float(G[row, col + 1])
+        lxx = gl - 2 * gc + gr
+        unc = unc or abs(lxx) <= 8 * 3 * U * (abs(gl) + 2 * abs(gc) + abs(gr))
+        typ = 0 if lxx > 0 else 1
+    return (resp, typ, dx, dy, ds), unc
 
 
-# ---- ComputeOrientation_Kernel, ProgramCU.cu:1221-1605 (multi-orientation branch) -----------------
-def orientations(grad, theta, x, y, s, half=False, gaussian_factor=1.5, window_factor=2.0):
-    """-> list of up to 4 rotations in bin units (rot in [0,36)), strongest first."""
+def scan_level(C, P, N, G, T, edge=10.0, subpixel=True, keep08=False):
+    """All interior pixels of one level (ProgramCU.cu:702-882) -> ({(row, col): result}, {(row, col)} uncertain, number
+    of candidates).  The exact part is vectorised: |r| against a threshold loosened by its margin and r against its 26
+    neighbours with non-strict comparisons (a superset of the triple rule); key_test_ex sees the survivors only."""
+    C, P, N = (np.asarray(a, dtype=np.float32) for a in (C, P, N))
+    h, w = C.shape
+    thr0 = (0.8 if (subpixel or keep08) else 1.0) * float(T)
+    c = C[1:h - 1, 1:w - 1]
+    ge = np.ones(c.shape, bool)
+    le = np.ones(c.shape, bool)
+    for pl in (C, P, N):
+        for dy in (0, 1, 2):
+            for dx in (0, 1, 2):
+                if pl is C and dy == 1 and dx == 1:
+                    continue
+                nb = pl[dy:dy + h - 2, dx:dx + w - 2]
+                ge &= c >= nb
+                le &= c <= nb
+    cand = (np.abs(c) > thr0 * (1 - 16 * U)) & (ge | le)
+    found, unsure = {}, set()
+    for row, col in np.argwhere(cand) + 1:
+        res, unc = key_test_ex(C, P, N, G, int(row), int(col), T, edge, subpixel, keep08)
+        if unc:
+            unsure.add((int(row), int(col)))
+        if res is not None:
+            found[(int(row), int(col))] = res
+    return found, unsure, int(cand.sum())
+
+
+# ---- ComputeOrientation_Kernel, both branches, with rounding margins ------------------------------------------------
+def orientations_ex(grad, theta, x, y, s, half=False, gaussian_factor=1.5, window_factor=2.0, single=False,
+                    fold_refresh=False, single_last=False):
+    """-> (rotations in bin units, uncertain).  multi (ProgramCU.cu:1430-1489): every strict local maximum above 0.8 x the
+    largest vote, the 4 strongest, strongest first, equal weights in bin order.  single (:1398-1420, -m 1 and keypoint
+    lists): the FIRST strict maximum (`vote[i] > max_vote`), no 0.8 rule; its right neighbour is vote[index + 1], whose
+    slot 36 holds the UNFOLDED vote[0] under -half (:1381-1392).  uncertain: a comparison that decides the set or the
+    order of the peaks lies within 8 x (error bound of the two votes)."""
     h, w = grad.shape
     gs = s * gaussian_factor
     win = abs(s) * gaussian_factor * window_factor
     factor = -0.5 / (gs * gs)
     xmin, ymin = max(1.5, math.floor(x - win) + 0.5), max(1.5, math.floor(y - win) + 0.5)
     xmax, ymax = min(w - 1.5, math.floor(x + win) + 0.5), min(h - 1.5, math.floor(y + win) + 0.5)
-    vote = [0.0] * 37
-    yy = ymin
-    while yy <= ymax:
-        xx = xmin
-        while xx <= xmax:
-            d2 = (xx - x) ** 2 + (yy - y) ** 2
-            if d2 < win * win + 0.5:
-                g, t = grad[int(yy), int(xx)], theta[int(yy), int(xx)]
-                b = int(math.floor(t * 5.7295779513082320876798154814105))
-                if b < 0:
-                    b += 36
-                vote[b] += g * math.exp(d2 * factor)
-            xx += 1.0
-        yy += 1.0
+    vote = np.zeros(37)
+    err = np.zeros(37)
+    if xmax >= xmin and ymax >= ymin:
+        xs = np.arange(xmin, xmax + 0.25)
+        ys = np.arange(ymin, ymax + 0.25)
+        d2 = (xs[None, :] - x) ** 2 + (ys[:, None] - y) ** 2
+        g = grad[int(ymin):int(ymin) + len(ys), int(xmin):int(xmin) + len(xs)]
+        t = theta[int(ymin):int(ymin) + len(ys), int(xmin):int(xmin) + len(xs)] * TEN_DEG
+        inside = d2 < win * win + 0.5
+        b = np.floor(t).astype(int)
+        wgt = np.where(inside, g * np.exp(d2 * factor), 0.0)
+        near = inside & (np.abs(t - np.rint(t)) <= 4 * U * np.abs(t) + 1e-12)     # the bin itself may differ
+        # |win^2 + 0.5 - d2| tiny: membership may differ
+        edge = np.abs(d2 - (win * win + 0.5)) <= 8 * U * (d2 + win * win)
+        np.add.at(vote, b % 36, wgt)
+        cnt = np.bincount((b % 36)[inside], minlength=37)[:37]
+        err[:36] = U * (cnt[:36] + 6) * vote[:36]                                 # n additions, exp, product
+        for m in (near, edge):
+            if m.any():
+                wg = g * np.exp(d2 * factor)
+                np.add.at(err, (b % 36)[m], wg[m])
+                np.add.at(err, ((b - 1) % 36)[m], wg[m])
+                np.add.at(err, ((b + 1) % 36)[m], wg[m])
     for _ in range(6):
-        old = vote[:36]
-        for j in range(36):
-            vote[j] = (old[j - 1] + old[j] + old[(j + 1) % 36]) / 3.0
-    vote[36] = vote[0]
+        old, olde = vote[:36].copy(), err[:36].copy()
+        vote[:36] = (np.roll(old, 1) + old + np.roll(old, -1)) / 3.0
+        err[:36] = (np.roll(olde, 1) + olde + np.roll(olde, -1)) / 3.0 + 4 * U * vote[:36]
+    vote[36], err[36] = vote[0], err[0]
     if half:
-        for i in range(18):
-            vote[i] += vote[i + 18]
-            vote[i + 18] = 0.0
-    mx = max(vote[:36])
+        vote[:18] += vote[18:36]
+        err[:18] += err[18:36] + U * vote[:18]
+        vote[18:36] = 0.0
+        err[18:36] = 0.0
+        if fold_refresh:
+            vote[36], err[36] = vote[0], err[0]
+    v = vote
+    mx = float(v[:36].max())
+    unc = False
+    if single:
+        imax = 0
+        for i in range(1, 36):
+            if (v[i] >= v[imax]) if single_last else (v[i] > v[imax]):
+                imax = i
+        unc = any(i != imax and abs(v[i] - mx) <= 8 * (err[i] + err[imax]) for i in range(36))
+        pre, nxt = v[35 if imax == 0 else imax - 1], v[imax + 1]
+        den = 2 * mx - nxt - pre
+        off = 0.5 * (nxt - pre) / den if den != 0 else 0.0
+        return [imax + 0.5 + off], bool(unc) or den == 0
     peaks = []
+    imx = int(v[:36].argmax())
     for i in range(36):
-        pre, nxt = vote[i - 1] if i else vote[35], vote[i + 1]
-        if vote[i] > 0.8 * mx and vote[i] > pre and vote[i] > nxt:
-            di = 0.5 * (nxt - pre) / (2 * vote[i] - nxt - pre)
-            peaks.append((vote[i], i + di + 0.5))
-    peaks.sort(key=lambda p: -p[0])  # stable: equal weights keep bin order
-    return [p[1] for p in peaks[:4]]
+        pre, nxt = v[i - 1] if i else v[35], v[i + 1]
+        m = 8 * (err[i] + max(err[i - 1] if i else err[35], err[i + 1], err[imx]))
+        is_peak = v[i] > 0.8 * mx and v[i] > pre and v[i] > nxt
+        if v[i] > 0.8 * mx - m and v[i] > pre - m and v[i] > nxt - m:             # a peak within the margin
+            if abs(v[i] - 0.8 * mx) <= m or abs(v[i] - pre) <= m or abs(v[i] - nxt) <= m:
+                unc = True
+        if is_peak:
+            di = 0.5 * (nxt - pre) / (2 * v[i] - nxt - pre)
+            peaks.append((v[i], i + di + 0.5, err[i]))
+    peaks.sort(key=lambda p: -p[0])
+    for a, b_ in zip(peaks, peaks[1:]):                                             # the order, and who is 4th
+        if abs(a[0] - b_[0]) <= 8 * (a[2] + b_[2]):
+            unc = True
+    return [p[1] for p in peaks[:4]], bool(unc)
 
 
-# ---- ComputeDescriptor_Kernel + NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054 -----------------
-def descriptor(grad, theta, x, y, s, angle, half=False, window_factor=3.0):
+def descriptor_ex(grad, theta, x, y, s, angle, half=False, window_factor=3.0, dynamic_indexing=False, normalize=True):
+    """ComputeDescriptor_Kernel + NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054, with -di and normalize=0.  A sample whose bin coordinate is 8.0 AS A binary32 NUMBER
+    (th < 0 by less than half an ulp of 8, so th + 8 rounds up) falls into no bin, or into des[8] with -di
+    (ProgramCU.cu:1745-1776): the one place where the float64 model has to ask for the float32 value."""
     h, w = grad.shape
     spt = abs(s * window_factor)
     sn, cs = math.sin(angle), math.cos(angle)
@@ -249,28 +454,257 @@ def descriptor(grad, theta, x, y, s, angle, half=False, window_factor=3.0):
         bsz = abs(cs * spt) + abs(sn * spt)
         xmin, ymin = max(1.5, math.floor(px - bsz) + 0.5), max(1.5, math.floor(py - bsz) + 0.5)
         xmax, ymax = min(w - 1.5, math.floor(px + bsz) + 0.5), min(h - 1.5, math.floor(py + bsz) + 0.5)
-        des = [0.0] * 9
-        yy = ymin
-        while yy <= ymax:
-            xx = xmin
-            while xx <= xmax:
-                dx, dy = xx - px, yy - py
-                nx = (cs * dx + sn * dy) / spt
-                ny = (cs * dy - sn * dx) / spt
-                if abs(nx) < 1 and abs(ny) < 1:
-                    g, t = grad[int(yy), int(xx)], theta[int(yy), int(xx)]
-                    wgt = math.exp(-0.125 * ((nx + ox) ** 2 + (ny + oy) ** 2)) * (1 - abs(nx)) * (1 - abs(ny)) * g
-                    th = (anglef - t) * 4.0 / PI
-                    if th < 0:
-                        th += 8.0
-                    fo = math.floor(th)
-                    if 0 <= fo < 8:
-                        des[int(fo)] += (fo + 1 - th) * wgt
-                        des[int(fo) + 1] += (th - fo) * wgt
-                xx += 1.0
-            yy += 1.0
+        des = np.zeros(9)
+        if xmax >= xmin and ymax >= ymin:
+            xs, ys = np.arange(xmin, xmax + 0.25), np.arange(ymin, ymax + 0.25)
+            dx, dy = (xs - px)[None, :], (ys - py)[:, None]
+            nx, ny = (cs * dx + sn * dy) / spt, (cs * dy - sn * dx) / spt
+            g = grad[int(ymin):int(ymin) + len(ys), int(xmin):int(xmin) + len(xs)]
+            t = theta[int(ymin):int(ymin) + len(ys), int(xmin):int(xmin) + len(xs)]
+            ok = (np.abs(nx) < 1) & (np.abs(ny) < 1)
+            wgt = np.exp(-0.125 * ((nx + ox) ** 2 + (ny + oy) ** 2)) * (1 - np.abs(nx)) * (1 - np.abs(ny)) * g
+            th = (anglef - t) * 4.0 / PI
+            th = np.where(th < 0, th + 8.0, th)
+            th = np.where(th.astype(np.float32) >= np.float32(8.0), 8.0, th)
+            fo = np.floor(th)
+            ok &= (fo >= 0) & ((fo <= 8) if dynamic_indexing else (fo < 8))
+            fo_i = fo.astype(int)[ok]
+            np.add.at(des, fo_i, ((fo + 1 - th) * wgt)[ok])
+            hi = fo_i + 1
+            np.add.at(des, hi[hi <= 8], ((th - fo) * wgt)[ok][hi <= 8])
         des[0] += des[8]
         out.extend([des[k] + des[k + 4] for k in range(4)] if half else des[:8])
     d = np.array(out)
+    if not normalize:
+        return d
     d = np.minimum(0.2, d / np.sqrt((d * d).sum()))
     return d / np.sqrt((d * d).sum())
+
+
+class DetectorModel:
+    """One parameter set -> every rule of the path as a method.  `params` is anything with the fields of hess_params
+    (a Session's .params, or a dict); a field that is 0 takes the default ParseSiftParam gives it (SiftGPU.cpp:491-563)."""
+
+    def __init__(self, params=None, **wrong):
+        if params is None or isinstance(params, dict):
+            table = params or {}
+            get = table.get
+        else:
+            get = lambda k, d: getattr(params, k)
+        self.wrong = dict(topk_tie_high=False, topk_float_key=False, no_second_pass=False, upsample_clamp=False,
+                          no_skip=False, no_clamp33=False, fold_refresh=False, single_last=False, keep08=False,
+                          no_wrap=False, whole_step=False, lowe_before_scale=False)
+        assert set(wrong) <= set(self.wrong), wrong
+        self.wrong.update(wrong)
+        self.dog = int(get("dog_level_num", 3)) or 3
+        self.sigma0 = float(get("sigma0", 1.6)) or float(np.float32(1.6))
+        self.sigman = float(get("sigman", 0.5)) or 0.5
+        self.T = float(get("dog_threshold", 0.0)) or float(np.float32(0.02) / np.float32(self.dog))
+        self.edge = float(get("edge_threshold", 10.0)) or 10.0
+        self.fwf = float(get("filter_width_factor", 4.0))
+        self.owf = float(get("orient_window_factor", 2.0))
+        self.ogf = float(get("orient_gaussian_factor", 1.5))
+        self.dwf = float(get("desc_window_factor", 3.0))
+        self.first_octave = int(get("first_octave", 0))
+        self.octave_num = int(get("octave_num", -1))
+        self.subpixel = bool(get("subpixel", 1))
+        self.max_orientation = int(get("max_orientation", 2))
+        self.fixed_orientation = bool(get("fixed_orientation", 0))
+        self.lowe_origin = bool(get("lowe_origin", 0))
+        self.half = bool(get("half_sift", 0))
+        self.normalize = bool(get("normalize", 1))
+        self.method = int(get("truncate_method", 0))
+        self.fct = int(get("feature_count_threshold", -1))
+        self.maxd = int(get("tex_max_dim", 3200))
+        self.ads = bool(get("auto_downscale", 0))
+        self.di = bool(get("dynamic_indexing", 0))
+        k = 2.0 ** (1.0 / self.dog)
+        self.sigma_step = k
+        dsigma0 = self.sigma0 * math.sqrt(k * k - 1.0)
+        self.inter = [dsigma0 * k ** i for i in range(self.dog + 1)]                 # SiftGPU.cpp:547-556
+        self.single = self.max_orientation == 1                                     # ProgramCU.cu:1398
+
+    # -- schedule ---------------------------------------------------------------------------------------------------
+    def level_sigma(self, l):
+        return self.sigma0 * 2.0 ** (l / self.dog)                                  # SiftGPU.cpp:1422-1425
+
+    def initial_sigma(self, octave_min):
+        """GetInitialSmoothSigma, SiftGPU.cpp:482-489: 0 = no blur when sa <= sb + 0.001.  PROJECT: 'no blur' leaves
+        the plane as it is; the reference would build a 5-tap table from sigma = 0, which is NaN (ProgramCU.cu:440-445)."""
+        sa, sb = self.sigma0, self.sigman / 2.0 ** octave_min
+        if sa > sb + 0.001:
+            return math.sqrt(sa * sa - sb * sb)
+        return math.sqrt(abs(sa * sa - sb * sb)) if self.wrong["no_skip"] else 0.0
+
+    def taps(self, sigma):
+        return filter_taps(sigma, self.fwf, clamp33=not self.wrong["no_clamp33"])
+
+    def level_taps(self, l, octave_min=0):
+        """Taps of the blur that produces level l (l = 0: the first blur; None when it is skipped)."""
+        if l == 0:
+            s = self.initial_sigma(octave_min)
+            return self.taps(s) if s > 0 else None
+        return self.taps(self.inter[l - 1])
+
+    # -- geometry: GLTexImage.cpp:933-982 (ds on input), PyramidCU.cpp:113-176 (InitPyramid), :232-310 -----------------
+    def plan(self, w, h):
+        """-> (ds, octave_min, [(aligned width, height)], [scale of every octave]).  ds: log2 of the decimation on input;
+        octave_min < 0: log2 of the up-sampling.  A pyramid that would still begin below the input's resolution after the
+        -ads stepping (octave_min > 0 with ds == 0) does not occur for inputs that fit tex_max_dim and is not modelled."""
+        fo, ds = self.first_octave, 0
+        ws, hs = w, h
+        if fo > 0:                                                                   # _PreProcessOnCPU = 1, GlobalUtil.cpp:79
+            ds, ws, hs = fo, w >> fo, h >> fo
+        while ws > self.maxd or hs > self.maxd:
+            if not self.ads:
+                raise ValueError("too big without auto_downscale")
+            ds, ws, hs = ds + 1, ws >> 1, hs >> 1
+        if ds == 0:
+            w &= ~3
+            fo = max(-3, fo)                                                         # "can't upsample by more than 8", :132
+            wp, hp = (w << -fo, h << -fo) if fo < 0 else (w, h)
+            omin = fo
+        else:
+            omin, wp, hp = 0, (w >> ds) & ~3, h >> ds
+        while wp > self.maxd or hp > self.maxd:                                      # :154-166, whatever the sign of omin
+            if not self.ads:
+                raise ValueError("too big without auto_downscale")
+            omin, wp, hp = omin + 1, wp >> 1, hp >> 1
+        assert not (omin > 0 and ds == 0)
+        nmax = max(1, int(math.floor(math.log(min(wp, hp)) / math.log(2.0))) - 3)    # :238-245
+        # PROJECT: an octave_num beyond the automatic count is capped to it (the reference would allocate empty octaves)
+        n = self.octave_num if 1 <= self.octave_num < nmax else nmax
+        geo, scales = [], []
+        sc = 2.0 ** (omin + ds)
+        for _ in range(n):
+            geo.append((((wp + 3) // 4) * 4, hp))
+            scales.append(sc)
+            wp, hp, sc = wp >> 1, hp >> 1, sc * 2
+        return ds, omin, geo, scales
+
+    def base_plane(self, img, fmt=None):
+        """-> (level 0 of the first octave BEFORE the first blur, taps of the first blur or None)."""
+        a = np.asarray(img)
+        ds, omin, _, _ = self.plan(a.shape[1], a.shape[0])
+        lum = input_plane(a, fmt, ds, no_wrap=self.wrong["no_wrap"])
+        if omin < 0:
+            lum = upsample(lum, -omin, clamp=self.wrong["upsample_clamp"])           # PyramidCU.cpp:1523-1524
+        return lum, self.level_taps(0, omin + ds)
+
+    # -- detection --------------------------------------------------------------------------------------------------
+    def scan(self, C, P, N, G):
+        return scan_level(C, P, N, G, np.float32(self.T), self.edge, self.subpixel, keep08=self.wrong["keep08"])
+
+    def reduce_first(self, counts):
+        """Per-level counts (octave-major, ascending) -> counts kept after list generation and the first LimitFeatureCount.
+        PyramidCU.cpp:1283-1345: -tc2 walks octaves and levels downwards, -tc2 and -tc3 stop generating lists once the
+        running total EXCEEDS the threshold; SiftPyramid.cpp:224-277: -tc3 keeps levels from the bottom while the total is
+        below the threshold, the others drop levels from the bottom while the rest still exceeds it."""
+        c = list(counts)
+        if self.fct <= 0 or self.method == TRUNC_TOPK:
+            return c
+        if self.method in (TRUNC_HIGHEST_1, TRUNC_LOWEST):
+            order = range(len(c) - 1, -1, -1) if self.method == TRUNC_HIGHEST_1 else range(len(c))
+            total = 0
+            for i in order:
+                if total > self.fct:
+                    c[i] = 0
+                total += c[i]
+        return self.limit(c)
+
+    def limit(self, c):
+        c = list(c)
+        if self.fct <= 0 or self.method == TRUNC_TOPK:
+            return c
+        if self.method == TRUNC_LOWEST:
+            i = new = 0
+            while new < self.fct and i < len(c):
+                new += c[i]
+                i += 1
+            return c[:i] + [0] * (len(c) - i)
+        total, i = sum(c), 0
+        while total - c[i] > self.fct:
+            total -= c[i]
+            c[i] = 0
+            i += 1
+        return c
+
+    def reduce_second(self, multi_counts):
+        """After the multi-orientation reshape the counts are those of the FEATURES and LimitFeatureCount(1) runs again
+        on them (SiftPyramid.cpp:140-147); not with -m 1, -ofix (no reshape) or top-K (:213-214)."""
+        if self.wrong["no_second_pass"] or self.single or self.fixed_orientation:
+            return list(multi_counts)
+        return self.limit(multi_counts)
+
+    def topk(self, responses):
+        """responses of the whole list in list order -> sorted indices kept (PyramidCU.cpp:1881-1987): the K largest
+        abs(half(r')); skipped when the list is shorter than K.  PROJECT: equal keys go to the lower list index (the
+        reference's bitonic sort leaves their order to the network)."""
+        n, K = len(responses), self.fct
+        if self.method != TRUNC_TOPK or K <= 0 or n < K:
+            return list(range(n))
+        key = [abs(float(r)) if self.wrong["topk_float_key"] else abs(f2h(r)) for r in responses]
+        order = sorted(range(n), key=lambda i: (-key[i], -i if self.wrong["topk_tie_high"] else i))
+        return sorted(order[:K])
+
+    # -- orientation and export ---------------------------------------------------------------------------------------
+    def key_geometry(self, l, row, col, dx, dy, ds):
+        """ProgramCU.cu:1281-1298: position and scale of a detection in its octave."""
+        s = self.level_sigma(l)
+        if self.subpixel:
+            return col + 0.5 + dx, row + 0.5 + dy, s * self.sigma_step ** ds
+        return col + 0.5, row + 0.5, s
+
+    def rotations(self, grad, theta, x, y, s, user=False):
+        """-> (angles handed to the descriptor in radians, un-mirrored; uncertain).  -ofix: 0 (num_orientation = 0, :1312)."""
+        if self.fixed_orientation:
+            return [0.0], False
+        single = self.single or user
+        rots, unc = orientations_ex(grad, theta, x, y, s, self.half, self.ogf, self.owf, single=single,
+                                    fold_refresh=self.wrong["fold_refresh"], single_last=self.wrong["single_last"])
+        if single:
+            return [rots[0] / TEN_DEG], unc                                           # :1415
+        out = []
+        for rot in rots:
+            fr = rot / 36.0
+            if fr < 0:
+                fr += 1.0
+            out.append(math.floor(fr * 255.0) * 2 * PI / 255.0)                       # :1481-1486, PyramidCU.cpp:764
+        return out, unc
+
+    def export(self, xf, yf, sf, scale):
+        """PyramidCU.cpp:1097-1122: fixed-point record -> host keypoint."""
+        fx, fy, fs = fixed(xf, 10) / 1024.0, fixed(yf, 10) / 1024.0, (fixed(sf, 8) & 0xFFFF) / 256.0
+        off = 0.0 if self.lowe_origin else 0.5
+        if self.lowe_origin and self.wrong["lowe_before_scale"]:
+            return scale * (fx - 1.0) + 0.5, scale * (fy - 1.0) + 0.5, scale * fs
+        return scale * (fx - 0.5) + off, scale * (fy - 0.5) + off, scale * fs
+
+    @staticmethod
+    def mirrored(angle):
+        return math.fmod(2 * PI - angle, 2 * PI)                                      # PyramidCU.cpp:1134
+
+    def descriptor(self, grad, theta, x, y, s, angle):
+        return descriptor_ex(grad, theta, x, y, s, angle, self.half, self.dwf, self.di, self.normalize)
+
+    # -- keypoint lists, PyramidCU.cpp:555-718 ------------------------------------------------------------------------
+    def bin_key(self, s, scales):
+        """-> index of the level (octave * dog + level - 1) a caller's keypoint of scale s is put on, as a list (one entry, or two where the
+        catch-alls overlap a bin; the caller asks for exactly one): half a level
+        step either side of the level's sigma, the first and the last level catching everything beyond."""
+        step = 2.0 ** ((1.0 if self.wrong["whole_step"] else 0.5) / self.dog)
+        s = float(s)
+        hits = []
+        for o, sc in enumerate(scales):
+            for l in range(1, self.dog + 1):
+                ls = float(np.float32(self.level_sigma(l) * sc))
+                lo, hi = (ls, ls * step) if self.wrong["whole_step"] else (ls / step, ls * step)
+                if lo <= s < hi or (s < lo and o == 0 and l == 1) or (s > hi and o == len(scales) - 1 and l == self.dog):
+                    hits.append(o * self.dog + l - 1)
+        return hits
+
+    def user_key(self, x, y, s, scale):
+        """-> fixed-point position and scale in the octave (PyramidCU.cpp:616-657)."""
+        off = 0.0 if self.lowe_origin else 0.5
+        fx, fy, fs = (x - off) / scale + 0.5, (y - off) / scale + 0.5, s / scale
+        return (fixed(fx, 10) & 0xFFFFFF) / 1024.0, (fixed(fy, 10) & 0xFFFFFF) / 1024.0, (fixed(fs, 8) & 0xFFFF) / 256.0
