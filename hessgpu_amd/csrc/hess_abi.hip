@@ -199,13 +199,35 @@ int hess_reserve(hess_ctx* c, int width, int height, int batch) {
   return prime(c, width, height, batch);
 }
 
-static int check_run_args(hess_ctx* c, const void* pixels, int width, int height, int pitch, int batch, int format,
-                          int pixtype) {
+static size_t pix_bytes(int pixtype) { return pixtype == HESS_PIX_U8 ? 1 : pixtype == HESS_PIX_U16 ? 2 : 4; }
+
+// Everything a layout can be refused for is refused here, before anything is read or enqueued (include/hess_abi.h, above
+// hess_run_host).  `device`: the pointer is dereferenced by the kernels themselves, so it must be aligned to the channel
+// type; host pixels are copied bytewise into the context's own (aligned) staging area first.
+static int check_run_args(hess_ctx* c, const void* pixels, int width, int height, int pitch, size_t image_stride, int batch,
+                          int format, int pixtype, bool device) {
   if (!c) return HESS_ERR_ARG;
   if (refuse_poisoned(c)) return HESS_ERR_DEVICE;
   if (!pixels || width <= 0 || height <= 0 || batch <= 0 || pitch <= 0 || !fmt_channels(format) ||
       pixtype < HESS_PIX_U8 || pixtype > HESS_PIX_F32) {
     set_err(c, "bad argument");
+    return HESS_ERR_ARG;
+  }
+  const size_t esz = pix_bytes(pixtype), row = (size_t)width * fmt_channels(format) * esz;
+  if ((size_t)pitch < row) {
+    set_err(c, "pitch %d is below the %zu bytes of one row (width * channels * bytes per channel): rows would overlap", pitch, row);
+    return HESS_ERR_ARG;
+  }
+  if ((size_t)pitch % esz) {
+    set_err(c, "pitch %d is not a multiple of the channel type's size %zu", pitch, esz);
+    return HESS_ERR_ARG;
+  }
+  if (image_stride % esz) {
+    set_err(c, "image_stride %zu is not a multiple of the channel type's size %zu", image_stride, esz);
+    return HESS_ERR_ARG;
+  }
+  if (device && (uintptr_t)pixels % esz) {
+    set_err(c, "dev_pixels %p is not aligned to the channel type's size %zu", pixels, esz);
     return HESS_ERR_ARG;
   }
   return 0;
@@ -243,7 +265,7 @@ void chain_stamp_done(hess_ctx* c, double wait0) {
 
 int hess_submit_device(hess_ctx* c, const void* dev_pixels, int width, int height, int pitch, size_t image_stride,
                        int batch, int format, int pixtype) {
-  int rc = check_run_args(c, dev_pixels, width, height, pitch, batch, format, pixtype);
+  int rc = check_run_args(c, dev_pixels, width, height, pitch, image_stride, batch, format, pixtype, true);
   if (rc) return rc;
   if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -285,13 +307,16 @@ int hess_run_device(hess_ctx* c, const void* dev_pixels, int width, int height, 
 // (a hipMemcpyAsync from pageable memory does both).
 int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int pitch, size_t image_stride, int batch,
                      int format, int pixtype) {
-  int rc = check_run_args(c, pixels, width, height, pitch, batch, format, pixtype);
+  int rc = check_run_args(c, pixels, width, height, pitch, image_stride, batch, format, pixtype, false);
   if (rc) return rc;
   if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   c->batch = c->pyramid_batch = 0;  // the results and the pyramid of the run before are gone from here on
   if (!c->pend && !(c->pend = new (std::nothrow) PendingRun())) { set_err(c, "out of memory"); return HESS_ERR_NOMEM; }
-  const size_t bytes = (size_t)(batch - 1) * image_stride + (size_t)height * pitch;
+  // From the first pixel to the last one and not a byte more: the last row's padding is not the caller's to give (a ROI
+  // that ends in the last row of a frame, images side by side in one row of pitch bytes).  No kernel reads a row's padding.
+  const size_t bytes = (size_t)(batch - 1) * image_stride + (size_t)(height - 1) * pitch +
+                       (size_t)width * fmt_channels(format) * pix_bytes(pixtype);
   rc = ensure(c, c->stage, bytes + 16);
   if (rc) return rc;
   hipPointerAttribute_t at;

@@ -241,7 +241,11 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
     }
     bool first_fused = false;  // levels 0 and 1 of octave 0 came out of one launch (level 0 never written)
     if (o == 0 && direct_u8 && c->has_taps0 && !c->no_first_fusion && s.level_max >= 2 && s.level_ds != 1 && chain_from != 0 &&
-        gauss_first_available(c->taps0, s.taps[1])) {  // (decided BEFORE the profile scope: a refused launch must not book bytes)
+        gauss_first_available(c->taps0, s.taps[1])) {
+      // Decided BEFORE the profile scope: a refused launch must not book bytes.  The tap counts are the one refusal of
+      // launch_gauss_first that can still fire here: its alignment clauses (pitch % 4, img_stride % 4) repeat what
+      // direct_u8 already requires, and level_job(0, 1) has the plane pointers it asks for.  An unaligned pitch, image
+      // stride or base never gets this far: it goes through convert_kernel (tests/test_input_layouts_gpu.py).
       // u8 pixels -> level 0 (LDS) -> level 1, det-H of level 0: the level-0 plane is nobody's input but level 1's
       // (and, with the DoG detector, D_1's: the level is stored then)
       const GaussJob j1 = level_job(0, 1);

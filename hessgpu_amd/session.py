@@ -62,21 +62,40 @@ class Session:
 
     @staticmethod
     def _describe(images, fmt):
-        a = np.ascontiguousarray(images)
+        """-> (array that owns the pixels, batch, height, width, pitch, image_stride, format, pixel type).  An array whose
+        rows are contiguous runs of pixels is handed over as it lies in memory, with its own row pitch and image stride (a
+        region of interest of larger frames, padded rows, images side by side, one image repeated); anything else -- a
+        negative or misaligned stride, a channel axis that is not contiguous -- is copied into the packed layout."""
+        a = np.asarray(images)
         if a.dtype not in _PIX_BY_DTYPE:
             raise TypeError(f"unsupported pixel dtype {a.dtype}")
         if a.ndim == 2:
             a = a[None]
-        if a.ndim == 3:  # [B,H,W] luminance
-            nch = 1
-        elif a.ndim == 4:
-            nch = a.shape[3]
-        else:
+        if a.ndim not in (3, 4):   # [B,H,W] luminance or [B,H,W,C]
             raise ValueError("images must be [H,W], [B,H,W] or [B,H,W,C]")
+        nch = 1 if a.ndim == 3 else a.shape[3]
         b, h, w = a.shape[:3]
+        isz = a.dtype.itemsize
+        row = w * nch * isz
+        pitch, stride = a.strides[1], a.strides[0]
+        rows_contiguous = a.strides[2] == nch * isz and (a.ndim == 3 or a.strides[3] == isz)
+        if h == 1:
+            pitch = row        # (a dimension of one element has no stride of its own)
+        if b == 1:
+            stride = pitch * h
+        if not (a.size and rows_contiguous and pitch >= row and stride >= 0 and pitch % isz == 0 and stride % isz == 0
+                and pitch < 2 ** 31):
+            a = np.ascontiguousarray(a)
+            pitch, stride = row, row * h
         fmt = fmt or _FMT_BY_CHANNELS[nch]
-        pitch = w * nch * a.dtype.itemsize
-        return a, b, h, w, pitch, pitch * h, fmt, _PIX_BY_DTYPE[a.dtype]
+        return a, b, h, w, pitch, stride, fmt, _PIX_BY_DTYPE[a.dtype]
+
+    @staticmethod
+    def _layout(width, height, channels, pixtype, pitch, image_stride):
+        """pitch / image_stride of a raw pointer: None means packed rows / images back to back."""
+        isz = {_abi.PIX_U8: 1, _abi.PIX_U16: 2, _abi.PIX_F32: 4}[pixtype]
+        pitch = width * channels * isz if pitch is None else pitch
+        return pitch, pitch * height if image_stride is None else image_stride
 
     # -- the path ------------------------------------------------------------------------
     def run(self, images, fmt=None):
@@ -87,30 +106,33 @@ class Session:
         self._batch = b
         return [self.count(i) for i in range(b)]
 
-    def run_device(self, dev_ptr, batch, height, width, channels=1, pixtype=_abi.PIX_U8, fmt=None):
-        """Pixels already in HBM (raw device pointer, e.g. torch tensor .data_ptr())."""
+    def run_device(self, dev_ptr, batch, height, width, channels=1, pixtype=_abi.PIX_U8, fmt=None, pitch=None,
+                   image_stride=None):
+        """Pixels already in HBM (raw device pointer, e.g. torch tensor .data_ptr()); pitch / image_stride in bytes,
+        None = packed."""
         fmt = fmt or _FMT_BY_CHANNELS[channels]
-        isz = {_abi.PIX_U8: 1, _abi.PIX_U16: 2, _abi.PIX_F32: 4}[pixtype]
-        pitch = width * channels * isz
+        pitch, image_stride = self._layout(width, height, channels, pixtype, pitch, image_stride)
         self._check(self._f["run_device"](self._h, C.c_void_p(dev_ptr), width, height, pitch,
-                                          pitch * height, batch, fmt, pixtype))
+                                          image_stride, batch, fmt, pixtype))
         self._batch = batch
 
-    def submit_device(self, dev_ptr, batch, height, width, channels=1, pixtype=_abi.PIX_U8, fmt=None):
+    def submit_device(self, dev_ptr, batch, height, width, channels=1, pixtype=_abi.PIX_U8, fmt=None, pitch=None,
+                      image_stride=None):
         """Asynchronous half of run_device: enqueue on the context's stream and return."""
         fmt = fmt or _FMT_BY_CHANNELS[channels]
-        isz = {_abi.PIX_U8: 1, _abi.PIX_U16: 2, _abi.PIX_F32: 4}[pixtype]
-        pitch = width * channels * isz
+        pitch, image_stride = self._layout(width, height, channels, pixtype, pitch, image_stride)
         self._check(self._f["submit_device"](self._h, C.c_void_p(dev_ptr), width, height, pitch,
-                                             pitch * height, batch, fmt, pixtype))
+                                             image_stride, batch, fmt, pixtype))
         self._batch = batch
 
-    def submit_host(self, images=None, fmt=None, ptr=None, batch=None, height=None, width=None):
+    def submit_host(self, images=None, fmt=None, ptr=None, batch=None, height=None, width=None, pitch=None,
+                    image_stride=None):
         """Asynchronous half of run(): host pixels (a numpy array, or a raw host pointer `ptr` to `batch` u8
-        luminance images, e.g. a pinned torch tensor's .data_ptr()) -> enqueue transfer + path, return."""
+        luminance images, e.g. a pinned torch tensor's .data_ptr(), rows `pitch` and images `image_stride` bytes apart,
+        None = packed) -> enqueue transfer + path, return."""
         if ptr is not None:
-            pitch = width
-            self._check(self._f["submit_host"](self._h, C.c_void_p(ptr), width, height, pitch, pitch * height, batch,
+            pitch, image_stride = self._layout(width, height, 1, _abi.PIX_U8, pitch, image_stride)
+            self._check(self._f["submit_host"](self._h, C.c_void_p(ptr), width, height, pitch, image_stride, batch,
                                                _abi.FMT_LUM, _abi.PIX_U8))
             self._batch = batch
             return
@@ -190,6 +212,12 @@ class Session:
         k, d, cap = C.c_void_p(), C.c_void_p(), C.c_int()
         self._check(self._f["device_results"](self._h, C.byref(k), C.byref(d), C.byref(cap)))
         return k.value, d.value, cap.value
+
+    def last_input(self, nbytes):
+        """The first `nbytes` bytes of the span the last run() / submit_host() handed over (product only; hess_last_input)."""
+        out = np.zeros(nbytes, dtype=np.uint8)
+        self._check(self._f["last_input"](self._h, out.ctypes.data_as(C.c_void_p), nbytes))
+        return out
 
     def keep_levels(self, on=True):
         """Product: also store the top Gaussian level of every octave (never materialised by default) so that

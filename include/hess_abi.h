@@ -205,8 +205,23 @@ int hess_reserve(hess_ctx* ctx, int width, int height, int batch);
 
 /* Replaces SiftGPU::RunSIFT(w,h,data,fmt,type) -> GLTexInput::SetImageData (CUDA branch,
  * GLTexImage.cpp:918-1036) -> SiftPyramid::RunSIFT (SiftPyramid.cpp:53-198) for `batch`
- * independent images of identical size laid out back to back (`image_stride` bytes apart,
- * rows `pitch` bytes apart).  Host pointer version: pixels are copied to the device. */
+ * independent images of identical size (`image_stride` bytes apart, rows `pitch` bytes apart).
+ * Host pointer version: pixels are copied to the device.
+ *
+ * Layout (the same for all four hess_run_* / hess_submit_* entry points).  Pixel (x, y) of image b starts at byte
+ * b * image_stride + y * pitch + x * channels * bytes_per_channel of `pixels`; the pixels of a row are contiguous.
+ *   - pitch >= width * channels * bytes_per_channel.  Anything beyond the row's bytes is padding: never read by a kernel,
+ *     and -- with host pixels -- not copied beyond the last pixel.  The span the library touches is exactly
+ *     (batch - 1) * image_stride + (height - 1) * pitch + width * channels * bytes_per_channel  bytes from `pixels`, so a
+ *     region of interest may end in the last row of the caller's allocation.  hess_last_input retains that span.
+ *   - image_stride is free otherwise: 0 (one image `batch` times), below pitch (images side by side in one row of `pitch`
+ *     bytes), pitch * height (back to back) or larger (frames with a gap, a region of interest of larger frames).
+ *   - for 16-bit and float pixels pitch and image_stride are multiples of the channel type's size, and a DEVICE pointer is
+ *     aligned to it (a host pointer need not be: host pixels are copied bytewise first).
+ * HESS_ERR_ARG with a hess_last_error text naming the argument for: a pitch below the row's bytes; a pitch, image_stride
+ * or device pointer that breaks the rule for 16-bit and float pixels.  Refused before anything is read or enqueued.
+ * Alignment beyond that is a matter of speed, not of results: u8 luminance whose pitch, image_stride and device address
+ * are multiples of 4 is read by the first Gaussian kernel directly; every other layout goes through one conversion pass. */
 int hess_run_host(hess_ctx* ctx, const void* pixels, int width, int height, int pitch,
                   size_t image_stride, int batch, int format, int pixtype);
 /* Asynchronous pair: hess_submit_device enqueues the whole path on the context's stream and returns;

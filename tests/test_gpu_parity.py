@@ -13,6 +13,7 @@ import pytest
 import fixtures
 from hessgpu_amd import _abi
 from oracle_lib import OracleSession
+from parity_compare import assert_same_features as _assert_same_features, compare_all as _compare_all
 
 pytestmark = pytest.mark.gpu
 
@@ -58,55 +59,6 @@ def _assert_tied_to_reference_order(g, imgs, kw, what, threads=16):
     else:  # a float order: within rounding of the sequential one (tests/test_descriptor_order.py: 1e-6), as far from the formula as it
         assert worst["seq"] <= 1e-6 and worst["exact"] <= worst["seq_exact"] + 1e-6, f"{what}: {worst}"
     return worst
-
-
-def _assert_same_features(gk, gd, ok, od, what):
-    assert len(gk) == len(ok), f"{what}: feature count {len(gk)} != oracle {len(ok)}"
-    assert np.array_equal(gk["level"], ok["level"]) and np.array_equal(gk["type"], ok["type"]), f"{what}: level/type"
-    for f in ("x", "y", "s", "o", "response"):
-        if not np.array_equal(gk[f], ok[f]):
-            d = np.max(np.abs(gk[f].astype(np.float64) - ok[f].astype(np.float64)))
-            assert d <= TOL, f"{what}: keypoint field {f} max abs diff {d}"
-            pytest.fail(f"{what}: keypoint field {f} within 1e-4 (max {d}) but not bit-exact")
-    if od.size:
-        if not np.array_equal(gd.view(np.uint32), od.view(np.uint32)):
-            d = np.nanmax(np.abs(gd.astype(np.float64) - od.astype(np.float64)))
-            bad = np.sum(np.any(gd.view(np.uint32) != od.view(np.uint32), axis=1))
-            assert d <= TOL, f"{what}: descriptors max abs diff {d} ({bad} rows differ)"
-            pytest.fail(f"{what}: descriptors within 1e-4 (max {d}, {bad} rows) but not bit-exact")
-
-
-def _compare_all(g, o, imgs, what, stages=True):
-    g.keep_levels(stages)   # the top Gaussian level of an octave is only written to HBM on request (hess_debug_keep_levels)
-    ng = g.run(imgs)
-    no = o.run(imgs)
-    assert g.geometry() == o.geometry()
-    if stages:
-        nlev = o.params.dog_level_num + 2
-        for b in range(len(no)):
-            for oc in range(len(o.geometry())):
-                for l in range(nlev):
-                    a, r = g.level(b, oc, l, _abi.DBG_GAUSS), o.level(b, oc, l, _abi.DBG_GAUSS)
-                    assert np.array_equal(a.view(np.uint32), r.view(np.uint32)), \
-                        f"{what}: gauss img {b} oct {oc} lvl {l}: {np.sum(a != r)} px differ, max {np.max(np.abs(a - r))}"
-                for l in range(nlev):
-                    a, r = g.level(b, oc, l, _abi.DBG_DETH), o.level(b, oc, l, _abi.DBG_DETH)
-                    assert np.array_equal(a.view(np.uint32), r.view(np.uint32)), \
-                        f"{what}: det-H img {b} oct {oc} lvl {l}: {np.sum(a != r)} px differ, max {np.max(np.abs(a - r))}"
-                for l in range(1, nlev - 1):
-                    a, r = g.level(b, oc, l, _abi.DBG_GOT), o.level(b, oc, l, _abi.DBG_GOT)
-                    assert np.array_equal(a.view(np.uint32), r.view(np.uint32)), \
-                        f"{what}: grad/theta img {b} oct {oc} lvl {l}: {np.sum(a != r)} values differ"
-    for b in range(len(no)):
-        gl, ol = g.rawlist(b), o.rawlist(b)
-        assert len(gl) == len(ol), f"{what}: img {b} list length {len(gl)} != {len(ol)}"
-        assert gl.tobytes() == ol.tobytes(), f"{what}: img {b} detection list differs"
-    assert ng == no, f"{what}: feature counts {ng} != {no}"
-    for b in range(len(no)):
-        gk, gd = g.fetch(b)
-        ok, od = o.fetch(b)
-        _assert_same_features(gk, gd, ok, od, f"{what} img {b}")
-    return no
 
 
 def test_math_functions_bit_exact(gpu_ctx_factory):
