@@ -122,8 +122,12 @@ void hess_destroy(hess_ctx* c) {
   for (auto& ep : c->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   for (auto e : c->pool) (void)hipEventDestroy(e);
   if (c->st) (void)hipStreamDestroy(c->st);
-  delete c->pend;
   delete c;
+}
+
+static int refuse_pending(hess_ctx* c) {
+  if (c->run.active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
+  return 0;
 }
 
 static int refuse_poisoned(hess_ctx* c) {
@@ -142,7 +146,7 @@ static int refuse_poisoned(hess_ctx* c) {
 // own (the staging area may hold the caller's last input, hess_last_input) and leaves no results behind.
 // HESS_NO_PRIME_BATCH=1 switches it off (A/B).
 static int prime(hess_ctx* c, int width, int height, int batch) {
-  if (c->pend && c->pend->active) return 0;
+  if (c->run.active) return 0;
   choose_delivery(c, batch);
   if (c->delivery == kDeliverDma && c->batch == 0 && c->keys.p && c->h_keys.p && c->h_keys.bytes >= 64 && !c->cp.has_job) {
     Copier& cp = c->cp;
@@ -176,7 +180,8 @@ static int prime(hess_ctx* c, int width, int height, int batch) {
     void* const px = c->prime_px.p;
     int rc = 0;
     if (hipMemsetAsync(px, 0, bytes, c->st) != hipSuccess) rc = HESS_ERR_DEVICE;
-    const PendingRun r{px, width, height, width, batch, HESS_FMT_LUM, HESS_PIX_U8, (size_t)width * height, 0.0, false, false};
+    PendingRun r{.dev = px, .width = width, .height = height, .pitch = width, .batch = batch, .format = HESS_FMT_LUM,
+                 .pixtype = HESS_PIX_U8, .image_stride = (size_t)width * height};  // (a local: the stored run keeps its geometry)
     if (!rc) rc = submit_impl(c, r);
     if (!rc) rc = wait_impl(c, r);
     (void)hipStreamSynchronize(c->st);
@@ -263,30 +268,38 @@ void chain_stamp_done(hess_ctx* c, double wait0) {
 }
 }  // namespace
 
+// What hess_submit_* begin with: the checks; then the results and the pyramid of the run before are gone.
+static int begin_submit(hess_ctx* c, const void* pixels, int width, int height, int pitch, size_t image_stride, int batch,
+                        int format, int pixtype, bool device) {
+  if (int rc = check_run_args(c, pixels, width, height, pitch, image_stride, batch, format, pixtype, device)) return rc;
+  if (int rc = refuse_pending(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->batch = c->pyramid_batch = 0;
+  c->accepted_submit = true;
+  return 0;
+}
+
 int hess_submit_device(hess_ctx* c, const void* dev_pixels, int width, int height, int pitch, size_t image_stride,
                        int batch, int format, int pixtype) {
-  int rc = check_run_args(c, dev_pixels, width, height, pitch, image_stride, batch, format, pixtype, true);
+  int rc = begin_submit(c, dev_pixels, width, height, pitch, image_stride, batch, format, pixtype, true);
   if (rc) return rc;
-  if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->batch = c->pyramid_batch = 0;  // the results and the pyramid of the run before are gone from here on
-  if (!c->pend && !(c->pend = new (std::nothrow) PendingRun())) { set_err(c, "out of memory"); return HESS_ERR_NOMEM; }
-  *c->pend = PendingRun{dev_pixels, width, height, pitch, batch, format, pixtype, image_stride, 0.0, false, false};
+  c->run = PendingRun{.dev = dev_pixels, .width = width, .height = height, .pitch = pitch, .batch = batch, .format = format,
+                      .pixtype = pixtype, .image_stride = image_stride};
   chain_stamp_submit(c, true);
-  rc = submit_impl(c, *c->pend);
+  rc = submit_impl(c, c->run);
   chain_stamp_submit(c, false);
   if (rc) return rc;
-  c->pend->active = true;
+  c->run.active = true;
   return 0;
 }
 
 int hess_wait(hess_ctx* c) {
   if (!c) return HESS_ERR_ARG;
-  if (!c->pend || !c->pend->active) { set_err(c, "nothing submitted"); return HESS_ERR_STATE; }
+  if (!c->run.active) { set_err(c, "nothing submitted"); return HESS_ERR_STATE; }
   HIP_TRY(c, hipSetDevice(c->device));
-  c->pend->active = false;
+  c->run.active = false;
   const double wait0 = g_stamps.on && g_stamps.base ? g_stamps.now() : 0.0;
-  const int rc = wait_impl(c, *c->pend);
+  const int rc = wait_impl(c, c->run);
   if (!rc) chain_stamp_done(c, wait0);
   return rc;
 }
@@ -307,18 +320,16 @@ int hess_run_device(hess_ctx* c, const void* dev_pixels, int width, int height, 
 // (a hipMemcpyAsync from pageable memory does both).
 int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int pitch, size_t image_stride, int batch,
                      int format, int pixtype) {
-  int rc = check_run_args(c, pixels, width, height, pitch, image_stride, batch, format, pixtype, false);
+  int rc = begin_submit(c, pixels, width, height, pitch, image_stride, batch, format, pixtype, false);
   if (rc) return rc;
-  if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->batch = c->pyramid_batch = 0;  // the results and the pyramid of the run before are gone from here on
-  if (!c->pend && !(c->pend = new (std::nothrow) PendingRun())) { set_err(c, "out of memory"); return HESS_ERR_NOMEM; }
   // From the first pixel to the last one and not a byte more: the last row's padding is not the caller's to give (a ROI
   // that ends in the last row of a frame, images side by side in one row of pitch bytes).  No kernel reads a row's padding.
   const size_t bytes = (size_t)(batch - 1) * image_stride + (size_t)(height - 1) * pitch +
                        (size_t)width * fmt_channels(format) * pix_bytes(pixtype);
   rc = ensure(c, c->stage, bytes + 16);
   if (rc) return rc;
+  c->run = PendingRun{.dev = c->stage.p, .width = width, .height = height, .pitch = pitch, .batch = batch, .format = format,
+                      .pixtype = pixtype, .image_stride = image_stride};  // (the pixels will be in the staging area)
   hipPointerAttribute_t at;
   const bool pinned = hipPointerGetAttributes(&at, pixels) == hipSuccess && at.type == hipMemoryTypeHost;
   if (pinned && c->user_keys.empty() && !c->no_host_upload) {
@@ -347,19 +358,8 @@ int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int
         up = hsa_amd_memory_async_copy(c->stage.p, cp.gpu_agent, pixels, pi.agentOwner, bytes, 0, nullptr, cp.sig_in);
       if (up == HSA_STATUS_SUCCESS) {
         c->last_input_bytes = bytes;
-        *c->pend = PendingRun{c->stage.p, width, height, pitch, batch, format, pixtype, image_stride, 0.0, false, false};
-        {
-          std::lock_guard<std::mutex> lk(cp.mu);
-          cp.batch = batch;
-          cp.upload_first = true;
-          cp.run = c->pend;
-          cp.nparts = 1;
-          cp.part_features = false;
-          cp.done = false;
-          cp.has_job = true;
-          cp.cv.notify_all();
-        }
-        c->pend->active = true;
+        copier_post(c, &c->run, true);
+        c->run.active = true;
         return 0;
       }
     }
@@ -414,10 +414,10 @@ int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int
   }
   HIP_TRY(c, hipEventRecord(c->ev_load[1], c->st));
   c->last_input_bytes = bytes;
-  *c->pend = PendingRun{c->stage.p, width, height, pitch, batch, format, pixtype, image_stride, 0.0, false, true};
-  rc = submit_impl(c, *c->pend);
+  c->run.timed_load = true;
+  rc = submit_impl(c, c->run);
   if (rc) return rc;
-  c->pend->active = true;
+  c->run.active = true;
   return 0;
 }
 
@@ -432,39 +432,38 @@ int hess_run_host(hess_ctx* c, const void* pixels, int width, int height, int pi
 
 int hess_last_input(hess_ctx* c, void* out, size_t bytes) {
   if (!c || !out) return HESS_ERR_ARG;
-  if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
+  if (refuse_pending(c)) return HESS_ERR_STATE;
   if (!c->last_input_bytes || bytes > c->last_input_bytes) { set_err(c, "no host input of that size is retained"); return HESS_ERR_STATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpy(out, c->stage.p, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
-int hess_set_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation) {
-  if (!c || num < 0 || (num > 0 && !keys)) return HESS_ERR_ARG;
+// The caller's key list for the next run (nothing thrown crosses the C ABI).
+static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation, bool on_current) {
   try {
     c->user_keys.assign(keys, keys + num);
   } catch (...) { c->user_keys.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
   c->user_have_orientation = keys_have_orientation != 0;
-  c->user_on_current = false;
+  c->user_on_current = on_current;
   return 0;
+}
+
+int hess_set_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation) {
+  if (!c || num < 0 || (num > 0 && !keys)) return HESS_ERR_ARG;
+  return store_user_keys(c, keys, num, keys_have_orientation, false);
 }
 
 int hess_run_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation) {
   if (!c || num <= 0 || !keys) return HESS_ERR_ARG;
   if (refuse_poisoned(c)) return HESS_ERR_DEVICE;
   if (!c->planned || c->pyramid_batch < 1) { set_err(c, "no current image: run an image first"); return HESS_ERR_STATE; }
-  if (c->pend && c->pend->active) { set_err(c, "a submitted batch is still pending: call hess_wait first"); return HESS_ERR_STATE; }
+  if (refuse_pending(c)) return HESS_ERR_STATE;
   HIP_TRY(c, hipSetDevice(c->device));
-  try {
-    c->user_keys.assign(keys, keys + num);
-  } catch (...) { c->user_keys.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
-  c->user_have_orientation = keys_have_orientation != 0;
-  c->user_on_current = true;
-  if (!c->pend) { c->user_keys.clear(); set_err(c, "no current image"); return HESS_ERR_STATE; }
-  PendingRun r = *c->pend;  // geometry of the current image
+  if (int rc = store_user_keys(c, keys, num, keys_have_orientation, true)) return rc;
+  PendingRun r = c->run;  // geometry of the current image (a local: the stored run keeps its batch)
   if (r.width <= 0) { c->user_keys.clear(); set_err(c, "no current image"); return HESS_ERR_STATE; }
-  r.batch = 1;
-  r.t_load_ms = 0.0;
+  r.batch = 1; r.t_load_ms = 0.0;
   const int keep_pyramid = c->pyramid_batch;
   c->batch = 0;  // results of the run before: gone; the pyramid stays (that is the point of this entry)
   int rc = submit_impl(c, r);
@@ -561,7 +560,7 @@ int hess_share_results(hess_ctx* c, const char* name) {
     set_err(c, "hess_share_results: the name must be 1..200 characters without '/'");
     return HESS_ERR_ARG;
   }
-  if (c->pend) { set_err(c, "a batch is in flight"); return HESS_ERR_ARG; }
+  if (c->accepted_submit) { set_err(c, "hess_share_results: call before the context's first batch"); return HESS_ERR_ARG; }
   if (c->share_dir) { set_err(c, "the results of this context are shared already (as %s)", c->share.c_str()); return HESS_ERR_ARG; }
   HIP_TRY(c, hipSetDevice(c->device));
   char dir[256];

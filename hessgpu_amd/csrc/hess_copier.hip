@@ -191,7 +191,7 @@ void copier_main(hess_ctx* c) {
   for (;;) {
     cp.cv.wait(lk, [&] { return cp.stop || cp.has_job; });
     if (cp.stop) return;
-    const int batch = cp.batch;
+    const int batch = cp.run->batch;
     lk.unlock();
     int rc = 0;
     bool overflow = false;
@@ -215,25 +215,20 @@ void copier_main(hess_ctx* c) {
       }
       PendingRun& r = *cp.run;
       r.t_load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      cp.nparts = 1;
-      cp.part_features = false;
       if (!rc) {
         try {
           rc = enqueue(c, r.dev, r.pitch, r.image_stride, r.batch, r.format, r.pixtype);
         } catch (...) { rc = HESS_ERR_NOMEM; snprintf(msg, sizeof(msg), "out of host memory (copier)"); }
         if (!rc && (e = hipEventRecord(cp.ev_done, c->st)) != hipSuccess) fail("hipEventRecord", e);
         if (rc && !msg[0]) snprintf(msg, sizeof(msg), "%s", c->err.c_str());
-        if (!rc) {  // (a half-run enqueue leaves no parts to wait for)
-          cp.nparts = c->nparts;
-          cp.part_features = c->part_features;
-          for (int k = 0; k < Copier::kMaxParts; k++) cp.part_end[k] = c->part_end[k];
-        }
       }
     }
     // Several parts when the batch's descriptors were launched in groups of images (nparts > 1): a group's results
     // cross while the next group is computed; else one part behind the last kernel.  The counts (and the overflow
     // words) are in the pinned count block since feature_scan_kernel, i.e. before any of the events.
-    const int nparts = cp.nparts > 1 ? cp.nparts : 1;
+    // (hess_ctx::parts says why no lock is needed; after a failed upload or a half-run enqueue rc is set: no parts to wait for)
+    const Parts& parts = c->parts;
+    const int nparts = parts.n;
     if (!rc && (e = hipEventSynchronize(nparts > 1 ? cp.ev_part[0] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
     if (!rc) {
       const int* hs = (const int*)c->h_small.p;
@@ -268,8 +263,8 @@ void copier_main(hess_ctx* c) {
       for (int k = 0; k < nparts; k++) {
         if (k > 0 && (e = hipEventSynchronize(k < nparts - 1 ? cp.ev_part[k] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
         // features of the images so far -- or, of one image's list, the bound the part's launch formed (k_feature.hip, feature_part)
-        const size_t upto = overflow ? 0 : (k == nparts - 1 ? total : cp.part_features ? (size_t)((long long)total * (k + 1) / nparts)
-                                                                                     : (size_t)hs[cp.part_end[k]]);
+        const size_t upto = overflow ? 0 : (k == nparts - 1 ? total : parts.features ? (size_t)((long long)total * (k + 1) / nparts)
+                                                                                   : (size_t)hs[parts.end[k]]);
         copy_part(done_feats, upto - done_feats);
         done_feats = upto;
       }
@@ -341,9 +336,21 @@ void choose_delivery(hess_ctx* c, int batch) {
   c->host_direct = d == kDeliverMirror;
 }
 
+// The one hand-off to the copier thread: `run` (which outlives the job: hess_ctx::run, or a local of a caller that waits
+// before it returns) and whether the thread is to wait for the pixels' upload and enqueue the batch itself.
+void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
+  Copier& cp = c->cp;
+  std::lock_guard<std::mutex> lk(cp.mu);
+  cp.run = run;
+  cp.upload_first = upload_first;
+  cp.done = false;
+  cp.has_job = true;
+  cp.cv.notify_all();
+}
+
 // Enqueue the whole path (the per-image counts reach the pinned count block by feature_scan_kernel's own stores);
 // returns without waiting.
-int submit_inner(hess_ctx* c, const PendingRun& r) {
+int submit_inner(hess_ctx* c, PendingRun& r) {
   if (!c->user_keys.empty() && r.batch != 1) {
     set_err(c, "a keypoint list applies to a single image");
     return HESS_ERR_ARG;
@@ -356,23 +363,14 @@ int submit_inner(hess_ctx* c, const PendingRun& r) {
   if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   if (c->delivery == kDeliverDma) {
-    Copier& cp = c->cp;
-    HIP_TRY(c, hipEventRecord(cp.ev_done, c->st));
-    std::lock_guard<std::mutex> lk(cp.mu);
-    cp.batch = r.batch;
-    cp.upload_first = false;
-    cp.nparts = c->nparts;
-    cp.part_features = c->part_features;
-    for (int k = 0; k < Copier::kMaxParts; k++) cp.part_end[k] = c->part_end[k];
-    cp.done = false;
-    cp.has_job = true;
-    cp.cv.notify_all();
+    HIP_TRY(c, hipEventRecord(c->cp.ev_done, c->st));
+    copier_post(c, &r, false);
   }
   return 0;
 }
 
 // (nothing thrown crosses the C ABI: enqueue_user builds host vectors)
-int submit_impl(hess_ctx* c, const PendingRun& r) {
+int submit_impl(hess_ctx* c, PendingRun& r) {
   try {
     return submit_inner(c, r);
   } catch (...) {
@@ -384,7 +382,7 @@ int submit_impl(hess_ctx* c, const PendingRun& r) {
 // Wait for the submitted batch, grow storage and re-run if a list overflowed; with kDeliverBlit bring the
 // keypoints and descriptors of the whole batch to the host with one transfer each (the other modes have
 // delivered them by now).
-int wait_inner(hess_ctx* c, const PendingRun& r) {
+int wait_inner(hess_ctx* c, PendingRun& r) {
   int rc;
   int* hs = (int*)c->h_small.p;
   const int batch = r.batch;
@@ -398,8 +396,8 @@ int wait_inner(hess_ctx* c, const PendingRun& r) {
       HIP_TRY(c, hipStreamSynchronize(c->st));
     }
     const int of_raw = hs[batch + 1], of_feat = hs[batch + 2];
-    if (hs[batch + 3]) {  // raised by a kernel that gave up a bounded wait (topk_select_kernel's look-back): no results
-      set_err(c, "device-side wait did not complete (top-K look-back); the batch has no results");
+    if (hs[batch + 3]) {  // a kernel gave up a bounded wait (extrema_place_kernel: the image's flag; topk_select_kernel: its look-back): no results
+      set_err(c, "device-side wait did not complete (extrema placement's flag wait or top-K look-back); the batch has no results");
       return HESS_ERR_DEVICE;
     }
     if (!of_raw && !of_feat) break;
@@ -472,7 +470,7 @@ int wait_inner(hess_ctx* c, const PendingRun& r) {
   return 0;
 }
 
-int wait_impl(hess_ctx* c, const PendingRun& r) {
+int wait_impl(hess_ctx* c, PendingRun& r) {
   try {
     return wait_inner(c, r);
   } catch (...) {  // the host-side count / keypoint-list vectors

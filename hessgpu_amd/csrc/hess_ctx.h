@@ -107,16 +107,17 @@ constexpr size_t kStagerHelpFrom = (size_t)8 << 20;
 using namespace hess;
 
 
+// One batch's pixels and their layout, built with designated initialisers (what is not named is zero).
 struct PendingRun {
-  const void* dev;
-  int width, height, pitch, batch, format, pixtype;
-  size_t image_stride;
-  double t_load_ms;
-  bool active;
-  bool timed_load;  // ev_load[] bracket a host->device transfer of this batch
+  const void* dev = nullptr;
+  int width = 0, height = 0, pitch = 0, batch = 0, format = 0, pixtype = 0;
+  size_t image_stride = 0;
+  double t_load_ms = 0.0;
+  bool active = false;      // submitted and not yet waited for
+  bool timed_load = false;  // ev_load[] bracket a host->device transfer of this batch
 };
 
-// Result delivery ("Result delivery and PCIe").  Three ways for the packed keypoints and
+// Result delivery ("Result delivery").  Three ways for the packed keypoints and
 // descriptors of a batch to reach pinned host memory:
 //   kDeliverMirror  the descriptor kernel stores them into the pinned buffers as well (posted PCIe writes out of the
 //                   kernel): no command after the kernels, the shortest path for one image -- but a kernel that waits
@@ -138,18 +139,14 @@ struct Copier {
   std::mutex mu;
   std::condition_variable cv;
   bool started = false, stop = false, has_job = false, done = true;
-  int batch = 0;
   int rc = 0;            // result of the last job (hess_status)
   bool overflow = false; // the batch overflowed its feature storage: nothing was copied
   char err[320] = "";    // message of the last failed job (a fixed array: the copier thread must not throw)
   hipStream_t cs = nullptr;     // copy-only stream (fallback path)
   hipEvent_t ev_done = nullptr; // recorded on the context's stream behind the last kernel of a batch
-  // A batch's descriptors may be launched in up to kMaxParts groups of images; ev_part[k] is recorded behind group k
-  // (the last group's event is ev_done), part_end[k] = first image after group k.  nparts <= 1: one launch.
+  // A batch's descriptors may come from up to kMaxParts launches (hess_ctx::parts); ev_part[k] is recorded behind launch k, ev_done behind the last.
   static constexpr int kMaxParts = 4;
   hipEvent_t ev_part[kMaxParts - 1] = {nullptr, nullptr, nullptr};
-  int nparts = 1, part_end[kMaxParts] = {0, 0, 0, 0};
-  bool part_features = false;  // the parts are ranges of ONE image's features (part k ends at feature n (k + 1) / nparts), not groups of images
   // ROCr side (SDMA): agents owning the device / pinned host buffers, engine, completion signal
   bool hsa_ready = false, hsa_failed = false;
   hsa_agent_t gpu_agent{}, cpu_agent{};
@@ -157,14 +154,21 @@ struct Copier {
   uint32_t engine_in = 0;       // the same for the host->device upload of pinned pixels
   hsa_signal_t sig{}, sig2{};   // one completion signal per copy in flight (keypoints, descriptors), each armed with 1: tools that
                                 // interpose on ROCr (rocprofv3 --memory-copy-trace) expect exactly that of a copy's signal
-  // A job that begins with the batch's pixels still on their way (hess_submit_host, pinned input): the upload is an
-  // SDMA copy started by the submitting thread with sig_in as its completion signal; the copier thread waits for it ON
-  // THE HOST and only then enqueues the kernels -- no command that waits for the transfer ever sits in a hardware
-  // queue, which the context's stream shares with other contexts.
+  // The job (copier_post): the run to deliver and whether it begins with the batch's pixels still on their way
+  // (hess_submit_host, pinned input).  Then the upload is an SDMA copy started by the submitting thread with sig_in as
+  // its completion signal; the copier thread waits for it ON THE HOST and only then enqueues the kernels -- no command
+  // that waits for the transfer ever sits in a hardware queue, which the context's stream shares with other contexts.
+  PendingRun* run = nullptr;
   bool upload_first = false;
   bool have_sig_in = false;
   hsa_signal_t sig_in{};
-  PendingRun* run = nullptr;
+};
+
+// The descriptor launches of the batch being enqueued (choose_parts, hess_schedule.hip): n groups of images, end[k] = first
+// image after group k -- or, for ONE image, n ranges of its features (part k ends at feature total (k + 1) / n, DescParams::part).
+struct Parts {
+  int n = 1, end[Copier::kMaxParts] = {0, 0, 0, 0};
+  bool features = false;
 };
 
 // Persistent helper threads that copy pageable input pixels into the context's pinned staging buffer
@@ -243,8 +247,11 @@ struct hess_ctx {
   bool host_direct = false;        // delivery == kDeliverMirror for the submitted batch
   bool host_fits = false;          // the pinned result buffers hold the worst case of the current plan
   int delivery = kDeliverMirror;   // of the submitted batch (choose_delivery)
-  int nparts = 1, part_end[Copier::kMaxParts] = {0, 0, 0, 0};  // the submitted batch's descriptor launches (groups of images)
-  bool part_features = false;      // ... or, for one large image, ranges of its features (DescParams::part)
+  // The one copy; the copier thread reads it without a lock.  enqueue() writes it: on the submitting thread BEFORE that thread
+  // takes cp.mu to post the job (copier_post), or on the copier thread itself when the job uploads first.  Nothing writes it
+  // while a job is posted: every entry that enqueues refuses while run.active, hess_reserve's dry batch returns early then,
+  // and wait_inner's regrow loop resubmits only after it has seen cp.done under cp.mu.
+  Parts parts;
   size_t mirror_max_bytes = policy::kMirrorMaxBytes;   // (dev: HESS_MIRROR_MAX_MB)
   size_t last_result_bytes = 0;    // keypoints + descriptors the last batch delivered, and its size
   int last_result_batch = 0;
@@ -273,7 +280,8 @@ struct hess_ctx {
   long long primed_shapes[4] = {-1, -1, -1, -1};  // shapes (width, height, batch) hess_reserve has run a dry batch for
   unsigned primed_next = 0;
   DevBuf prime_px;                 // the dry batch's scratch image (zero pixels)
-  PendingRun* pend = nullptr;      // batch submitted with hess_submit_device and not yet waited for
+  PendingRun run;                  // the batch submitted last: pending while run.active, then the current image's geometry (width 0: none)
+  bool accepted_submit = false;    // hess_submit_* has accepted a batch at least once (hess_share_results comes before that)
   // user-supplied keypoint list (SiftPyramid::SetKeypointList): used by the next run, then cleared
   std::vector<hess_keypoint> user_keys;
   bool user_have_orientation = false;
@@ -354,7 +362,8 @@ int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_valu
 int copier_start(hess_ctx* c);
 void copier_stop(hess_ctx* c);
 void choose_delivery(hess_ctx* c, int batch);
-int submit_impl(hess_ctx* c, const PendingRun& r);
-int wait_impl(hess_ctx* c, const PendingRun& r);
+void copier_post(hess_ctx* c, PendingRun* run, bool upload_first);
+int submit_impl(hess_ctx* c, PendingRun& r);
+int wait_impl(hess_ctx* c, PendingRun& r);
 
 }  // namespace hess

@@ -90,6 +90,66 @@ static inline float first_octave_sigma(const hess_ctx* c) {
 
 int enqueue_user(hess_ctx* c);
 
+// Orientation stage (GetFeatureOrientations).  existing: a caller's keypoints -- position and scale as packed, one angle written.
+static OrientParams orient_params(const hess_ctx* c, bool existing) {
+  const hess_params& p = c->p;
+  OrientParams op;
+  op.gaussian_factor = p.orient_gaussian_factor;
+  op.sample_factor = p.orient_gaussian_factor * p.orient_window_factor;  // ProgramCU.cu:1638
+  op.ln_sigma_step = c->sch.ln_sigma_step;
+  op.num_orientation = p.fixed_orientation ? 0 : p.max_orientation;      // ProgramCU.cu:1639
+  op.subpixel = existing ? 0 : p.subpixel;
+  op.half_sift = p.half_sift;
+  op.existing = existing ? 1 : 0;
+  op.two_peaks = !existing && c->sch.detector == HESS_DETECTOR_DOG && op.num_orientation > 1;
+  for (int l = 0; l < kMaxLev; l++) op.level_sigma[l] = l <= c->sch.level_max ? c->sch.level_sigma[l] : 0.0f;
+  return op;
+}
+
+// Descriptor stage (GetFeatureDescriptors).  user: a caller's keypoints -- one float angle each, never the fixed-point pixel order.
+static DescParams desc_params(const hess_ctx* c, int pixtype, bool user) {
+  const hess_params& p = c->p;
+  DescParams dsp;
+  dsp.window_factor = p.desc_window_factor;
+  dsp.half_sift = p.half_sift;
+  dsp.normalize = p.normalize;
+  dsp.multi = (user || !c->multi) ? 0 : (c->sch.detector == HESS_DETECTOR_DOG ? 2 : 1);
+  dsp.lowe_origin = p.lowe_origin;
+  dsp.octave_sigma = first_octave_sigma(c);  // PyramidCU.cpp:746-748
+  dsp.dog = c->g.dog;
+  dsp.dynamic_indexing = p.dynamic_indexing ? 1 : 0;
+  dsp.hkeys = c->host_direct ? (HostKeypoint*)c->h_keys.p : nullptr;
+  dsp.hdesc = (c->host_direct && c->dim) ? (float*)c->h_desc.p : nullptr;
+  dsp.first_image = 0; dsp.part = 0; dsp.part_den = 1;  // (one launch over the whole list)
+  dsp.xcd_block = c->desc_xcd_block; dsp.px_band = c->desc_px_band;
+  dsp.sequential = p.descriptor_order == HESS_DESC_ORDER_SEQUENTIAL;
+  // the pixel order's fixed point assumes luminance in [0, 1] (8- and 16-bit inputs); float pixels are taken as they are
+  // and keep the interleaved order (the test oracle applies the same rule)
+  dsp.pixel = !user && p.descriptor_order == HESS_DESC_ORDER_PIXEL && pixtype != HESS_PIX_F32;
+  return dsp;
+}
+
+// Delivered by the copier thread, a batch of four or more images gets its descriptors in two launches (the images
+// are independent and packed back to back): the first half's results cross the host link while the second half is
+// computed -- half of the transfer (0.53 ms for eight 1080p images) leaves the batch's critical path.  Four groups
+// shorten a lone batch a little more (1.75 / 1.58 / 1.53 ms for 1 / 2 / 4) but cost the pipelined rate 1 %:
+// HESS_DESC_PARTS=n overrides (1: one launch, up to kMaxParts).
+// ONE image delivered by the copier thread (a large one: choose_delivery) gets its descriptors in four launches over
+// quarters of its feature list, for the same reason (a 4096^2 image with 102 k half descriptors: 28 MB, 0.58 ms on the
+// link; 2.09 -> 1.7 ms per image on one context).
+static void choose_parts(hess_ctx* c, int batch) {
+  Parts& pt = c->parts;
+  int want = batch >= policy::kSplitDescriptorsFrom ? 2 : 1;
+  pt.features = false;
+  static_assert(policy::kLargeImageParts <= Copier::kMaxParts, "parts of one image");
+  if (batch == 1 && c->delivery == kDeliverDma) { want = policy::kLargeImageParts; pt.features = true; }
+  if (c->desc_parts > 0) want = std::max(1, std::min<int>(Copier::kMaxParts, pt.features ? c->desc_parts : std::min(batch, c->desc_parts)));
+  if (c->delivery != kDeliverDma || !c->cp.ev_part[0]) want = 1;
+  if (want == 1) pt.features = false;
+  pt.n = want;
+  for (int k = 0; k < want; k++) pt.end[k] = pt.features ? 1 : (int)((long long)batch * (k + 1) / want);
+}
+
 // Enqueue the whole path for `batch` images whose pixels are at device address `dev`.
 int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int batch, int format, int pixtype) {
   const hess_params& p = c->p;
@@ -399,16 +459,7 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
   c->cap_list = cap_list;
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[4], st));
   // ---- orientation (GetFeatureOrientations) ----
-  OrientParams op;
-  op.gaussian_factor = p.orient_gaussian_factor;
-  op.sample_factor = p.orient_gaussian_factor * p.orient_window_factor;  // ProgramCU.cu:1638
-  op.ln_sigma_step = s.ln_sigma_step;
-  op.num_orientation = p.fixed_orientation ? 0 : p.max_orientation;      // ProgramCU.cu:1639
-  op.subpixel = p.subpixel;
-  op.half_sift = p.half_sift;
-  op.existing = 0;
-  op.two_peaks = s.detector == HESS_DETECTOR_DOG && op.num_orientation > 1;
-  for (int l = 0; l < kMaxLev; l++) op.level_sigma[l] = l <= s.level_max ? s.level_sigma[l] : 0.0f;
+  const OrientParams op = orient_params(c, false);
   {
     ProfScope ps(c, HESS_K_ORIENT, 0.0);
     launch_orientation(st, g, op, list, list_total, cap_list, got, (FRec*)c->recs.p, (int*)c->ocount.p, batch);
@@ -420,57 +471,22 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
                       (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, batch);
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
   // ---- descriptors (GetFeatureDescriptors) ----
-  DescParams dsp;
-  dsp.window_factor = p.desc_window_factor;
-  dsp.half_sift = p.half_sift;
-  dsp.normalize = p.normalize;
-  dsp.multi = c->multi ? (s.detector == HESS_DETECTOR_DOG ? 2 : 1) : 0;
-  dsp.lowe_origin = p.lowe_origin;
-  dsp.octave_sigma = first_octave_sigma(c);  // PyramidCU.cpp:746-748
-  dsp.dog = g.dog;
-  dsp.dynamic_indexing = p.dynamic_indexing ? 1 : 0;
-  dsp.hkeys = c->host_direct ? (HostKeypoint*)c->h_keys.p : nullptr;
-  dsp.hdesc = (c->host_direct && c->dim) ? (float*)c->h_desc.p : nullptr;
-  dsp.first_image = 0;
-  dsp.part = 0; dsp.part_den = 1;
-  dsp.xcd_block = c->desc_xcd_block;
-  dsp.px_band = c->desc_px_band;
-  dsp.sequential = p.descriptor_order == HESS_DESC_ORDER_SEQUENTIAL;
-  // the pixel order's fixed point assumes luminance in [0, 1] (8- and 16-bit inputs); float pixels are taken as they are
-  // and keep the interleaved order (the test oracle applies the same rule)
-  dsp.pixel = p.descriptor_order == HESS_DESC_ORDER_PIXEL && pixtype != HESS_PIX_F32;
-  // Delivered by the copier thread, a batch of four or more images gets its descriptors in two launches (the images
-  // are independent and packed back to back): the first half's results cross the host link while the second half is
-  // computed -- half of the transfer (0.53 ms for eight 1080p images) leaves the batch's critical path.  Four groups
-  // shorten a lone batch a little more (1.75 / 1.58 / 1.53 ms for 1 / 2 / 4) but cost the pipelined rate 1 %:
-  // HESS_DESC_PARTS=n overrides (1: one launch, up to kMaxParts).
-  // ONE image delivered by the copier thread (a large one: choose_delivery) gets its descriptors in four launches over
-  // quarters of its feature list, for the same reason (a 4096^2 image with 102 k half descriptors: 28 MB, 0.58 ms on the
-  // link; 2.09 -> 1.7 ms per image on one context).
-  {
-    int want = batch >= policy::kSplitDescriptorsFrom ? 2 : 1;
-    c->part_features = false;
-    static_assert(policy::kLargeImageParts <= Copier::kMaxParts, "parts of one image");
-    if (batch == 1 && c->delivery == kDeliverDma) { want = policy::kLargeImageParts; c->part_features = true; }
-    if (c->desc_parts > 0) want = std::max(1, std::min<int>(Copier::kMaxParts, c->part_features ? c->desc_parts : std::min(batch, c->desc_parts)));
-    if (c->delivery != kDeliverDma || !c->cp.ev_part[0]) want = 1;
-    if (want == 1) c->part_features = false;
-    c->nparts = want;
-    for (int k = 0; k < want; k++) c->part_end[k] = c->part_features ? 1 : (int)((long long)batch * (k + 1) / want);
-  }
+  DescParams dsp = desc_params(c, pixtype, false);
+  choose_parts(c, batch);
+  const Parts& parts = c->parts;
   {
     int first = 0;
-    for (int k = 0; k < c->nparts; k++) {
+    for (int k = 0; k < parts.n; k++) {
       ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (per launch, so that the counts agree with a kernel trace)
       dsp.first_image = first;
-      dsp.part = c->part_features ? k : 0;
-      dsp.part_den = c->part_features ? c->nparts : 1;
+      dsp.part = parts.features ? k : 0;
+      dsp.part_den = parts.features ? parts.n : 1;
       launch_descriptor(st, g, dsp, list, cap_list, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
                         (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
-                        (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, c->part_end[k] - first,
+                        (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, parts.end[k] - first,
                         c->seen_features);
-      if (k < c->nparts - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
-      if (!c->part_features) first = c->part_end[k];
+      if (k < parts.n - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
+      if (!parts.features) first = parts.end[k];
     }
   }
   HIP_TRY(c, hipEventRecord(c->ev[7], st));
@@ -554,16 +570,8 @@ int enqueue_user(hess_ctx* c) {
   if (c->stage_events) for (int e = 1; e <= 4; e++) HIP_TRY(c, hipEventRecord(c->ev[e], st));
   float* got = (float*)c->got.p;
   if (!c->user_have_orientation) {
-    OrientParams op;
-    op.gaussian_factor = p.orient_gaussian_factor;
-    op.sample_factor = p.orient_gaussian_factor * p.orient_window_factor;
-    op.ln_sigma_step = s.ln_sigma_step;
-    op.num_orientation = p.fixed_orientation ? 0 : p.max_orientation;
-    op.subpixel = 0;
-    op.half_sift = p.half_sift;
-    op.existing = 1;
-    for (int l = 0; l < kMaxLev; l++) op.level_sigma[l] = l <= s.level_max ? s.level_sigma[l] : 0.0f;
-    launch_orientation(st, g, op, list, list_total, c->cap_raw, got, (FRec*)c->recs.p, (int*)c->ocount.p, 1);
+    ProfScope ps(c, HESS_K_ORIENT, 0.0);
+    launch_orientation(st, g, orient_params(c, true), list, list_total, c->cap_raw, got, (FRec*)c->recs.p, (int*)c->ocount.p, 1);
   }
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[5], st));
   LimitParams lp;
@@ -573,28 +581,13 @@ int enqueue_user(hess_ctx* c) {
                       (int*)c->fsrc.p, (int*)c->feat_total.p, (int*)c->feat_first.p, c->cap_feat,
                       (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, 1);
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
-  DescParams dsp;
-  dsp.window_factor = p.desc_window_factor;
-  dsp.half_sift = p.half_sift;
-  dsp.normalize = p.normalize;
-  dsp.multi = 0;
-  dsp.lowe_origin = p.lowe_origin;
-  dsp.octave_sigma = first_octave_sigma(c);
-  dsp.dog = g.dog;
-  dsp.dynamic_indexing = p.dynamic_indexing ? 1 : 0;
-  dsp.hkeys = c->host_direct ? (HostKeypoint*)c->h_keys.p : nullptr;
-  dsp.hdesc = (c->host_direct && c->dim) ? (float*)c->h_desc.p : nullptr;
-  dsp.first_image = 0;
-  dsp.part = 0; dsp.part_den = 1;
-  dsp.xcd_block = c->desc_xcd_block;
-  dsp.px_band = c->desc_px_band;
-  dsp.sequential = p.descriptor_order == HESS_DESC_ORDER_SEQUENTIAL;
-  dsp.pixel = 0;  // a keypoint list is described in a floating-point order (interleaved unless the sequential one is asked for)
-  c->nparts = 1;
-  c->part_features = false;
-  launch_descriptor(st, g, dsp, list, c->cap_raw, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
-                    (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
-                    (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, 1);
+  c->parts = Parts{};  // one launch
+  {
+    ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (counted like enqueue()'s: the profile's launches agree with a kernel trace)
+    launch_descriptor(st, g, desc_params(c, HESS_PIX_U8, true), list, c->cap_raw, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
+                      (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
+                      (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, 1);
+  }
   HIP_TRY(c, hipEventRecord(c->ev[7], st));
   return 0;
 }

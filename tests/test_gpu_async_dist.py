@@ -39,6 +39,62 @@ def test_submit_wait_two_contexts_match_synchronous_run(gpu_ctx_factory):
         a.wait()  # nothing submitted
 
 
+def test_every_hand_off_on_one_context_in_a_row(gpu_ctx_factory, monkeypatch):
+    """One context takes every route from submit to wait, one after the other: the copier thread enqueues (pinned pixels), the
+    caller enqueues and the copier delivers (device pixels, a pageable pair), the in-kernel mirror (a synchronous run), a
+    keypoint list on the current image -- and the first route again, which would show descriptor parts left over by the
+    others.  Reference: a context with HESS_DELIVERY=blit running the same images synchronously (no copier thread, no split
+    descriptor launches)."""
+    import torch
+
+    from hessgpu_amd.session import HessError
+
+    ab_switch = any(v in os.environ for v in ("HESS_DELIVERY", "HESS_DESC_PARTS", "HESS_MIRROR_MAX_MB", "HESS_MIRROR_MAX_BATCH"))
+    g = gpu_ctx_factory()
+    with monkeypatch.context() as m:
+        m.setenv("HESS_DELIVERY", "blit")
+        ref = gpu_ctx_factory()
+    imgs = _imgs(6)
+    four, four_dev, one, pair = imgs[:4], imgs[2:], imgs[5:], imgs[4:]
+    pinned = torch.from_numpy(four).pin_memory()
+    dev = torch.from_numpy(four_dev).cuda()
+    g.profile_enable(True)
+
+    def check(step, batch, launches, ref_counts):
+        got = g.profile()["descriptor"]["launches"]
+        g.profile_reset()
+        assert [g.count(k) for k in range(batch)] == ref_counts and min(ref_counts) > 0, step
+        for k in range(batch):
+            (kk, dd), (rk, rd) = g.fetch(k), ref.fetch(k)
+            assert kk.tobytes() == rk.tobytes() and dd.tobytes() == rd.tobytes(), (step, k)
+        if not ab_switch:   # (the A/B switches choose otherwise)
+            assert got == launches, (step, got)
+
+    def pinned_four(step):   # upload first: the copier thread enqueues; two descriptor launches (policy::kSplitDescriptorsFrom)
+        g.submit_host(ptr=pinned.data_ptr(), batch=4, height=240, width=320)
+        g.wait()
+        check(step, 4, 2, ref.run(four))
+
+    g.profile_reset()
+    pinned_four(1)
+    g.submit_device(dev.data_ptr(), 4, 240, 320)       # the caller enqueues, the copier delivers
+    with pytest.raises(HessError):                     # one batch in flight per context
+        g.submit_device(dev.data_ptr(), 4, 240, 320)
+    g.wait()
+    check(2, 4, 2, ref.run(four_dev))
+    g.run(one)                                         # the in-kernel mirror
+    check(3, 1, 1, ref.run(one))
+    keys = g.fetch(0)[0][:10].copy()
+    assert len(keys) == 10
+    g.run_keypoints(keys)                              # the current image's pyramid, a local run of one image
+    check(4, 1, 1, [ref.run_keypoints(keys)])
+    g.submit_host(pair)                                # pageable: staged, the caller enqueues, the copier delivers
+    g.wait()
+    check(5, 2, 1, ref.run(pair))
+    pinned_four(6)
+    g.profile_enable(False)
+
+
 def test_device_results_are_packed_and_gather_over_nccl(gpu_ctx_factory):
     import torch
     import torch.distributed as dist
