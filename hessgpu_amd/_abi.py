@@ -24,6 +24,7 @@ FMT_LUM, FMT_LUM_ALPHA, FMT_RGB, FMT_RGBA, FMT_BGR, FMT_BGRA = 1, 2, 3, 4, 5, 6
 PIX_U8, PIX_U16, PIX_F32 = 1, 2, 3
 DBG_GAUSS, DBG_DETH, DBG_GOT = 0, 1, 2
 DETECTOR_HESSIAN, DETECTOR_DOG = 0, 1
+DESC_FORMAT_F32, DESC_FORMAT_U8 = 0, 1
 (T_LOAD, T_ALLOC, T_PYRAMID, T_DETECT, T_LIST, T_ORIENT, T_MULTI_ORIENT, T_DOWNLOAD,
  T_DESCRIPTOR, T_VBO, T_REDUCTION, T_TOTAL, T_COUNT) = range(13)
 (K_GAUSS, K_DOWNSAMPLE, K_HESSIAN, K_EXTREMA, K_TOPK, K_ORIENT, K_DESCRIPTOR, K_INPUT,
@@ -144,6 +145,11 @@ PRODUCT_PROTOTYPES = {
     "share_results": (C.c_int, [_ctx, C.c_char_p]),
     "shared_results_info": (C.c_int, [_ctx, _P(C.c_uint), _P(C.c_uint), _P(C.c_size_t), _P(C.c_size_t)]),
     "dev_switches": (C.c_int, []),
+    # byte descriptors (added during version 5 without a bump)
+    "set_descriptor_format": (C.c_int, [_ctx, C.c_int]),
+    "desc_format": (C.c_int, [_ctx]),
+    "fetch_u8": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
+    "matcher_bank_set_device_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -181,7 +181,7 @@ static int prime(hess_ctx* c, int width, int height, int batch) {
     int rc = 0;
     if (hipMemsetAsync(px, 0, bytes, c->st) != hipSuccess) rc = HESS_ERR_DEVICE;
     PendingRun r{.dev = px, .width = width, .height = height, .pitch = width, .batch = batch, .format = HESS_FMT_LUM,
-                 .pixtype = HESS_PIX_U8, .image_stride = (size_t)width * height};  // (a local: the stored run keeps its geometry)
+                 .pixtype = HESS_PIX_U8, .image_stride = (size_t)width * height, .desc_format = c->desc_format};  // (a local: the stored run keeps its geometry)
     if (!rc) rc = submit_impl(c, r);
     if (!rc) rc = wait_impl(c, r);
     (void)hipStreamSynchronize(c->st);
@@ -284,7 +284,7 @@ int hess_submit_device(hess_ctx* c, const void* dev_pixels, int width, int heigh
   int rc = begin_submit(c, dev_pixels, width, height, pitch, image_stride, batch, format, pixtype, true);
   if (rc) return rc;
   c->run = PendingRun{.dev = dev_pixels, .width = width, .height = height, .pitch = pitch, .batch = batch, .format = format,
-                      .pixtype = pixtype, .image_stride = image_stride};
+                      .pixtype = pixtype, .image_stride = image_stride, .desc_format = c->desc_format};
   chain_stamp_submit(c, true);
   rc = submit_impl(c, c->run);
   chain_stamp_submit(c, false);
@@ -329,7 +329,7 @@ int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int
   rc = ensure(c, c->stage, bytes + 16);
   if (rc) return rc;
   c->run = PendingRun{.dev = c->stage.p, .width = width, .height = height, .pitch = pitch, .batch = batch, .format = format,
-                      .pixtype = pixtype, .image_stride = image_stride};  // (the pixels will be in the staging area)
+                      .pixtype = pixtype, .image_stride = image_stride, .desc_format = c->desc_format};  // (the pixels will be in the staging area)
   hipPointerAttribute_t at;
   const bool pinned = hipPointerGetAttributes(&at, pixels) == hipSuccess && at.type == hipMemoryTypeHost;
   if (pinned && c->user_keys.empty() && !c->no_host_upload) {
@@ -464,6 +464,7 @@ int hess_run_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys
   PendingRun r = c->run;  // geometry of the current image (a local: the stored run keeps its batch)
   if (r.width <= 0) { c->user_keys.clear(); set_err(c, "no current image"); return HESS_ERR_STATE; }
   r.batch = 1; r.t_load_ms = 0.0;
+  r.desc_format = c->desc_format;  // (the list's run takes the format set now, not the image's)
   const int keep_pyramid = c->pyramid_batch;
   c->batch = 0;  // results of the run before: gone; the pyramid stays (that is the point of this entry)
   int rc = submit_impl(c, r);
@@ -471,6 +472,7 @@ int hess_run_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys
   rc = wait_impl(c, r);
   c->pyramid_batch = keep_pyramid;
   if (rc) c->user_keys.clear();
+  else c->run.desc_format = r.desc_format;  // the results the context now holds are this run's
   return rc;
 }
 
@@ -490,18 +492,53 @@ int hess_count(hess_ctx* c, int img) {
 
 int hess_desc_dim(hess_ctx* c) { return c ? c->dim : HESS_ERR_ARG; }
 
-int hess_fetch(hess_ctx* c, int img, hess_keypoint* keys, float* desc) {
+static const char* desc_format_name(int format) { return format == HESS_DESC_FORMAT_U8 ? "u8" : "f32"; }
+
+// hess_fetch / hess_fetch_u8: the results in the format they were made in, or nothing.
+static int fetch_as(hess_ctx* c, int format, int img, hess_keypoint* keys, void* desc) {
   if (!c || img < 0 || img >= c->batch) return HESS_ERR_ARG;
-  const size_t n = (size_t)c->counts[img];
+  if (c->run.desc_format != format) {
+    set_err(c, "the last run's descriptors are %s: fetch them with %s (nothing is converted)", desc_format_name(c->run.desc_format),
+            c->run.desc_format == HESS_DESC_FORMAT_U8 ? "hess_fetch_u8" : "hess_fetch");
+    return HESS_ERR_STATE;
+  }
+  const size_t n = (size_t)c->counts[img], db = run_desc_bytes(c, format);
   if (c->user_result) {
     if (keys && n) memcpy(keys, c->u_keys.data(), n * sizeof(hess_keypoint));
-    if (desc && c->dim && n) memcpy(desc, c->u_desc.data(), n * c->dim * 4);
+    if (desc && c->dim && n) memcpy(desc, c->u_desc.data(), n * db);
     return 0;
   }
   if (keys && n) memcpy(keys, (HostKeypoint*)c->h_keys.p + c->offs[img], n * sizeof(HostKeypoint));
-  if (desc && c->dim && n) memcpy(desc, (float*)c->h_desc.p + c->offs[img] * c->dim, n * c->dim * 4);
+  if (desc && c->dim && n) memcpy(desc, (const char*)c->h_desc.p + c->offs[img] * db, n * db);
   return 0;
 }
+
+int hess_fetch(hess_ctx* c, int img, hess_keypoint* keys, float* desc) { return fetch_as(c, HESS_DESC_FORMAT_F32, img, keys, desc); }
+int hess_fetch_u8(hess_ctx* c, int img, hess_keypoint* keys, unsigned char* desc) { return fetch_as(c, HESS_DESC_FORMAT_U8, img, keys, desc); }
+
+int hess_set_descriptor_format(hess_ctx* c, int format) {
+  if (!c) return HESS_ERR_ARG;
+  if (format != HESS_DESC_FORMAT_F32 && format != HESS_DESC_FORMAT_U8) {
+    set_err(c, "hess_set_descriptor_format: %d is neither HESS_DESC_FORMAT_F32 nor HESS_DESC_FORMAT_U8", format);
+    return HESS_ERR_ARG;
+  }
+  if (refuse_pending(c)) return HESS_ERR_STATE;
+  if (format == HESS_DESC_FORMAT_U8 && !c->p.normalize) {
+    set_err(c, "byte descriptors need normalised values (hess_params.normalize): unnormalised ones are unbounded");
+    return HESS_ERR_UNSUPPORTED;
+  }
+  if (format == HESS_DESC_FORMAT_U8 && c->share_dir) {
+    set_err(c, "byte descriptors are not available on a context whose results are shared (hess_share_results)");
+    return HESS_ERR_UNSUPPORTED;
+  }
+  if (format != c->desc_format) {
+    c->desc_format = format;  // (plan() sizes the result buffers of the next run by it: hess_ctx::planned_format)
+    if (!c->batch) c->run.desc_format = format;  // no results to describe: hess_desc_format reports the runs to come
+  }
+  return 0;
+}
+
+int hess_desc_format(hess_ctx* c) { return c ? c->run.desc_format : HESS_ERR_ARG; }
 
 int hess_device_results(hess_ctx* c, const void** keys, const void** desc, int* capacity) {
   if (!c || !c->batch) return HESS_ERR_STATE;
@@ -562,6 +599,10 @@ int hess_share_results(hess_ctx* c, const char* name) {
   }
   if (c->accepted_submit) { set_err(c, "hess_share_results: call before the context's first batch"); return HESS_ERR_ARG; }
   if (c->share_dir) { set_err(c, "the results of this context are shared already (as %s)", c->share.c_str()); return HESS_ERR_ARG; }
+  if (c->desc_format == HESS_DESC_FORMAT_U8) {
+    set_err(c, "hess_share_results: shared result buffers carry float descriptors; this context is set to byte descriptors");
+    return HESS_ERR_UNSUPPORTED;
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   char dir[256];
   snprintf(dir, sizeof(dir), "/%s.h", name);

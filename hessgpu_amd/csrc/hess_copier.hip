@@ -150,6 +150,7 @@ int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_valu
 // to take the copy, use the fallback; 2: a copy was taken and did not complete (timeout or error, `why`): the batch fails.
 int copier_hsa_copy(hess_ctx* c, size_t first, size_t total, char* why, size_t why_len) {
   Copier& cp = c->cp;
+  const size_t db = run_desc_bytes(c, cp.run->desc_format);
   hsa_signal_value_t seen = 0;
   bool real = false;
   auto lost = [&](int w) {
@@ -172,7 +173,7 @@ int copier_hsa_copy(hess_ctx* c, size_t first, size_t total, char* why, size_t w
   if (!one(cp.sig, (char*)c->h_keys.p + first * sizeof(HostKeypoint), (const char*)c->keys.p + first * sizeof(HostKeypoint),
            total * sizeof(HostKeypoint)))
     return 1;
-  const bool second = c->dim && one(cp.sig2, (char*)c->h_desc.p + first * c->dim * 4, (const char*)c->desc.p + first * c->dim * 4, total * c->dim * 4);
+  const bool second = c->dim && one(cp.sig2, (char*)c->h_desc.p + first * db, (const char*)c->desc.p + first * db, total * db);
   // (both copies are in flight on the same engine; each has its own signal)
   if (const int w = wait_copy_signal(cp.sig, 1, &seen, true, &real)) {
     if (second) { bool r2 = false; (void)wait_copy_signal(cp.sig2, 1, nullptr, false, &r2); real = real || r2; }
@@ -192,6 +193,7 @@ void copier_main(hess_ctx* c) {
     cp.cv.wait(lk, [&] { return cp.stop || cp.has_job; });
     if (cp.stop) return;
     const int batch = cp.run->batch;
+    const size_t db = run_desc_bytes(c, cp.run->desc_format);  // (plan() ran before the job was posted)
     lk.unlock();
     int rc = 0;
     bool overflow = false;
@@ -217,7 +219,7 @@ void copier_main(hess_ctx* c) {
       r.t_load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       if (!rc) {
         try {
-          rc = enqueue(c, r.dev, r.pitch, r.image_stride, r.batch, r.format, r.pixtype);
+          rc = enqueue(c, r);
         } catch (...) { rc = HESS_ERR_NOMEM; snprintf(msg, sizeof(msg), "out of host memory (copier)"); }
         if (!rc && (e = hipEventRecord(cp.ev_done, c->st)) != hipSuccess) fail("hipEventRecord", e);
         if (rc && !msg[0]) snprintf(msg, sizeof(msg), "%s", c->err.c_str());
@@ -237,8 +239,8 @@ void copier_main(hess_ctx* c) {
       DevBuf *hk = &c->h_keys, *hd = &c->h_desc;
       if (total) {
         // (the pinned buffers hold the worst case unless that exceeds 512 MB: then they grow here, rarely)
-        if (hk->bytes < total * sizeof(HostKeypoint) || (c->dim && hd->bytes < total * c->dim * 4)) {
-          if (ensure(c, *hk, total * sizeof(HostKeypoint), true) || (c->dim && ensure(c, *hd, total * c->dim * 4, true))) {
+        if (hk->bytes < total * sizeof(HostKeypoint) || (c->dim && hd->bytes < total * db)) {
+          if (ensure(c, *hk, total * sizeof(HostKeypoint), true) || (c->dim && ensure(c, *hd, total * db, true))) {
             snprintf(msg, sizeof(msg), "pinned result buffers: %s (copier)", c->err.empty() ? "allocation failed" : c->err.c_str());
             rc = HESS_ERR_NOMEM;
           }
@@ -251,7 +253,7 @@ void copier_main(hess_ctx* c) {
           if (hr == 0) return;  // both blocks are in host memory
           if (hr == 2) { rc = HESS_ERR_DEVICE; return; }
         }
-        const size_t kb = sizeof(HostKeypoint), db = (size_t)c->dim * 4;
+        const size_t kb = sizeof(HostKeypoint);
         if ((e = hipMemcpyAsync((char*)hk->p + first * kb, (const char*)c->keys.p + first * kb, n * kb, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess)
           fail("hipMemcpyAsync(keys)", e);
         if (!rc && c->dim &&
@@ -359,7 +361,7 @@ int submit_inner(hess_ctx* c, PendingRun& r) {
   if (rc) return rc;
   choose_delivery(c, r.batch);
   HIP_TRY(c, hipGetLastError());
-  rc = enqueue(c, r.dev, r.pitch, r.image_stride, r.batch, r.format, r.pixtype);
+  rc = enqueue(c, r);
   if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   if (c->delivery == kDeliverDma) {
@@ -420,14 +422,15 @@ int wait_inner(hess_ctx* c, PendingRun& r) {
   }
   const size_t total = c->offs[batch];
   c->seen_features = batch ? *std::max_element(c->counts.begin(), c->counts.end()) : 0;
-  c->last_result_bytes = total * (sizeof(HostKeypoint) + (size_t)c->dim * 4);
+  const size_t db = run_desc_bytes(c, r.desc_format);
+  c->last_result_bytes = total * (sizeof(HostKeypoint) + db);
   c->last_result_batch = batch;
   if ((rc = ensure(c, c->h_keys, (total ? total : 1) * sizeof(HostKeypoint), true))) return rc;
-  if (c->dim && (rc = ensure(c, c->h_desc, (total ? total : 1) * c->dim * 4, true))) return rc;
+  if (c->dim && (rc = ensure(c, c->h_desc, (total ? total : 1) * db, true))) return rc;
   if (total && c->delivery == kDeliverBlit) {
     HIP_TRY(c, hipMemcpyAsync(c->h_keys.p, c->keys.p, total * sizeof(HostKeypoint), hipMemcpyDeviceToHost, c->st));
     if (c->dim)
-      HIP_TRY(c, hipMemcpyAsync(c->h_desc.p, c->desc.p, total * c->dim * 4, hipMemcpyDeviceToHost, c->st));
+      HIP_TRY(c, hipMemcpyAsync(c->h_desc.p, c->desc.p, total * db, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
   }
   c->user_result = false;
@@ -438,11 +441,11 @@ int wait_inner(hess_ctx* c, PendingRun& r) {
     const int listed = (int)std::min<size_t>(total, (size_t)num);
     const bool download = !c->user_have_orientation && ((c->p.max_orientation < 2) || c->p.fixed_orientation);
     c->u_keys = c->user_keys;
-    c->u_desc.assign((size_t)num * (c->dim ? c->dim : 1), 0.0f);
+    c->u_desc.assign((size_t)num * (db ? db : 1), 0);
     for (int i = 0; i < listed; i++) {
       const int k = c->user_kindex[i];
       if (download) memcpy(&c->u_keys[k], (HostKeypoint*)c->h_keys.p + i, sizeof(hess_keypoint));
-      if (c->dim) memcpy(&c->u_desc[(size_t)k * c->dim], (float*)c->h_desc.p + (size_t)i * c->dim, (size_t)c->dim * 4);
+      if (c->dim) memcpy(&c->u_desc[(size_t)k * db], (const char*)c->h_desc.p + (size_t)i * db, db);
     }
     c->counts[0] = num;
     c->offs[1] = (size_t)num;

@@ -112,6 +112,8 @@ struct PendingRun {
   const void* dev = nullptr;
   int width = 0, height = 0, pitch = 0, batch = 0, format = 0, pixtype = 0;
   size_t image_stride = 0;
+  int desc_format = HESS_DESC_FORMAT_F32;  // of this batch's descriptors: what the kernels store, the copier carries, hess_wait
+                                           // sizes and re-runs with, and -- of hess_ctx::run -- what the results are fetched as
   double t_load_ms = 0.0;
   bool active = false;      // submitted and not yet waited for
   bool timed_load = false;  // ev_load[] bracket a host->device transfer of this batch
@@ -209,6 +211,11 @@ struct hess_ctx {
   int cap_raw = 0, cap_sel = 0, cap_feat = 0;
   bool use_topk = false, multi = false;
   int dim = 0;
+  // hess_set_descriptor_format: the format of the runs to come.  Every run record is built with it (PendingRun::desc_format)
+  // and the setter refuses while one is pending, so for the length of a run -- plan(), enqueue(), the copier thread, hess_wait
+  // and its overflow re-run -- it equals the run's.  Afterwards the run record alone says what the results are.
+  int desc_format = HESS_DESC_FORMAT_F32;
+  int planned_format = HESS_DESC_FORMAT_F32;  // the format the current plan's result buffers are sized for
   // device buffers (grow-only, like CuTexImage::InitTexture)
   int found_tasks = 0;  // scan tasks per image the detection store is laid out for (plan)
   DevBuf gauss, deth, got, input_f32, upsampled, stage, rowoff, level_count, raw_total, found, task_count, raw, sel,
@@ -290,7 +297,7 @@ struct hess_ctx {
   std::vector<int> user_levels;     // parity hook: explicit level index per user keypoint (hess_debug_key_levels)
   bool user_result = false;         // last results are in u_keys / u_desc (input order)
   std::vector<hess_keypoint> u_keys;
-  std::vector<float> u_desc;
+  std::vector<unsigned char> u_desc;  // [num][run_desc_bytes]: floats or bytes, as the run's format says
   const RawKey* d_list = nullptr;  // list fed to the orientation stage in the last run
   const int* d_list_total = nullptr;
   int cap_list = 0;
@@ -314,6 +321,9 @@ namespace hess {
 
 
 void set_err(hess_ctx* c, const char* fmt, ...);
+
+// Bytes of one descriptor of a run in format `format` (HESS_DESC_FORMAT_*): the one place that knows the element size.
+inline size_t run_desc_bytes(const hess_ctx* c, int format) { return desc_bytes(c->dim, format); }
 
 // Environment switches.  The shipped library reads four: HESS_SHARE_DIR (and TMPDIR) -- where node-shared result buffers go
 // when /dev/shm has no room --, HESS_COPY_TIMEOUT_S -- how long a result copy may take before the context is poisoned --
@@ -352,7 +362,7 @@ int plan(hess_ctx* c, int width, int height, int batch);
 int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which);
 // hess_schedule.hip
 void drain_profile(hess_ctx* c);
-int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int batch, int format, int pixtype);
+int enqueue(hess_ctx* c, const PendingRun& r);
 // hess_copier.hip
 void stager_start(Stager& sg);
 void stager_copy(Stager& sg, int k);

@@ -45,6 +45,20 @@ __device__ __forceinline__ void store_stream_f4(float* p, float x, float y, floa
 #endif
 }
 
+// Byte descriptors (HESS_DESC_FORMAT_U8, include/hess_abi.h) -- THE rule, used by the descriptor kernels' byte stores, by
+// the matcher's device quantisation of float descriptors (bank_build_kernel) and by its host one (quantise()):
+//   byte = low byte of (int)((double)(512.0f * d) + 0.5)     product in float, sum in double, truncation
+// (the reference's SiftMatchCU.cpp:88-100).  The low byte WRAPS and that stays: d >= 0.49902 wraps, 1.0 gives 0.  The
+// point of one rule is that a bank built from byte results is byte-equal to the bank built from the float results.
+// A descriptor that is not finite (a footprint of norm zero) gets whatever the conversion makes of it, as before.
+__host__ __device__ inline uint32_t desc_byte(float d) { return (uint32_t)(int)((double)(512.0f * d) + 0.5) & 255u; }
+// four consecutive values -> one little-endian dword: value k in byte k (lane l of a 128-d descriptor holds values 4 l + k)
+__host__ __device__ inline uint32_t desc_pack4(float a, float b, float c, float d) {
+  return desc_byte(a) | (desc_byte(b) << 8) | (desc_byte(c) << 16) | (desc_byte(d) << 24);
+}
+// bytes of one descriptor of `dim` elements in format HESS_DESC_FORMAT_* (0: float, 1: byte)
+__host__ __device__ inline size_t desc_bytes(int dim, int format) { return (size_t)dim * (format ? 1 : 4); }
+
 struct OctGeom {
   int wa, h;            // 4-aligned width, height (PyramidCU.cpp:274-309)
   int plane;            // wa*h
@@ -135,7 +149,8 @@ struct DescParams {
   int dog;
   int dynamic_indexing;  // -di: theta == 8.0 goes to des[8] (ProgramCU.cu:1755-1759) instead of being dropped
   HostKeypoint* hkeys;   // optional pinned-host mirrors of the packed results (same indexing as keys/desc)
-  float* hdesc;
+  void* hdesc;           // float [..][dim], or unsigned char [..][dim] when `u8`
+  int u8;                // HESS_DESC_FORMAT_U8: `desc` / `hdesc` take dim BYTES per feature (desc_byte), not dim floats
   int first_image;       // the launch covers images first_image .. first_image + gridDim.y - 1 of the batch
   int xcd_block;         // features per block of the list handed to one XCD's workgroups (0: plain order)
   int sequential;        // HESS_DESC_ORDER_SEQUENTIAL: bins summed in the reference's sample order (else four interleaved partial sums)
@@ -291,6 +306,7 @@ void launch_feature_scan(hipStream_t st, const Geom& g, const LimitParams& lp, i
                          int batch);
 // Descriptor + normalisation + host keypoint record (ComputeDescriptor_Kernel /
 // NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054; keypoint unpack PyramidCU.cpp:866-906).
+// desc: float [..][dim], or with dp.u8 unsigned char [..][dim] behind the same pointer.
 void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, const RawKey* list,
                        int cap_list, const FRec* recs, const int* fsrc, const int* feat_total,
                        const int* feat_first, const int* img_base, const float* got, HostKeypoint* keys,

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/hess_abi.h"
+#include "hess_dev.h"
 
 namespace {
 
@@ -489,7 +490,7 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const PairJob* jobs, 
 // Descriptor sets: back to back on the device, each padded with zero descriptors to whole 256-row blocks, with the score
 // offsets of both sides.  Build: 8 descriptors per workgroup, 32 lanes x 4 bytes each.  sets[s] = (first padded row, first
 // source row, rows) in ascending padded rows; padded rows past a set's count are zero.  Float sources are quantised as the
-// host does, (unsigned char)(int)(512 * d + 0.5) -- the product in float, the sum in double, truncation, the low byte.
+// host does and as the descriptor kernels' byte output is: desc_pack4 (hess_dev.h).
 template <bool F32>
 __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const int3* sets, int nsets, int total,
                                                          uint8_t* bank, int* rfix, int* cfix) {
@@ -508,9 +509,7 @@ __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const 
     const size_t e = ((size_t)S.y + r) * KD + 4 * l;
     if (F32) {
       const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(src) + e);
-      const float q[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-      for (int k = 0; k < 4; k++) v |= ((uint32_t)(int)((double)(512.0f * q[k]) + 0.5) & 255u) << (8 * k);
+      v = hess::desc_pack4(f.x, f.y, f.z, f.w);
     } else {
       v = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + e);
     }
@@ -715,7 +714,7 @@ std::vector<unsigned char> quantise(const float* des, int nsets, const int* coun
   std::vector<unsigned char> q(nk * KD);
   size_t src = 0, dst = 0;
   for (int k = 0; k < nsets; k++) {
-    for (size_t i = 0; i < (size_t)kept[k] * KD; ++i) q[dst + i] = (unsigned char)(int)(512 * des[src + i] + 0.5);
+    for (size_t i = 0; i < (size_t)kept[k] * KD; ++i) q[dst + i] = (unsigned char)hess::desc_byte(des[src + i]);
     src += (size_t)counts[k] * KD;
     dst += (size_t)kept[k] * KD;
   }
@@ -985,12 +984,18 @@ int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, con
   return hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
 }
 
-int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, const float* dev_desc) {
+// The bank from descriptors in device memory, float (quantised by bank_build_kernel<true>) or bytes (<false>: stored as they
+// are).  Everything about the pointer is checked before anything is launched.
+static int bank_set_device(hess_matcher* m, int nsets, const int* counts, const void* dev_desc, bool f32) {
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, dev_desc, &rows)) return rc;
   M_TRY(m, hipSetDevice(m->device));
   if (rows) {
-    if ((uintptr_t)dev_desc % 16) { m->err = "bank_set_device: the descriptors must be 16-byte aligned"; return HESS_ERR_ARG; }
+    const size_t align = f32 ? 16 : 4, esz = f32 ? sizeof(float) : 1;  // what one lane of bank_build_kernel loads
+    if ((uintptr_t)dev_desc % align) {
+      m->err = "bank_set_device: the descriptors must be " + std::to_string(align) + "-byte aligned";
+      return HESS_ERR_ARG;
+    }
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof(at));
     const hipError_t e = hipPointerGetAttributes(&at, dev_desc);
@@ -1002,7 +1007,7 @@ int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, 
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_desc) != hipSuccess ||
-        (const char*)dev_desc + rows * KD * sizeof(float) > (const char*)base + size) {
+        (const char*)dev_desc + rows * KD * esz > (const char*)base + size) {
       (void)hipGetLastError();
       m->err = "bank_set_device: the counts reach past the end of the descriptors' allocation";
       return HESS_ERR_ARG;
@@ -1010,9 +1015,17 @@ int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, 
     (void)hipGetLastError();
   }
   sets_clear(m->bank);
-  const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, true);
+  const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, f32);
   if (rc) sets_clear(m->bank);
   return rc;
+}
+
+int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, const float* dev_desc) {
+  return bank_set_device(m, nsets, counts, dev_desc, true);
+}
+
+int hess_matcher_bank_set_device_u8(hess_matcher* m, int nsets, const int* counts, const unsigned char* dev_desc) {
+  return bank_set_device(m, nsets, counts, dev_desc, false);
 }
 
 int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {

@@ -177,7 +177,8 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   ws &= ~3;  // TruncateWidthCU
   if (ws < 4 || hs < 1) { set_err(c, "image too small"); return HESS_ERR_ARG; }
   const bool same = c->planned && c->in_w == width && c->in_h == height && batch <= c->g.B &&
-                    (int)(2 * c->user_keys.size() + 8) <= c->cap_sel && (int)(2 * c->user_keys.size() + 8) <= c->cap_feat;
+                    (int)(2 * c->user_keys.size() + 8) <= c->cap_sel && (int)(2 * c->user_keys.size() + 8) <= c->cap_feat &&
+                    c->planned_format == c->desc_format;  // (the result buffers are sized in bytes of the format)
   if (same) return 0;
   const int B = (c->planned && c->g.B > batch) ? c->g.B : batch;
 
@@ -286,12 +287,13 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   if ((rc = ensure(c, c->foffset, (size_t)B * cap_sel * 4))) return rc;
   if ((rc = ensure(c, c->fsrc, (size_t)B * cap_feat * 4))) return rc;
   if ((rc = ensure(c, c->keys, (size_t)B * cap_feat * sizeof(HostKeypoint)))) return rc;
-  if (c->dim && (rc = ensure(c, c->desc, (size_t)B * cap_feat * c->dim * 4))) return rc;
+  const size_t dbytes = run_desc_bytes(c, c->desc_format);  // (grow-only in BYTES: a buffer that held floats holds the bytes of the same plan)
+  if (c->dim && (rc = ensure(c, c->desc, (size_t)B * cap_feat * dbytes))) return rc;
   if ((rc = ensure(c, c->h_small, (size_t)(3 * B + 8) * 4, true))) return rc;
   {
     // The pinned result buffers hold the worst case B * cap_feat records up front while that stays moderate; beyond
     // it they grow on demand once the counts are known (wait_impl / the copier), and the in-kernel mirror is not used.
-    const size_t host_bytes = (size_t)B * cap_feat * (sizeof(HostKeypoint) + (size_t)c->dim * 4);
+    const size_t host_bytes = (size_t)B * cap_feat * (sizeof(HostKeypoint) + dbytes);
     // Node-shared result buffers of a batch the copier delivers are sized by the batches seen (+ 25 %), not for the
     // worst case B * cap_feat: 79 MB per context, 3.8 - 4.4 GB of /dev/shm for a node's six or seven contexts x eight
     // ranks, where the results are 24 MB per context; the copier (or hess_wait) grows them under a new generation when a batch needs more.
@@ -299,7 +301,7 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
     c->host_fits = !c->share_by_need && host_bytes <= policy::kHostWorstCaseMax;
     if (c->host_fits) {
       if ((rc = ensure(c, c->h_keys, (size_t)B * cap_feat * sizeof(HostKeypoint), true))) return rc;
-      if (c->dim && (rc = ensure(c, c->h_desc, (size_t)B * cap_feat * c->dim * 4, true))) return rc;
+      if (c->dim && (rc = ensure(c, c->h_desc, (size_t)B * cap_feat * dbytes, true))) return rc;
     }
   }
 
@@ -313,6 +315,7 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   c->cap_sel = cap_sel;
   c->cap_feat = cap_feat;
   c->planned = true;
+  c->planned_format = c->desc_format;
   const float s0 = initial_smooth_sigma(c, ds);
   c->has_taps0 = s0 > 0.0f;
   if (c->has_taps0) make_taps(p, s0, &c->taps0);

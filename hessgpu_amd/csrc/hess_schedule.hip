@@ -88,7 +88,7 @@ static inline float first_octave_sigma(const hess_ctx* c) {
   return c->ds > 0 ? (float)(1 << c->ds) : (c->ds < 0 ? 1.0f / (float)(1 << (-c->ds)) : 1.0f);
 }
 
-int enqueue_user(hess_ctx* c);
+int enqueue_user(hess_ctx* c, int desc_format);
 
 // Orientation stage (GetFeatureOrientations).  existing: a caller's keypoints -- position and scale as packed, one angle written.
 static OrientParams orient_params(const hess_ctx* c, bool existing) {
@@ -107,7 +107,7 @@ static OrientParams orient_params(const hess_ctx* c, bool existing) {
 }
 
 // Descriptor stage (GetFeatureDescriptors).  user: a caller's keypoints -- one float angle each, never the fixed-point pixel order.
-static DescParams desc_params(const hess_ctx* c, int pixtype, bool user) {
+static DescParams desc_params(const hess_ctx* c, int pixtype, int desc_format, bool user) {
   const hess_params& p = c->p;
   DescParams dsp;
   dsp.window_factor = p.desc_window_factor;
@@ -119,7 +119,8 @@ static DescParams desc_params(const hess_ctx* c, int pixtype, bool user) {
   dsp.dog = c->g.dog;
   dsp.dynamic_indexing = p.dynamic_indexing ? 1 : 0;
   dsp.hkeys = c->host_direct ? (HostKeypoint*)c->h_keys.p : nullptr;
-  dsp.hdesc = (c->host_direct && c->dim) ? (float*)c->h_desc.p : nullptr;
+  dsp.hdesc = (c->host_direct && c->dim) ? c->h_desc.p : nullptr;
+  dsp.u8 = desc_format == HESS_DESC_FORMAT_U8;
   dsp.first_image = 0; dsp.part = 0; dsp.part_den = 1;  // (one launch over the whole list)
   dsp.xcd_block = c->desc_xcd_block; dsp.px_band = c->desc_px_band;
   dsp.sequential = p.descriptor_order == HESS_DESC_ORDER_SEQUENTIAL;
@@ -150,8 +151,11 @@ static void choose_parts(hess_ctx* c, int batch) {
   for (int k = 0; k < want; k++) pt.end[k] = pt.features ? 1 : (int)((long long)batch * (k + 1) / want);
 }
 
-// Enqueue the whole path for `batch` images whose pixels are at device address `dev`.
-int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int batch, int format, int pixtype) {
+// Enqueue the whole path for the run's `batch` images, whose pixels are at device address `dev`.
+int enqueue(hess_ctx* c, const PendingRun& r) {
+  const void* const dev = r.dev;
+  const int pitch = r.pitch, batch = r.batch, format = r.format, pixtype = r.pixtype;
+  const size_t image_stride = r.image_stride;
   const hess_params& p = c->p;
   const Schedule& s = c->sch;
   const Geom& g = c->g;
@@ -410,7 +414,7 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
     launch_dog_planes(st, g, gauss, deth, s.level_max, batch);
   }
   }  // !(user_mode && on_current)
-  if (user_mode) return enqueue_user(c);
+  if (user_mode) return enqueue_user(c, r.desc_format);
   // ---- extrema + ordered list (DetectKeypointsEX part 2 + GenerateFeatureList) ----
   LimitParams lp;
   lp.method = p.truncate_method;
@@ -471,7 +475,7 @@ int enqueue(hess_ctx* c, const void* dev, int pitch, size_t image_stride, int ba
                       (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, batch);
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
   // ---- descriptors (GetFeatureDescriptors) ----
-  DescParams dsp = desc_params(c, pixtype, false);
+  DescParams dsp = desc_params(c, pixtype, r.desc_format, false);
   choose_parts(c, batch);
   const Parts& parts = c->parts;
   {
@@ -501,7 +505,7 @@ static inline int float_to_fixed_host(float v, int n) {
 // User-supplied keypoints (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718): bin the keys to
 // levels by scale, pack fixed-point records on the host, upload, strongest orientation on the device
 // unless supplied, descriptors.  One image.
-int enqueue_user(hess_ctx* c) {
+int enqueue_user(hess_ctx* c, int desc_format) {
   const hess_params& p = c->p;
   const Schedule& s = c->sch;
   const Geom& g = c->g;
@@ -584,7 +588,7 @@ int enqueue_user(hess_ctx* c) {
   c->parts = Parts{};  // one launch
   {
     ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (counted like enqueue()'s: the profile's launches agree with a kernel trace)
-    launch_descriptor(st, g, desc_params(c, HESS_PIX_U8, true), list, c->cap_raw, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
+    launch_descriptor(st, g, desc_params(c, HESS_PIX_U8, desc_format, true), list, c->cap_raw, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
                       (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
                       (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, 1);
   }

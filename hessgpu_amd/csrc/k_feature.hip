@@ -598,10 +598,27 @@ __device__ __forceinline__ void keypoint_records(const DescParams& dp, uint32_t*
   }
 }
 
+// The lane index as a value the compiler cannot move out of the loop over the features.  The byte stores' lane offsets
+// (4 lane, 2 lane: invariant over that loop) are otherwise formed ahead of it and held across the whole raster of
+// descriptor_pixel_kernel, which has no register to spare (PX_WAVES): its byte forms then take 72 registers and 8 - 16
+// bytes of scratch per lane; with this, 71 and none, like the float forms.
+__device__ __forceinline__ int unhoisted(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// Where feature `o` of the packed output begins: `dim` floats per feature, or -- u8 -- `dim` bytes behind the same base.
+__device__ __forceinline__ float* desc_at(void* base, long long o, int dim, bool u8) {
+  return u8 ? reinterpret_cast<float*>(static_cast<char*>(base) + o * dim) : static_cast<float*>(base) + o * dim;
+}
+
 // Normalisation with the reference's 32-lane tree (NormalizeDescriptor_Kernel + ND_WarpReduction, ProgramCU.cu:1950-2054)
 // and the 512-byte (256-byte) coalesced store of one descriptor; lanes 0..31 hold four (two) consecutive values each.
+// u8 (HESS_DESC_FORMAT_U8; uniform over the launch -- dp.u8 in descriptor_kernel, a template parameter of
+// descriptor_pixel_kernel): the same values after the same normalisation go out as bytes, desc_pack4 / desc_byte of
+// hess_dev.h -- 128 (64) contiguous bytes per feature; dout / hout then address the feature's bytes (desc_at).
 template <bool HOST_MIRROR>
-__device__ __forceinline__ void finish_descriptor128(const DescParams& dp, int lane, float4 v, float* dout, float* hout) {
+__device__ __forceinline__ void finish_descriptor128(const DescParams& dp, bool u8, int lane, float4 v, float* dout, float* hout) {
   if (dp.normalize) {
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
@@ -615,12 +632,19 @@ __device__ __forceinline__ void finish_descriptor128(const DescParams& dp, int l
       } else { v.x *= nrm; v.y *= nrm; v.z *= nrm; v.w *= nrm; }
     }
   }
+  if (u8) {  // one dword per lane: bytes 4 lane .. 4 lane + 3
+    const uint32_t q = desc_pack4(v.x, v.y, v.z, v.w);
+    const int at = 4 * unhoisted(lane);
+    if (lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + at) = q;
+    if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + at) = q;
+    return;
+  }
   if (lane < 32) *reinterpret_cast<float4*>(dout + lane * 4) = v;
   // (streaming stores for the mirror were measured: 0.341 - 0.346 against 0.333 - 0.339 ms per single image, same call)
   if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<float4*>(hout + lane * 4) = v;
 }
 template <bool HOST_MIRROR>
-__device__ __forceinline__ void finish_descriptor64(const DescParams& dp, int lane, float2 v, float* dout, float* hout) {
+__device__ __forceinline__ void finish_descriptor64(const DescParams& dp, bool u8, int lane, float2 v, float* dout, float* hout) {
   if (dp.normalize) {
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
@@ -631,6 +655,18 @@ __device__ __forceinline__ void finish_descriptor64(const DescParams& dp, int la
       if (pass == 0) { v.x = fminf(0.2f, v.x * nrm); v.y = fminf(0.2f, v.y * nrm); }
       else { v.x *= nrm; v.y *= nrm; }
     }
+  }
+  if (u8) {
+    // a lane's two bytes, and those of its odd neighbour by a DPP quad permute (lanes [1,1,3,3] of the quad: no LDS, and
+    // executed by all lanes): the 16 even lanes below 32 store one dword each, bytes 2 lane .. 2 lane + 3
+    const uint32_t h = desc_byte(v.x) | (desc_byte(v.y) << 8);
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_mov_dpp((int)h, 0xF5 /* quad_perm:[1,1,3,3] */, 0xF, 0xF, true);
+    const uint32_t q = h | (nb << 16);
+    const int l = unhoisted(lane);
+    const bool mine = l < 32 && !(l & 1);
+    if (mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + 2 * l) = q;
+    if (HOST_MIRROR && hout && mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + 2 * l) = q;
+    return;
   }
   if (lane < 32) *reinterpret_cast<float2*>(dout + lane * 2) = v;
   if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<float2*>(hout + lane * 2) = v;
@@ -902,16 +938,16 @@ __global__ __launch_bounds__(256) void descriptor_kernel(Geom g, DescParams dp, 
     }
     // same wavefront wrote dl[wv]; LDS operations of one wavefront complete in order
     __builtin_amdgcn_wave_barrier();
-    float* dout = desc + (obase + oidx) * dim;
-    float* hout = (HOST_MIRROR && dp.hdesc) ? dp.hdesc + (obase + oidx) * dim : nullptr;
+    float* dout = desc_at(desc, obase + oidx, dim, dp.u8 != 0);
+    float* hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, obase + oidx, dim, dp.u8 != 0) : nullptr;
     if (dp.half_sift) {
       float2 v = make_float2(0, 0);
       if (lane < 32) v = *reinterpret_cast<const float2*>(&dl[wv][lane * 2]);
-      finish_descriptor64<HOST_MIRROR>(dp, lane, v, dout, hout);
+      finish_descriptor64<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
     } else {
       float4 v = make_float4(0, 0, 0, 0);
       if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
-      finish_descriptor128<HOST_MIRROR>(dp, lane, v, dout, hout);
+      finish_descriptor128<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
     }
   }
 }
@@ -969,265 +1005,17 @@ typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 
 // (amdgpu_waves_per_eu(7, 7): 23 040 bytes of LDS per workgroup admit seven workgroups per CU; left alone the register
 // allocator takes 77 registers = six wavefronts per SIMD.  71 registers, nothing spilled, launch 86.6 -> 85.1 us.)
-template <bool HOST_MIRROR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, PX_WAVES))) void descriptor_pixel_kernel(Geom g, DescParams dp, const RawKey* list,
-                                                               int cap_list, const FRec* recs,
-                                                               const int* fsrc, const int* feat_total,
-                                                               const int* feat_first, const int* img_base,
-                                                               const float* got, HostKeypoint* keys, float* desc,
-                                                               int cap_feat) {
-  __shared__ __attribute__((aligned(16))) float dl[4][128];
-  __shared__ __attribute__((aligned(16))) unsigned long long hist[4][PX_WAVE_U64];
-  __shared__ __attribute__((aligned(16))) uint4 rowtab[4][64];  // per wavefront: the rows of the current raster band
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.y + dp.first_image;
-  int ftotal = feat_total[b], ffirst = feat_first[b];
-  long long obase = img_base[b];
-  feature_part(dp, &ftotal, &ffirst, &obase);
-  const int nwaves = gridDim.x * 4;
-  const float rpi = (float)(4.0 / kPI);
-  const int dim = dp.half_sift ? 64 : 128;
-
-  static_assert(sizeof(HostKeypoint) == 24 && sizeof(hist) >= 256 * 24, "record staging fits the sums");
-  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), list, cap_list, recs, fsrc, cap_feat, b, ftotal, ffirst, obase, keys);
-  if (!desc) return;
-  unsigned long long* const sums = &hist[wv][0];
-  {
-    uint4* const z = reinterpret_cast<uint4*>(sums);
-    for (int i = lane; i < PX_WAVE_U64 / 2; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  // LDS byte address of the lane's copy, as a float (stage B adds the word's offset in floating point)
-  const float mycopy_f = (float)(unsigned)(unsigned long long)(lds_u64*)(sums + (lane % PX_COPIES) * PX_COPY_U64);
-  const uint32_t theta_end_bits = dp.dynamic_indexing ? 0x41000001u : 0x41000000u;  // 8.0f, or the next float (admits theta == 8)
-
-  // feature order: as descriptor_kernel (largest footprints first, blocks of consecutive features per XCD)
-  int mw0 = blockIdx.x * 4 + wv;
-  if (dp.xcd_block) {
-    const int xcd = blockIdx.x & 7, wx = (int)(blockIdx.x >> 3) * 4 + wv;
-    mw0 = ((wx / dp.xcd_block) * 8 + xcd) * dp.xcd_block + wx % dp.xcd_block;
-  }
-  for (int mw = mw0; mw < ftotal; mw += nwaves) {
-    const int m = ffirst + ftotal - 1 - mw;
-    const int src = fsrc[(long long)b * cap_feat + m];
-    const int i = src >> 2, k = src & 3;
-    const int oidx = m - ffirst;
-    const FRec rec = recs[(long long)b * cap_list + i];
-    const int li = list[(long long)b * cap_list + i].level_index;
-    int o, l;
-    level_of(g, li, &o, &l);
-    const OctGeom& og = g.o[o];
-    const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
-                                                        ((long long)(l - 1) * g.B + b) * og.plane);
-    const GlobalBytes gp = (GlobalBytes)(
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
-        (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
-    const int width = og.wa, height = og.h;
-
-    const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
-                              : __uint_as_float(rec.w);
-    const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
-    const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
-    const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
-    const float spt = fabsf(kz * dp.window_factor);
-    float s, c;
-    dm_sincosf(kw, &s, &c);
-    const float anglef = (kw > kPI) ? (float)(kw - (2.0 * kPI)) : kw;
-    const float cspt = c * spt, sspt = s * spt;
-    const float crspt = c / spt, srspt = s / spt;
-    const float bsz = fabsf(cspt) + fabsf(sspt);
-    const float ext = 2.5f * bsz;  // half extent of the footprint's bounding box
-    const float xmin = fmaxf(1.5f, floorf(kx - ext) + 0.5f);
-    const float ymin = fmaxf(1.5f, floorf(ky - ext) + 0.5f);
-    const float xmax = fminf(width - 1.5f, floorf(kx + ext) + 0.5f);
-    const float ymax = fminf(height - 1.5f, floorf(ky + ext) + 0.5f);
-    // fixed-point scale 2^sh: 0.75 (spt + 1)^2 < 2^e bounds every sum, sh = 32 - e (the oracle's frexpf)
-    const float bound = 0.75f * (spt + 1.0f) * (spt + 1.0f);
-    const int sh = min(max(32 - ((int)((__float_as_uint(bound) >> 23) & 0xFFu) - 126), 0), 30);
-    const float scale = __uint_as_float((uint32_t)(127 + sh) << 23), rscale = __uint_as_float((uint32_t)(127 - sh) << 23);
-    // (the same in every lane: the box is the feature's)
-    const int nxs = __builtin_amdgcn_readfirstlane((xmax >= xmin) ? (int)(xmax - xmin) + 1 : 0);
-    const int nys = __builtin_amdgcn_readfirstlane((ymax >= ymin) ? (int)(ymax - ymin) + 1 : 0);
-    // Row spans.  The window |u| < 2.5, |v| < 2.5 is a rotated square: of the box's pixels 1 / (|c| + |s|)^2 lie inside
-    // (0.61 on average over the angles), so the raster runs over the window's own rows instead: row y of the box keeps
-    // the pixels x_lo(y) .. x_hi(y), the real-arithmetic solution of the two inequalities for x, slightly widened (a
-    // SUPERSET of the pixels that pass the test: every pixel is still tested with the floats the oracle uses, so which
-    // pixels count does not depend on the spans; integer sums do not depend on the order either).
-    // Bands of <= 64 rows (lane = row) and <= dp.px_band pixels: prefix sums of the span lengths give every row its first
-    // place S in the band's sequence; a 64-bit word per step holds the places where rows start (bit S mod 64 of word
-    // S / 64, lane w keeps word w), so the lane of place t = 64 step + lane finds its row with two mbcnt and reads the
-    // row's entry (first pixel's index - S, x - S, y) from LDS.
-    // (a coefficient below 1e-3 per pixel: that inequality is left out -- it cuts the corners of the box only -- so that the
-    // rounding of u, v, 1e-6 at most, stays below 1e-3 pixel in x; the spans are widened by PX_SPAN_EPS = 0.02)
-    const float rA = (fabsf(crspt) > 1.0e-3f) ? 1.0f / crspt : 0.0f, rB = (fabsf(srspt) > 1.0e-3f) ? 1.0f / srspt : 0.0f;
-    const int px_band = __builtin_amdgcn_readfirstlane(dp.px_band);
-    for (int ib = 0; ib < nxs; ib += px_band) {  // (column bands: a box wider than a band -- no detected feature's is)
-    const int ncol = min(nxs - ib, px_band);
-    const int band_rows = min(64, px_band / ncol);
-    for (int jb = 0; jb < nys; jb += band_rows) {
-    const int nrow = min(band_rows, nys - jb);
-    int T;
-    uint32_t mword_lo, mword_hi;
-    {
-      const float yrow = ymin + (float)(jb + lane), dyr = yrow - ky;
-      float lo = -3.0e38f, hi = 3.0e38f;
-      if (rA != 0.0f) {  // |crspt dx + srspt dy| < 2.5
-        const float t1 = (-2.5f - srspt * dyr) * rA, t2 = (2.5f - srspt * dyr) * rA;
-        lo = fminf(t1, t2); hi = fmaxf(t1, t2);
-      }
-      if (rB != 0.0f) {  // |crspt dy - srspt dx| < 2.5
-        const float t1 = (crspt * dyr - 2.5f) * rB, t2 = (crspt * dyr + 2.5f) * rB;
-        lo = fmaxf(lo, fminf(t1, t2)); hi = fminf(hi, fmaxf(t1, t2));
-      }
-      const float off = kx - xmin;  // pixel i of the row: x = xmin + i, dx = i - off
-      const float flo = fmaxf(ceilf(lo + off - PX_SPAN_EPS), (float)ib), fhi = fminf(floorf(hi + off + PX_SPAN_EPS), (float)(ib + ncol - 1));
-      const int len = (lane < nrow && fhi >= flo) ? (int)(fhi - flo) + 1 : 0;
-      const int ilo = (int)flo;
-      const int incl = wave_inclusive_scan(len);
-      const int S = incl - len;
-      T = __builtin_amdgcn_readlane(incl, 63);
-      const uint64_t ne = __builtin_amdgcn_ballot_w64(len > 0);
-      const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ne >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ne, 0u));
-      // (dl[wv] is also the float staging area of the feature's end: wavefront fences keep the compiler from moving the
-      // 64-bit accesses across the float ones, which type-based alias analysis would allow; they emit no instruction)
-      unsigned long long* const starts = reinterpret_cast<unsigned long long*>(&dl[wv][0]);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      starts[lane] = 0ull;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (len > 0) {
-        (void)__hip_atomic_fetch_or(starts + (S >> 6), 1ull << (S & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        rowtab[wv][r] = make_uint4((uint32_t)(((int)ymin + jb + lane) * width + (int)xmin + ilo - S),
-                                   __float_as_uint(xmin + (float)(ilo - S)), __float_as_uint(yrow), 0u);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const unsigned long long mw = starts[lane];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      mword_lo = (uint32_t)mw; mword_hi = (uint32_t)(mw >> 32);
-    }
-    const int nit = (T + 63) >> 6;
-    int step = 0, rows_before = -1;  // (rows that started before this step's 64 places) - 1
-    int tl = lane;
-    float tf = (float)lane;
-
-    // stage A: the lane's pixel of N steps (row by the start bits, place in the row), keypoint-frame coordinates, window
-    // test and gather, issued back to back
-    auto stage_a = [&](auto& ck) {
-      constexpr int N = std::remove_reference_t<decltype(ck)>::N;
-#pragma unroll
-      for (int q = 0; q < N; q++) {
-        const uint32_t mlo = (uint32_t)__builtin_amdgcn_readlane((int)mword_lo, step), mhi = (uint32_t)__builtin_amdgcn_readlane((int)mword_hi, step);
-        const uint64_t m64 = ((uint64_t)mhi << 32) | mlo;
-        int rr = rows_before + (int)__builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)) + (__builtin_amdgcn_inverse_ballot_w64(m64) ? 1 : 0);
-        rows_before += __builtin_popcountll(m64);
-        rr = (int)min((unsigned)rr, 63u);  // (steps past the band's end: any entry, the lane is switched off below)
-        const uint4 e = rowtab[wv][rr];
-        const float xf = __uint_as_float(e.y) + tf, yf = __uint_as_float(e.z);
-        const unsigned goff = (e.x + (unsigned)tl) * 8u;
-        const float dx = xf - kx, dy = yf - ky;
-        const float u = fmaf(crspt, dx, srspt * dy);
-        ck.v[q] = fmaf(crspt, dy, -(srspt * dx));
-        const bool in = (tl < T) & (fabsf(u) < 2.5f) & (fabsf(ck.v[q]) < 2.5f);
-        ck.u[q] = in ? u : 3.0f;  // (outside the window)
-        const dfloat2 gv = __builtin_amdgcn_raw_buffer_load_b64(grsrc, (int)(in ? goff : 0u), 0, 0);
-        ck.cc[q] = make_float2(gv.x, gv.y);
-        tl += 64; tf += 64.0f; step++;
-      }
-    };
-    // stage B: the pixel's weight, bin and cell split; four 64-bit additions of two fixed-point values each.
-    // (The word's LDS address is formed in floating point from the three floors -- small integers, exact -- and
-    // converted once; the four cells' validity masks are combined as wave masks on the scalar unit.)
-    auto stage_b = [&](const auto& ck) {
-      constexpr int N = std::remove_reference_t<decltype(ck)>::N;
-#pragma unroll
-      for (int q = 0; q < N; q++) {
-        const float u = ck.u[q], v = ck.v[q];
-        if (!__any(u < 2.5f)) continue;  // (wave-uniform) a step wholly outside the window: the box's corners
-        const float ww = dm_expf_inrange(-0.125f * fmaf(u, u, v * v));
-        float theta = (anglef - ck.cc[q].y) * rpi;
-        theta = (theta < 0) ? theta + 8.0f : theta;
-        // 0 <= theta < theta_end as ONE unsigned compare of the bit patterns (see descriptor_kernel)
-        const uint64_t m_hit = __builtin_amdgcn_ballot_w64((u < 2.5f) & (__float_as_uint(theta) < theta_end_bits));
-        // b0 = floor(theta), 0..7; theta == 8 (-di only) counts as b0 = 7 with weights (0, 1): the same sums, since word
-        // 7 = [bin 7 | bin 0] (the oracle says bin 0 += weight, bin 1 += 0)
-        const float fo = fminf(floorf(theta), 7.0f);
-        const float wb1 = theta - fo, wb0 = 1.0f - wb1;
-        const float au = u + 1.5f, av = v + 1.5f;
-        const float fu = floorf(au), fv = floorf(av);  // -1 .. 3: cells fu, fu + 1 / fv, fv + 1 where they exist
-        const float wx1 = au - fu, wx0 = 1.0f - wx1;
-        const float wy1 = av - fv, wy0 = 1.0f - wy1;
-        const float wt = (ww * ck.cc[q].x) * scale;
-        const float a0 = wt * wy0, a1 = wt * wy1;
-        const float b00 = a0 * wx0, b01 = a0 * wx1, b10 = a1 * wx0, b11 = a1 * wx1;
-        const unsigned addr = (unsigned)(int)fmaf(fv, 256.0f, fmaf(fu, 64.0f, fmaf(fo, 8.0f, mycopy_f)));  // byte address in LDS
-        lds_u64* const p = (lds_u64*)(unsigned long long)addr;
-        const uint64_t mx0 = __builtin_amdgcn_ballot_w64(fu >= 0.0f), mx1 = __builtin_amdgcn_ballot_w64(fu <= 2.0f);
-        const uint64_t my0 = m_hit & __builtin_amdgcn_ballot_w64(fv >= 0.0f), my1 = m_hit & __builtin_amdgcn_ballot_w64(fv <= 2.0f);
-#define HESS_PX_ADD(P, B)                                                                                          \
-  (void)__hip_atomic_fetch_add((P), (unsigned long long)__float2uint_rz(fmaf((B), wb0, 0.5f)) |                    \
-                                       ((unsigned long long)__float2uint_rz(fmaf((B), wb1, 0.5f)) << 32),           \
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-        if (__builtin_amdgcn_inverse_ballot_w64(my0 & mx0)) HESS_PX_ADD(p, b00);
-        if (__builtin_amdgcn_inverse_ballot_w64(my0 & mx1)) HESS_PX_ADD(p + 8, b01);
-        if (__builtin_amdgcn_inverse_ballot_w64(my1 & mx0)) HESS_PX_ADD(p + 32, b10);
-        if (__builtin_amdgcn_inverse_ballot_w64(my1 & mx1)) HESS_PX_ADD(p + 40, b11);
-#undef HESS_PX_ADD
-      }
-    };
-    {
-      constexpr int UN = HESS_PX_UNROLL;
-      // software pipeline: the gathers of the next chunk are in flight while the current chunk is accumulated
-      PixChunk<UN> ca, cb;
-      stage_a(ca);
-      for (int it0 = 0; it0 < nit; it0 += 2 * UN) {
-        stage_a(cb);
-        stage_b(ca);
-        if (it0 + UN >= nit) break;
-        stage_a(ca);
-        stage_b(cb);
-      }
-    }
-    }  // row bands
-    }  // column bands
-    // The copies' sums: lane (cell, q) reads words 2q, 2q+1 of its cell in every copy (one 16-byte read each), adds the
-    // four 32-bit halves apart and clears the words for the next feature.  It owns bins 2q, 2q+1:
-    //   bin 2q   = low half of word 2q   + high half of word 2q-1 (lane q-1 of the quad, q = 0: word 7, lane q = 3)
-    //   bin 2q+1 = low half of word 2q+1 + high half of word 2q
-    __builtin_amdgcn_wave_barrier();
-    uint4 t = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int cpy = 0; cpy < PX_COPIES; cpy++) {
-      uint4* const w = reinterpret_cast<uint4*>(sums + cpy * PX_COPY_U64 + 2 * lane);
-      const uint4 x = *w;
-      t.x += x.x; t.y += x.y; t.z += x.z; t.w += x.w;
-      *w = make_uint4(0u, 0u, 0u, 0u);
-    }
-    {
-      const uint32_t prev_hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)t.w, 0x93 /* quad_perm:[3,0,1,2] */, 0xF, 0xF, true);
-      const float f0 = (float)(t.x + prev_hi) * rscale, f1 = (float)(t.z + t.y) * rscale;
-      *reinterpret_cast<float2*>(&dl[wv][2 * lane]) = make_float2(f0, f1);
-    }
-    __builtin_amdgcn_wave_barrier();
-    float* dout = desc + (obase + oidx) * dim;
-    float* hout = (HOST_MIRROR && dp.hdesc) ? dp.hdesc + (obase + oidx) * dim : nullptr;
-    if (dp.half_sift) {  // des[k] += des[k+4], ProgramCU.cu:1782-1785: lane < 32 -> cell lane/2, k = 2 (lane & 1) + {0, 1}
-      float2 v = make_float2(0, 0);
-      if (lane < 32) {
-        const float* cellp = &dl[wv][(lane >> 1) * 8 + (lane & 1) * 2];
-        const float2 lo = *reinterpret_cast<const float2*>(cellp), hi = *reinterpret_cast<const float2*>(cellp + 4);
-        v = make_float2(lo.x + hi.x, lo.y + hi.y);
-      }
-      finish_descriptor64<HOST_MIRROR>(dp, lane, v, dout, hout);
-    } else {
-      float4 v = make_float4(0, 0, 0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
-      finish_descriptor128<HOST_MIRROR>(dp, lane, v, dout, hout);
-    }
-    __builtin_amdgcn_wave_barrier();  // (dl and the sums are rewritten by the next feature)
-  }
-}
+// The kernel's text is k_feature_pixel.h, compiled once per output format (see there).
+#define HESS_PIXEL_KERNEL descriptor_pixel_kernel
+#define HESS_PIXEL_U8 false
+#include "k_feature_pixel.h"
+#undef HESS_PIXEL_KERNEL
+#undef HESS_PIXEL_U8
+#define HESS_PIXEL_KERNEL descriptor_pixel_u8_kernel
+#define HESS_PIXEL_U8 true
+#include "k_feature_pixel.h"
+#undef HESS_PIXEL_KERNEL
+#undef HESS_PIXEL_U8
 
 }  // namespace
 
@@ -1284,8 +1072,12 @@ void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, cons
                      recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat)
   const bool mirror = dp.hkeys || dp.hdesc;
   if (dp.pixel) {
-    if (mirror) hipLaunchKernelGGL((descriptor_pixel_kernel<true>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list, recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
-    else hipLaunchKernelGGL((descriptor_pixel_kernel<false>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list, recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
+#define HESS_PIXEL_LAUNCH(KERNEL, MIRROR)                                                                               \
+  hipLaunchKernelGGL((KERNEL<MIRROR>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list, recs, fsrc, feat_total, \
+                     feat_first, img_base, got, keys, desc, cap_feat)
+    if (dp.u8) { if (mirror) HESS_PIXEL_LAUNCH(descriptor_pixel_u8_kernel, true); else HESS_PIXEL_LAUNCH(descriptor_pixel_u8_kernel, false); }
+    else { if (mirror) HESS_PIXEL_LAUNCH(descriptor_pixel_kernel, true); else HESS_PIXEL_LAUNCH(descriptor_pixel_kernel, false); }
+#undef HESS_PIXEL_LAUNCH
   } else if (dp.sequential) { if (mirror) HESS_DESC_LAUNCH(true, true); else HESS_DESC_LAUNCH(false, true); }
   else { if (mirror) HESS_DESC_LAUNCH(true, false); else HESS_DESC_LAUNCH(false, false); }
 #undef HESS_DESC_LAUNCH

@@ -27,6 +27,7 @@ def _lib():
         L.hess_matcher_bank_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hess_matcher_bank_set_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hess_matcher_bank_set_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hess_matcher_bank_set_device_u8.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hess_matcher_bank_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hess_matcher_match_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_float, C.c_float, C.c_int]
@@ -129,16 +130,20 @@ class Matcher:
         self._check(fn(self.h, len(counts), counts.ctypes.data, flat.ctypes.data if flat.size else None))
         self._bank_sets = len(counts)
 
-    def set_bank_device(self, ptr, counts):
-        """ptr: device address of float [sum(counts)][128] on the matcher's device (quantised on the device).  The
-        producer must have finished writing it."""
+    def set_bank_device(self, ptr, counts, dtype=np.float32):
+        """ptr: device address of float [sum(counts)][128] on the matcher's device (quantised on the device), or with
+        dtype=np.uint8 of bytes [sum(counts)][128] (stored as they are).  The producer must have finished writing it."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"device descriptors are float32 or uint8, not {dt}")
         c = np.ascontiguousarray(counts, dtype=np.int32)
-        self._check(self.L.hess_matcher_bank_set_device(self.h, len(c), c.ctypes.data, ptr))
+        fn = self.L.hess_matcher_bank_set_device_u8 if dt == np.uint8 else self.L.hess_matcher_bank_set_device
+        self._check(fn(self.h, len(c), c.ctypes.data, ptr))
         self._bank_sets = len(c)
 
     def set_bank_from_session(self, session):
         """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,
-        without leaving the device."""
+        without leaving the device -- floats or bytes, whichever the run made."""
         dim = session.desc_dim()
         if dim != 128:
             raise ValueError(f"the matcher takes 128-d descriptors; this context's are {dim}-d (-half / -sd)")
@@ -146,7 +151,7 @@ class Matcher:
         counts = [session.count(i) for i in range(session._batch)]
         if sum(counts) != total:
             raise ValueError(f"the context's counts ({sum(counts)}) do not cover its device results ({total})")
-        self.set_bank_device(desc, counts)
+        self.set_bank_device(desc, counts, dtype=np.uint8 if session.desc_format() == "u8" else np.float32)
 
     def bank(self, i):
         """The stored bytes of set i: [n, 128] u8."""

@@ -19,6 +19,7 @@ class HessError(RuntimeError):
 _FMT_BY_CHANNELS = {1: _abi.FMT_LUM, 2: _abi.FMT_LUM_ALPHA, 3: _abi.FMT_RGB, 4: _abi.FMT_RGBA}
 _PIX_BY_DTYPE = {np.dtype(np.uint8): _abi.PIX_U8, np.dtype(np.uint16): _abi.PIX_U16,
                  np.dtype(np.float32): _abi.PIX_F32}
+_DESC_FORMATS = {"f32": _abi.DESC_FORMAT_F32, "u8": _abi.DESC_FORMAT_U8}
 
 
 def make_params(fn_default, **overrides):
@@ -172,14 +173,29 @@ class Session:
     def desc_dim(self):
         return self._check(self._f["desc_dim"](self._h))
 
+    def set_descriptor_format(self, fmt):
+        """"f32" (the default) or "u8": what the following runs store per descriptor element (product only;
+        hess_set_descriptor_format).  Bytes are the matcher's quantisation of the floats, made by the descriptor kernels."""
+        if fmt not in _DESC_FORMATS:
+            raise ValueError(f"descriptor format must be one of {sorted(_DESC_FORMATS)}, not {fmt!r}")
+        self._check(self._f["set_descriptor_format"](self._h, _DESC_FORMATS[fmt]))
+
+    def desc_format(self):
+        """"f32" or "u8": the format of the last run's descriptors (product only)."""
+        if "desc_format" not in self._f:
+            return "f32"
+        code = self._check(self._f["desc_format"](self._h))
+        return next(k for k, v in _DESC_FORMATS.items() if v == code)
+
     def fetch(self, img=0):
-        """-> (keys structured array [N], descriptors float32 [N, dim])."""
+        """-> (keys structured array [N], descriptors float32 [N, dim] -- uint8 [N, dim] after a "u8" run)."""
         n = self.count(img)
         dim = self.desc_dim()
+        u8 = self.desc_format() == "u8"
         keys = np.zeros(n, dtype=_abi.KEYPOINT_DTYPE)
-        desc = np.zeros((n, dim), dtype=np.float32)
-        self._check(self._f["fetch"](self._h, img, keys.ctypes.data_as(C.c_void_p),
-                                     desc.ctypes.data_as(C.c_void_p) if dim else None))
+        desc = np.zeros((n, dim), dtype=np.uint8 if u8 else np.float32)
+        self._check(self._f["fetch_u8" if u8 else "fetch"](self._h, img, keys.ctypes.data_as(C.c_void_p),
+                                                           desc.ctypes.data_as(C.c_void_p) if dim else None))
         return keys, desc
 
     def geometry(self):
@@ -208,7 +224,8 @@ class Session:
         return np.array([p[i] for i in range(_abi.T_COUNT)], dtype=np.float32)
 
     def device_results(self):
-        """-> (keys_ptr, desc_ptr, total): packed device results of the last run (product only)."""
+        """-> (keys_ptr, desc_ptr, total): packed device results of the last run (product only); desc_ptr addresses
+        float [total][dim], or uint8 [total][dim] after a "u8" run."""
         k, d, cap = C.c_void_p(), C.c_void_p(), C.c_int()
         self._check(self._f["device_results"](self._h, C.byref(k), C.byref(d), C.byref(cap)))
         return k.value, d.value, cap.value

@@ -37,7 +37,9 @@ extern "C" {
  * 5: hess_params.detector (word 0 of reserved[], which a version-2, -3 or -4 struct leaves zero: the Hessian detector):
  *    HESS_DETECTOR_DOG runs the difference-of-Gaussians detector of the reference's build without GPU_HESSIAN.
  *    hess_matcher_bank_set / _set_f32 / _set_device / _read and hess_matcher_match_pairs (added during version 5
- *    without a bump). */
+ *    without a bump).  hess_set_descriptor_format / hess_desc_format / hess_fetch_u8 and
+ *    hess_matcher_bank_set_device_u8 (byte descriptors; added during version 5 without a bump: hess_params keeps its
+ *    layout, and a context that never calls the setter behaves as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -257,14 +259,39 @@ int hess_run_keypoints(hess_ctx* ctx, const hess_keypoint* keys, int num, int ke
 
 /* Replaces SiftGPU::GetFeatureNum (SiftGPU.cpp:1551-1554) for image `img` of the last batch. */
 int hess_count(hess_ctx* ctx, int img);
-/* Descriptor length of the last run: 128, 64 (-half) or 0 (-sd). */
+/* Descriptor length of the last run in ELEMENTS, whatever the format: 128, 64 (-half) or 0 (-sd). */
 int hess_desc_dim(hess_ctx* ctx);
 /* Replaces SiftGPU::GetFeatureVector -> SiftPyramid::CopyFeatureVector (SiftPyramid.cpp:313-324).
- * Either output may be NULL.  keys: hess_count() records; desc: hess_count()*hess_desc_dim() floats. */
+ * Either output may be NULL.  keys: hess_count() records; desc: hess_count()*hess_desc_dim() floats.
+ * After a HESS_DESC_FORMAT_U8 run: HESS_ERR_STATE, nothing written (hess_fetch_u8 is the call; nothing converts). */
 int hess_fetch(hess_ctx* ctx, int img, hess_keypoint* keys, float* desc);
 
+/* Descriptor output format of a context.  F32 (the default): float[dim] per feature, as always.  U8: the descriptor
+ * kernels store dim BYTES per feature -- what the matcher, SiftMatchGPU::SetDescriptors and the .sift files take -- and
+ * everything behind them carries bytes: device and pinned result buffers, every delivery, hess_fetch_u8,
+ * hess_device_results, hess_matcher_bank_set_device_u8.  A quarter of the result bytes in HBM and over the host link.
+ *   byte = low byte of (int)((double)(512.0f * d) + 0.5)      (product in float, sum in double, truncation)
+ * -- the matcher's own rule (hess_matcher_set_descriptors_f32, SiftMatchCU.cpp:88-100), so a bank built from byte
+ * results is byte-equal to the bank built from the float results of the same images.  The low byte WRAPS, as it does
+ * there: d >= 0.49902 (512 d + 0.5 >= 256) wraps, d = 1.0 gives byte 0; normalised descriptors are clamped to 0.2
+ * before the second normalisation and stay far below that in practice.
+ * hess_set_descriptor_format applies to the FOLLOWING runs (keypoint-list runs included) and may be changed between
+ * runs in both directions; the results of the run before stay fetchable in their own format.
+ *   HESS_ERR_ARG          ctx NULL, or a format that is neither
+ *   HESS_ERR_STATE        a submitted batch is pending (call hess_wait first)
+ *   HESS_ERR_UNSUPPORTED  U8 with hess_params.normalize == 0 (unbounded values), or on a context whose results are
+ *                         shared (hess_share_results, which in turn refuses a U8 context)
+ * hess_desc_format: the format of the last run (of the following runs while the context has not run yet).
+ * hess_fetch_u8: as hess_fetch after a U8 run; desc gets exactly hess_count() * hess_desc_dim() bytes.  After an F32
+ * run: HESS_ERR_STATE, nothing written. */
+enum { HESS_DESC_FORMAT_F32 = 0, HESS_DESC_FORMAT_U8 = 1 };
+int hess_set_descriptor_format(hess_ctx* ctx, int format);
+int hess_desc_format(hess_ctx* ctx);
+int hess_fetch_u8(hess_ctx* ctx, int img, hess_keypoint* keys, unsigned char* desc);
+
 /* Device-resident results of the last run, for consumers that stay on the GPU (the multi-GPU
- * gather over RCCL): keys = [total] hess_keypoint, desc = [total][dim] float, the images of the
+ * gather over RCCL): keys = [total] hess_keypoint, desc = [total][dim] float -- unsigned char [total][dim] after a
+ * HESS_DESC_FORMAT_U8 run (hess_desc_format tells) --, the images of the
  * batch back to back (image b starts at hess_count(0)+..+hess_count(b-1)); *total = records in use.
  * Pointers stay valid until the next run. */
 int hess_device_results(hess_ctx* ctx, const void** keys, const void** desc, int* total);
@@ -300,7 +327,8 @@ int hess_debug_keep_levels(hess_ctx* ctx, int on);
  * A generation number grows when a buffer is reallocated (a reader re-maps when it changes; the old object is
  * unlinked).  The per-image counts travel by the job's own control channel (hess_count); the data of a batch is
  * complete when hess_wait / hess_run_* has returned and stays until the context's next batch is submitted.
- * Call after hess_create, before the first batch; the objects are unlinked by hess_destroy.  name: no '/'. */
+ * Call after hess_create, before the first batch; the objects are unlinked by hess_destroy.  name: no '/'.
+ * Float descriptors only: HESS_ERR_UNSUPPORTED on a context set to HESS_DESC_FORMAT_U8. */
 int hess_share_results(hess_ctx* ctx, const char* name);
 int hess_shared_results_info(hess_ctx* ctx, unsigned* gen_keys, unsigned* gen_desc, size_t* keys_bytes, size_t* desc_bytes);
 /* Raw detections of image `img` in list order; returns the count (<= cap written). */
@@ -351,6 +379,9 @@ int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, con
  * waited for the run that produced the descriptors (hess_wait / hess_run_*); the call returns when the bank is built,
  * so the context's next run may start at once.  A pointer that is not device memory of that device: HESS_ERR_ARG. */
 int hess_matcher_bank_set_device(hess_matcher* m, int nsets, const int* counts, const float* dev_desc);
+/* The same from device BYTES, unsigned char [sum of counts][128] (hess_device_results after a HESS_DESC_FORMAT_U8 run):
+ * stored as they are.  Same pointer check (4-byte alignment here), truncation to max_sift and return-when-built. */
+int hess_matcher_bank_set_device_u8(hess_matcher* m, int nsets, const int* counts, const unsigned char* dev_desc);
 /* The stored bytes of set `set` (its count x 128; out may be NULL).  Returns the count. */
 int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out);
 /* Unguided GetSiftMatch for every pair p: set 1 = bank[pairs_ab[2p]], set 2 = bank[pairs_ab[2p+1]].  Pair p's result is
