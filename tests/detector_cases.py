@@ -9,13 +9,22 @@ names the stage and the rule:
   gauss         level 0 from the pixels (conversion, decimation, up-sampling, first blur or its skip), level l from
                 the session's level l - 1, level 0 of the next octave from the session's level `dog`               TOL_GAUSS
   det-H, grad, theta   from the session's Gaussian level                                                            TOL_*
-  detect        the raw list from the session's det-H planes: positions, order, type; list reduction and top-K     exact *
+  response      DoG mode, instead of det-H: D_l = G_l - G_(l-1) from the session's two Gaussian levels              exact
+  detect        the raw list from the session's response planes: positions, order, type; list reduction and top-K  exact *
                 offsets and response                                                                                2e-3, 1e-3
   orient        per raw item from the session's gradient planes: number of orientations, second truncation pass    exact *
                 exported position / scale from the session's own offsets                                            one quantum
                 orientation                                                                                         one quantum
   descriptor    a sample of <= 40, at the session's own quantised key                                               1e-4
   (*) except at items the model flags as uncertain (np_restatement.key_test_ex, orientations_ex): either answer passes.
+
+The mode comes from session.params.detector.  In the difference-of-Gaussians mode an octave has the Gaussian levels
+0 .. dog + 2 and the response planes 1 .. dog + 2 (the detector never reads response level 0, and neither does the
+checker); list level l is scanned in the planes l, l + 1, l + 2 and described from Gaussian level l; where the two-peak
+orientation branch ran the quantum is that of its 16-bit angles.
+
+A case with batch_at = (n, i) runs as image i of a stack of n; the other images are seeded noise of the same size and
+type, and image i is checked exactly as a single image would be.
 
 Images come from seeds; nothing here reads a file.
 """
@@ -37,11 +46,17 @@ TOL_THETA = 1e-5         # where the gradient is > 1e-6
 TOL_OFFSET = 2e-3
 TOL_RESP = 1e-3          # relative
 QUANTUM = 2 * R.PI / 255.0
+QUANTUM_16 = 2 * R.PI / 65535.0     # the two-peak branch of the difference-of-Gaussians mode
+# Over one quantum (the floor of the code) an angle may differ by the binary32 error of what is floored.  The slack was set
+# for the 8-bit angles and is kept for the 16-bit ones, a tenth of their quantum: the largest excess over one quantum that
+# any case shows is 7e-8 rad, once the model takes the key position as the binary32 number it is (DetectorModel.key_geometry).
+TOL_ANGLE = 1e-5
 TOL_DESC = 1e-4
 MAX_DESC = 40
 MAX_UNCERTAIN_SHARE = 0.01
 
 NOISE_KW = dict(dog_threshold=0.0005, edge_threshold=50.0)
+DOG = dict(detector=_abi.DETECTOR_DOG)
 
 
 def noise(w, h, seed=None):
@@ -101,9 +116,21 @@ def _user_keys(w, h, seed=2):
     return keys
 
 
-def _case(name, image, fmt=None, keys=None, have_orientation=1, min_features=1, **kw):
+def _case(name, image, fmt=None, keys=None, have_orientation=1, min_features=1, batch_at=None, min_three_peaks=0, **kw):
     return SimpleNamespace(name=name, image=image, fmt=fmt, keys=keys, have_orientation=have_orientation,
-                           min_features=min_features, kw=kw)
+                           min_features=min_features, batch_at=batch_at, min_three_peaks=min_three_peaks, kw=kw)
+
+
+def case_input(case):
+    """-> (stack [n, H, W(, C)], index of the case's image in it).  batch_at = (n, i): the image at index i, seeded noise of
+    the same shape and type elsewhere."""
+    img = np.asarray(case.image)
+    if case.batch_at is None:
+        return img[None], 0
+    n, at = case.batch_at
+    top = 1.0 if img.dtype == np.float32 else float(np.iinfo(img.dtype).max)
+    stack = [img if j == at else (np.random.RandomState(7919 + j).rand(*img.shape) * top).astype(img.dtype) for j in range(n)]
+    return np.stack(stack), at
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,7 +191,50 @@ def cases():
     out.append(_case("keypoint list half_sift", b, keys=keys, have_orientation=0, half_sift=1))
     out.append(_case("keypoint list max_orientation 1", b, keys=keys, have_orientation=0, max_orientation=1))
     out.append(_case("keypoint list fixed_orientation", b, keys=keys, have_orientation=0, fixed_orientation=1))
+    out.append(_case("noise 260x49 batch 3", noise(260, 49), batch_at=(3, 1), **NOISE_KW))
+    out.extend(_dog_cases(b, g, c, keys))
     return {c.name: c for c in out}
+
+
+def _dog_cases(b, g, c, keys):
+    """The difference-of-Gaussians mode (kw carries detector = 1).  White noise has few extrema in scale -- the finer
+    difference is the stronger one nearly everywhere -- so the two small noise images come from seeds chosen for their
+    number of detections (DOG_NOISE_SEEDS), and the thresholds of the Hessian cases, which count det-H, are not taken over:
+    the defaults (0.02 / dog, 10) serve unless a case says otherwise.  b6: blobs_noise with another seed, for three cases
+    in which the usual one has a flagged orientation among fewer than 100 candidates."""
+    d = DOG
+    b6 = blobs_noise(seed=6)
+    out = []
+    for w, h in ((132, 25), (260, 49), (324, 223)):
+        out.append(_case(f"dog: noise {w}x{h}", noise(w, h, DOG_NOISE_SEEDS.get((w, h))), **NOISE_KW, **d))
+    out.append(_case("dog: noise 260x49 batch 3", noise(260, 49, DOG_NOISE_SEEDS[260, 49]), batch_at=(3, 1), **NOISE_KW, **d))
+    out.append(_case("dog: defaults", b, **d))
+    out.append(_case("dog: first_octave -1", b6, first_octave=-1, **d))
+    out.append(_case("dog: first_octave 1", noise(324, 223), first_octave=1, **NOISE_KW, **d))
+    out.append(_case("dog: first_octave -2", b, first_octave=-2, **d))
+    for dog in (1, 2, 5, 6):
+        out.append(_case(f"dog: dog_level_num {dog}", b6 if dog == 1 else b, dog_level_num=dog, **d))
+    out.append(_case("dog: subpixel 0", b, subpixel=0, **d))
+    out.append(_case("dog: max_orientation 1", b, max_orientation=1, **d))
+    # the dot grid: dots of three periods overlap into patches with several dominant directions
+    out.append(_case("dog: max_orientation 4", g, max_orientation=4, min_three_peaks=5, **d))
+    out.append(_case("dog: fixed_orientation", b, fixed_orientation=1, **d))
+    out.append(_case("dog: half_sift", b, half_sift=1, **d))
+    out.append(_case("dog: half_sift max_orientation 4", b, half_sift=1, max_orientation=4, **d))
+    out.append(_case("dog: lowe_origin first_octave -1", b6, lowe_origin=1, first_octave=-1, **d))
+    for name, method, thr in (("highest0", _abi.TRUNC_HIGHEST_0, DOG_GRID_THRESHOLD), ("highest1", _abi.TRUNC_HIGHEST_1, DOG_GRID_THRESHOLD),
+                              ("lowest", _abi.TRUNC_LOWEST, DOG_GRID_THRESHOLD_LOWEST)):
+        out.append(_case(f"dog: truncate {name}", g, truncate_method=method, feature_count_threshold=thr, **d))
+    out.append(_case("dog: top-K", g, truncate_method=_abi.TRUNC_TOPK, feature_count_threshold=DOG_GRID_TOPK, **d))
+    ck = DOG_COLOUR_KW
+    out.append(_case("dog: u8 rgb", c, **ck, **d))
+    out.append(_case("dog: u16 rgb", c.astype(np.uint16) * 257, **ck, **d))
+    out.append(_case("dog: f32 lum", (c[..., 1] / 255.0).astype(np.float32), **ck, **d))
+    out.append(_case("dog: keypoint list orient=1", b, keys=keys, have_orientation=1, **d))
+    out.append(_case("dog: keypoint list orient=0", b, keys=keys, have_orientation=0, **d))
+    out.append(_case("dog: keypoint list orient=0 first_octave -1 lowe", b, keys=keys, have_orientation=0, first_octave=-1,
+                     lowe_origin=1, **d))
+    return out
 
 
 # The dot grid has [345, 219, 34, 1, 50, 10, 2, 7] detections and [381, 282, 43, 1, 59, 14, 3, 22] features per level
@@ -184,6 +254,18 @@ COLOUR_KW = dict(dog_threshold=0.0015, edge_threshold=20.0)
 GRID_THRESHOLD = 120
 GRID_THRESHOLD_LOWEST = 400
 GRID_TOPK = 192
+# The same grid in the difference-of-Gaussians mode, at the default thresholds: [173, 68, 1, 2, 21, 0, 0, 0] detections and
+# [196, 89, 2, 3, 26, 0, 0, 0] features per level (test_dog_grid_thresholds_fall_inside_a_level).  27: the levels above level
+# 1 hold 24 detections, so the first pass keeps level 1 (92 with it); above it are 31 features, so the second pass drops it.
+# 200 lies inside level 1 counted from the bottom (173, 241 with it).  124: the detections ranked 123, 124 and 125 by
+# abs(half(response)) are equal.
+DOG_GRID_THRESHOLD = 27
+DOG_GRID_THRESHOLD_LOWEST = 200
+DOG_GRID_TOPK = 124
+DOG_COLOUR_KW = dict(dog_threshold=0.003, edge_threshold=10.0)
+# noise(w, h, seed) with at least 8 detections in the difference-of-Gaussians mode at NOISE_KW; of the seeds 0 .. 64399 one
+# gives 8 on 132 x 25 (the median is 1), 394 is the best of 0 .. 399 on 260 x 49 (14; the median is 6)
+DOG_NOISE_SEEDS = {(132, 25): 21600, (260, 49): 394}
 
 
 def _circ(a, b):
@@ -215,17 +297,23 @@ def check_against_model(session, case, model=None, dense=True, log=None):
     m = model or R.DetectorModel(session.params)
     img = np.asarray(case.image)
     h, w = img.shape[:2]
-    st = dict(candidates=0, uncertain=0, orient_uncertain=0, gauss=0.0, deth=0.0, grad=0.0, theta=0.0, desc=0.0)
+    st = dict(candidates=0, uncertain=0, orient_uncertain=0, gauss=0.0, deth=0.0, grad=0.0, theta=0.0, desc=0.0,
+              angle=0.0, three_peaks=0)
+    is_dog = int(session.params.detector) == _abi.DETECTOR_DOG
+    _need(m.is_dog == is_dog, "geometry", "the model is not in the session's mode")
     session.keep_levels(True)
-    counts = session.run(img[None], fmt=case.fmt)
+    stack, bi = case_input(case)
+    session.run(stack, fmt=case.fmt)
     ds, omin, geo, scales = m.plan(w, h)
     _need(session.geometry() == geo, "geometry", lambda: f"{session.geometry()} != {geo}")
-    dog, nlev = m.dog, m.dog + 2
+    dog, nlev = m.dog, m.nlev
+    # the response planes the scans read (a wrong-rule model may ask for level 0; the right DoG rules never do)
+    first_d = min(min(m.scan_planes(l)) for l in range(1, dog + 1)) if is_dog else 0
 
     # ---- dense planes
-    G = [[session.level(0, oc, l, _abi.DBG_GAUSS) for l in range(nlev)] for oc in range(len(geo))]
-    D = [[session.level(0, oc, l, _abi.DBG_DETH) for l in range(nlev)] for oc in range(len(geo))]
-    GOT = [[session.level(0, oc, l, _abi.DBG_GOT).astype(np.float64) if 1 <= l <= dog else None for l in range(nlev)]
+    G = [[session.level(bi, oc, l, _abi.DBG_GAUSS) for l in range(nlev)] for oc in range(len(geo))]
+    D = [[session.level(bi, oc, l, _abi.DBG_DETH) if l >= first_d else None for l in range(nlev)] for oc in range(len(geo))]
+    GOT = [[session.level(bi, oc, l, _abi.DBG_GOT).astype(np.float64) if 1 <= l <= dog else None for l in range(nlev)]
            for oc in range(len(geo))]
     if dense:
         base, taps0 = m.base_plane(img, case.fmt)
@@ -238,17 +326,24 @@ def check_against_model(session, case, model=None, dense=True, log=None):
                 if l == 0 and oc == 0:
                     want = base if taps0 is None else R.gaussian(base, taps0)
                 elif l == 0:
-                    want = R.downsample(G[oc - 1][dog].astype(np.float64), wa, hh)
+                    want = R.downsample(G[oc - 1][m.level_ds].astype(np.float64), wa, hh)
                 else:
                     want = R.gaussian(G[oc][l - 1].astype(np.float64), m.level_taps(l))
                 _need(a.shape == want.shape, "gauss", lambda: f"octave {oc} level {l}: shape {a.shape} != {want.shape}")
                 d = float(np.abs(a - want).max())
                 st["gauss"] = max(st["gauss"], d)
                 _need(d < TOL_GAUSS * mag, "gauss", lambda: f"octave {oc} level {l}: max |d| {d:.3g}")
+                # (gradient and angle are the same lines in both kernels: ProgramCU.cu:567-591 and :612-621)
                 deth, grad, theta = R.hessian_planes(a, m.level_sigma(l))
-                d = float(np.abs(D[oc][l] - deth).max()) / max(1.0, float(np.abs(deth).max()))
-                st["deth"] = max(st["deth"], d)
-                _need(d < TOL_DETH, "det-H", lambda: f"octave {oc} level {l}: {d:.3g} of the plane's maximum")
+                if is_dog:
+                    if l >= 1:       # exact: a correctly rounded binary32 subtraction of these two planes has one answer
+                        want = m.response_plane(G[oc][l], G[oc][l - 1])
+                        bad = int((D[oc][l] != want).sum())
+                        _need(bad == 0, "response", lambda: f"octave {oc} level {l}: {bad} pixels are not G_l - G_(l-1)")
+                else:
+                    d = float(np.abs(D[oc][l] - deth).max()) / max(1.0, float(np.abs(deth).max()))
+                    st["deth"] = max(st["deth"], d)
+                    _need(d < TOL_DETH, "det-H", lambda: f"octave {oc} level {l}: {d:.3g} of the plane's maximum")
                 if 1 <= l <= dog:
                     got = GOT[oc][l]
                     d = float(np.abs(got[..., 0] - grad).max())
@@ -264,12 +359,13 @@ def check_against_model(session, case, model=None, dense=True, log=None):
         _check_keypoint_list(session, case, m, GOT, scales, st)
         return st
 
-    # ---- detection from the session's det-H planes
-    raw = session.rawlist(0)
+    # ---- detection from the session's response planes
+    raw = session.rawlist(bi)
     found, unsure = [], []
     for oc in range(len(geo)):
         for l in range(1, dog + 1):
-            f, u, n = m.scan(D[oc][l], D[oc][l - 1], D[oc][l + 1], G[oc][l])
+            pc, pp, pn = m.scan_planes(l)
+            f, u, n = m.scan(D[oc][pc], D[oc][pp], D[oc][pn], G[oc][l])
             found.append(f)
             unsure.append(u)
             st["candidates"] += n
@@ -316,7 +412,7 @@ def check_against_model(session, case, model=None, dense=True, log=None):
     st["detections"] = len(raw)
 
     # ---- orientation per raw item, from the session's gradient planes
-    keys, desc = session.fetch(0)
+    keys, desc = session.fetch(bi)
     groups = []                                   # runs of equal (level, x, y, s): the orientations of one location
     for i, k in enumerate(keys):
         ident = (int(k["level"]), float(k["x"]), float(k["y"]), float(k["s"]))
@@ -329,9 +425,11 @@ def check_against_model(session, case, model=None, dense=True, log=None):
         li = int(rk["level_index"])
         oc, l = li // dog, li % dog + 1
         x, y, s = m.key_geometry(l, int(rk["row"]), int(rk["col"]), float(rk["dx"]), float(rk["dy"]), float(rk["ds"]))
-        angles, unc = m.rotations(GOT[oc][l][..., 0], GOT[oc][l][..., 1], x, y, s)
+        info = {}
+        angles, unc = m.rotations(GOT[oc][l][..., 0], GOT[oc][l][..., 1], x, y, s, info=info)
         items.append((li, oc, l, x, y, s, angles, unc, rk))
         st["orient_uncertain"] += int(unc)
+        st["three_peaks"] += int(info.get("peaks", 0) >= 3)
     multi = [0] * len(expect)
     for it in items:
         multi[it[0]] += len(it[6])
@@ -342,6 +440,8 @@ def check_against_model(session, case, model=None, dense=True, log=None):
     _need(len(groups) == len(items), "orient", lambda: f"{len(groups)} locations among the features, model {len(items)} "
                                                        f"(features per level {np.bincount(keys['level'], minlength=len(multi)).tolist()}, model {kept2})")
     off = 0.0 if m.lowe_origin else 0.5
+    # the quantum of the session's mode, whatever the model believes: 16-bit angles where the two-peak branch ran
+    quantum = QUANTUM_16 if is_dog and not m.single and not m.fixed_orientation else QUANTUM
     todo = []
     for (ident, idx), (li, oc, l, x, y, s, angles, unc, rk) in zip(groups, items):
         sc = scales[oc]
@@ -358,7 +458,9 @@ def check_against_model(session, case, model=None, dense=True, log=None):
         if len(idx) == len(angles):
             for j, a in zip(idx, angles):
                 d = _circ(float(keys[j]["o"]), m.mirrored(a))
-                _need(d <= QUANTUM + 1e-5 or unc, "orient", f"feature {j} level {li}: orientation {keys[j]['o']}, model {m.mirrored(a)}")
+                if not unc:
+                    st["angle"] = max(st["angle"], d - quantum)
+                _need(d <= quantum + TOL_ANGLE or unc, "orient", f"feature {j} level {li}: orientation {keys[j]['o']}, model {m.mirrored(a)}")
         for j in idx:
             todo.append((j, oc, l, sc))
     st["features"] = len(keys)
@@ -394,6 +496,8 @@ def check_statistics(st, case):
     assert st["detections"] >= 8, st
     assert st["uncertain"] + st["orient_uncertain"] <= MAX_UNCERTAIN_SHARE * st["candidates"], st
     assert st["descriptors"] >= min(30, st["features"]) and st["clipped"] >= 5, st
+    # the two-strongest rule is exercised only where three or more peaks qualify
+    assert st["three_peaks"] >= case.min_three_peaks, st
 
 
 def _clipped(k, sc, dwf, geo, off):
@@ -409,7 +513,7 @@ def _check_keypoint_list(session, case, m, GOT, scales, st):
     keys = case.keys
     n = session.run_keypoints(keys, case.have_orientation)
     _need(n == len(keys), "keylist", f"{n} features for {len(keys)} keys")
-    out, desc = session.fetch(0)
+    out, desc = session.fetch(0)          # (a keypoint list runs on one image: no case has both keys and batch_at)
     # -m 1 and -ofix download the list again after the orientation pass (SiftPyramid.cpp:165-172): position and scale come
     # back through the fixed-point record, with the level; otherwise the caller's keys are returned as they came and only
     # the descriptor shows the orientation that was found
@@ -435,7 +539,7 @@ def _check_keypoint_list(session, case, m, GOT, scales, st):
             _need(max(abs(out[i]["x"] - ex), abs(out[i]["y"] - ey)) <= 1e-6 * (1 + abs(ex) + abs(ey)) and abs(out[i]["s"] - es) <= 1e-6 * es,
                   "keylist", f"key {i}: {(out[i]['x'], out[i]['y'], out[i]['s'])}, model {(ex, ey, es)}")
             d = _circ(float(out[i]["o"]), m.mirrored(ang))
-            _need(d <= QUANTUM + 1e-5 or unc, "keylist", f"key {i} (level {hits[0]}): orientation {out[i]['o']}, model {m.mirrored(ang)}")
+            _need(d <= QUANTUM + TOL_ANGLE or unc, "keylist", f"key {i} (level {hits[0]}): orientation {out[i]['o']}, model {m.mirrored(ang)}")
             ang = (2 * R.PI - float(out[i]["o"])) % (2 * R.PI)
         else:
             _need(out[i].tobytes() == k.tobytes(), "keylist", f"key {i}: the caller's key changed")

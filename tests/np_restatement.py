@@ -141,11 +141,30 @@ def descriptor(grad, theta, x, y, s, angle, half=False, window_factor=3.0):
 
 
 # =====================================================================================================================
-# DetectorModel: every option of the Hessian detector, end to end on a small image, in float64.
+# DetectorModel: every option of the Hessian detector and of the difference-of-Gaussians detector, end to end on a small
+# image, in float64.
 #
 # Written from the reference source (lines cited per rule) and SURVEY.md section 8.  A rule marked PROJECT is the
 # project's own: the reference does not state it (or cannot reach it).  Keyword switches of DetectorModel state
 # plausible WRONG rules with the same code (WRONG_RULES); tests/test_detector_model.py shows that each one is caught.
+#
+# The difference-of-Gaussians mode (detector = 1) is the reference compiled WITHOUT GPU_HESSIAN, stated from the #else /
+# #ifndef lines alone.  Its rules, each once, where the Hessian rule is stated, behind a switch:
+#   schedule    DetectorModel.__init__, level_sigma, initial_sigma       SiftGPU.cpp:466-556
+#   planes      response_plane, scan_planes                               ProgramCU.cu:598-637, PyramidCU.cpp:1593-1605, 1654-1670
+#   key test    key_test_ex(dog=True)                                     ProgramCU.cu:680-699, 853-854
+#   orientation orientations_ex(two_peaks=True), rotations                ProgramCU.cu:1493-1548, PyramidCU.cpp:763-767, 800-820
+# Shared code that the build without GPU_HESSIAN reaches through other lines, or not at all -- the product keeps the
+# records of the GPU_HESSIAN / GPU_SIFT_MODIFIED builds in both modes, so these are PROJECT in DoG mode:
+#   * the list record: that build stores x, y and the scale as floats (ProgramCU.cu:1417-1419, 1557-1559), not as 14.10 /
+#     8.8 fixed point with the half-precision response and the type (:1574-1596, the GPU_SIFT_MODIFIED form kept here);
+#     export() and user_key() therefore round as in the Hessian mode;
+#   * keypoint lists: binned by the same half-step rule on GetLevelSigma(level + _level_min + 1), levels counted from 0
+#     (PyramidCU.cpp:575, 583, 607-610) -- the same sigmas and the same catch-alls in this numbering; the record is the
+#     float one (:668-692);
+#   * top-K exists only with GPU_HESSIAN or GPU_SIFT_MODIFIED (config.h:81-85, PyramidCU.cpp:1879-1989); the level
+#     truncation passes (SiftPyramid.cpp:224-277, PyramidCU.cpp:1283-1345) and the descriptor (ProgramCU.cu:1650-2054)
+#     are the same lines in every build.
 # =====================================================================================================================
 U = 2.0 ** -24                      # unit round-off of binary32
 TEN_DEG = 5.7295779513082320876798154814105
@@ -165,6 +184,14 @@ WRONG_RULES = {
     "16-bit RGB does not wrap": dict(no_wrap=True),
     "level binning rounds at whole steps": dict(whole_step=True),
     "lowe_origin offset before the octave scale": dict(lowe_before_scale=True),
+    # the difference-of-Gaussians mode (detector = 1)
+    "DoG extrema keep the Hessian sign tests": dict(dog_sign_tests=True),
+    "DoG list level sought one plane lower": dict(dog_plane_lower=True),
+    "DoG type from L_xx": dict(dog_type_lxx=True),
+    "DoG angles are 8-bit": dict(dog_angle8=True),
+    "DoG keeps up to four peaks": dict(dog_four_peaks=True),
+    "DoG next octave from the level above": dict(dog_ds_above=True),
+    "DoG level sigma one level off": dict(dog_sigma_off=True),
 }
 
 
@@ -229,11 +256,18 @@ def upsample(src, k, clamp=False):
 
 
 # ---- ComputeKEY_Kernel with rounding margins ------------------------------------------------------------------------
-def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False):
+def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False, dog=False, dog_sign_tests=False,
+                dog_type_lxx=False):
     """ComputeKEY_Kernel, ProgramCU.cu:702-882 (pure Python, one pixel) -> (result, uncertain); result is None or
     (response, type, dx, dy, ds).  uncertain: a gate value lies within 8 x a first-order bound of the
     binary32 evaluation's error of its threshold, so the float32 implementation may decide either way (the comparisons
-    of r with its neighbours are exact on float32 planes and never flagged)."""
+    of r with its neighbours are exact on float32 planes and never flagged).
+    dog: the kernel as compiled without GPU_HESSIAN.  READ_CMP_DOG_DATA (:680-699) has no sign conditions -- a maximum may
+    be negative and a minimum positive -- and the type is BRIGHT where `response > nmax` and DARK otherwise (:853-854),
+    with the response AFTER the sub-pixel step and nmax as the neighbour tests left it: the largest of all 26 neighbours
+    at a maximum, of the left and right neighbour only at a minimum (the else branch never touches nmax).  There is no
+    saddle type.  dog_sign_tests, dog_type_lxx: the WRONG rules that keep the Hessian lines."""
+    signs = not dog or dog_sign_tests
     T = float(T)
     thr0 = (0.8 if (subpixel or keep08) else 1.0) * T
     edge_t = (edge + 1.0) ** 2 / edge
@@ -251,9 +285,9 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False)
         vals = [float(plane[rr, col - 1]), float(plane[rr, col]), float(plane[rr, col + 1])]
         if r > state[0]:
             state[0] = max([state[0]] + vals)
-            return not (r < state[0] or r < 0)
+            return not (r < state[0] or (signs and r < 0))
         state[1] = min([state[1]] + vals)
-        return not (r > state[1] or r > 0)
+        return not (r > state[1] or (signs and r > 0))
 
     if not triple(C, row - 1) or not triple(C, row + 1):
         return None, False
@@ -276,6 +310,7 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False)
                 return None, False
     dx = dy = ds = 0.0
     resp = r
+    eresp = 0.0
     if subpixel:
         pc, nc = float(P[row, col]), float(N[row, col])
         fx, fy, fs = 0.5 * (right - left), 0.5 * (dn - up), 0.5 * (nc - pc)
@@ -317,7 +352,10 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False)
             unc = unc or any(abs(abs(v) - 1.0) <= 8 * eoff for v in (dx, dy, ds)) or abs(abs(resp) - T) <= 8 * eresp
             if not (abs(resp) > T and abs(ds) < 1 and abs(dx) < 1 and abs(dy) < 1):
                 return None, unc
-    if resp < 0:
+    if dog and not dog_type_lxx:
+        unc = unc or (eresp > 0 and abs(resp - state[0]) <= 8 * eresp)
+        typ = 1 if resp > state[0] else 0
+    elif resp < 0 and not dog:
         typ = 2
     else:
         gl, gc, gr = float(G[row, col - 1]), float(G[row, col]), float(G[row, col + 1])
@@ -327,10 +365,11 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False)
     return (resp, typ, dx, dy, ds), unc
 
 
-def scan_level(C, P, N, G, T, edge=10.0, subpixel=True, keep08=False):
+def scan_level(C, P, N, G, T, edge=10.0, subpixel=True, keep08=False, **dog):
     """All interior pixels of one level (ProgramCU.cu:702-882) -> ({(row, col): result}, {(row, col)} uncertain, number
     of candidates).  The exact part is vectorised: |r| against a threshold loosened by its margin and r against its 26
-    neighbours with non-strict comparisons (a superset of the triple rule); key_test_ex sees the survivors only."""
+    neighbours with non-strict comparisons (a superset of the triple rule, with or without the sign conditions);
+    key_test_ex sees the survivors only.  dog: key_test_ex's keywords of the difference-of-Gaussians build."""
     C, P, N = (np.asarray(a, dtype=np.float32) for a in (C, P, N))
     h, w = C.shape
     thr0 = (0.8 if (subpixel or keep08) else 1.0) * float(T)
@@ -348,7 +387,7 @@ def scan_level(C, P, N, G, T, edge=10.0, subpixel=True, keep08=False):
     cand = (np.abs(c) > thr0 * (1 - 16 * U)) & (ge | le)
     found, unsure = {}, set()
     for row, col in np.argwhere(cand) + 1:
-        res, unc = key_test_ex(C, P, N, G, int(row), int(col), T, edge, subpixel, keep08)
+        res, unc = key_test_ex(C, P, N, G, int(row), int(col), T, edge, subpixel, keep08, **dog)
         if unc:
             unsure.add((int(row), int(col)))
         if res is not None:
@@ -358,12 +397,17 @@ def scan_level(C, P, N, G, T, edge=10.0, subpixel=True, keep08=False):
 
 # ---- ComputeOrientation_Kernel, both branches, with rounding margins ------------------------------------------------
 def orientations_ex(grad, theta, x, y, s, half=False, gaussian_factor=1.5, window_factor=2.0, single=False,
-                    fold_refresh=False, single_last=False):
+                    fold_refresh=False, single_last=False, two_peaks=False, info=None):
     """-> (rotations in bin units, uncertain).  multi (ProgramCU.cu:1430-1489): every strict local maximum above 0.8 x the
     largest vote, the 4 strongest, strongest first, equal weights in bin order.  single (:1398-1420, -m 1 and keypoint
     lists): the FIRST strict maximum (`vote[i] > max_vote`), no 0.8 rule; its right neighbour is vote[index + 1], whose
     slot 36 holds the UNFOLDED vote[0] under -half (:1381-1392).  uncertain: a comparison that decides the set or the
-    order of the peaks lies within 8 x (error bound of the two votes)."""
+    order of the peaks lies within 8 x (error bound of the two votes).
+    two_peaks (the build without GPU_HESSIAN, :1493-1548): the same qualifying peaks, visited in bin order and kept in two
+    slots that start at weight 0: a peak above slot 1 goes into slot 0 if it is above slot 0 (whose holder moves to slot
+    1), else into slot 1; both comparisons are strict, so of equal peaks the one met first stays ahead and a third equal
+    one is dropped.  That leaves the two strongest, stronger first.  info: a dict that receives `peaks`, the number of
+    qualifying peaks."""
     h, w = grad.shape
     gs = s * gaussian_factor
     win = abs(s) * gaussian_factor * window_factor
@@ -430,11 +474,29 @@ def orientations_ex(grad, theta, x, y, s, half=False, gaussian_factor=1.5, windo
         if is_peak:
             di = 0.5 * (nxt - pre) / (2 * v[i] - nxt - pre)
             peaks.append((v[i], i + di + 0.5, err[i]))
-    peaks.sort(key=lambda p: -p[0])
-    for a, b_ in zip(peaks, peaks[1:]):                                             # the order, and who is 4th
+    if info is not None:
+        info["peaks"] = len(peaks)
+    if two_peaks:
+        kept = [peaks[i] for i in two_slots([p[0] for p in peaks])]
+    else:
+        kept = sorted(peaks, key=lambda p: -p[0])[:4]
+    ranked = sorted(peaks, key=lambda p: -p[0])
+    for a, b_ in zip(ranked, ranked[1:]):                                           # the order, and who is last
         if abs(a[0] - b_[0]) <= 8 * (a[2] + b_[2]):
             unc = True
-    return [p[1] for p in peaks[:4]], bool(unc)
+    return [p[1] for p in kept], bool(unc)
+
+
+def two_slots(weights):
+    """ProgramCU.cu:1500-1532, 1538-1541: the weights of the qualifying peaks in bin order -> indices of the kept ones,
+    slot 0 first.  max_vot = {0, 0}; a weight above slot 1 goes into slot 0 if it is above slot 0, whose holder moves to
+    slot 1, else into slot 1, and is counted; slot 0 is read if anything was counted, slot 1 if more than one was."""
+    slot, ocount = [(0.0, None), (0.0, None)], 0
+    for i, w in enumerate(weights):
+        if w > slot[1][0]:
+            slot = [(w, i), slot[0]] if w > slot[0][0] else [slot[0], (w, i)]
+            ocount += 1
+    return [sl[1] for sl in slot[:min(ocount, 2)]]
 
 
 def descriptor_ex(grad, theta, x, y, s, angle, half=False, window_factor=3.0, dynamic_indexing=False, normalize=True):
@@ -493,10 +555,18 @@ class DetectorModel:
             get = lambda k, d: getattr(params, k)
         self.wrong = dict(topk_tie_high=False, topk_float_key=False, no_second_pass=False, upsample_clamp=False,
                           no_skip=False, no_clamp33=False, fold_refresh=False, single_last=False, keep08=False,
-                          no_wrap=False, whole_step=False, lowe_before_scale=False)
+                          no_wrap=False, whole_step=False, lowe_before_scale=False, dog_sign_tests=False,
+                          dog_plane_lower=False, dog_type_lxx=False, dog_angle8=False, dog_four_peaks=False,
+                          dog_ds_above=False, dog_sigma_off=False)
         assert set(wrong) <= set(self.wrong), wrong
         self.wrong.update(wrong)
+        self.detector = int(get("detector", 0))
+        assert self.detector in (0, 1), "the model states the Hessian (0) and the difference-of-Gaussians (1) detector"
+        self.is_dog = self.detector == 1
         self.dog = int(get("dog_level_num", 3)) or 3
+        # PROJECT: sigma0 is the sigma of this numbering's level 0 in both modes.  The build without GPU_HESSIAN counts its
+        # levels from _level_min = -1 (SiftGPU.cpp:471) and its _sigma0 belongs to ITS level 0, this numbering's level 1:
+        # the default there is 1.6 * 2^(1/dog) (:503), i.e. 1.6 for the level below, as here.
         self.sigma0 = float(get("sigma0", 1.6)) or float(np.float32(1.6))
         self.sigman = float(get("sigman", 0.5)) or 0.5
         self.T = float(get("dog_threshold", 0.0)) or float(np.float32(0.02) / np.float32(self.dog))
@@ -520,17 +590,43 @@ class DetectorModel:
         self.di = bool(get("dynamic_indexing", 0))
         k = 2.0 ** (1.0 / self.dog)
         self.sigma_step = k
-        dsigma0 = self.sigma0 * math.sqrt(k * k - 1.0)
-        self.inter = [dsigma0 * k ** i for i in range(self.dog + 1)]                 # SiftGPU.cpp:547-556
+        if self.is_dog:
+            # SiftGPU.cpp:471, 496-497, 509: levels _level_min = -1 .. _level_max = dog + 1, dog + 3 of them: the build's
+            # level j - 1 is level j here, 0 .. dog + 2.  :531, 547-555: dsigma0 = _sigma0 sqrt(1 - 1/k^2) and the blur
+            # that takes the build's level i - 1 to i is dsigma0 k^i for i = 0 .. dog + 1, dog + 2 steps; with _sigma0 =
+            # sigma0 k the first of them is sigma0 sqrt(k^2 - 1), the Hessian build's, and the list is one step longer.
+            s0 = self.sigma0 * k
+            dsigma0 = s0 * math.sqrt(1.0 - 1.0 / (k * k))
+            self.top = self.dog + 2
+            # :511-513: _level_ds = _level_min + dog = dog - 1 there, level dog here, is decimated into the next octave
+            # (PyramidCU.cpp:1533).  dog_ds_above: the WRONG rule (one level up).
+            self.level_ds = self.dog + (1 if self.wrong["dog_ds_above"] else 0)
+        else:
+            dsigma0 = self.sigma0 * math.sqrt(k * k - 1.0)
+            self.top = self.dog + 1
+            self.level_ds = self.dog
+        self.nlev = self.top + 1
+        self.inter = [dsigma0 * k ** i for i in range(self.top)]                     # SiftGPU.cpp:547-556
         self.single = self.max_orientation == 1                                     # ProgramCU.cu:1398
+        # the two-slot branch of the build without GPU_HESSIAN runs for every max_orientation > 1 (:1398, 1491-1549)
+        self.two_peaks = self.is_dog and not self.single and not self.fixed_orientation
 
     # -- schedule ---------------------------------------------------------------------------------------------------
     def level_sigma(self, l):
-        return self.sigma0 * 2.0 ** (l / self.dog)                                  # SiftGPU.cpp:1422-1425
+        """GetLevelSigma, SiftGPU.cpp:1422-1425.  DoG: the build's level l - 1 with _sigma0 = sigma0 2^(1/dog):
+        sigma0 2^(1/dog) 2^((l - 1)/dog), the same number."""
+        return self.sigma0 * 2.0 ** (l / self.dog)
+
+    def orient_sigma(self, l):
+        """The sigma handed to ComputeOrientation for list level l (PyramidCU.cpp:1825-1848).  DoG: the loop counts
+        level = 0 .. dog - 1 for list levels 1 .. dog and asks GetLevelSigma(level + _level_min + 1) = GetLevelSigma(l - 1) of
+        the build's numbering, level l here.  dog_sigma_off: the WRONG rule that forgets _sigma0's factor 2^(1/dog)."""
+        return self.level_sigma(l - 1 if self.is_dog and self.wrong["dog_sigma_off"] else l)
 
     def initial_sigma(self, octave_min):
         """GetInitialSmoothSigma, SiftGPU.cpp:482-489: 0 = no blur when sa <= sb + 0.001.  PROJECT: 'no blur' leaves
-        the plane as it is; the reference would build a 5-tap table from sigma = 0, which is NaN (ProgramCU.cu:440-445)."""
+        the plane as it is; the reference would build a 5-tap table from sigma = 0, which is NaN (ProgramCU.cu:440-445).
+        DoG: sa = _sigma0 2^(_level_min / dog) = sigma0 2^(1/dog) 2^(-1/dog), the sigma of level 0 here as well."""
         sa, sb = self.sigma0, self.sigman / 2.0 ** octave_min
         if sa > sb + 0.001:
             return math.sqrt(sa * sa - sb * sb)
@@ -592,8 +688,25 @@ class DetectorModel:
         return lum, self.level_taps(0, omin + ds)
 
     # -- detection --------------------------------------------------------------------------------------------------
+    @staticmethod
+    def response_plane(g, g_below):
+        """ComputeDOG_Kernel, ProgramCU.cu:598-637: D_l = G_l - G_(l-1), one binary32 subtraction per pixel (texC is the
+        level, texP the one below it: `(gus - 1)->BindTexture(texP)`, :646-647).  PyramidCU.cpp:1593-1605 runs it for the
+        build's levels 0 .. dog + 1, levels 1 .. dog + 2 here; level 0 has no level below it and no plane."""
+        return np.asarray(g, dtype=np.float32) - np.asarray(g_below, dtype=np.float32)
+
+    def scan_planes(self, l):
+        """-> (centre, previous, next): the response planes list level l (1 .. dog) is sought in.  Hessian: det-H of levels
+        l, l - 1, l + 1 (PyramidCU.cpp:1631-1646).  DoG: :1654-1668 starts `dog` and `key` at base + 2 for the first list
+        level, so list level l has its centre in D_(l+1), between D_l and D_(l+2) -- while orientation and descriptor read
+        the gradient of Gaussian level l (`got = base + 1`, :1825).  dog_plane_lower: the WRONG rule, centre D_l."""
+        c = l + 1 if self.is_dog and not self.wrong["dog_plane_lower"] else l
+        return c, c - 1, c + 1
+
     def scan(self, C, P, N, G):
-        return scan_level(C, P, N, G, np.float32(self.T), self.edge, self.subpixel, keep08=self.wrong["keep08"])
+        return scan_level(C, P, N, G, np.float32(self.T), self.edge, self.subpixel, keep08=self.wrong["keep08"],
+                          dog=self.is_dog, dog_sign_tests=self.wrong["dog_sign_tests"],
+                          dog_type_lxx=self.wrong["dog_type_lxx"])
 
     def reduce_first(self, counts):
         """Per-level counts (octave-major, ascending) -> counts kept after list generation and the first LimitFeatureCount.
@@ -649,28 +762,43 @@ class DetectorModel:
 
     # -- orientation and export ---------------------------------------------------------------------------------------
     def key_geometry(self, l, row, col, dx, dy, ds):
-        """ProgramCU.cu:1281-1298: position and scale of a detection in its octave."""
-        s = self.level_sigma(l)
+        """ProgramCU.cu:1281-1298: position and scale of a detection in its octave.  key.x = ikey.x + 0.5f + offset.y is a
+        binary32 sum, and the model has to take it as one: at x = 500 it is a multiple of 2^-15, and moving the centre of
+        the orientation window by that much tilts a flat histogram peak by more than a 16-bit angle step (the votes change
+        by 1e-5 of their size, one-sidedly, and the peak interpolation divides by 2 v - next - pre, a small share of v)."""
+        s = self.orient_sigma(l)
         if self.subpixel:
-            return col + 0.5 + dx, row + 0.5 + dy, s * self.sigma_step ** ds
+            return float(np.float32(col + 0.5) + np.float32(dx)), float(np.float32(row + 0.5) + np.float32(dy)), s * self.sigma_step ** ds
         return col + 0.5, row + 0.5, s
 
-    def rotations(self, grad, theta, x, y, s, user=False):
-        """-> (angles handed to the descriptor in radians, un-mirrored; uncertain).  -ofix: 0 (num_orientation = 0, :1312)."""
+    def rotations(self, grad, theta, x, y, s, user=False, info=None):
+        """-> (angles handed to the descriptor in radians, un-mirrored; uncertain).  -ofix: 0 (num_orientation = 0, :1312).
+        DoG with max_orientation > 1 (ProgramCU.cu:1534-1551, PyramidCU.cpp:766, 798-820): the two slots become 16-bit
+        codes floor(fr * 65535), 65535 standing for 'none'; the first is expanded to a feature if it is not 'none', the
+        second if, besides, it is neither 'none' nor equal to the first; the angle is code * 2 pi / 65535.  max_orientation
+        1, -ofix and keypoint lists take the branches above it, which no build changes.  dog_angle8 and dog_four_peaks: the
+        WRONG rules that keep the GPU_HESSIAN lines (:1430-1489)."""
         if self.fixed_orientation:
             return [0.0], False
         single = self.single or user
+        two = self.two_peaks and not single and not self.wrong["dog_four_peaks"]
         rots, unc = orientations_ex(grad, theta, x, y, s, self.half, self.ogf, self.owf, single=single,
-                                    fold_refresh=self.wrong["fold_refresh"], single_last=self.wrong["single_last"])
+                                    fold_refresh=self.wrong["fold_refresh"], single_last=self.wrong["single_last"],
+                                    two_peaks=two, info=info)
         if single:
             return [rots[0] / TEN_DEG], unc                                           # :1415
-        out = []
+        steps = 65535.0 if self.is_dog and not self.wrong["dog_angle8"] else 255.0
+        codes = []
         for rot in rots:
             fr = rot / 36.0
             if fr < 0:
                 fr += 1.0
-            out.append(math.floor(fr * 255.0) * 2 * PI / 255.0)                       # :1481-1486, PyramidCU.cpp:764
-        return out, unc
+            codes.append(math.floor(fr * steps))                                      # :1481-1486 / :1538-1548
+        if self.is_dog and not self.wrong["dog_angle8"]:
+            if codes and codes[0] == 65535:
+                codes = []
+            codes = codes[:1] + [c for c in codes[1:] if c != 65535 and c != codes[0]]
+        return [c * 2 * PI / steps for c in codes], unc                               # PyramidCU.cpp:764-766
 
     def export(self, xf, yf, sf, scale):
         """PyramidCU.cpp:1097-1122: fixed-point record -> host keypoint."""
