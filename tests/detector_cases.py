@@ -24,7 +24,10 @@ checker); list level l is scanned in the planes l, l + 1, l + 2 and described fr
 orientation branch ran the quantum is that of its 16-bit angles.
 
 A case with batch_at = (n, i) runs as image i of a stack of n; the other images are seeded noise of the same size and
-type, and image i is checked exactly as a single image would be.
+type (or the case's own `stack`), and image i is checked exactly as a single image would be.
+
+small_cases() is a second dictionary, apart from cases(): planes below one tile of the kernels, with its own condition on
+the statistics (check_small_statistics).
 
 Images come from seeds; nothing here reads a file.
 """
@@ -116,9 +119,10 @@ def _user_keys(w, h, seed=2):
     return keys
 
 
-def _case(name, image, fmt=None, keys=None, have_orientation=1, min_features=1, batch_at=None, min_three_peaks=0, **kw):
+def _case(name, image, fmt=None, keys=None, have_orientation=1, min_features=1, batch_at=None, min_three_peaks=0, stack=None,
+          **kw):
     return SimpleNamespace(name=name, image=image, fmt=fmt, keys=keys, have_orientation=have_orientation,
-                           min_features=min_features, batch_at=batch_at, min_three_peaks=min_three_peaks, kw=kw)
+                           min_features=min_features, batch_at=batch_at, min_three_peaks=min_three_peaks, stack=stack, kw=kw)
 
 
 def case_input(case):
@@ -128,6 +132,8 @@ def case_input(case):
     if case.batch_at is None:
         return img[None], 0
     n, at = case.batch_at
+    if case.stack is not None:            # the whole stack is given: image `at` of it is the case's
+        return case.stack, at
     top = 1.0 if img.dtype == np.float32 else float(np.iinfo(img.dtype).max)
     stack = [img if j == at else (np.random.RandomState(7919 + j).rand(*img.shape) * top).astype(img.dtype) for j in range(n)]
     return np.stack(stack), at
@@ -237,6 +243,194 @@ def _dog_cases(b, g, c, keys):
     return out
 
 
+# ---- planes below one tile -------------------------------------------------------------------------------------------
+# The kernels work on fixed blocks -- 64 x 32 Gaussian tiles with halos of up to 16 taps, 32 x 32 chain tiles, 128 x 4
+# extrema tiles, 128-column scan strips in 24-row segments, 64-column row-mask words, a descriptor raster in 64-row bands
+# -- and cases() has few partial ones.  Here every block is partial, and every index a clamped or a wrapped one.
+SMALL_PLANES = {      # (w, h): what the size straddles
+    (4, 1): "the smallest legal plane",
+    (4, 2): "two rows, no interior row",
+    (4, 3): "one interior row",
+    (5, 5): "width truncated to 4",
+    (7, 2): "width truncated to 4, no interior row",
+    (8, 8): "below every halo",
+    (12, 3): "narrower than a halo",
+    (36, 5): "wider than a chain tile, lower than any tile",
+    (68, 4): "one word past a 64-column tile, one extrema row group",
+    (64, 1): "one row-mask word, one row",
+    (300, 3): "three scan strips, one interior row",
+    (4, 300): "one word wide, thirteen scan segments",
+    (17, 23): "width truncated to 16, below one tile",
+    (31, 31): "one short of a chain tile",
+    (200, 16): "as many rows as the widest filter's radius",
+}
+SMALL_PYRAMIDS = {
+    (32, 32): "second octave 16x16",
+    (35, 64): "second octave 16x32, odd half",
+    (64, 33): "second octave 32x16",
+    (65, 33): "second octave 32x16, odd halves",
+    (67, 35): "second octave 32x17, odd halves",
+    (1000, 33): "thin second octave 500x16",
+    (33, 700): "thin second octave 16x350",
+    (128, 64): "three octaves",
+}
+SMALL_INPUT = ((4, 1), (12, 3), (36, 5), (65, 33))
+SMALL_KEY_SIZES = ((4, 1), (4, 3), (7, 2), (12, 3), (36, 5), (64, 1), (17, 23), (4, 300), (300, 3))
+SMALL_KEY_MODES = {"defaults": {}, "dog": DOG, "half_sift": dict(half_sift=1), "normalize 0": dict(normalize=0),
+                   "first_octave -1": dict(first_octave=-1)}
+
+
+def constant_stack(w, h, n=8):
+    """Eight images of one size for the packed results: seeded noise, with constant images (no feature) at 0, 3, 4 and 7,
+    so that empty images stand first, last and between non-empty ones."""
+    stack = np.stack([noise(w, h, 4001 + j) for j in range(n)])
+    for j, v in ((0, 0), (3, 255), (4, 17), (7, 128)):
+        stack[j] = v
+    return stack
+
+
+@functools.lru_cache(maxsize=None)
+def small_cases():
+    """-> {name: case}: planes below one tile, the smallest pyramids, the input stages, batches and keypoint lists on
+    them.  Apart from cases(): its parametrisations and statistics stay as they are.  min_features is what the oracle
+    gives (SMALL_FEATURES; 0 where the plane has no interior, or nothing in it is found: those cases test the planes)."""
+    out = []
+    k = NOISE_KW
+
+    def add(name, image, **kw):
+        out.append(_case(name, image, min_features=SMALL_FEATURES[name], **kw))
+
+    for (w, h), what in SMALL_PLANES.items():
+        add(f"{w}x{h}: {what}", noise(w, h), **k)
+        add(f"dog: {w}x{h}: {what}", noise(w, h), **k, **DOG)
+    for w, h in ((4, 1), (8, 8), (12, 3), (4, 300), (200, 16)):           # 33 taps on fewer than 16 rows or columns
+        add(f"{w}x{h} dog_level_num 1", noise(w, h), dog_level_num=1, **k)
+    add("dog: 12x3 dog_level_num 1", noise(12, 3), dog_level_num=1, **k, **DOG)
+    for w, h in ((12, 3), (68, 4), (31, 31), (200, 16)):                  # the LDS-tiled extrema scan
+        add(f"{w}x{h} dog_level_num 6", noise(w, h), dog_level_num=6, **k)
+    add("dog: 31x31 dog_level_num 6", noise(31, 31), dog_level_num=6, **k, **DOG)
+    for (w, h), what in SMALL_PYRAMIDS.items():
+        add(f"{w}x{h}: {what}", noise(w, h), **k)
+        add(f"dog: {w}x{h}: {what}", noise(w, h), **k, **DOG)
+    for fo in (-1, -2):                                                   # the up-sampling kernel
+        for w, h in SMALL_INPUT + ((31, 31), (200, 16)):
+            add(f"first_octave {fo} {w}x{h}", noise(w, h), first_octave=fo, **k)
+    for w, h in ((8, 2), (8, 8), (12, 3), (300, 3)):                      # decimation down to 4 x 1
+        add(f"first_octave 1 {w}x{h}", noise(w, h), first_octave=1, **k)
+    for w, h in SMALL_INPUT:                                              # convert_kernel instead of the direct u8 path
+        rgb = np.stack([noise(w, h, 5000 + 7 * i + w) for i in range(3)], axis=-1)
+        add(f"u8 rgb {w}x{h}", rgb, **k)
+        add(f"f32 lum {w}x{h}", (noise(w, h) / 255.0).astype(np.float32), **k)
+    for w, h in SMALL_INPUT:
+        add(f"batch 8 image 5 {w}x{h}", noise(w, h), batch_at=(8, 5), **k)
+    cs = constant_stack(65, 33)                                           # feature-less images around and between the others
+    add("batch 8 image 5 65x33 between constant images", cs[5], batch_at=(8, 5), stack=cs, **k)
+    for sz in SMALL_KEY_SIZES:
+        w, h = sz
+        for mode, kw in SMALL_KEY_MODES.items():
+            for ho in (1, 0):
+                add(f"keypoint list {w}x{h} {mode} orient={ho}", noise(w, h), keys=_user_keys(w, h), have_orientation=ho, **kw)
+    assert len({c.name for c in out}) == len(out) and {c.name for c in out} == set(SMALL_FEATURES)
+    return {c.name: c for c in out}
+
+
+def check_small_statistics(st, case):
+    """A condition on check_against_model's statistics for a small case: it has the features the oracle finds; below 100
+    candidates no detection and no orientation is flagged (a flagged item passes with either answer, and a case of ten
+    candidates must not pass on one), above that at most MAX_UNCERTAIN_SHARE; no orientation of a keypoint list is
+    flagged: the all-zero histogram has a rule (np_restatement.orientations_ex)."""
+    assert st["features"] >= case.min_features, (st, case.min_features)
+    if case.keys is not None:
+        assert st["orient_uncertain"] == 0, st
+        return
+    flagged = st["uncertain"] + st["orient_uncertain"]
+    if st["candidates"] < 100:
+        assert flagged == 0, st
+    else:
+        assert flagged <= MAX_UNCERTAIN_SHARE * st["candidates"], st
+
+
+# Features per small case, from the oracle (tests/test_small_images.py holds the oracle to the model on each).  0: the plane
+# has no interior row, or nothing in it passes the tests; such a case is there for its planes.
+SMALL_FEATURES = {
+    "4x1: the smallest legal plane": 0, "dog: 4x1: the smallest legal plane": 0, "4x2: two rows, no interior row": 0,
+    "dog: 4x2: two rows, no interior row": 0, "4x3: one interior row": 0, "dog: 4x3: one interior row": 0,
+    "5x5: width truncated to 4": 0, "dog: 5x5: width truncated to 4": 0, "7x2: width truncated to 4, no interior row": 0,
+    "dog: 7x2: width truncated to 4, no interior row": 0, "8x8: below every halo": 0, "dog: 8x8: below every halo": 0,
+    "12x3: narrower than a halo": 0, "dog: 12x3: narrower than a halo": 0,
+    "36x5: wider than a chain tile, lower than any tile": 0, "dog: 36x5: wider than a chain tile, lower than any tile": 0,
+    "68x4: one word past a 64-column tile, one extrema row group": 0,
+    "dog: 68x4: one word past a 64-column tile, one extrema row group": 0, "64x1: one row-mask word, one row": 0,
+    "dog: 64x1: one row-mask word, one row": 0, "300x3: three scan strips, one interior row": 0,
+    "dog: 300x3: three scan strips, one interior row": 0, "4x300: one word wide, thirteen scan segments": 0,
+    "dog: 4x300: one word wide, thirteen scan segments": 0, "17x23: width truncated to 16, below one tile": 1,
+    "dog: 17x23: width truncated to 16, below one tile": 0, "31x31: one short of a chain tile": 2,
+    "dog: 31x31: one short of a chain tile": 0, "200x16: as many rows as the widest filter's radius": 9,
+    "dog: 200x16: as many rows as the widest filter's radius": 0, "4x1 dog_level_num 1": 0, "8x8 dog_level_num 1": 0,
+    "12x3 dog_level_num 1": 0, "4x300 dog_level_num 1": 0, "200x16 dog_level_num 1": 2, "dog: 12x3 dog_level_num 1": 0,
+    "12x3 dog_level_num 6": 0, "68x4 dog_level_num 6": 1, "31x31 dog_level_num 6": 3, "200x16 dog_level_num 6": 14,
+    "dog: 31x31 dog_level_num 6": 0, "32x32: second octave 16x16": 3, "dog: 32x32: second octave 16x16": 0,
+    "35x64: second octave 16x32, odd half": 15, "dog: 35x64: second octave 16x32, odd half": 4,
+    "64x33: second octave 32x16": 7, "dog: 64x33: second octave 32x16": 2, "65x33: second octave 32x16, odd halves": 6,
+    "dog: 65x33: second octave 32x16, odd halves": 2, "67x35: second octave 32x17, odd halves": 20,
+    "dog: 67x35: second octave 32x17, odd halves": 3, "1000x33: thin second octave 500x16": 126,
+    "dog: 1000x33: thin second octave 500x16": 19, "33x700: thin second octave 16x350": 63,
+    "dog: 33x700: thin second octave 16x350": 20, "128x64: three octaves": 33, "dog: 128x64: three octaves": 8,
+    "first_octave -1 4x1": 0, "first_octave -1 12x3": 0, "first_octave -1 36x5": 1, "first_octave -1 65x33": 40,
+    "first_octave -1 31x31": 15, "first_octave -1 200x16": 54, "first_octave -2 4x1": 0, "first_octave -2 12x3": 10,
+    "first_octave -2 36x5": 60, "first_octave -2 65x33": 863, "first_octave -2 31x31": 361,
+    "first_octave -2 200x16": 1375, "first_octave 1 8x2": 0, "first_octave 1 8x8": 0, "first_octave 1 12x3": 0,
+    "first_octave 1 300x3": 0, "u8 rgb 4x1": 0, "f32 lum 4x1": 0, "u8 rgb 12x3": 0, "f32 lum 12x3": 0, "u8 rgb 36x5": 0,
+    "f32 lum 36x5": 0, "u8 rgb 65x33": 7, "f32 lum 65x33": 6, "batch 8 image 5 4x1": 0, "batch 8 image 5 12x3": 0,
+    "batch 8 image 5 36x5": 0, "batch 8 image 5 65x33": 6, "batch 8 image 5 65x33 between constant images": 6,
+    "keypoint list 4x1 defaults orient=1": 40,
+    "keypoint list 4x1 defaults orient=0": 40, "keypoint list 4x1 dog orient=1": 40, "keypoint list 4x1 dog orient=0": 40,
+    "keypoint list 4x1 half_sift orient=1": 40, "keypoint list 4x1 half_sift orient=0": 40,
+    "keypoint list 4x1 normalize 0 orient=1": 40, "keypoint list 4x1 normalize 0 orient=0": 40,
+    "keypoint list 4x1 first_octave -1 orient=1": 40, "keypoint list 4x1 first_octave -1 orient=0": 40,
+    "keypoint list 4x3 defaults orient=1": 40, "keypoint list 4x3 defaults orient=0": 40,
+    "keypoint list 4x3 dog orient=1": 40, "keypoint list 4x3 dog orient=0": 40,
+    "keypoint list 4x3 half_sift orient=1": 40, "keypoint list 4x3 half_sift orient=0": 40,
+    "keypoint list 4x3 normalize 0 orient=1": 40, "keypoint list 4x3 normalize 0 orient=0": 40,
+    "keypoint list 4x3 first_octave -1 orient=1": 40, "keypoint list 4x3 first_octave -1 orient=0": 40,
+    "keypoint list 7x2 defaults orient=1": 40, "keypoint list 7x2 defaults orient=0": 40,
+    "keypoint list 7x2 dog orient=1": 40, "keypoint list 7x2 dog orient=0": 40,
+    "keypoint list 7x2 half_sift orient=1": 40, "keypoint list 7x2 half_sift orient=0": 40,
+    "keypoint list 7x2 normalize 0 orient=1": 40, "keypoint list 7x2 normalize 0 orient=0": 40,
+    "keypoint list 7x2 first_octave -1 orient=1": 40, "keypoint list 7x2 first_octave -1 orient=0": 40,
+    "keypoint list 12x3 defaults orient=1": 40, "keypoint list 12x3 defaults orient=0": 40,
+    "keypoint list 12x3 dog orient=1": 40, "keypoint list 12x3 dog orient=0": 40,
+    "keypoint list 12x3 half_sift orient=1": 40, "keypoint list 12x3 half_sift orient=0": 40,
+    "keypoint list 12x3 normalize 0 orient=1": 40, "keypoint list 12x3 normalize 0 orient=0": 40,
+    "keypoint list 12x3 first_octave -1 orient=1": 40, "keypoint list 12x3 first_octave -1 orient=0": 40,
+    "keypoint list 36x5 defaults orient=1": 40, "keypoint list 36x5 defaults orient=0": 40,
+    "keypoint list 36x5 dog orient=1": 40, "keypoint list 36x5 dog orient=0": 40,
+    "keypoint list 36x5 half_sift orient=1": 40, "keypoint list 36x5 half_sift orient=0": 40,
+    "keypoint list 36x5 normalize 0 orient=1": 40, "keypoint list 36x5 normalize 0 orient=0": 40,
+    "keypoint list 36x5 first_octave -1 orient=1": 40, "keypoint list 36x5 first_octave -1 orient=0": 40,
+    "keypoint list 64x1 defaults orient=1": 40, "keypoint list 64x1 defaults orient=0": 40,
+    "keypoint list 64x1 dog orient=1": 40, "keypoint list 64x1 dog orient=0": 40,
+    "keypoint list 64x1 half_sift orient=1": 40, "keypoint list 64x1 half_sift orient=0": 40,
+    "keypoint list 64x1 normalize 0 orient=1": 40, "keypoint list 64x1 normalize 0 orient=0": 40,
+    "keypoint list 64x1 first_octave -1 orient=1": 40, "keypoint list 64x1 first_octave -1 orient=0": 40,
+    "keypoint list 17x23 defaults orient=1": 40, "keypoint list 17x23 defaults orient=0": 40,
+    "keypoint list 17x23 dog orient=1": 40, "keypoint list 17x23 dog orient=0": 40,
+    "keypoint list 17x23 half_sift orient=1": 40, "keypoint list 17x23 half_sift orient=0": 40,
+    "keypoint list 17x23 normalize 0 orient=1": 40, "keypoint list 17x23 normalize 0 orient=0": 40,
+    "keypoint list 17x23 first_octave -1 orient=1": 40, "keypoint list 17x23 first_octave -1 orient=0": 40,
+    "keypoint list 4x300 defaults orient=1": 40, "keypoint list 4x300 defaults orient=0": 40,
+    "keypoint list 4x300 dog orient=1": 40, "keypoint list 4x300 dog orient=0": 40,
+    "keypoint list 4x300 half_sift orient=1": 40, "keypoint list 4x300 half_sift orient=0": 40,
+    "keypoint list 4x300 normalize 0 orient=1": 40, "keypoint list 4x300 normalize 0 orient=0": 40,
+    "keypoint list 4x300 first_octave -1 orient=1": 40, "keypoint list 4x300 first_octave -1 orient=0": 40,
+    "keypoint list 300x3 defaults orient=1": 40, "keypoint list 300x3 defaults orient=0": 40,
+    "keypoint list 300x3 dog orient=1": 40, "keypoint list 300x3 dog orient=0": 40,
+    "keypoint list 300x3 half_sift orient=1": 40, "keypoint list 300x3 half_sift orient=0": 40,
+    "keypoint list 300x3 normalize 0 orient=1": 40, "keypoint list 300x3 normalize 0 orient=0": 40,
+    "keypoint list 300x3 first_octave -1 orient=1": 40, "keypoint list 300x3 first_octave -1 orient=0": 40,
+}
+
+
 # The dot grid has [345, 219, 34, 1, 50, 10, 2, 7] detections and [381, 282, 43, 1, 59, 14, 3, 22] features per level
 # (tests/test_detector_model.py::test_grid_thresholds_fall_inside_a_level asserts it).  120 lies inside level 1 counted from
 # the top (104 detections above it, 323 with it): the first pass keeps level 1, the second, on the 424 features, drops it
@@ -334,7 +528,7 @@ def check_against_model(session, case, model=None, dense=True, log=None):
                 st["gauss"] = max(st["gauss"], d)
                 _need(d < TOL_GAUSS * mag, "gauss", lambda: f"octave {oc} level {l}: max |d| {d:.3g}")
                 # (gradient and angle are the same lines in both kernels: ProgramCU.cu:567-591 and :612-621)
-                deth, grad, theta = R.hessian_planes(a, m.level_sigma(l))
+                deth, grad, theta = m.planes(a, l)
                 if is_dog:
                     if l >= 1:       # exact: a correctly rounded binary32 subtraction of these two planes has one answer
                         want = m.response_plane(G[oc][l], G[oc][l - 1])
@@ -539,18 +733,20 @@ def _check_keypoint_list(session, case, m, GOT, scales, st):
             _need(max(abs(out[i]["x"] - ex), abs(out[i]["y"] - ey)) <= 1e-6 * (1 + abs(ex) + abs(ey)) and abs(out[i]["s"] - es) <= 1e-6 * es,
                   "keylist", f"key {i}: {(out[i]['x'], out[i]['y'], out[i]['s'])}, model {(ex, ey, es)}")
             d = _circ(float(out[i]["o"]), m.mirrored(ang))
+            if math.isnan(ang):           # the all-zero histogram: NaN on both sides
+                d = 0.0 if math.isnan(float(out[i]["o"])) else math.inf
             _need(d <= QUANTUM + TOL_ANGLE or unc, "keylist", f"key {i} (level {hits[0]}): orientation {out[i]['o']}, model {m.mirrored(ang)}")
             ang = (2 * R.PI - float(out[i]["o"])) % (2 * R.PI)
         else:
             _need(out[i].tobytes() == k.tobytes(), "keylist", f"key {i}: the caller's key changed")
         if unc:
-            continue                      # (an empty window: no strongest orientation)
+            continue                      # (two votes within rounding of each other: no strongest orientation)
         if fs == 0:
             continue                      # a scale below 1 / 512 of a pixel: the window is empty
+        # (nothing under the window: every component 1 / sqrt(dim), np_restatement.descriptor_ex; a NaN on either side
+        # fails the comparison)
         d = m.descriptor(grad, theta, fx, fy, fs, ang)
-        if not np.isfinite(d).all():      # nothing under the window: 0 / 0 in the normalisation on both sides
-            _need(not np.isfinite(desc[i]).all() or not desc[i].any(), "keylist", f"key {i}: descriptor of an empty window")
-            continue
+        st["empty_windows"] = st.get("empty_windows", 0) + int(float(np.ptp(d)) == 0.0)
         dev = float(np.abs(d - desc[i]).max())
         worst = max(worst, dev)
         _need(dev < TOL_DESC, "keylist", f"key {i} (level {hits[0]}, scale {k['s']}): descriptor max |d| {dev:.3g}")

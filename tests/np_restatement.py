@@ -99,18 +99,26 @@ def build_pyramid(lum, dog=3, octave_num=-1):
 
 
 # ---- ComputeHessian_Kernel, ProgramCU.cu:523-595: 1-D index neighbours, zero outside the plane -----
-def hessian_planes(g, sigma):
+def hessian_planes(g, sigma, clamp=False):
+    """The neighbour of pixel i at (dy, dx) is index i + dy w + dx of the FLAT plane: at a row's end that is the next
+    row's first pixel, before and past the plane a fetch returns 0.  On a plane of one row every vertical neighbour is 0,
+    on one of four columns half the horizontal ones are a row end.  clamp: the WRONG rule (replicated borders, as the
+    filters have them)."""
     h, w = g.shape
     flat = np.concatenate([np.zeros(w + 1), g.ravel(), np.zeros(w + 1)])
     base = w + 1
     n = h * w
+    edge = np.pad(g, 1, mode="edge") if clamp else None
 
-    def nb(off):
+    def nb(dy, dx):
+        if clamp:
+            return edge[1 + dy: 1 + dy + h, 1 + dx: 1 + dx + w]
+        off = dy * w + dx
         return flat[base + off: base + off + n].reshape(h, w)
 
-    v11, v12, v13 = nb(-w - 1), nb(-w), nb(-w + 1)
-    v21, v22, v23 = nb(-1), nb(0), nb(1)
-    v31, v32, v33 = nb(w - 1), nb(w), nb(w + 1)
+    v11, v12, v13 = nb(-1, -1), nb(-1, 0), nb(-1, 1)
+    v21, v22, v23 = nb(0, -1), nb(0, 0), nb(0, 1)
+    v31, v32, v33 = nb(1, -1), nb(1, 0), nb(1, 1)
     lxx = v21 - 2.0 * v22 + v23
     lyy = v12 - 2.0 * v22 + v32
     lxy = (v13 - v11 + v31 - v33) * 0.25
@@ -192,6 +200,9 @@ WRONG_RULES = {
     "DoG keeps up to four peaks": dict(dog_four_peaks=True),
     "DoG next octave from the level above": dict(dog_ds_above=True),
     "DoG level sigma one level off": dict(dog_sigma_off=True),
+    # planes below one tile (detector_cases.small_cases)
+    "empty window gives NaN": dict(empty_nan=True),
+    "det-H neighbours clamp at the row ends": dict(deth_clamp=True),
 }
 
 
@@ -452,6 +463,14 @@ def orientations_ex(grad, theta, x, y, s, half=False, gaussian_factor=1.5, windo
     v = vote
     mx = float(v[:36].max())
     unc = False
+    if single and not v[:36].any():
+        # THE ALL-ZERO HISTOGRAM (no sample under the window -- every key on a plane of one or two rows -- or no gradient
+        # there): exactly zero in binary32 too, so nothing is uncertain.  :1400-1415: no vote[i] > 0, index_max = 0,
+        # max_vote = pre = next = 0 and off = 0.5f * FDIV(0, 0); __fdividef is x * rcp(y) = 0 * inf, NaN like the IEEE
+        # quotient: key.w is NaN.  The multi-peak branches below need no line of their own: the threshold 0.8 * 0 admits
+        # no vote[i] > 0, so orientationsCount = 0 and the packed 8-bit angles are 0 (:1448, 1474-1489), in the build
+        # without GPU_HESSIAN ocount = 0 and both 16-bit codes are 65535, 'none' (:1500-1548): no feature either way.
+        return [float("nan")], False
     if single:
         imax = 0
         for i in range(1, 36):
@@ -499,11 +518,24 @@ def two_slots(weights):
     return [sl[1] for sl in slot[:min(ocount, 2)]]
 
 
-def descriptor_ex(grad, theta, x, y, s, angle, half=False, window_factor=3.0, dynamic_indexing=False, normalize=True):
+def descriptor_ex(grad, theta, x, y, s, angle, half=False, window_factor=3.0, dynamic_indexing=False, normalize=True,
+                  empty_nan=False):
     """ComputeDescriptor_Kernel + NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054, with -di and normalize=0.  A sample whose bin coordinate is 8.0 AS A binary32 NUMBER
     (th < 0 by less than half an ulp of 8, so th + 8 rounds up) falls into no bin, or into des[8] with -di
-    (ProgramCU.cu:1745-1776): the one place where the float64 model has to ask for the float32 value."""
+    (ProgramCU.cu:1745-1776): the one place where the float64 model has to ask for the float32 value.
+    THE EMPTY WINDOW.  A key whose 16 boxes hold no sample (any key on a plane of one or two rows: ymin = 1.5 > ymax =
+    h - 1.5; a key far outside the plane) has des = 0 everywhere.  The normalisation then forms min(0.2f, 0 * rsqrt(0))
+    = min(0.2f, NaN) (:1989-1995, the -half kernel :2034-2044, the build without GPU_HESSIAN :2077-2090), and CUDA's min
+    on floats returns the operand that is not NaN: every component becomes 0.2, and after the second pass 0.2 /
+    sqrt(dim 0.04) = 1 / sqrt(dim).  Not NaN, not zero.  With normalize=0 the zeros are returned as they are.
+    empty_nan: the WRONG rule (a min that propagates NaN, as np.minimum and a comparison-and-select do).
+    A NaN ANGLE (the single-peak orientation of an all-zero histogram, orientations_ex) makes nx and ny NaN for every
+    sample, `(nxn < 1.0f) && (nyn < 1.0f)` (:1735) false, and the window empty whatever the boxes are (max / min in
+    :1713-1716 drop the NaN operand as well: the boxes are the whole plane)."""
     h, w = grad.shape
+    if math.isnan(angle):
+        d = np.zeros(64 if half else 128)
+        return _normalized(d, empty_nan) if normalize else d
     spt = abs(s * window_factor)
     sn, cs = math.sin(angle), math.cos(angle)
     anglef = angle - 2 * PI if angle > PI else angle
@@ -537,10 +569,15 @@ def descriptor_ex(grad, theta, x, y, s, angle, half=False, window_factor=3.0, dy
         des[0] += des[8]
         out.extend([des[k] + des[k + 4] for k in range(4)] if half else des[:8])
     d = np.array(out)
-    if not normalize:
-        return d
-    d = np.minimum(0.2, d / np.sqrt((d * d).sum()))
-    return d / np.sqrt((d * d).sum())
+    return _normalized(d, empty_nan) if normalize else d
+
+
+def _normalized(d, empty_nan=False):
+    """NormalizeDescriptor_Kernel, ProgramCU.cu:1972-2054: unit length, the clamp to 0.2 by a min that keeps the operand
+    which is not NaN (np.fmin), unit length again."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = (np.minimum if empty_nan else np.fmin)(0.2, d * (1.0 / np.sqrt((d * d).sum())))
+        return d / np.sqrt((d * d).sum())
 
 
 class DetectorModel:
@@ -557,7 +594,7 @@ class DetectorModel:
                           no_skip=False, no_clamp33=False, fold_refresh=False, single_last=False, keep08=False,
                           no_wrap=False, whole_step=False, lowe_before_scale=False, dog_sign_tests=False,
                           dog_plane_lower=False, dog_type_lxx=False, dog_angle8=False, dog_four_peaks=False,
-                          dog_ds_above=False, dog_sigma_off=False)
+                          dog_ds_above=False, dog_sigma_off=False, empty_nan=False, deth_clamp=False)
         assert set(wrong) <= set(self.wrong), wrong
         self.wrong.update(wrong)
         self.detector = int(get("detector", 0))
@@ -813,7 +850,13 @@ class DetectorModel:
         return math.fmod(2 * PI - angle, 2 * PI)                                      # PyramidCU.cpp:1134
 
     def descriptor(self, grad, theta, x, y, s, angle):
-        return descriptor_ex(grad, theta, x, y, s, angle, self.half, self.dwf, self.di, self.normalize)
+        return descriptor_ex(grad, theta, x, y, s, angle, self.half, self.dwf, self.di, self.normalize,
+                             empty_nan=self.wrong["empty_nan"])
+
+    def planes(self, g, l):
+        """-> (det-H, gradient, theta) of Gaussian level l (ComputeHessian_Kernel, ProgramCU.cu:523-595).  deth_clamp: the
+        WRONG rule, replicated borders instead of the 1-D index."""
+        return hessian_planes(g, self.level_sigma(l), clamp=self.wrong["deth_clamp"])
 
     # -- keypoint lists, PyramidCU.cpp:555-718 ------------------------------------------------------------------------
     def bin_key(self, s, scales):

@@ -21,6 +21,9 @@ Wrong rule -> case that catches it (stage):
   DoG keeps up to four peaks                   dog: max_orientation 4 (orient)
   DoG next octave from the level above         dog: defaults (gauss)
   DoG level sigma one level off                dog: defaults (export)
+  empty window gives NaN                       small: keypoint list 4x1 defaults orient=1 (keylist)
+  det-H neighbours clamp at the row ends       small: 4x1: the smallest legal plane (det-H)
+(`small:` names a case of detector_cases.small_cases(), the planes below one tile; tests/test_small_images.py runs them.)
 Three switches are NOT caught by any case (test_switches_the_checker_does_not_see), for different reasons:
   half fold refreshes the 37th slot   UNOBSERVABLE.  Slot 36 is read only as the right neighbour of bin 35, and after the
                                       fold bin 35 holds 0, which is neither above a threshold >= 0 nor a strict maximum.
@@ -75,6 +78,9 @@ CATCHES = {
     "DoG keeps up to four peaks": ("dog: max_orientation 4", "orient"),
     "DoG next octave from the level above": ("dog: defaults", "gauss"),
     "DoG level sigma one level off": ("dog: defaults", "export"),
+    # every key of a one-row plane has an empty window; every column of a 4 x 1 plane is a row end
+    "empty window gives NaN": ("small: keypoint list 4x1 defaults orient=1", "keylist"),
+    "det-H neighbours clamp at the row ends": ("small: 4x1: the smallest legal plane", "det-H"),
 }
 UNOBSERVABLE = {        # not caught: the first and the third are unobservable, the second unpinned (module docstring)
     "half fold refreshes the 37th slot": ("half_sift", "half_sift max_orientation 1", "keypoint list half_sift"),
@@ -85,6 +91,10 @@ UNOBSERVABLE = {        # not caught: the first and the third are unobservable, 
 
 def _oracle(case):
     return OracleSession(threads=4, **case.kw)
+
+
+def _named(name):
+    return dc.small_cases()[name[len("small: "):]] if name.startswith("small: ") else dc.cases()[name]
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -99,7 +109,7 @@ def test_oracle_follows_the_model(name):
 @pytest.mark.parametrize("rule", list(CATCHES))
 def test_every_wrong_rule_is_caught(rule):
     name, stage = CATCHES[rule]
-    case = dc.cases()[name]
+    case = _named(name)
     with closing(_oracle(case)) as o, pytest.raises(dc.Mismatch) as e:
         dc.check_against_model(o, case, model=R.DetectorModel(o.params, **R.WRONG_RULES[rule]))
     print(rule, "->", name, ":", e.value)
