@@ -164,15 +164,13 @@ struct DescParams {
 // Separable Gaussian, one level for the whole batch: dst = G(taps) * src with replicated
 // borders, tap order and FMA chain of FilterH/FilterV (ProgramCU.cu:117-231).
 // src_u8 != nullptr: source is u8 luminance (value/255.0f, GLTexImage.cpp:828), pitch in bytes.
-// deth_src != nullptr (float source with src_pitch == wa, src_img_stride == wa*h only): the kernel
-// also emits det-Hessian*sigma^4 (and, if got_src != nullptr, gradient/theta) of the SOURCE level
-// from the window it has staged anyway (ComputeHessian_Kernel, ProgramCU.cu:523-595).
 void launch_gauss(hipStream_t st, const float* src, const uint8_t* src_u8, long long src_pitch,
-                  long long src_img_stride, float* dst, int wa, int h, int batch, const Taps& taps,
-                  float* deth_src = nullptr, float* got_src = nullptr, float norm_src = 0.0f,
-                  float* decim_dst = nullptr, int decim_w = 0, int decim_h = 0);
+                  long long src_img_stride, float* dst, int wa, int h, int batch, const Taps& taps);
 
-// One level launch as data (float source with pitch wa), for launch_gauss_pair.
+// One level launch as data (float source with pitch wa == row length, image stride wa*h).
+// deth_src != nullptr: the kernel also emits det-Hessian*sigma^4 (and, if got_src != nullptr, gradient/theta) of the
+// SOURCE level from the window it has staged anyway (ComputeHessian_Kernel, ProgramCU.cu:523-595); decim_dst != nullptr:
+// and the even rows and columns of the produced level, level 0 of the next octave (DownsampleKernel, ProgramCU.cu:312-326).
 struct GaussJob {
   const float* src;
   float* dst;
@@ -233,10 +231,6 @@ void launch_convert(hipStream_t st, const void* src, int format, int pixtype, lo
 // Linear up-sampling by 2^log_scale of the converted input (UpsampleKernel, ProgramCU.cu:233-310); only for
 // an up-sampled first octave (first_octave < 0 through the C ABI).  src: [batch][h][w], dst: [batch][h<<k][w<<k].
 void launch_upsample(hipStream_t st, const float* src, int w, int h, int log_scale, float* dst, int batch);
-
-// Nearest decimation to the next octave (DownsampleKernel, ProgramCU.cu:312-326).
-void launch_downsample(hipStream_t st, const float* src, int sw, int splane, float* dst, int dw,
-                       int dh, int batch);
 
 // det-Hessian * sigma^4 for levels 0..dog+1 of one octave, and (gradient, theta) for levels
 // 1..dog (ComputeHessian_Kernel, ProgramCU.cu:523-595).

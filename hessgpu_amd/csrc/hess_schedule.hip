@@ -1,6 +1,4 @@
 // hess_schedule.hip -- the launch order of one batch on the context's stream (see hess_ctx.h).
-#include <optional>
-
 #include "hess_ctx.h"
 
 namespace hess {
@@ -12,42 +10,22 @@ hipEvent_t get_event(hess_ctx* c) {
   if (hipEventCreate(&e) != hipSuccess) { set_err(c, "hipEventCreate failed: profiling disabled"); c->prof = false; return nullptr; }
   return e;
 }
-struct ProfScope {
-  hess_ctx* c;
-  EventPair ep;
-  bool on;
-  ProfScope(hess_ctx* ctx, int kernel, double bytes, int kernel2 = -1, double in_lds = 0.0) : c(ctx), on(ctx->prof) {
-    if (!on) return;
-    ep.a = get_event(c); ep.b = get_event(c); ep.kernel = kernel; ep.bytes = bytes; ep.kernel2 = kernel2; ep.in_lds = in_lds;
-    if (!ep.a || !ep.b) {  // event creation failed: no record for this launch
-      if (ep.a) c->pool.push_back(ep.a);
-      if (ep.b) c->pool.push_back(ep.b);
-      on = false;
-      return;
-    }
-    if (hipEventRecord(ep.a, c->st) != hipSuccess) { c->pool.push_back(ep.a); c->pool.push_back(ep.b); on = false; }
-  }
-  ~ProfScope() {
-    if (!on) return;
-    if (hipEventRecord(ep.b, c->st) != hipSuccess) { c->pool.push_back(ep.a); c->pool.push_back(ep.b); return; }
-    c->pending.push_back(ep);
-  }
-};
 // A RUN of consecutive launches of one kernel family between ONE pair of events: an event record between two kernels leaves
 // the stream idle for a few microseconds, which per-launch pairs book on 22 pyramid launches a step (the hipEvent figure of
 // the Gaussian stage read 0.53 ms where the kernel trace sums 0.47).  The launches of octave 0 keep a pair each (their
 // share of the stage is reported apart); the small octaves' launches, which follow them back to back, share one.
+// The first add() takes two events and records `a`, close() (or the end of the scope) records `b` and queues the pair for
+// drain_profile(); without profiling, or when an event cannot be had, nothing is recorded.
 struct ProfRun {
   hess_ctx* c;
-  int kernel;
-  EventPair ep;
+  EventPair ep{};
   bool open = false;
-  ProfRun(hess_ctx* ctx, int k) : c(ctx), kernel(k) {}
+  ProfRun(hess_ctx* ctx, int kernel, int kernel2 = -1) : c(ctx) { ep.kernel = kernel; ep.kernel2 = kernel2; }
+  ProfRun(const ProfRun&) = delete;
   void add(double bytes, double in_lds = 0.0) {
     if (!c->prof) return;
     if (!open) {
-      ep = EventPair{};
-      ep.a = get_event(c); ep.b = get_event(c); ep.kernel = kernel; ep.bytes = 0.0; ep.count = 0;
+      ep.a = get_event(c); ep.b = get_event(c); ep.bytes = 0.0; ep.in_lds = 0.0; ep.count = 0;
       if (!ep.a || !ep.b || hipEventRecord(ep.a, c->st) != hipSuccess) {
         if (ep.a) c->pool.push_back(ep.a);
         if (ep.b) c->pool.push_back(ep.b);
@@ -65,6 +43,21 @@ struct ProfRun {
   }
   ~ProfRun() { close(); }
 };
+// What follows in the scope between a pair of events of its own (wanted = false: no pair, see book_pyramid).
+struct ProfScope : ProfRun {
+  ProfScope(hess_ctx* ctx, int kernel, double bytes, int kernel2 = -1, double in_lds = 0.0, bool wanted = true)
+      : ProfRun(ctx, kernel, kernel2) {
+    if (wanted) add(bytes, in_lds);
+  }
+};
+// How every pyramid launch is booked.  One that belongs to octave 0 (the pair whose first job is octave 0's top level
+// included) ends the running run and gets the returned pair of its own, on HESS_K_GAUSS and HESS_K_GAUSS_OCT0; any other
+// launch joins the run.
+static ProfScope book_pyramid(ProfRun& run, bool octave0, double bytes, double in_lds = 0.0) {
+  if (octave0) run.close();
+  else run.add(bytes, in_lds);
+  return ProfScope(run.c, HESS_K_GAUSS, bytes, HESS_K_GAUSS_OCT0, in_lds, octave0);
+}
 void drain_profile(hess_ctx* c) {
   for (auto& ep : c->pending) {
     float ms = 0;
@@ -151,12 +144,12 @@ static void choose_parts(hess_ctx* c, int batch) {
   for (int k = 0; k < want; k++) pt.end[k] = pt.features ? 1 : (int)((long long)batch * (k + 1) / want);
 }
 
-// Enqueue the whole path for the run's `batch` images, whose pixels are at device address `dev`.
-int enqueue(hess_ctx* c, const PendingRun& r) {
+// ---- input + pyramid (BuildPyramid, PyramidCU.cpp:1486-1558), det-H + gradient (DetectKeypointsEX part 1, :1576-1591) ----
+// From the run's `batch` images, whose pixels are at device address r.dev, to the det-H (or DoG) and gradient planes.
+static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
   const void* const dev = r.dev;
   const int pitch = r.pitch, batch = r.batch, format = r.format, pixtype = r.pixtype;
   const size_t image_stride = r.image_stride;
-  const hess_params& p = c->p;
   const Schedule& s = c->sch;
   const Geom& g = c->g;
   hipStream_t st = c->st;
@@ -164,23 +157,7 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   float* deth = (float*)c->deth.p;
   float* got = (float*)c->got.p;
   auto plane_ptr = [&](float* base, int o, int l) { return base + g.o[o].lvl_off + (long long)l * g.B * g.o[o].plane; };
-
-  // Stage timers (SiftGPU::_timing[2..10]) only when asked for: hess_params.verbose bit 1 (the reference's _timingS,
-  // SiftGPU.cpp:433-464: its stage times, too, are only meaningful when it synchronises at stage ends) or the bench's
-  // per-kernel profile.  An event record between two kernels leaves the stream idle for about 6 us.
-  c->stage_events = (c->p.verbose & 2) != 0;
-  HIP_TRY(c, hipEventRecord(c->ev[0], st));
   const bool user_mode = !c->user_keys.empty();
-  DetectParams dp;
-  dp.thr = p.dog_threshold;
-  dp.thr0 = (p.subpixel ? 0.8f : 1.0f) * p.dog_threshold;                            // ProgramCU.cu:897
-  dp.edge = (p.edge_threshold + 1) * (p.edge_threshold + 1) / p.edge_threshold;      // ProgramCU.cu:913
-  dp.subpixel = p.subpixel;
-  Geom gx = g;  // the extrema scan's segment length
-  if (c->stream_rows > 0) set_stream_rows(gx, c->stream_rows);      // HESS_STREAM_ROWS (A/B switch; a multiple of 3)
-  else if (batch <= policy::kLatencyBatch) set_stream_rows(gx, kStreamRows / policy::kLatencyStreamRowsDiv);  // shorter segments, twice the wavefronts
-  if (!(user_mode && c->user_on_current)) {  // SIFT_SKIP_FILTERING: the resident pyramid is reused
-  // ---- input + pyramid (BuildPyramid, PyramidCU.cpp:1486-1558) ----
   const bool direct_u8 = (format == HESS_FMT_LUM && pixtype == HESS_PIX_U8 && c->ds == 0 && c->has_taps0 &&
                           (pitch % 4) == 0 && (image_stride % 4) == 0 && ((uintptr_t)dev % 4) == 0);
   const float* src_f = nullptr;
@@ -195,28 +172,33 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
       src_f = (const float*)c->upsampled.p;
     }
   }
-  // The launch that produces the down-sampling level also writes level 0 of the next octave (its even rows and
-  // columns): no decimation launches.  (A down-sampling level 0 is nobody's product: separate kernel then.)
-  const bool fused_decim = s.level_ds >= 1 && s.level_ds <= s.level_max;
+  // The launch that produces the down-sampling level (level_ds = dog, one of levels 1 .. level_max - 1 in both detector
+  // modes: resolve()) also writes level 0 of the next octave (its even rows and columns): no decimation launches.
   // det-H of the top level by the launch that produces it (k_gauss.hip, TOP tiles); HESS_NO_TOP_FUSION=1: the round-4
   // form (the level is stored, hessian_rows4_kernel reads it back) for A/B runs
-  const bool top_fused = s.level_max == g.dog + 1 && s.level_max >= 1 && !c->no_top_fusion;
+  const bool top_fused = s.level_max == g.dog + 1 && !c->no_top_fusion;
   c->zero_filled = false;
   // Level l of octave o from level l-1; the same launch emits det-H (+ gradient/theta) of level l-1 from the source
   // window it stages: 8 B R+W for the blur, 4 B (+8 B) W for the fused planes (+ 4 B per pixel of the next octave's
   // level 0 when it is the down-sampling level).
-  auto level_job = [&](int o, int l) {
+  // (a fused top level reads its source and writes its own det-H instead of the level: the same 8 bytes)
+  // in_lds: SURVEY 8d books every array of the reference's layout written once and read once; a level this build keeps in
+  // LDS -- the octave's top level, level 0 of octave 0 -- is 8 bytes per pixel of that layout which no launch here moves.
+  struct Level { GaussJob job; double bytes, in_lds; };
+  auto level = [&](int o, int l) {
     const OctGeom& og = g.o[o];
     const bool src_got = (l - 1 >= 1 && l - 1 <= g.dog);
-    const bool decim = fused_decim && l == s.level_ds && o + 1 < g.noct;
-    GaussJob j;
+    const bool decim = l == s.level_ds && o + 1 < g.noct;
+    const bool top = top_fused && l == s.level_max;
+    Level lv;
+    GaussJob& j = lv.job;
     j.src = plane_ptr(gauss, o, l - 1); j.dst = plane_ptr(gauss, o, l); j.wa = og.wa; j.h = og.h; j.taps = s.taps[l];
     j.deth_src = plane_ptr(deth, o, l - 1);
     j.got_src = src_got ? got + 2 * (og.got_off + (long long)(l - 2) * g.B * og.plane) : nullptr;
     j.norm_src = s.norm[l - 1];
     j.decim_dst = decim ? plane_ptr(gauss, o + 1, 0) : nullptr;
     j.decim_w = decim ? g.o[o + 1].wa : 0; j.decim_h = decim ? g.o[o + 1].h : 0;
-    if (top_fused && l == s.level_max) {
+    if (top) {
       // The octave's top level is nobody's source: its det-H comes out of the launch that produces it (from the output
       // tile in LDS) and the level itself is not written to HBM -- unless the parity tests ask (hess_debug_keep_levels).
       j.deth_dst = plane_ptr(deth, o, l);
@@ -227,19 +209,9 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
         j.zero_bytes = c->zeroed_used;
       }
     }
-    return j;
-  };
-  // (a fused top level reads its source and writes its own det-H instead of the level: the same 8 bytes)
-  auto level_bytes = [&](int o, int l) {
-    const OctGeom& og = g.o[o];
-    const bool src_got = (l - 1 >= 1 && l - 1 <= g.dog);
-    const bool decim = fused_decim && l == s.level_ds && o + 1 < g.noct;
-    return (double)batch * og.plane * (8.0 + 4.0 + (src_got ? 8.0 : 0.0)) + (decim ? (double)batch * g.o[o + 1].plane * 4.0 : 0.0);
-  };
-  // (SURVEY 8d books every array of the reference's layout written once and read once; a level this build keeps in LDS
-  // -- the octave's top level, level 0 of octave 0 -- is 8 bytes per pixel of that layout which no launch here moves)
-  auto level_in_lds = [&](int o, int l) {
-    return (top_fused && l == s.level_max && !c->keep_levels) ? (double)batch * g.o[o].plane * 8.0 : 0.0;
+    lv.bytes = (double)batch * og.plane * (8.0 + 4.0 + (src_got ? 8.0 : 0.0)) + (decim ? (double)batch * g.o[o + 1].plane * 4.0 : 0.0);
+    lv.in_lds = (top && !c->keep_levels) ? (double)batch * og.plane * 8.0 : 0.0;
+    return lv;
   };
   auto launch_level = [&](const GaussJob& j) {
     if (j.zero) c->zero_filled = true;
@@ -248,7 +220,7 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   // T(o, l) = 3o + l is the earliest step of level l of octave o (level 0 of octave o+1 is the decimated level_ds of
   // octave o): the top level of an octave and level 1 of the next are due together and independent, so they share a
   // launch (launch_gauss_pair) -- one launch fewer per octave in the dependent chain.
-  const bool pair_levels = fused_decim && s.level_ds < s.level_max && s.level_max >= 2 && !c->no_pair;
+  const bool pair_levels = !c->no_pair;
   // A single image (or two): octaves from 1 on get levels 1..level_ds -- what the next octave waits for -- from ONE
   // launch each (gauss_chain_kernel: 32x32 tiles computed in LDS on a shrinking halo): below 960x540 a level launch is a
   // few dozen workgroups that mostly wait, and the eighteen of them for octaves 1-6 of a 1080p image were two thirds of
@@ -261,7 +233,7 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   // octave 1 is 4 096 such workgroups: configs[4] 2.19 against 2.12 ms).  Needs the default schedule's tap counts.
   // HESS_CHAIN_FROM=n forces the first chained octave (99: never).
   int chain_from = g.noct;
-  if (fused_decim && s.level_max == s.level_ds + 1 && gauss_chain_available(s.taps, s.level_ds)) {
+  if (s.level_max == s.level_ds + 1 && gauss_chain_available(s.taps, s.level_ds)) {
     chain_from = c->chain_from;
     if (chain_from <= 0) {  // by size: the first octave (>= 1) whose planes of the whole batch are at most two 960x540 planes
       chain_from = g.noct;
@@ -273,58 +245,58 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
     if (chain_from > g.noct) chain_from = g.noct;
   }
   const bool chained = chain_from < g.noct;
+  // Where the top level of octave o goes: with a chain, the tops of the octave before it and of every chained one are
+  // collected for one launch after the loop; otherwise it rides with level 1 of the next octave (pair_levels) or, without
+  // one, gets a launch of its own.
+  enum TopRoute { kTopCollected, kTopRides, kTopOwnLaunch };
+  auto top_route = [&](int o) {
+    return chained && o + 1 >= chain_from ? kTopCollected : (pair_levels && o + 1 < g.noct ? kTopRides : kTopOwnLaunch);
+  };
   ProfRun small_octaves(c, HESS_K_GAUSS);  // one event pair for the consecutive launches of octaves >= 1 (see ProfRun)
-  GaussJob top_jobs[kMaxOct];  // the top levels of the octaves that do not ride with the next octave's level 1
+  GaussJob top_jobs[kMaxOct];  // the collected top levels
   int ntop = 0;
   double top_bytes = 0.0, top_in_lds = 0.0;
-  int deferred_o = -1;
   for (int o = 0; o < g.noct; o++) {
     const OctGeom& og = g.o[o];
-    if (o >= chain_from && o >= 1) {  // (its level 0 is the decimated level_ds of octave o-1, written by that launch)
+    int l = 1;  // the first level that still needs a launch
+    if (o >= chain_from) {  // (>= 1: its level 0 is the decimated level_ds of octave o-1, written by that launch)
       ChainJob cj;
       double bytes = 0.0;
       cj.src0 = plane_ptr(gauss, o, 0);
-      for (int l = 0; l <= s.level_ds; l++) {
-        cj.dst[l] = plane_ptr(gauss, o, l);
-        cj.taps[l] = s.taps[l];
+      for (int k = 0; k <= s.level_ds; k++) {
+        cj.dst[k] = plane_ptr(gauss, o, k);
+        cj.taps[k] = s.taps[k];
         // (the bytes of the fused planes are booked here although hessian_low_levels writes them: per step the sums agree)
-        if (l >= 1) bytes += level_bytes(o, l);
+        if (k >= 1) bytes += level(o, k).bytes;
       }
       cj.nlevels = s.level_ds; cj.wa = og.wa; cj.h = og.h;
       const bool decim = o + 1 < g.noct;
       cj.decim_dst = decim ? plane_ptr(gauss, o + 1, 0) : nullptr;
       cj.decim_w = decim ? g.o[o + 1].wa : 0; cj.decim_h = decim ? g.o[o + 1].h : 0;
-      {
-        small_octaves.add(bytes);
-        if (!launch_gauss_chain(st, cj, batch)) { set_err(c, "level-chain launch refused"); return HESS_ERR_DEVICE; }
-      }
-      top_jobs[ntop++] = level_job(o, s.level_max);
-      top_bytes += level_bytes(o, s.level_max);
-      top_in_lds += level_in_lds(o, s.level_max);
-      continue;
-    }
-    bool first_fused = false;  // levels 0 and 1 of octave 0 came out of one launch (level 0 never written)
-    if (o == 0 && direct_u8 && c->has_taps0 && !c->no_first_fusion && s.level_max >= 2 && s.level_ds != 1 && chain_from != 0 &&
-        gauss_first_available(c->taps0, s.taps[1])) {
-      // Decided BEFORE the profile scope: a refused launch must not book bytes.  The tap counts are the one refusal of
-      // launch_gauss_first that can still fire here: its alignment clauses (pitch % 4, img_stride % 4) repeat what
-      // direct_u8 already requires, and level_job(0, 1) has the plane pointers it asks for.  An unaligned pitch, image
-      // stride or base never gets this far: it goes through convert_kernel (tests/test_input_layouts_gpu.py).
-      // u8 pixels -> level 0 (LDS) -> level 1, det-H of level 0: the level-0 plane is nobody's input but level 1's
-      // (and, with the DoG detector, D_1's: the level is stored then)
-      const GaussJob j1 = level_job(0, 1);
-      const bool store0 = c->keep_levels || s.detector == HESS_DETECTOR_DOG;
-      ProfScope ps(c, HESS_K_GAUSS, (double)batch * og.plane * (1.0 + 4.0 + 4.0 + (s.detector == HESS_DETECTOR_DOG ? 4.0 : 0.0)),
-                   HESS_K_GAUSS_OCT0, store0 ? 0.0 : (double)batch * og.plane * 8.0);
-      first_fused = launch_gauss_first(st, (const uint8_t*)dev, pitch, (long long)image_stride, c->taps0, j1,
-                                       store0 ? plane_ptr(gauss, 0, 0) : nullptr, batch);
-    }
-    if (o == 0) c->level0_in_lds = first_fused && !c->keep_levels && s.detector != HESS_DETECTOR_DOG;
-    if (o == 0 && first_fused) {
-      // (nothing: level 1 exists, the loop below starts at level 2)
+      ProfScope ps = book_pyramid(small_octaves, false, bytes);
+      if (!launch_gauss_chain(st, cj, batch)) { set_err(c, "level-chain launch refused"); return HESS_ERR_DEVICE; }
+      l = s.level_max;
     } else if (o == 0) {
-      if (c->has_taps0) {
-        ProfScope ps(c, HESS_K_GAUSS, (double)batch * og.plane * (direct_u8 ? 5.0 : 8.0), HESS_K_GAUSS_OCT0);
+      bool first_fused = false;  // levels 0 and 1 come out of one launch (level 0 never written)
+      if (direct_u8 && !c->no_first_fusion && s.level_ds != 1 && gauss_first_available(c->taps0, s.taps[1])) {
+        // Decided BEFORE the profile scope: a refused launch must not book bytes.  The tap counts are the one refusal of
+        // launch_gauss_first that can still fire here: its alignment clauses (pitch % 4, img_stride % 4) repeat what
+        // direct_u8 already requires, and level(0, 1) has the plane pointers it asks for.  An unaligned pitch, image
+        // stride or base never gets this far: it goes through convert_kernel (tests/test_input_layouts_gpu.py).
+        // u8 pixels -> level 0 (LDS) -> level 1, det-H of level 0: the level-0 plane is nobody's input but level 1's
+        // (and, with the DoG detector, D_1's: the level is stored then)
+        const bool store0 = c->keep_levels || s.detector == HESS_DETECTOR_DOG;
+        ProfScope ps = book_pyramid(small_octaves, true,
+                                    (double)batch * og.plane * (1.0 + 4.0 + 4.0 + (s.detector == HESS_DETECTOR_DOG ? 4.0 : 0.0)),
+                                    store0 ? 0.0 : (double)batch * og.plane * 8.0);
+        first_fused = launch_gauss_first(st, (const uint8_t*)dev, pitch, (long long)image_stride, c->taps0, level(0, 1).job,
+                                         store0 ? plane_ptr(gauss, 0, 0) : nullptr, batch);
+      }
+      c->level0_in_lds = first_fused && !c->keep_levels && s.detector != HESS_DETECTOR_DOG;
+      if (first_fused) {
+        l = 2;
+      } else if (c->has_taps0) {
+        ProfScope ps = book_pyramid(small_octaves, true, (double)batch * og.plane * (direct_u8 ? 5.0 : 8.0));
         if (direct_u8)
           launch_gauss(st, nullptr, (const uint8_t*)dev, pitch, (long long)image_stride, plane_ptr(gauss, 0, 0),
                        og.wa, og.h, batch, c->taps0);
@@ -333,75 +305,55 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
       } else {
         HIP_TRY(c, hipMemcpyAsync(plane_ptr(gauss, 0, 0), src_f, (size_t)batch * og.plane * 4, hipMemcpyDeviceToDevice, st));
       }
-    } else if (!fused_decim) {
-      ProfScope ps(c, HESS_K_DOWNSAMPLE, (double)batch * og.plane * 8.0);
-      launch_downsample(st, plane_ptr(gauss, o - 1, s.level_ds), g.o[o - 1].wa, g.o[o - 1].plane,
-                        plane_ptr(gauss, o, 0), og.wa, og.h, batch);
     }
-    for (int l = first_fused ? 2 : 1; l <= s.level_max; l++) {
-      if (l == 1 && deferred_o >= 0) {  // the previous octave's top level rides with this octave's level 1
-        const int top_o = deferred_o;
-        {
-          const GaussJob ja = level_job(top_o, s.level_max), jb = level_job(o, 1);
-          std::optional<ProfScope> ps;
-          if (top_o == 0) {
-            small_octaves.close();
-            ps.emplace(c, HESS_K_GAUSS, level_bytes(top_o, s.level_max) + level_bytes(o, 1), HESS_K_GAUSS_OCT0, level_in_lds(top_o, s.level_max));
-          } else {
-            small_octaves.add(level_bytes(top_o, s.level_max) + level_bytes(o, 1), level_in_lds(top_o, s.level_max));
-          }
-          if (launch_gauss_pair(st, ja, jb, batch)) c->zero_filled = c->zero_filled || ja.zero != nullptr;
-          else { launch_level(ja); launch_level(jb); }
-        }
-        deferred_o = -1;
-        continue;
+    for (; l < s.level_max; l++) {
+      const Level lv = level(o, l);
+      if (l == 1 && o >= 1 && top_route(o - 1) == kTopRides) {  // with the previous octave's top level
+        const Level top = level(o - 1, s.level_max);
+        ProfScope ps = book_pyramid(small_octaves, o - 1 == 0, top.bytes + lv.bytes, top.in_lds);
+        if (launch_gauss_pair(st, top.job, lv.job, batch)) c->zero_filled = c->zero_filled || top.job.zero != nullptr;
+        else { launch_level(top.job); launch_level(lv.job); }
+      } else {
+        ProfScope ps = book_pyramid(small_octaves, o == 0, lv.bytes, lv.in_lds);
+        launch_level(lv.job);
       }
-      if (l == s.level_max && chained && o + 1 >= chain_from) {  // with the chained octaves' top levels, after the chain
-        top_jobs[ntop++] = level_job(o, l);
-        top_bytes += level_bytes(o, l);
-        top_in_lds += level_in_lds(o, l);
-        continue;
+    }
+    if (top_route(o) != kTopRides) {  // (a riding one is launched by octave o + 1, above)
+      const Level top = level(o, s.level_max);
+      if (top_route(o) == kTopCollected) {
+        top_jobs[ntop++] = top.job;
+        top_bytes += top.bytes;
+        top_in_lds += top.in_lds;
+      } else {
+        ProfScope ps = book_pyramid(small_octaves, o == 0, top.bytes, top.in_lds);
+        launch_level(top.job);
       }
-      if (l == s.level_max && pair_levels && o + 1 < g.noct) { deferred_o = o; continue; }
-      std::optional<ProfScope> ps;
-      if (o == 0) { small_octaves.close(); ps.emplace(c, HESS_K_GAUSS, level_bytes(o, l), HESS_K_GAUSS_OCT0, level_in_lds(o, l)); }
-      else small_octaves.add(level_bytes(o, l), level_in_lds(o, l));
-      launch_level(level_job(o, l));
     }
   }
-  if (deferred_o >= 0) {  // (cannot happen: the last octave never defers)
-    small_octaves.add(level_bytes(deferred_o, s.level_max), level_in_lds(deferred_o, s.level_max));
-    launch_level(level_job(deferred_o, s.level_max));
-  }
-  if (ntop) {  // the top levels left over by the chain, one launch
-    small_octaves.add(top_bytes, top_in_lds);
+  if (ntop) {  // the top levels collected beside the chain, one launch (booked as one, whatever it takes)
+    ProfScope ps = book_pyramid(small_octaves, false, top_bytes, top_in_lds);
     // (+ det-H / gradient of levels 0..level_ds-1 of the chain-launched octaves, from HBM: hessian_low_levels)
-    LowLevels low{&g, gauss, deth, got, s.norm, chain_from, chained ? s.level_ds : 0};
+    LowLevels low{&g, gauss, deth, got, s.norm, chain_from, s.level_ds};
     if (launch_gauss_multi(st, top_jobs, ntop, batch, &low)) {
       for (int k = 0; k < ntop; k++) c->zero_filled = c->zero_filled || top_jobs[k].zero != nullptr;
     } else {
+      // refused: other tap counts than 17-25, or top levels without det-H of their own (HESS_NO_TOP_FUSION with a chain)
       for (int k = 0; k < ntop; k++) launch_level(top_jobs[k]);
-      if (chained)  // (not reached with the schedules the chain is instantiated for)
-        for (int o = chain_from; o < g.noct; o++) launch_hessian(st, g, o, gauss, deth, got, s.norm, batch, 0, s.level_ds - 1);
+      for (int o = chain_from; o < g.noct; o++) launch_hessian(st, g, o, gauss, deth, got, s.norm, batch, 0, s.level_ds - 1);
     }
   }
   small_octaves.close();
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[1], st));
-  // ---- det-Hessian + gradient (DetectKeypointsEX part 1, PyramidCU.cpp:1576-1591) ----
-  // (levels 0 .. level_max-1: by the launch that reads the level as its source; the top level: by the launch that
-  // produces it -- no launch here with the reference's level layout)
+  // (det-H of levels 0 .. level_max-1: by the launch that reads the level as its source; of the top level: by the launch
+  // that produces it, or here)
   if (!top_fused) {  // the octaves' top levels from HBM, one launch for all of them
     double px = 0;
     for (int o = 0; o < g.noct; o++) px += g.o[o].plane;
     ProfScope ps(c, HESS_K_HESSIAN, (double)batch * px * 8.0);
-    if (s.level_max >= 1 && s.level_max <= g.dog) {  // (never with the reference's level layout: level_max = dog + 1)
-      for (int o = 0; o < g.noct; o++) launch_hessian(st, g, o, gauss, deth, got, s.norm, batch, s.level_max, s.level_max);
-    } else {
-      // this launch also clears the buffers of the detection stages (no fill launch of its own in the chain)
-      launch_hessian_level(st, g, gauss, deth, s.level_max, s.norm[s.level_max], batch, user_mode ? nullptr : c->zeroed.p,
-                           c->zeroed_used);
-      c->zero_filled = !user_mode;
-    }
+    // this launch also clears the buffers of the detection stages (no fill launch of its own in the chain)
+    launch_hessian_level(st, g, gauss, deth, s.level_max, s.norm[s.level_max], batch, user_mode ? nullptr : c->zeroed.p,
+                         c->zeroed_used);
+    c->zero_filled = !user_mode;
   }
   if (s.detector == HESS_DETECTOR_DOG) {
     // ---- difference of Gaussians (ComputeDOG_Kernel): D_l = G_l - G_(l-1), levels 1..dog+2, over the det-H planes the
@@ -413,12 +365,25 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
     ProfScope ps(c, HESS_K_HESSIAN, (double)batch * px * 12.0 * s.level_max);
     launch_dog_planes(st, g, gauss, deth, s.level_max, batch);
   }
-  }  // !(user_mode && on_current)
-  if (user_mode) return enqueue_user(c, r.desc_format);
-  // ---- extrema + ordered list (DetectKeypointsEX part 2 + GenerateFeatureList) ----
-  LimitParams lp;
-  lp.method = p.truncate_method;
-  lp.threshold = p.feature_count_threshold;
+  return 0;
+}
+
+// ---- extrema + ordered list (DetectKeypointsEX part 2 + GenerateFeatureList), top-K: the list is left in c->d_list ----
+static int enqueue_detection(hess_ctx* c, int batch, const LimitParams& lp) {
+  const hess_params& p = c->p;
+  const Schedule& s = c->sch;
+  const Geom& g = c->g;
+  hipStream_t st = c->st;
+  const float* gauss = (const float*)c->gauss.p;
+  const float* deth = (const float*)c->deth.p;
+  DetectParams dp;
+  dp.thr = p.dog_threshold;
+  dp.thr0 = (p.subpixel ? 0.8f : 1.0f) * p.dog_threshold;                            // ProgramCU.cu:897
+  dp.edge = (p.edge_threshold + 1) * (p.edge_threshold + 1) / p.edge_threshold;      // ProgramCU.cu:913
+  dp.subpixel = p.subpixel;
+  Geom gx = g;  // the extrema scan's segment length
+  if (c->stream_rows > 0) set_stream_rows(gx, c->stream_rows);      // HESS_STREAM_ROWS (A/B switch; a multiple of 3)
+  else if (batch <= policy::kLatencyBatch) set_stream_rows(gx, kStreamRows / policy::kLatencyStreamRowsDiv);  // shorter segments, twice the wavefronts
   if (!c->zero_filled)  // overflow flags, row counts, histogram, masks (normally cleared by octave 0's top-level launch)
     HIP_TRY(c, hipMemsetAsync(c->zeroed.p, 0, c->zeroed_used, st));
   DetectStore dstore;
@@ -447,54 +412,78 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   }
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[3], st));
   // ---- top-K (LimitFeatureCount(0) -> SelectTopK) ----
-  const RawKey* list = (const RawKey*)c->raw.p;
-  const int* list_total = (const int*)c->raw_total.p;
-  int cap_list = c->cap_raw;
+  c->d_list = (const RawKey*)c->raw.p;
+  c->d_list_total = (const int*)c->raw_total.p;
+  c->cap_list = c->cap_raw;
   if (c->use_topk) {
     ProfScope ps(c, HESS_K_TOPK, 0.0);
-    launch_topk(st, g, p.feature_count_threshold, (const RawKey*)c->raw.p, (const int*)c->raw_total.p, c->cap_raw,
+    launch_topk(st, g, p.feature_count_threshold, c->d_list, c->d_list_total, c->cap_raw,
                 (unsigned*)c->hist.p, (RawKey*)c->sel.p, (int*)c->sel_total.p, c->cap_sel, batch, c->tk.p, (int*)c->overflow.p);
-    list = (const RawKey*)c->sel.p;
-    list_total = (const int*)c->sel_total.p;
-    cap_list = c->cap_sel;
+    c->d_list = (const RawKey*)c->sel.p;
+    c->d_list_total = (const int*)c->sel_total.p;
+    c->cap_list = c->cap_sel;
   }
-  c->d_list = list;
-  c->d_list_total = list_total;
-  c->cap_list = cap_list;
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[4], st));
-  // ---- orientation (GetFeatureOrientations) ----
-  const OrientParams op = orient_params(c, false);
-  {
+  return 0;
+}
+
+// ---- orientation (GetFeatureOrientations), multi-orientation expansion (ReshapeFeatureListCPU), descriptors
+// (GetFeatureDescriptors) over the list in c->d_list ----
+// user: a caller's keypoints (enqueue_user: one image, no expansion, one descriptor launch over its whole list); orient =
+// false: they came with their angle.
+static int enqueue_features(hess_ctx* c, const LimitParams& lp, int batch, int pixtype, int desc_format, bool user, bool orient) {
+  const Geom& g = c->g;
+  hipStream_t st = c->st;
+  const RawKey* list = c->d_list;
+  const int* list_total = c->d_list_total;
+  const int cap_list = c->cap_list;
+  const float* got = (const float*)c->got.p;
+  if (orient) {
     ProfScope ps(c, HESS_K_ORIENT, 0.0);
-    launch_orientation(st, g, op, list, list_total, cap_list, got, (FRec*)c->recs.p, (int*)c->ocount.p, batch);
+    launch_orientation(st, g, orient_params(c, user), list, list_total, cap_list, got, (FRec*)c->recs.p, (int*)c->ocount.p, batch);
   }
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[5], st));
-  // ---- multi-orientation expansion (ReshapeFeatureListCPU) ----
-  launch_feature_scan(st, g, lp, c->multi ? 1 : 0, list, list_total, cap_list, (const int*)c->ocount.p,
+  launch_feature_scan(st, g, lp, (c->multi && !user) ? 1 : 0, list, list_total, cap_list, (const int*)c->ocount.p,
                       (int*)c->foffset.p, (int*)c->fsrc.p, (int*)c->feat_total.p, (int*)c->feat_first.p, c->cap_feat,
                       (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, batch);
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
-  // ---- descriptors (GetFeatureDescriptors) ----
-  DescParams dsp = desc_params(c, pixtype, r.desc_format, false);
-  choose_parts(c, batch);
+  DescParams dsp = desc_params(c, pixtype, desc_format, user);
+  if (user) c->parts = Parts{};  // one launch
+  else choose_parts(c, batch);
   const Parts& parts = c->parts;
-  {
-    int first = 0;
-    for (int k = 0; k < parts.n; k++) {
-      ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (per launch, so that the counts agree with a kernel trace)
-      dsp.first_image = first;
-      dsp.part = parts.features ? k : 0;
-      dsp.part_den = parts.features ? parts.n : 1;
-      launch_descriptor(st, g, dsp, list, cap_list, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
-                        (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
-                        (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, parts.end[k] - first,
-                        c->seen_features);
-      if (k < parts.n - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
-      if (!parts.features) first = parts.end[k];
-    }
+  int first = 0;
+  for (int k = 0; k < parts.n; k++) {
+    ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (per launch, so that the counts agree with a kernel trace)
+    dsp.first_image = first;
+    dsp.part = parts.features ? k : 0;
+    dsp.part_den = parts.features ? parts.n : 1;
+    launch_descriptor(st, g, dsp, list, cap_list, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
+                      (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
+                      (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat,
+                      user ? 1 : parts.end[k] - first, user ? 0 : c->seen_features);
+    if (k < parts.n - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
+    if (!parts.features) first = parts.end[k];
   }
   HIP_TRY(c, hipEventRecord(c->ev[7], st));
   return 0;
+}
+
+// Enqueue the whole path for the run's `batch` images.
+int enqueue(hess_ctx* c, const PendingRun& r) {
+  // Stage timers (SiftGPU::_timing[2..10]) only when asked for: hess_params.verbose bit 1 (the reference's _timingS,
+  // SiftGPU.cpp:433-464: its stage times, too, are only meaningful when it synchronises at stage ends) or the bench's
+  // per-kernel profile.  An event record between two kernels leaves the stream idle for about 6 us.
+  c->stage_events = (c->p.verbose & 2) != 0;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->st));
+  const bool user_mode = !c->user_keys.empty();
+  if (!(user_mode && c->user_on_current))  // SIFT_SKIP_FILTERING: the resident pyramid is reused
+    if (int rc = enqueue_pyramid(c, r)) return rc;
+  if (user_mode) return enqueue_user(c, r.desc_format);
+  LimitParams lp;
+  lp.method = c->p.truncate_method;
+  lp.threshold = c->p.feature_count_threshold;
+  if (int rc = enqueue_detection(c, r.batch, lp)) return rc;
+  return enqueue_features(c, lp, r.batch, r.pixtype, r.desc_format, false, true);
 }
 
 // FLOAT_TO_FIXED_POINT (config.h:73-74), host version.
@@ -566,34 +555,14 @@ int enqueue_user(hess_ctx* c, int desc_format) {
   }
   HIP_TRY(c, hipMemcpyAsync(c->raw_total.p, hs + 3 * g.B + 4, 4, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipStreamSynchronize(st));  // hl/hr are pageable host vectors: finish before they go away
-  const RawKey* list = (const RawKey*)c->raw.p;
-  const int* list_total = (const int*)c->raw_total.p;
-  c->d_list = list;
-  c->d_list_total = list_total;
+  c->d_list = (const RawKey*)c->raw.p;
+  c->d_list_total = (const int*)c->raw_total.p;
   c->cap_list = c->cap_raw;
   if (c->stage_events) for (int e = 1; e <= 4; e++) HIP_TRY(c, hipEventRecord(c->ev[e], st));
-  float* got = (float*)c->got.p;
-  if (!c->user_have_orientation) {
-    ProfScope ps(c, HESS_K_ORIENT, 0.0);
-    launch_orientation(st, g, orient_params(c, true), list, list_total, c->cap_raw, got, (FRec*)c->recs.p, (int*)c->ocount.p, 1);
-  }
-  if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[5], st));
   LimitParams lp;
   lp.method = 0;
   lp.threshold = -1;  // LimitFeatureCount returns at once for existing keypoints (SiftPyramid.cpp:203)
-  launch_feature_scan(st, g, lp, 0, list, list_total, c->cap_raw, (const int*)c->ocount.p, (int*)c->foffset.p,
-                      (int*)c->fsrc.p, (int*)c->feat_total.p, (int*)c->feat_first.p, c->cap_feat,
-                      (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, 1);
-  if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
-  c->parts = Parts{};  // one launch
-  {
-    ProfScope ps(c, HESS_K_DESCRIPTOR, 0.0);  // (counted like enqueue()'s: the profile's launches agree with a kernel trace)
-    launch_descriptor(st, g, desc_params(c, HESS_PIX_U8, desc_format, true), list, c->cap_raw, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
-                      (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
-                      (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat, 1);
-  }
-  HIP_TRY(c, hipEventRecord(c->ev[7], st));
-  return 0;
+  return enqueue_features(c, lp, 1, HESS_PIX_U8, desc_format, true, !c->user_have_orientation);
 }
 
 

@@ -1095,28 +1095,17 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* src, int wid
   }
 }
 
-// ---- DownsampleKernel<1>, ProgramCU.cu:312-326: dst(x,y) = src(min(2x, sw-1), 2y) ----
-__global__ __launch_bounds__(256) void downsample_kernel(const float* src, int sw, int splane, float* dst,
-                                                         int dw, int dh) {
-  int x = blockIdx.x * 256 + threadIdx.x;
-  int y = blockIdx.y;
-  if (x >= dw) return;
-  int sc = min(x << 1, sw - 1);
-  dst[((long long)blockIdx.z * dh + y) * dw + x] = src[(long long)blockIdx.z * splane + (long long)(y << 1) * sw + sc];
-}
-
 }  // namespace
 
 namespace { void launch_by_radius(hipStream_t st, const GaussArgs& a, int batch); }
 
 void launch_gauss(hipStream_t st, const float* src, const uint8_t* src_u8, long long src_pitch,
-                  long long src_img_stride, float* dst, int wa, int h, int batch, const Taps& taps,
-                  float* deth_src, float* got_src, float norm_src, float* decim_dst, int decim_w, int decim_h) {
+                  long long src_img_stride, float* dst, int wa, int h, int batch, const Taps& taps) {
   GaussArgs a;
-  a.decim_dst = decim_dst; a.dw = decim_w; a.dh = decim_h;
+  a.decim_dst = nullptr; a.dw = 0; a.dh = 0;
   a.src = src; a.src_u8 = src_u8; a.src_pitch = src_pitch; a.src_img_stride = src_img_stride;
   a.dst = dst; a.w = wa; a.h = h; a.taps = taps;
-  a.deth_src = deth_src; a.got_src = reinterpret_cast<float2*>(got_src); a.norm_src = norm_src;
+  a.deth_src = nullptr; a.got_src = nullptr; a.norm_src = 0.0f;
   a.deth_dst = nullptr; a.norm_dst = 0.0f; a.zero = nullptr; a.zero_n16 = 0;
   launch_by_radius(st, a, batch);
 }
@@ -1292,12 +1281,6 @@ void launch_convert(hipStream_t st, const void* src, int format, int pixtype, lo
 void launch_upsample(hipStream_t st, const float* src, int w, int h, int log_scale, float* dst, int batch) {
   hipLaunchKernelGGL(upsample_kernel, dim3((w + 255) / 256, h << log_scale, batch), dim3(256), 0, st, src, w, h,
                      log_scale, dst);
-}
-
-void launch_downsample(hipStream_t st, const float* src, int sw, int splane, float* dst, int dw, int dh,
-                       int batch) {
-  hipLaunchKernelGGL(downsample_kernel, dim3((dw + 255) / 256, dh, batch), dim3(256), 0, st, src, sw, splane,
-                     dst, dw, dh);
 }
 
 }  // namespace hess

@@ -192,6 +192,16 @@ def test_the_case_runs_the_kernel_form_it_is_there_for(ctx, form):
     got = {k: prof[k]["launches"] for k in want}
     print(form, got, "counts", ng)
     assert got == want, f"{form}: launches {got}, expected {want}"
+    if want["input"] == 0 and "detector" not in kw:
+        # Whatever launches the form takes, their booked bytes sum to SURVEY 8(d)'s layout (the identity of test_gpu_parity.py::
+        # test_profile_bytes_are_the_layouts_of_survey_8d, for dog levels): per octave pixel dog + 2 Gaussian levels x (4 W + 4 R),
+        # dog + 2 det-H planes x 4 W and dog gradient/theta planes x 8 W = 20 dog + 24 B, + 1 B per u8 pixel read directly.
+        dog = kw.get("dog_level_num") or 3
+        planes = [w * h for w, h in g.geometry()]
+        layout = len(stack) * ((20.0 * dog + 24.0) * sum(planes) + 1.0 * planes[0])
+        booked = prof["gauss"]["bytes"] + prof["gauss"]["bytes_in_lds"] + prof["hessian"]["bytes"]
+        print(form, "booked bytes", booked, "layout", layout)
+        assert abs(booked - layout) < 1e-6 * layout, (prof["gauss"], prof["hessian"], layout)
     if form.startswith("gauss_first_kernel"):   # level 0 of octave 0 existed in LDS only: the dump is refused
         with pytest.raises(HessError):
             g.level(0, 0, 0, _abi.DBG_GAUSS)
