@@ -206,7 +206,11 @@ __device__ __forceinline__ void feature_scan_image(const Geom& g, const FeatScan
         while (i < g.nlev && (total - lc[i]) > lp.threshold) { total -= lc[i]; first += lc[i]; i++; }
       }
     }
-    if (total > cap_feat) { atomicMax(overflow + 1, total); total = cap_feat; }
+    // The kept features are entries first .. first + total of the table, and the table was filled from entry 0 up to
+    // cap_feat: a rule that drops the lowest levels after the reshape needs it up to the EXPANDED total, not the kept one
+    // (first == 0 without such a rule).  Until tests/test_list_boundaries_gpu.py only `total` was compared, and the
+    // features beyond cap_feat - first came from whatever the table held.
+    if (first + total > cap_feat) { atomicMax(overflow + 1, first + total); total = cap_feat > first ? cap_feat - first : 0; }
     feat_total[b] = total;
     feat_first[b] = first;
     // Packed output offsets of the batch (images back to back), by whichever workgroup finishes last.  With
