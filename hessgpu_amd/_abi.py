@@ -150,6 +150,9 @@ PRODUCT_PROTOTYPES = {
     "desc_format": (C.c_int, [_ctx]),
     "fetch_u8": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
     "matcher_bank_set_device_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # 64-d descriptors in the matcher (added during version 5 without a bump)
+    "matcher_set_dim": (C.c_int, [C.c_void_p, C.c_int]),
+    "matcher_dim": (C.c_int, [C.c_void_p]),
 }
 
 

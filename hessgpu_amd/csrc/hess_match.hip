@@ -39,7 +39,10 @@
 
 namespace {
 
-constexpr int TM = 64, TN = 64, KD = 128;
+constexpr int TM = 64, TN = 64;
+// Descriptor length KD (bytes per row): 128, or 64 (-half: hess_matcher_set_dim).  A template parameter of the kernels that
+// read descriptor bytes; everything that counts scores (tiles, segments, plans, the finish) does not depend on it.
+constexpr bool dim_ok(int dim) { return dim == 128 || dim == 64; }
 
 struct GeoParams {
   int guided;
@@ -50,6 +53,7 @@ struct GeoParams {
 // dotm[i][j] = what RowMatch reads (clamped at 0 in guided mode).  cpart[tile_row][j] = (max, index,
 // second) of the reference's unclamped `results` over the tile's 64 rows in ascending order -- the
 // d_temp partials of MultiplyDescriptor_Kernel (ProgramCU.cu:3510-3524), 64 rows at a time instead of 8.
+template <int KD>
 __global__ __launch_bounds__(256) void match_dot_kernel(const uint8_t* des1, int num1, const uint8_t* des2, int num2,
                                                         const float2* loc1, const float2* loc2, GeoParams gp,
                                                         int3* cpart, int* dotm) {
@@ -59,7 +63,7 @@ __global__ __launch_bounds__(256) void match_dot_kernel(const uint8_t* des1, int
   __shared__ int3 cp[TM / 4][TN];
   const int i0 = blockIdx.y * TM, j0 = blockIdx.x * TN, tid = threadIdx.x;
   for (int g = tid; g < TM * (KD / 16); g += 256) {  // 16-byte loads
-    const int r = g >> 3, q = g & 7;
+    const int r = g / (KD / 16), q = g % (KD / 16);
     uint4 va = make_uint4(0, 0, 0, 0), vb = make_uint4(0, 0, 0, 0);
     if (i0 + r < num1) va = *reinterpret_cast<const uint4*>(des1 + (size_t)(i0 + r) * KD + q * 16);
     if (j0 + r < num2) vb = *reinterpret_cast<const uint4*>(des2 + (size_t)(j0 + r) * KD + q * 16);
@@ -239,10 +243,12 @@ __global__ __launch_bounds__(256) void match_col_kernel(const int3* cpart, int n
 // offsets into LDS -- one coalesced 16-byte load per thread and quarter, issued a whole super tile ahead, double
 // buffered, one barrier per super tile -- and every wavefront reads its B fragments from there: set 2 crosses L2 once
 // per 256 rows (round 1-5's kernel: once per 32 rows, straight from L2, 16 bytes per lane at a 32-byte stride).
-// Per 32-column tile a wavefront issues 2 x 4 v_mfma_i32_32x32x32_i8.
+// Per 32-column tile a wavefront issues 2 x 4 v_mfma_i32_32x32x32_i8.  (Figures for 128-d descriptors.  At KD = 64 a
+// super tile is 8 KB, staged as two 16-byte pieces per thread, and a tile takes 2 x 2 MFMAs; the tiles, the folds and the
+// keys are the same: a score is at most 64 * 255^2 < 2^22.)
 //
 // Scores.  Descriptors are unsigned bytes, the instruction multiplies signed ones: bytes are biased by -128 (xor 0x80)
-// and the exact dot product is dot_s + 128 (sum a + sum b) - 128^2 * 128.  The row part (rfix) rides in as the MFMA's
+// and the exact dot product is dot_s + 128 (sum a + sum b) - 128^2 * KD.  The row part (rfix) rides in as the MFMA's
 // C operand, the column part (cfix) is added while the key is formed.  Both sets are padded with zero descriptors to
 // whole blocks (rows: 256, columns: 128), whose exact score is 0 -- never a maximum (the reference's scans start at 0
 // and replace on '>' only), so there is no validity test anywhere in the loop.
@@ -265,9 +271,20 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int MM_ROWS = 256;            // rows of set 1 per workgroup (64 per wavefront)
 constexpr int MM_SUPER = 128;           // columns per super tile
-constexpr int MM_PITCH = KD + 16;       // LDS bytes per staged descriptor: 36 dwords, 16-byte reads of 32 columns spread over the banks
+// LDS bytes per staged descriptor: KD + 16, i.e. 36 dwords (128-d) or 20 (64-d).  A 16-byte read is served in groups of 16
+// lanes whose columns are distinct mod 16 (0-3, 12-15, 20-27 | 4-11, 16-19, 28-31), each lane taking 4 consecutive banks of
+// 64: the group is conflict-free exactly when pitch / 16 bytes is odd (9, 5), a bijection of the columns mod 16 onto the 16
+// four-bank slots.  The unpadded 64 bytes (4) would be 4-way.  (Staging stores at 64-d: 8 lanes write two columns, 20 dwords
+// apart over 32 banks: one of their 8 pieces meets a busy bank.)
+template <int KD> constexpr int mm_pitch() { return KD + 16; }
 constexpr int MM_MAX_TILES = 60;        // tiles per segment: the tile index shares 6 key bits with "none"
 constexpr int MM_RS_PITCH = 33;         // row-state exchange: 8-byte entries per row (32 classes + 1 pad)
+constexpr int MM_RS_BYTES = 4 * 32 * MM_RS_PITCH * 8;
+// One of the two descriptor buffers: a super tile, and half of the row-state exchange that reuses both at the end (at 64-d
+// the exchange, 33 792 B, is larger than two staged super tiles, 20 480 B)
+template <int KD> constexpr int mm_buf_bytes() {
+  return MM_SUPER * mm_pitch<KD>() > MM_RS_BYTES / 2 ? MM_SUPER * mm_pitch<KD>() : MM_RS_BYTES / 2;
+}
 
 __device__ __forceinline__ void col_merge(int3& a, const int3& b) {  // a: earlier rows, b: later rows
   if (a.x < b.x) a = make_int3(b.x, b.y, max(a.x, b.z));
@@ -293,14 +310,15 @@ struct PairJob {
 
 // The work of one workgroup: work[blockIdx.x] = (job, rb | sg << 16), row block rb of the job's set 1 against its column
 // segment sg of set 2.
-template <bool COLS>
+template <bool COLS, int KD>
 __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, const int* rfix, const uint8_t* rows2,
                                                          const int* cfix, const PairJob* jobs, const int2* work,
                                                          int3* cpart, int3* rstate) {
-  __shared__ __attribute__((aligned(16))) uint8_t bufB[2][MM_SUPER * MM_PITCH];
+  constexpr int MM_PITCH = mm_pitch<KD>(), KK = KD / 32;  // MFMAs (32 bytes of every descriptor each) per block and tile
+  __shared__ __attribute__((aligned(16))) uint8_t bufB[2][mm_buf_bytes<KD>()];
   __shared__ int bufC[2][MM_SUPER];
   __shared__ int3 cp[2][4][MM_SUPER];  // the four wavefronts' column partials of a super tile, merged after its barrier
-  static_assert(sizeof(bufB) >= 4 * 32 * MM_RS_PITCH * 8, "the row-state exchange reuses the descriptor buffers");
+  static_assert(sizeof(bufB) >= MM_RS_BYTES && mm_buf_bytes<KD>() % 16 == 0, "the row-state exchange reuses the descriptor buffers");
   const int2 w = work[blockIdx.x];
   const PairJob& J = jobs[w.x];
   const unsigned rb = w.y & 0xffff;
@@ -316,7 +334,7 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
   const int r = lane & 31, h = lane >> 5;
   const int i0 = rb * MM_ROWS + wv * 64;  // this wavefront's first row
   const int s0 = sg * J.sps, s1 = min(s0 + J.sps, nsuper);
-  v4i a[2][4];
+  v4i a[2][KK];
   v16i ra[2];
   {
     // hardware row r of a tile carries descriptor row perm(r) of the block, chosen so that the 16 accumulator registers
@@ -326,7 +344,7 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
     for (int blk = 0; blk < 2; blk++) {
       const uint8_t* pa = des1 + (size_t)(i0 + 32 * blk + prow) * KD + 16 * h;  // (set 1 is padded to whole workgroups)
 #pragma unroll
-      for (int kk = 0; kk < 4; kk++) a[blk][kk] = *reinterpret_cast<const v4i*>(pa + kk * 32) ^ (int)0x80808080;
+      for (int kk = 0; kk < KK; kk++) a[blk][kk] = *reinterpret_cast<const v4i*>(pa + kk * 32) ^ (int)0x80808080;
       const v4i* const pr = reinterpret_cast<const v4i*>(rfix + i0 + 32 * blk + 16 * h);  // (16 consecutive rows: 64-byte aligned)
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -341,20 +359,21 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) { rmx[blk][reg] = 63; rnx[blk][reg] = 0; }
 
-  // staging: thread t copies 16-byte pieces t, t + 256, t + 512, t + 768 of a super tile (piece = 8 x column + part)
-  v4i st[4];
+  // staging: thread t copies 16-byte pieces t, t + 256, ... (KD / 32 of them) of a super tile (piece = KD / 16 x column + part)
+  v4i st[KK];
   int stc = 0;
   auto stage_load = [&](int sup) {
     const uint8_t* src = des2 + (size_t)sup * MM_SUPER * KD + (size_t)tid * 16;
 #pragma unroll
-    for (int q = 0; q < 4; q++) st[q] = *reinterpret_cast<const v4i*>(src + q * 4096);
+    for (int q = 0; q < KK; q++) st[q] = *reinterpret_cast<const v4i*>(src + q * 4096);
     if (tid < MM_SUPER) stc = cfix[sup * MM_SUPER + tid];
   };
   auto stage_store = [&](int buf) {
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
+    for (int q = 0; q < KK; q++) {
       const int piece = tid + 256 * q;
-      *reinterpret_cast<v4i*>(&bufB[buf][(piece >> 3) * MM_PITCH + (piece & 7) * 16]) = st[q] ^ (int)0x80808080;
+      constexpr int PS = KD == 128 ? 3 : 2;  // log2 of the pieces per column
+      *reinterpret_cast<v4i*>(&bufB[buf][(piece >> PS) * MM_PITCH + (piece & (KD / 16 - 1)) * 16]) = st[q] ^ (int)0x80808080;
     }
     if (tid < MM_SUPER) bufC[buf][tid] = stc;
   };
@@ -373,16 +392,16 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
       const int tl = (sup - s0) * 4 + tt;     // tile index in the segment
       const int ct = 62 - tl;
       const uint8_t* pb = &bufB[cur][(tt * 32 + r) * MM_PITCH + 16 * h];
-      v4i b[4];
+      v4i b[KK];
 #pragma unroll
-      for (int kk = 0; kk < 4; kk++) b[kk] = *reinterpret_cast<const v4i*>(pb + kk * 32);
+      for (int kk = 0; kk < KK; kk++) b[kk] = *reinterpret_cast<const v4i*>(pb + kk * 32);
       const int cbk = (bufC[cur][tt * 32 + r] << 6) | ct;
       int cx = 63, cz = 0;  // column partial over this lane's 32 rows
 #pragma unroll
       for (int blk = 0; blk < 2; blk++) {
         v16i c = ra[blk];
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[blk][kk], b[kk], c, 0, 0, 0);
+        for (int kk = 0; kk < KK; kk++) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[blk][kk], b[kk], c, 0, 0, 0);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
           const int k = (int)(((unsigned)c[reg] << 6) + (unsigned)cbk);  // (score << 6) | ct: score = c + column offset >= 0
@@ -488,14 +507,15 @@ __global__ __launch_bounds__(256) void match_finish_kernel(const PairJob* jobs, 
 }
 
 // Descriptor sets: back to back on the device, each padded with zero descriptors to whole 256-row blocks, with the score
-// offsets of both sides.  Build: 8 descriptors per workgroup, 32 lanes x 4 bytes each.  sets[s] = (first padded row, first
-// source row, rows) in ascending padded rows; padded rows past a set's count are zero.  Float sources are quantised as the
-// host does and as the descriptor kernels' byte output is: desc_pack4 (hess_dev.h).
-template <bool F32>
+// offsets of both sides.  Build: KD / 4 lanes x 4 bytes per descriptor, 8 (128-d) or 16 (64-d) per workgroup.  sets[s] =
+// (first padded row, first source row, rows) in ascending padded rows; padded rows past a set's count are zero.  Float
+// sources are quantised as the host does and as the descriptor kernels' byte output is: desc_pack4 (hess_dev.h).
+template <bool F32, int KD>
 __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const int3* sets, int nsets, int total,
                                                          uint8_t* bank, int* rfix, int* cfix) {
-  const int g = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
-  if (g >= total) return;  // (uniform over the 32 lanes of a descriptor)
+  constexpr int LPD = KD / 4;  // lanes per descriptor
+  const int g = blockIdx.x * (256 / LPD) + threadIdx.x / LPD, l = threadIdx.x % LPD;
+  if (g >= total) return;  // (uniform over the lanes of a descriptor)
   int lo = 0, hi = nsets - 1;  // the last set starting at or before g (empty sets share their successor's start)
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -517,8 +537,8 @@ __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const 
   *reinterpret_cast<uint32_t*>(bank + (size_t)g * KD + 4 * l) = v;
   int sum = (int)(v & 255) + (int)((v >> 8) & 255) + (int)((v >> 16) & 255) + (int)(v >> 24);
 #pragma unroll
-  for (int d = 16; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 32);
-  if (l == 0) {  // score offsets of match_mfma_kernel: rows 128*sum - 128^2*128, columns 128*sum
+  for (int d = LPD / 2; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, LPD);
+  if (l == 0) {  // score offsets of match_mfma_kernel: rows 128*sum - 128^2*KD, columns 128*sum
     cfix[g] = 128 * sum;
     rfix[g] = 128 * sum - 128 * 128 * KD;
   }
@@ -557,6 +577,7 @@ __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob*
 
 // Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.
 struct DescSets {
+  int dim = 128;  // bytes per row (the matcher's dim when the sets were built)
   uint8_t* rows = nullptr;
   int *rfix = nullptr, *cfix = nullptr;  // one allocation: cfix = rfix + padded rows
   std::vector<int> off, num;             // first padded row and stored descriptors of each set
@@ -567,6 +588,7 @@ struct DescSets {
 
 struct hess_matcher {
   int device = 0, max_sift = 4096;
+  int dim = 128;  // descriptor length of every set and argument: hess_matcher_set_dim
   hipStream_t st = nullptr;
   DescSets bank, slot[2];  // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
   float2* loc[2] = {nullptr, nullptr};
@@ -645,9 +667,21 @@ void sets_clear(DescSets& s) {
   s.num.clear();
 }
 
-// `s` (cleared) from `src` (device memory, u8 or f32 [sum of counts][128]): set k is counts[k] rows, of which the first
+template <int KD>
+void launch_bank_build(hipStream_t st, size_t padded, bool f32, const void* src, const int3* dsets, int nsets, uint8_t* rows,
+                       int* rfix, int* cfix) {
+  const dim3 grid((unsigned)((padded + 1024 / KD - 1) / (1024 / KD)));
+  if (f32)
+    hipLaunchKernelGGL((bank_build_kernel<true, KD>), grid, dim3(256), 0, st, src, dsets, nsets, (int)padded, rows, rfix, cfix);
+  else
+    hipLaunchKernelGGL((bank_build_kernel<false, KD>), grid, dim3(256), 0, st, src, dsets, nsets, (int)padded, rows, rfix, cfix);
+}
+
+// `s` (cleared) from `src` (device memory, u8 or f32 [sum of counts][dim]): set k is counts[k] rows, of which the first
 // max_sift are kept (SetDescriptors).  Returns after the sets are built.
 int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const void* src, bool f32) {
+  const size_t KD = (size_t)m->dim;
+  s.dim = m->dim;
   std::vector<int3> sets((size_t)nsets);
   std::vector<int> off((size_t)nsets), num((size_t)nsets);
   size_t padded = 0, srow = 0;
@@ -671,13 +705,8 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
     M_TRY(m, hipMalloc(&dsets, sets.size() * sizeof(int3)));
     hipError_t e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
     if (e == hipSuccess) {
-      const dim3 grid((unsigned)((padded + 7) / 8));
-      if (f32)
-        hipLaunchKernelGGL(bank_build_kernel<true>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, s.rows,
-                           s.rfix, s.cfix);
-      else
-        hipLaunchKernelGGL(bank_build_kernel<false>, grid, dim3(256), 0, m->st, src, dsets, nsets, (int)padded, s.rows,
-                           s.rfix, s.cfix);
+      if (m->dim == 128) launch_bank_build<128>(m->st, padded, f32, src, dsets, nsets, s.rows, s.rfix, s.cfix);
+      else launch_bank_build<64>(m->st, padded, f32, src, dsets, nsets, s.rows, s.rfix, s.cfix);
       e = hipGetLastError();
     }
     const hipError_t es = hipStreamSynchronize(m->st);
@@ -693,6 +722,7 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
 // `s` from host bytes: `rows` (the sum of counts) staged on the device, then sets_build.  On failure `s` is empty.
 int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const unsigned char* des, size_t rows) {
   sets_clear(s);
+  const size_t KD = (size_t)m->dim;
   uint8_t* staging = nullptr;
   if (rows) {
     M_TRY(m, hipMalloc(&staging, rows * KD));
@@ -707,8 +737,8 @@ int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const 
 }
 
 // Host floats quantised as the reference does, int(512*d + 0.5) into a byte (SiftMatchCU.cpp:88-100): set k is counts[k]
-// rows, of which the first max_sift (kept[k]) are kept.
-std::vector<unsigned char> quantise(const float* des, int nsets, const int* counts, int max_sift, int* kept) {
+// rows of KD floats, of which the first max_sift (kept[k]) are kept.
+std::vector<unsigned char> quantise(const float* des, size_t KD, int nsets, const int* counts, int max_sift, int* kept) {
   size_t nk = 0;
   for (int k = 0; k < nsets; k++) nk += (size_t)(kept[k] = counts[k] > max_sift ? max_sift : counts[k]);
   std::vector<unsigned char> q(nk * KD);
@@ -795,12 +825,11 @@ hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, co
   if (e != hipSuccess) return e;
   (void)hipEventRecord(start, m->st);
   if (c.nwg) {
-    if (mutual_best)
-      hipLaunchKernelGGL(match_mfma_kernel<true>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows,
-                         s2.cfix, djobs, dwork, m->mm_cpart, m->mm_rstate);
-    else
-      hipLaunchKernelGGL(match_mfma_kernel<false>, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows,
-                         s2.cfix, djobs, dwork, m->mm_cpart, m->mm_rstate);
+    if (s1.dim != s2.dim || !dim_ok(s1.dim)) return hipErrorInvalidValue;  // (set_dim empties every set: not reached)
+    auto* const kern = s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128> : match_mfma_kernel<false, 128>)
+                                     : (mutual_best ? match_mfma_kernel<true, 64> : match_mfma_kernel<false, 64>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs, dwork,
+                       m->mm_cpart, m->mm_rstate);
     hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, dwork + c.nwg,
                        m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
   }
@@ -855,6 +884,30 @@ int hess_matcher_set_max(hess_matcher* m, int max_sift) {
   return 0;
 }
 
+// Descriptor length of every set and descriptor argument: 128 (a new matcher) or 64.  A change empties the bank, the two
+// single-pair slots and their locations: their rows have the other pitch.
+int hess_matcher_set_dim(hess_matcher* m, int dim) {
+  if (!m) return HESS_ERR_ARG;
+  if (!dim_ok(dim)) {
+    m->err = "set_dim: descriptors are 128-d or 64-d, not " + std::to_string(dim) + "-d";
+    return HESS_ERR_ARG;
+  }
+  if (dim == m->dim) return 0;
+  M_TRY(m, hipSetDevice(m->device));
+  M_TRY(m, hipStreamSynchronize(m->st));
+  sets_clear(m->bank);
+  for (int k = 0; k < 2; k++) {
+    sets_clear(m->slot[k]);
+    (void)hipFree(m->loc[k]);
+    m->loc[k] = nullptr;
+    m->have_loc[k] = 0;
+  }
+  m->dim = dim;
+  return 0;
+}
+
+int hess_matcher_dim(hess_matcher* m) { return m ? m->dim : HESS_ERR_ARG; }
+
 // SiftMatchCU::SetDescriptors(index, num, const unsigned char*), SiftMatchCU.cpp:71-85: slot `index` becomes a one-set bank.
 int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsigned char* des) {
   if (!m || !des || num < 0) return HESS_ERR_ARG;
@@ -869,7 +922,7 @@ int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsi
 int hess_matcher_set_descriptors_f32(hess_matcher* m, int index, int num, const float* des) {
   if (!m || !des || num < 0) return HESS_ERR_ARG;
   int kept = 0;
-  std::vector<unsigned char> q = quantise(des, 1, &num, m->max_sift, &kept);
+  std::vector<unsigned char> q = quantise(des, (size_t)m->dim, 1, &num, m->max_sift, &kept);
   return hess_matcher_set_descriptors(m, index, kept, q.data());
 }
 
@@ -939,8 +992,9 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
   gp.guided = guided ? 1 : 0;
   if (guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
   (void)hipEventRecord(m->e0, m->st);
-  hipLaunchKernelGGL(match_dot_kernel, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM), dim3(256), 0, m->st, m->slot[0].rows,
-                     n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp, mutual_best ? m->cpart : nullptr, m->dotm);
+  hipLaunchKernelGGL(m->dim == 128 ? match_dot_kernel<128> : match_dot_kernel<64>, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM),
+                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp,
+                     mutual_best ? m->cpart : nullptr, m->dotm);
   hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
                      m->rowm);
   if (mutual_best)
@@ -980,7 +1034,7 @@ int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, con
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   std::vector<int> kept((size_t)nsets);
-  std::vector<unsigned char> q = quantise(des, nsets, counts, m->max_sift, kept.data());
+  std::vector<unsigned char> q = quantise(des, (size_t)m->dim, nsets, counts, m->max_sift, kept.data());
   return hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
 }
 
@@ -1007,7 +1061,7 @@ static int bank_set_device(hess_matcher* m, int nsets, const int* counts, const 
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_desc) != hipSuccess ||
-        (const char*)dev_desc + rows * KD * esz > (const char*)base + size) {
+        (const char*)dev_desc + rows * (size_t)m->dim * esz > (const char*)base + size) {
       (void)hipGetLastError();
       m->err = "bank_set_device: the counts reach past the end of the descriptors' allocation";
       return HESS_ERR_ARG;
@@ -1037,6 +1091,7 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
   const int n = m->bank.num[set];
   if (out && n) {
     M_TRY(m, hipSetDevice(m->device));
+    const size_t KD = (size_t)m->bank.dim;
     M_TRY(m, hipMemcpy(out, m->bank.rows + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
   }
   return n;

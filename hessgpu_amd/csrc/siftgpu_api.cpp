@@ -896,7 +896,8 @@ void SiftGPU::SaveSIFT(const char* szFileName) {  // SiftPyramid::SaveSIFT, Sift
 
 // ------------------------------------------------------------------------------------------------
 // SiftMatchGPU on the matcher entry points of the C ABI (reference: SiftMatch.cpp's dispatcher +
-// SiftMatchCU.cpp).  __matcher holds the hess_matcher handle.
+// SiftMatchCU.cpp).  __matcher holds the hess_matcher handle.  The object layout is ABI, so "-half" (64-d descriptors)
+// is kept in a spare bit of __language, whose values are small.
 
 static hess_matcher* MH(SiftMatchGPU* m_as_ptr) { return reinterpret_cast<hess_matcher*>(m_as_ptr); }
 
@@ -905,14 +906,30 @@ SiftMatchGPU::~SiftMatchGPU() {
   if (__matcher) hess_matcher_destroy(MH(__matcher));
 }
 int SiftMatchGPU::_CreateContextGL() { return _VerifyContextGL(); }
+static const int MATCH_HALF = 1 << 30;  // in __language: the matcher takes 64-d descriptors
 int SiftMatchGPU::_VerifyContextGL() {
-  if (!__matcher) __matcher = reinterpret_cast<SiftMatchGPU*>(hess_matcher_create(__language >= 3 ? __language - 3 : 0, __max_sift));
+  if (!__matcher) {
+    const int language = __language & ~MATCH_HALF;
+    __matcher = reinterpret_cast<SiftMatchGPU*>(hess_matcher_create(language >= 3 ? language - 3 : 0, __max_sift));
+    if (__matcher && (__language & MATCH_HALF)) hess_matcher_set_dim(MH(__matcher), 64);
+  }
   return __matcher ? 1 : 0;
 }
-void SiftMatchGPU::SetLanguage(int language) { __language = language; }  // SIFTMATCH_CUDA_DEVICE0 + i selects device i
+// SIFTMATCH_CUDA_DEVICE0 + i selects device i
+void SiftMatchGPU::SetLanguage(int language) { __language = (language & ~MATCH_HALF) | (__language & MATCH_HALF); }
+// "-cuda N": device N; "-half": 64-d descriptors, the word SiftGPU::ParseParam takes (a ComboSiftGPU caller passes one argv
+// to both).  On a matcher that exists already "-half" empties its descriptor slots (hess_matcher_set_dim).
 void SiftMatchGPU::SetDeviceParam(int argc, char** argv) {
-  for (int i = 0; i + 1 < argc; i++)
-    if (!strcasecmp(argv[i], "-cuda")) { int d = 0; if (sscanf(argv[i + 1], "%d", &d) == 1 && d >= 0) __language = 3 + d; }
+  for (int i = 0; i < argc; i++) {
+    if (!argv[i]) continue;
+    if (!strcasecmp(argv[i], "-cuda") && i + 1 < argc && argv[i + 1]) {
+      int d = 0;
+      if (sscanf(argv[i + 1], "%d", &d) == 1 && d >= 0) __language = (3 + d) | (__language & MATCH_HALF);
+    } else if (!strcasecmp(argv[i], "-half")) {
+      __language |= MATCH_HALF;
+      if (__matcher) hess_matcher_set_dim(MH(__matcher), 64);
+    }
+  }
 }
 void SiftMatchGPU::SetMaxSift(int max_sift) {
   __max_sift = max_sift;
@@ -985,7 +1002,9 @@ SiftMatchGPU* siftmatch_create(int max_sift) {
   return m;
 }
 void siftmatch_destroy(SiftMatchGPU* m) { delete m; }
+void siftmatch_set_device_param(SiftMatchGPU* m, int argc, char** argv) { m->SetDeviceParam(argc, argv); }
 void siftmatch_set_descriptors_f32(SiftMatchGPU* m, int index, int num, const float* d) { m->SetDescriptors(index, num, d, -1); }
+void siftmatch_set_descriptors_u8(SiftMatchGPU* m, int index, int num, const unsigned char* d) { m->SetDescriptors(index, num, d, -1); }
 int siftmatch_get_match(SiftMatchGPU* m, int max_match, int* buf, float distmax, float ratiomax, int mbm) {
   return m->GetSiftMatch(max_match, reinterpret_cast<int(*)[2]>(buf), distmax, ratiomax, mbm);
 }

@@ -19,6 +19,8 @@ def _lib():
         L.hess_matcher_create.argtypes = [C.c_int, C.c_int]
         L.hess_matcher_destroy.argtypes = [C.c_void_p]
         L.hess_matcher_set_max.argtypes = [C.c_void_p, C.c_int]
+        L.hess_matcher_set_dim.argtypes = [C.c_void_p, C.c_int]
+        L.hess_matcher_dim.argtypes = [C.c_void_p]
         L.hess_matcher_set_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.hess_matcher_set_descriptors_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.hess_matcher_set_locations.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -65,12 +67,32 @@ def check_pairs(pairs):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+DIMS = (128, 64)
+
+
 class Matcher:
-    def __init__(self, device=0, max_sift=4096):
+    """dim: the descriptor length of every set this matcher takes, 128 or 64 (the -half descriptors of a
+    HessContext(half_sift=1)).  64-d sets give what the same rows with 64 zero columns appended give at 128."""
+
+    def __init__(self, device=0, max_sift=4096, dim=128):
+        if dim not in DIMS:
+            raise ValueError(f"the matcher takes 128-d or 64-d descriptors, not {dim}-d")
         self.L = _lib()
+        self._dim = 128
         self.h = self.L.hess_matcher_create(device, max_sift)
         if not self.h:
             raise HessError(-3, f"hess_matcher_create failed on device {device}")
+        if dim != 128:
+            self.set_dim(dim)
+
+    @property
+    def dim(self):
+        return self._dim
+
+    def set_dim(self, dim):
+        """Changing the length empties the bank, both single-pair slots and their locations."""
+        self._check(self.L.hess_matcher_set_dim(self.h, int(dim)))
+        self._dim = int(self.L.hess_matcher_dim(self.h))
 
     def close(self):
         if self.h:
@@ -90,6 +112,12 @@ class Matcher:
 
     def set_descriptors(self, index, desc):
         d = np.ascontiguousarray(desc)
+        if d.ndim == 2 and d.shape[1] != self.dim:
+            raise ValueError(f"this matcher takes [n, {self.dim}] descriptors, not {d.shape}")
+        if d.ndim != 2 and d.size % self.dim:
+            raise ValueError(f"{d.size} values are no whole number of {self.dim}-d descriptors")
+        if d.ndim != 2:
+            d = d.reshape(-1, self.dim)
         if d.dtype == np.uint8:
             self._check(self.L.hess_matcher_set_descriptors(self.h, index, len(d), d.ctypes.data))
         else:
@@ -116,23 +144,23 @@ class Matcher:
 
     # ---- bank of descriptor sets on the device, many pairs per call ----
     def set_bank(self, sets):
-        """sets: a list of [n_i, 128] arrays, all u8 (stored as they are) or all float (quantised like
+        """sets: a list of [n_i, dim] arrays, all u8 (stored as they are) or all float (quantised like
         set_descriptors)."""
         sets = [np.asarray(d) for d in sets]
         for d in sets:
-            if d.ndim != 2 or d.shape[1] != 128:
-                raise ValueError(f"a bank set must be [n, 128], not {d.shape}")
+            if d.ndim != 2 or d.shape[1] != self.dim:
+                raise ValueError(f"a bank set must be [n, {self.dim}], not {d.shape}")
         counts = np.array([len(d) for d in sets], dtype=np.int32)
         u8 = all(d.dtype == np.uint8 for d in sets)
         dt = np.uint8 if u8 else np.float32
-        flat = np.ascontiguousarray(np.concatenate(sets).astype(dt, copy=False) if sets else np.zeros((0, 128), dt))
+        flat = np.ascontiguousarray(np.concatenate(sets).astype(dt, copy=False) if sets else np.zeros((0, self.dim), dt))
         fn = self.L.hess_matcher_bank_set if u8 else self.L.hess_matcher_bank_set_f32
         self._check(fn(self.h, len(counts), counts.ctypes.data, flat.ctypes.data if flat.size else None))
         self._bank_sets = len(counts)
 
     def set_bank_device(self, ptr, counts, dtype=np.float32):
-        """ptr: device address of float [sum(counts)][128] on the matcher's device (quantised on the device), or with
-        dtype=np.uint8 of bytes [sum(counts)][128] (stored as they are).  The producer must have finished writing it."""
+        """ptr: device address of float [sum(counts)][dim] on the matcher's device (quantised on the device), or with
+        dtype=np.uint8 of bytes [sum(counts)][dim] (stored as they are).  The producer must have finished writing it."""
         dt = np.dtype(dtype)
         if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError(f"device descriptors are float32 or uint8, not {dt}")
@@ -143,10 +171,11 @@ class Matcher:
 
     def set_bank_from_session(self, session):
         """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,
-        without leaving the device -- floats or bytes, whichever the run made."""
+        without leaving the device -- floats or bytes, whichever the run made.  The context's descriptor length must be the
+        matcher's: Matcher(dim=64) for a half_sift context."""
         dim = session.desc_dim()
-        if dim != 128:
-            raise ValueError(f"the matcher takes 128-d descriptors; this context's are {dim}-d (-half / -sd)")
+        if dim != self.dim:
+            raise ValueError(f"the matcher takes {self.dim}-d descriptors; this context's are {dim}-d (-half / -sd)")
         _, desc, total = session.device_results()
         counts = [session.count(i) for i in range(session._batch)]
         if sum(counts) != total:
@@ -154,9 +183,9 @@ class Matcher:
         self.set_bank_device(desc, counts, dtype=np.uint8 if session.desc_format() == "u8" else np.float32)
 
     def bank(self, i):
-        """The stored bytes of set i: [n, 128] u8."""
+        """The stored bytes of set i: [n, dim] u8."""
         n = self._check(self.L.hess_matcher_bank_read(self.h, int(i), None))
-        out = np.zeros((n, 128), dtype=np.uint8)
+        out = np.zeros((n, self.dim), dtype=np.uint8)
         if n:
             self._check(self.L.hess_matcher_bank_read(self.h, int(i), out.ctypes.data))
         return out

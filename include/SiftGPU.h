@@ -138,7 +138,7 @@ class SiftMatchGPU {
   inline int VerifyContextGL() { return _VerifyContextGL(); }
   SiftMatchGPU(int max_sift = 4096);
   virtual void SetLanguage(int gpu_language);
-  virtual void SetDeviceParam(int argc, char** argv);
+  virtual void SetDeviceParam(int argc, char** argv);  // "-cuda N"; "-half": descriptors are [num][64]
   virtual void SetMaxSift(int max_sift);
   virtual ~SiftMatchGPU();
   virtual void SetDescriptors(int index, int num, const float* descriptors, int id = -1);
@@ -183,7 +183,10 @@ void siftgpu_set_verbose(SiftGPU* s, int v);
 int siftgpu_image_count(SiftGPU* s);
 SiftMatchGPU* siftmatch_create(int max_sift);
 void siftmatch_destroy(SiftMatchGPU* m);
+// SetDeviceParam: "-cuda N", and "-half" for 64-d descriptors ([num][64] from then on, as SiftGPU's "-half" makes them)
+void siftmatch_set_device_param(SiftMatchGPU* m, int argc, char** argv);
 void siftmatch_set_descriptors_f32(SiftMatchGPU* m, int index, int num, const float* d);
+void siftmatch_set_descriptors_u8(SiftMatchGPU* m, int index, int num, const unsigned char* d);
 int siftmatch_get_match(SiftMatchGPU* m, int max_match, int* buf, float distmax, float ratiomax, int mbm);
 void siftmatch_set_locations(SiftMatchGPU* m, int index, const float* loc, int gap);
 // H, F: 3x3 row-major or NULL (GetGuidedSiftMatch's rule for a missing matrix)

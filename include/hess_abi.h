@@ -39,7 +39,9 @@ extern "C" {
  *    hess_matcher_bank_set / _set_f32 / _set_device / _read and hess_matcher_match_pairs (added during version 5
  *    without a bump).  hess_set_descriptor_format / hess_desc_format / hess_fetch_u8 and
  *    hess_matcher_bank_set_device_u8 (byte descriptors; added during version 5 without a bump: hess_params keeps its
- *    layout, and a context that never calls the setter behaves as before). */
+ *    layout, and a context that never calls the setter behaves as before).  hess_matcher_set_dim / hess_matcher_dim
+ *    (64-d descriptors of a half_sift run in the matcher; added during version 5 without a bump: a matcher that never
+ *    calls the setter is 128-d as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -356,11 +358,23 @@ int hess_profile_get_in_lds(hess_ctx* ctx, int kernel, double* bytes);
 
 /* ---- Descriptor matcher: replaces SiftMatchGPU's CUDA flavour, SiftMatchCU
  * (SiftMatchCU.cpp:71-176) and MultiplyDescriptor(_G)_Kernel / RowMatch_Kernel / ColMatch_Kernel
- * (ProgramCU.cu:3455-3843).  Descriptors: num x 128 unsigned bytes (512*d rounded); locations: (x,y). */
+ * (ProgramCU.cu:3455-3843).  Descriptors: num x dim unsigned bytes (512*d rounded), dim = 128 unless
+ * hess_matcher_set_dim says 64; locations: (x,y). */
 typedef struct hess_matcher hess_matcher;
 hess_matcher* hess_matcher_create(int device, int max_sift);          /* SiftMatchGPU(max_sift) */
 void hess_matcher_destroy(hess_matcher* m);
 int hess_matcher_set_max(hess_matcher* m, int max_sift);              /* SetMaxSift */
+/* Descriptor length: 128 (a new matcher) or 64, the unsigned-gradient descriptors of a half_sift (-half) run.  From then
+ * on EVERY descriptor argument of every matcher entry point is [n][dim]: hess_matcher_set_descriptors / _f32,
+ * hess_matcher_bank_set / _set_f32 / _set_device / _set_device_u8 (at 64 exactly what hess_device_results hands out after
+ * a half_sift run: 64 floats or 64 bytes per feature) and hess_matcher_bank_read.  Pointer checks, truncation to
+ * max_sift, the quantisation rule, matching (unguided, guided, match_pairs) and locations are the same at either length;
+ * the result for 64-d sets is what the 128-d matcher returns for the same rows with 64 zero columns appended.
+ * Setting the current dim is a no-op and the sets stay.  Setting the other one EMPTIES the bank, both single-pair slots
+ * and their locations (their rows have the other pitch): load them again.  Any other value: HESS_ERR_ARG, with
+ * hess_matcher_last_error naming it, and the matcher unchanged.  NULL matcher: HESS_ERR_ARG. */
+int hess_matcher_set_dim(hess_matcher* m, int dim);
+int hess_matcher_dim(hess_matcher* m);                                /* 128 or 64; NULL: HESS_ERR_ARG */
 int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsigned char* des);
 int hess_matcher_set_descriptors_f32(hess_matcher* m, int index, int num, const float* des);
 int hess_matcher_set_locations(hess_matcher* m, int index, const float* locations, int gap);
@@ -370,8 +384,8 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
 
 /* Batched matching (no reference counterpart): a BANK of descriptor sets stays on the device and one call matches a
  * list of (a, b) pairs of it.  Independent of the two single-pair slots above.  Loading a bank replaces the previous
- * one; each set is truncated to max_sift as hess_matcher_set_descriptors does (at load time).  128-d descriptors only.
- * counts[s]: descriptors of set s; the sets lie back to back in `des` (u8 or host floats, quantised as _f32 does). */
+ * one; each set is truncated to max_sift as hess_matcher_set_descriptors does (at load time).  Rows of dim bytes or floats (hess_matcher_set_dim;
+ * "128" below is the default dim).  counts[s]: descriptors of set s; the sets lie back to back in `des` (u8 or host floats, quantised as _f32 does). */
 int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const unsigned char* des);
 int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, const float* des);
 /* dev_desc: float [sum of counts][128] in device memory of the matcher's device -- e.g. what hess_device_results hands
