@@ -10,7 +10,7 @@ import ctypes as _C
 import os as _os
 
 from . import _abi
-from .session import HessError, Session, make_params
+from .session import HessError, Session, make_params, rect_keys
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 LIB_PATH = _os.environ.get("HESS_LIB") or _os.path.join(_HERE, "libhessgpu.so")  # HESS_LIB: developer override

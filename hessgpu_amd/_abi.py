@@ -25,6 +25,7 @@ PIX_U8, PIX_U16, PIX_F32 = 1, 2, 3
 DBG_GAUSS, DBG_DETH, DBG_GOT = 0, 1, 2
 DETECTOR_HESSIAN, DETECTOR_DOG = 0, 1
 DESC_FORMAT_F32, DESC_FORMAT_U8 = 0, 1
+KEYS_NONE, KEYS_ORIENTED, KEYS_RECTANGLES = 0, 1, -1   # keys_have_orientation of set_keypoints / run_keypoints
 (T_LOAD, T_ALLOC, T_PYRAMID, T_DETECT, T_LIST, T_ORIENT, T_MULTI_ORIENT, T_DOWNLOAD,
  T_DESCRIPTOR, T_VBO, T_REDUCTION, T_TOTAL, T_COUNT) = range(13)
 (K_GAUSS, K_DOWNSAMPLE, K_HESSIAN, K_EXTREMA, K_TOPK, K_ORIENT, K_DESCRIPTOR, K_INPUT,

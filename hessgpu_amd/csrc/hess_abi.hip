@@ -444,7 +444,8 @@ static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, int num, int 
   try {
     c->user_keys.assign(keys, keys + num);
   } catch (...) { c->user_keys.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
-  c->user_have_orientation = keys_have_orientation != 0;
+  c->user_have_orientation = keys_have_orientation != 0;  // the reference tests the flag's truth (PyramidCU.cpp:522) ...
+  c->user_rect = keys_have_orientation == HESS_KEYS_RECTANGLES;  // ... and -1 alone for rectangles (SiftPyramid.cpp:345-354)
   c->user_on_current = on_current;
   return 0;
 }

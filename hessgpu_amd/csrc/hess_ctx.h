@@ -292,6 +292,7 @@ struct hess_ctx {
   // user-supplied keypoint list (SiftPyramid::SetKeypointList): used by the next run, then cleared
   std::vector<hess_keypoint> user_keys;
   bool user_have_orientation = false;
+  bool user_rect = false;           // HESS_KEYS_RECTANGLES: the keys are rectangles (x, y, width, height); implies user_have_orientation
   bool user_on_current = false;     // RunSIFT(num, keys, flag): skip filtering, reuse the resident pyramid
   std::vector<int> user_kindex;     // list position -> input index (_keypoint_index)
   std::vector<int> user_levels;     // parity hook: explicit level index per user keypoint (hess_debug_key_levels)

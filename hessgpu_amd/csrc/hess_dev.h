@@ -156,6 +156,7 @@ struct DescParams {
   int sequential;        // HESS_DESC_ORDER_SEQUENTIAL: bins summed in the reference's sample order (else four interleaved partial sums)
   int pixel;             // HESS_DESC_ORDER_PIXEL: one raster over the footprint, fixed-point sums (descriptor_pixel_kernel); wins over `sequential`
   int px_band;           // pixel raster: pixels per band of rows, 64 .. 4096 (4096 unless HESS_PX_BAND of the developer build says otherwise)
+  int rect;              // a caller's rectangles (keys_have_orientation == -1): FRec = corner, width 8.8, height as a float; descriptor_rect_kernel, whatever `sequential` and `pixel` say
   int part, part_den;    // part_den > 1 (one image per launch): the launch does features [n part / part_den, n (part + 1) / part_den) of the image's n
 };
 

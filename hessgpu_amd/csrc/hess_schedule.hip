@@ -120,6 +120,7 @@ static DescParams desc_params(const hess_ctx* c, int pixtype, int desc_format, b
   // the pixel order's fixed point assumes luminance in [0, 1] (8- and 16-bit inputs); float pixels are taken as they are
   // and keep the interleaved order (the test oracle applies the same rule)
   dsp.pixel = !user && p.descriptor_order == HESS_DESC_ORDER_PIXEL && pixtype != HESS_PIX_F32;
+  dsp.rect = (user && c->user_rect) ? 1 : 0;  // HESS_KEYS_RECTANGLES: descriptor_rect_kernel, whatever the order
   return dsp;
 }
 
@@ -494,6 +495,10 @@ static inline int float_to_fixed_host(float v, int n) {
 // User-supplied keypoints (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718): bin the keys to
 // levels by scale, pack fixed-point records on the host, upload, strongest orientation on the device
 // unless supplied, descriptors.  One image.
+// Rectangles (HESS_KEYS_RECTANGLES; IsUsingRectDescription, SiftPyramid.cpp:345-354): (x, y) is the corner, s the width
+// and o the height; the scale that is binned is min(s, o) / 12 (PyramidCU.cpp:598-599), the record holds the width as the
+// scale's 8.8 fixed point and the height o / octave_sigma as it is, a float (:618-622); no orientation pass
+// (PyramidCU.cpp:522), and the descriptor launch is descriptor_rect_kernel's.
 int enqueue_user(hess_ctx* c, int desc_format) {
   const hess_params& p = c->p;
   const Schedule& s = c->sch;
@@ -501,6 +506,7 @@ int enqueue_user(hess_ctx* c, int desc_format) {
   hipStream_t st = c->st;
   const int num = (int)c->user_keys.size();
   const double twopi = 2.0 * 3.14159265358979323846;
+  const bool rect = c->user_rect;
   const float sigma_half_step = powf(2.0f, 0.5f / g.dog);
   float octave_sigma = first_octave_sigma(c);
   const float offset = p.lowe_origin ? 0.0f : 0.5f;
@@ -515,7 +521,7 @@ int enqueue_user(hess_ctx* c, int desc_format) {
       const float sigma_max = level_sigma * sigma_half_step;
       for (int k = 0; k < num && hl.size() < cap; k++) {
         const hess_keypoint& key = c->user_keys[k];
-        float sigmak = key.s;
+        float sigmak = rect ? (key.s < key.o ? key.s : key.o) / 12.0f : key.s;
         if ((int)c->user_levels.size() == num && c->user_levels[k] >= 0) {  // parity hook: level given, not derived
           if (c->user_levels[k] != octave * g.dog + (level - 1)) continue;
           sigmak = level_sigma;
@@ -525,7 +531,7 @@ int enqueue_user(hess_ctx* c, int desc_format) {
           const float fX = (key.x - offset) / octave_sigma + 0.5f;
           const float fY = (key.y - offset) / octave_sigma + 0.5f;
           const float fScale = key.s / octave_sigma;
-          const float fOrientation = (float)fmod(twopi - key.o, twopi);
+          const float fOrientation = rect ? key.o / octave_sigma : (float)fmod(twopi - key.o, twopi);
           FRec r;
           r.x = (uint32_t)float_to_fixed_host(fX, 10) & 0x00FFFFFFu;
           r.y = (uint32_t)float_to_fixed_host(fY, 10) & 0x00FFFFFFu;

@@ -1021,6 +1021,222 @@ typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 #undef HESS_PIXEL_KERNEL
 #undef HESS_PIXEL_U8
 
+// ================================= descriptor, rectangles =====================================
+//
+// DescParams::rect (a caller's key list with keys_have_orientation == -1, include/hess_abi.h): the record of list entry i
+// holds an axis-aligned rectangle of its level -- corner (X, Y) = 14.10 fixed point, width W = 8.8 fixed point, height H =
+// the binary32 number in FRec::w -- and the descriptor is the 4 x 4-cell, 8-bin gradient histogram over it
+// (ComputeDescriptorRECT_Kernel, ProgramCU.cu:1806-1948): no rotation, no Gaussian weight, window_factor unread.
+// The reference gives a cell to a thread that walks the cell's 2 sptx x 2 spty box alone.  Here one wavefront takes a
+// rectangle: lane = column of the union of the four cell columns' boxes (1.25 W wide), in bands of 64 columns; for each
+// of the four cell rows iy the wavefront marches down the rows of that cell row's box, one coalesced 512-byte read of
+// (gradient, theta) per row.  What depends on the column alone (the cells ix a column counts for, at most two unless
+// rounding says otherwise, and their weights wx) is formed once per band and lane, what depends on the row alone (wy)
+// once per row; per pixel remain the bin split and two fused multiply-adds for each of the lane's cells.
+//
+// THE EXPRESSIONS (binary32, no contraction other than the fmaf written out; `/` is the correctly rounded division):
+//   sptx = W * 0.25f, spty = H * 0.25f;  cx = sptx * (ix + 0.5f) + X, cy = spty * (iy + 0.5f) + Y
+//   cell box: x from max(1.5f, floorf(cx - sptx) + 0.5f) to min(width - 1.5f, floorf(cx + sptx) + 0.5f), y alike
+//   nx = (x - cx) / sptx, ny = (y - cy) / spty; the sample counts where fabsf(nx) < 1 and fabsf(ny) < 1
+//   weight = ((1 - fabsf(nx)) * (1 - fabsf(ny))) * gradient
+//   t = (-theta) * (float)(4 / pi); t < 0: t += 8;  fo = floorf(t), w1 = fo + 1 - t, w2 = t - fo
+//   t == 8.0f: dropped, or with dynamic_indexing w1 = 0, w2 = 1 at fo = 7 (the whole weight to "bin 8")
+//   sum[fo] = fmaf(w1, weight, sum[fo]);  sum[(fo + 1) mod 8] = fmaf(w2, weight, sum[(fo + 1) mod 8])
+// THE ORDER.  The reference's ninth bin is bin 0 from the start ((fo + 1) mod 8), so a bin has ONE sum per lane:
+//   per lane    a (cell, bin) sum of a lane starts at 0 and takes the lane's samples band by band (band k: columns
+//               xlo + 64 k + lane), within a band row by row with y ascending;
+//   over lanes  row r = 8 ix + bin of the cell row: s_h = sequential sum, from 0, over k = 0 .. 31 of the sum of lane
+//               32 h + ((k + r) mod 32), for h = 0, 1; the bin is s_0 + s_1;
+//   half_sift   bin k + bin (k + 4), then the shared normalisation (finish_descriptor128 / 64).
+// All of it is a function of the record and the plane: no atomics, nothing depends on which wavefront does the work.
+// LDS per wavefront: [4 ix][8 bins][64 lanes] floats, a lane's own column of it (conflict-free), 8 KB.
+// Bounds: every gathered pixel lies in the clipped boxes, [1, width - 2] x [1, height - 2] of the plane, through a buffer
+// resource of the plane's size; every loop count comes from the clipped boxes, so it is at most the plane's.
+constexpr int RC_ROWS = 32;                // (ix, bin) sums of one cell row
+constexpr int RC_WAVE = RC_ROWS * 64;      // floats per wavefront
+constexpr int RC_UNROLL = 4;               // rows whose gathers are in flight together
+
+template <bool HOST_MIRROR>
+__global__ __launch_bounds__(256) void descriptor_rect_kernel(Geom g, DescParams dp, const RawKey* list, int cap_list,
+                                                              const FRec* recs, const int* fsrc, const int* feat_total,
+                                                              const int* feat_first, const int* img_base, const float* got,
+                                                              HostKeypoint* keys, float* desc, int cap_feat) {
+  __shared__ __attribute__((aligned(16))) float dl[4][128];
+  __shared__ __attribute__((aligned(16))) float hist[4][RC_WAVE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.y + dp.first_image;
+  int ftotal = feat_total[b], ffirst = feat_first[b];
+  long long obase = img_base[b];
+  feature_part(dp, &ftotal, &ffirst, &obase);
+  const int nwaves = gridDim.x * 4;
+  const float rpi = (float)(4.0 / kPI);
+  const int dim = dp.half_sift ? 64 : 128;
+
+  static_assert(sizeof(HostKeypoint) == 24 && 4 * RC_WAVE * 4 >= 256 * 24, "record staging fits the histograms");
+  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), list, cap_list, recs, fsrc, cap_feat, b, ftotal, ffirst, obase, keys);
+  if (!desc) return;
+  float* const hw = &hist[wv][0];
+  for (int i = lane; i < RC_WAVE; i += 64) hw[i] = 0.0f;
+  float* const mine = hw + lane;  // + 64 * (8 ix + bin)
+  const uint32_t theta_end_bits = dp.dynamic_indexing ? 0x41000001u : 0x41000000u;  // 8.0f, or the next float (admits t == 8)
+
+  // from the end of the list backwards: (octave, level) order, and a level's rectangles grow with the level
+  for (int mw = blockIdx.x * 4 + wv; mw < ftotal; mw += nwaves) {
+    const int m = ffirst + ftotal - 1 - mw;
+    const int src = fsrc[(long long)b * cap_feat + m];
+    const int i = src >> 2;
+    const int oidx = m - ffirst;
+    const FRec rec = recs[(long long)b * cap_list + i];
+    const int li = list[(long long)b * cap_list + i].level_index;
+    int o, l;
+    level_of(g, li, &o, &l);
+    const OctGeom& og = g.o[o];
+    // the plane as a buffer resource, as descriptor_kernel makes it: an offset outside it reads 0
+    const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
+                                                        ((long long)(l - 1) * g.B + b) * og.plane);
+    const GlobalBytes gp = (GlobalBytes)(
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
+        (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
+    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
+    const int width = og.wa, height = og.h;
+
+    const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
+    const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
+    const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
+    const float kh = __uint_as_float(rec.w);
+    const float sptx = kz * 0.25f, spty = kh * 0.25f;
+
+    // the four cell columns: centre and clipped box in x (ProgramCU.cu:1859-1864)
+    float cx[4], bx0[4], bx1[4];
+#pragma unroll
+    for (int ix = 0; ix < 4; ix++) {
+      cx[ix] = sptx * ((float)ix + 0.5f) + kx;
+      bx0[ix] = fmaxf(1.5f, floorf(cx[ix] - sptx) + 0.5f);
+      bx1[ix] = fminf((float)width - 1.5f, floorf(cx[ix] + sptx) + 0.5f);
+    }
+    const float xlo = fminf(fminf(bx0[0], bx0[1]), fminf(bx0[2], bx0[3]));
+    const float xhi = fmaxf(fmaxf(bx1[0], bx1[1]), fmaxf(bx1[2], bx1[3]));
+    const int ncols = (xhi >= xlo) ? (int)(xhi - xlo) + 1 : 0;  // <= width - 2
+
+    for (int iy = 0; iy < 4; iy++) {
+      const float cy = spty * ((float)iy + 0.5f) + ky;
+      const float ymin = fmaxf(1.5f, floorf(cy - spty) + 0.5f);
+      const float ymax = fminf((float)height - 1.5f, floorf(cy + spty) + 0.5f);
+      const int nrows = (ymax >= ymin) ? (int)(ymax - ymin) + 1 : 0;  // <= height - 2
+      for (int c0 = 0; c0 < ncols && nrows > 0; c0 += 64) {
+        const int col = c0 + lane;
+        const float x = xlo + (float)col;  // an integer + 0.5 below 2^23: exact
+        const bool xin = col < ncols;
+        // the cells this column counts for, compacted: slot s of the lane is the s-th such cell, the others follow with
+        // weight 0 (every slot another cell, so that a lane's read-modify-writes of one pixel never share an address)
+        bool on[4];
+        float wx[4];
+        int non = 0;
+#pragma unroll
+        for (int ix = 0; ix < 4; ix++) {
+          const float nx = (x - cx[ix]) / sptx;
+          on[ix] = xin & (x >= bx0[ix]) & (x <= bx1[ix]) & (fabsf(nx) < 1.0f);
+          wx[ix] = on[ix] ? 1.0f - fabsf(nx) : 0.0f;
+          non += on[ix] ? 1 : 0;
+        }
+        float swx[4];
+        int scol[4];  // float offset of the slot's cell column in the lane's histogram column: 8 bins x 64 lanes per cell
+        {
+          int ron = 0, roff = 0;
+#pragma unroll
+          for (int s = 0; s < 4; s++) { swx[s] = 0.0f; scol[s] = 0; }
+#pragma unroll
+          for (int ix = 0; ix < 4; ix++) {
+            const int p = on[ix] ? ron : non + roff;
+            ron += on[ix] ? 1 : 0;
+            roff += on[ix] ? 0 : 1;
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+              if (p == s) { swx[s] = wx[ix]; scol[s] = ix * 8 * 64; }
+          }
+        }
+        int nslot = non;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) nslot = max(nslot, __shfl_xor(nslot, d));
+        nslot = rli(nslot, 0);  // (uniform: the slots the band's rows go through)
+        if (nslot == 0) continue;
+        const unsigned coloff = (unsigned)((int)xlo + col) * 8u;
+
+        for (int r0 = 0; r0 < nrows; r0 += RC_UNROLL) {
+          float wy[RC_UNROLL];
+          dfloat2 gv[RC_UNROLL];
+#pragma unroll
+          for (int u = 0; u < RC_UNROLL; u++) {  // the row's weight (uniform) and the gathers of RC_UNROLL rows
+            const float y = ymin + (float)(r0 + u);
+            const float ny = (y - cy) / spty;
+            const bool live = (r0 + u < nrows) & (fabsf(ny) < 1.0f);
+            wy[u] = live ? 1.0f - fabsf(ny) : 0.0f;
+            const bool ld = live & (non > 0);
+            const unsigned off = (unsigned)((int)y * width) * 8u + coloff;
+            gv[u] = __builtin_amdgcn_raw_buffer_load_b64(grsrc, (int)(ld ? off : 0u), 0, 0);
+          }
+#pragma unroll
+          for (int u = 0; u < RC_UNROLL; u++) {
+            if (!(wy[u] > 0.0f)) continue;  // (uniform) a row outside the cell row's window adds nothing
+            float t = (-gv[u].y) * rpi;
+            t = (t < 0) ? t + 8.0f : t;
+            t = (t == 0.0f) ? 0.0f : t;  // -0 (theta = +0) is bin coordinate 0
+            const bool hit = __float_as_uint(t) < theta_end_bits;  // 0 <= t < end; NaN and negatives compare above
+            float fo = floorf(t);
+            float w1 = fo + 1.0f - t, w2 = t - fo;
+            if (fo >= 8.0f) { fo = 7.0f; w1 = 0.0f; w2 = 1.0f; }  // t == 8 with dynamic_indexing: all of it to bin 8 = bin 0
+            if (!hit) { fo = 0.0f; w1 = 0.0f; w2 = 0.0f; }        // t == 8 without it, a theta that is no number: dropped
+            const int f0 = min(max((int)fo, 0), 7), f1 = (f0 + 1) & 7;
+            const float mag = gv[u].x;
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+              if (s >= nslot) break;  // (uniform)
+              // a slot past the lane's own cells adds +0 to a cell of its own: no change (the sums are never -0)
+              const float wt = (s < non) ? (swx[s] * wy[u]) * mag : 0.0f;
+              float* const h0 = mine + (scol[s] + f0 * 64);
+              float* const h1 = mine + (scol[s] + f1 * 64);
+              const float a0 = *h0, a1 = *h1;
+              *h0 = fmaf(w1, wt, a0);
+              *h1 = fmaf(w2, wt, a1);
+            }
+          }
+        }
+      }
+      // the cell row's 32 sums over the lanes (THE ORDER above), and the histograms cleared for the next cell row
+      __builtin_amdgcn_wave_barrier();
+      const int r = lane & 31, hh = lane >> 5;
+      float part = 0.0f;
+#pragma unroll 8
+      for (int k = 0; k < 32; k++) part += hw[r * 64 + 32 * hh + ((k + r) & 31)];
+      const float tot = part + __shfl_down(part, 32);
+      __builtin_amdgcn_wave_barrier();
+      const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int k = 0; k < RC_WAVE / 256; k++) *reinterpret_cast<float4*>(hw + (k * 64 + lane) * 4) = z4;
+      const float fold = tot + __shfl_down(tot, 4);  // bin k + bin (k + 4) in the lanes of bins 0 .. 3
+      const int ix = r >> 3, bin = r & 7;
+      if (dp.half_sift) {
+        if (lane < 32 && bin < 4) dl[wv][(iy * 4 + ix) * 4 + bin] = fold;
+      } else if (lane < 32) {
+        dl[wv][(iy * 4 + ix) * 8 + bin] = tot;
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+    float* dout = desc_at(desc, obase + oidx, dim, dp.u8 != 0);
+    float* hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, obase + oidx, dim, dp.u8 != 0) : nullptr;
+    if (dp.half_sift) {
+      float2 v = make_float2(0, 0);
+      if (lane < 32) v = *reinterpret_cast<const float2*>(&dl[wv][lane * 2]);
+      finish_descriptor64<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
+    } else {
+      float4 v = make_float4(0, 0, 0, 0);
+      if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
+      finish_descriptor128<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
+    }
+  }
+}
+
 }  // namespace
 
 void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const RawKey* list,
@@ -1075,7 +1291,13 @@ void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, cons
   hipLaunchKernelGGL((descriptor_kernel<MIRROR, SEQ>), dim3(blocks, batch), dim3(256), lds_pad, st, g, dpx, list, cap_list, \
                      recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat)
   const bool mirror = dp.hkeys || dp.hdesc;
-  if (dp.pixel) {
+  if (dp.rect) {  // a caller's rectangles: one kernel whatever the pixel type and descriptor_order
+    dpx.xcd_block = 0;
+    if (mirror) hipLaunchKernelGGL((descriptor_rect_kernel<true>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list,
+                                   recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
+    else hipLaunchKernelGGL((descriptor_rect_kernel<false>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list,
+                            recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
+  } else if (dp.pixel) {
 #define HESS_PIXEL_LAUNCH(KERNEL, MIRROR)                                                                               \
   hipLaunchKernelGGL((KERNEL<MIRROR>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list, recs, fsrc, feat_total, \
                      feat_first, img_base, got, keys, desc, cap_feat)

@@ -22,6 +22,15 @@ _PIX_BY_DTYPE = {np.dtype(np.uint8): _abi.PIX_U8, np.dtype(np.uint16): _abi.PIX_
 _DESC_FORMATS = {"f32": _abi.DESC_FORMAT_F32, "u8": _abi.DESC_FORMAT_U8}
 
 
+def rect_keys(rects):
+    """(n, 4) array of x, y, width, height (top-left corner and size in image pixels) -> the KEYPOINT_DTYPE array that
+    set_keypoints / run_keypoints take with _abi.KEYS_RECTANGLES: the width travels in `s`, the height in `o`."""
+    r = np.asarray(rects, dtype=np.float32).reshape(-1, 4)
+    keys = np.zeros(len(r), dtype=_abi.KEYPOINT_DTYPE)
+    keys["x"], keys["y"], keys["s"], keys["o"] = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+    return keys
+
+
 def make_params(fn_default, **overrides):
     p = _abi.HessParams()
     fn_default(C.byref(p))
@@ -146,12 +155,16 @@ class Session:
         self._check(self._f["wait"](self._h))
 
     def set_keypoints(self, keys, have_orientation=True):
-        """SiftGPU::SetKeypointList: the next run() of ONE image uses these keypoints, no detection."""
+        """SiftGPU::SetKeypointList: the next run() of ONE image uses these keypoints, no detection.
+        have_orientation: False / _abi.KEYS_NONE (the orientation is computed), True / _abi.KEYS_ORIENTED (the keys' own),
+        or _abi.KEYS_RECTANGLES (-1): the keys are rectangles (rect_keys) and each gets a 4 x 4-cell gradient histogram over
+        its rectangle (include/hess_abi.h, HESS_KEYS_RECTANGLES); the keys come back as given."""
         k = np.ascontiguousarray(keys, dtype=_abi.KEYPOINT_DTYPE)
         self._check(self._f["set_keypoints"](self._h, k.ctypes.data_as(C.c_void_p), len(k), int(have_orientation)))
 
     def run_keypoints(self, keys, have_orientation=True):
-        """SiftGPU::RunSIFT(num, keys, flag): orientation/descriptors for `keys` on the current image."""
+        """SiftGPU::RunSIFT(num, keys, flag): orientation/descriptors for `keys` on the current image; have_orientation
+        as for set_keypoints, _abi.KEYS_RECTANGLES included."""
         k = np.ascontiguousarray(keys, dtype=_abi.KEYPOINT_DTYPE)
         self._check(self._f["run_keypoints"](self._h, k.ctypes.data_as(C.c_void_p), len(k), int(have_orientation)))
         return self.count(0)

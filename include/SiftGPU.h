@@ -7,8 +7,7 @@
 // extern "C" factories.  Everything behind it is new: the methods drive the C ABI of
 // include/hess_abi.h (hand-written HIP kernels for gfx950); there is no OpenGL, CUDA or DevIL.
 //
-// Not provided in this build: CreateRemoteSiftGPU (TCP server mode; returns NULL), SiftGPUEX (viewer),
-// the rectangle-descriptor hack of SetKeypointList (keys_have_orientation == -1).
+// Not provided in this build: CreateRemoteSiftGPU (TCP server mode; returns NULL), SiftGPUEX (viewer).
 #ifndef GPU_SIFT_H
 #define GPU_SIFT_H
 
@@ -94,6 +93,10 @@ class SiftGPU : public SiftParam {
   virtual int GetFeatureNum();
   virtual void SaveSIFT(const char* szFileName);
   virtual void GetFeatureVector(SiftKeypoint* keys, float* descriptors);
+  // keys_have_orientation, here and at RunSIFT(num, keys, flag): 0 the orientation is computed, non-zero it is the keys',
+  // and -1 the keys are rectangles -- (x, y) the top-left corner, s the width, o the height in image pixels -- each described
+  // by a 4 x 4-cell, 8-bin gradient histogram over it, from the level min(s, o) / 12 falls on; the keys come back as they
+  // were given (the rule: HESS_KEYS_RECTANGLES, hess_abi.h)
   virtual void SetKeypointList(int num, const SiftKeypoint* keys, int keys_have_orientation = 1);
   virtual int CreateContextGL();   // creates the HIP context; returns SIFTGPU_FULL_SUPPORTED or 0
   virtual int VerifyContextGL();

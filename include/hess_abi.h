@@ -92,7 +92,9 @@ enum { HESS_TRUNC_HIGHEST_0 = 0, HESS_TRUNC_HIGHEST_1 = 1, HESS_TRUNC_LOWEST = 2
  *                          Needs luminance in [0, 1] for its overflow bound, so two inputs keep the INTERLEAVED order --
  *                          permanently, not as a transition: float pixels (HESS_PIX_F32, taken as they are) and user
  *                          keypoint lists (hess_set_keypoints: any scale at any level).  All three orders have a bitwise
- *                          oracle restatement and stay in tools/fuzz_parity.py and the robustness matrix. */
+ *                          oracle restatement and stay in tools/fuzz_parity.py and the robustness matrix.
+ * Rectangles (HESS_KEYS_RECTANGLES at hess_set_keypoints) take none of the three: descriptor_rect_kernel has one order
+ * of its own -- per raster column, then a fixed order over the lanes -- stated at that enum and in the kernel's header. */
 enum { HESS_DESC_ORDER_INTERLEAVED = 0, HESS_DESC_ORDER_SEQUENTIAL = 1, HESS_DESC_ORDER_PIXEL = 2 };
 
 /* Pixel formats accepted by hess_run_* (the GL enums of SiftGPU::RunSIFT(w,h,data,fmt,type)
@@ -250,10 +252,48 @@ int hess_run_device(hess_ctx* ctx, const void* dev_pixels, int width, int height
  * and only comes back for the pixels if the image is run again without being handed over again. */
 int hess_last_input(hess_ctx* ctx, void* out, size_t bytes);
 
+/* What keys_have_orientation of hess_set_keypoints / hess_run_keypoints says about the caller's keys.  The reference
+ * tests the flag's truth for "oriented" and the value -1 for rectangles (SiftPyramid.cpp:349-354): any other non-zero
+ * value means ORIENTED here as well.
+ *   NONE        (x, y, s): the strongest orientation is found on the device
+ *   ORIENTED    (x, y, s, o): no orientation pass
+ *   RECTANGLES  (x, y) is the top-left corner of an axis-aligned rectangle, s its width and o its height, in image
+ *               pixels; the result is a 4 x 4-cell, 8-bin gradient histogram over the rectangle -- the reference's way of
+ *               describing regions with the SIFT machinery (SiftPyramid.cpp:345-354, PyramidCU.cpp:522, 591-666,
+ *               ProgramCU.cu:1806-1948, 2105-2143):
+ *               level     the binning of every caller key, applied to min(s, o) / 12.0f instead of s (the catch-all
+ *                         first and last levels as always; hess_debug_key_levels overrides as always);
+ *               record    corner as any key's position ((v - origin offset) / scale + 0.5 in 14.10 fixed point,
+ *                         masked); W = s / scale in 8.8 fixed point masked to 16 bits (256 level pixels wrap);
+ *                         H = o / scale as the binary32 quotient; response and type bits zero;
+ *               samples   from the level's (gradient, theta) plane: sptx = W/4, spty = H/4; cell (ix, iy), 0..3 each,
+ *                         has its centre c at (X + sptx (ix + 0.5), Y + spty (iy + 0.5)) and the pixel centres from
+ *                         floor(c - spt) + 0.5 to floor(c + spt) + 0.5 per axis, clipped to [1.5, width - 1.5] x
+ *                         [1.5, height - 1.5]; a sample counts where |nx| < 1 and |ny| < 1, nx = (x - cx)/sptx,
+ *                         ny = (y - cy)/spty, with weight (1 - |nx|)(1 - |ny|) gradient -- no Gaussian weight, no
+ *                         rotation, desc_window_factor unread (the reference passes it and never reads it);
+ *               bins      t = -theta 4/pi, + 8 where negative; the weight is split between bin floor(t) and the next
+ *                         by the fractional part, bin 8 is bin 0; t == 8.0 as a binary32 number is dropped, or goes to
+ *                         bin 8 with dynamic_indexing (the rule of hess_params.dynamic_indexing); half_sift folds bin
+ *                         k + 4 into bin k; components as in every descriptor: cell iy 4 + ix, then bin;
+ *               W quantised to 0 or H equal to 0: every test is false, the empty window;
+ *               normalisation and HESS_DESC_FORMAT_U8 as for every descriptor (the empty window: 1/sqrt(dim), or
+ *               zeros with normalize = 0);
+ *               returned: hess_count == num, the caller's keys byte for byte in input order (no orientation pass and no
+ *               download, whatever max_orientation and fixed_orientation say), descriptors in input order.
+ *               hess_params.descriptor_order selects nothing in this mode.  One kernel for every pixel type
+ *               (descriptor_rect_kernel, csrc/k_feature.hip, whose header states the binary32 expressions): a bin's sum
+ *               is formed per raster column first (columns xlo + 64 k + lane of the rectangle's box, band k after band
+ *               k - 1, rows downwards), then over the 64 lanes in a fixed order (two sequential 32-lane sums starting
+ *               at lane (8 ix + bin) mod 32 of each half, added) -- a function of the rectangle and the plane alone,
+ *               the same bits whatever the list's length or order. */
+enum { HESS_KEYS_NONE = 0, HESS_KEYS_ORIENTED = 1, HESS_KEYS_RECTANGLES = -1 };
+
 /* Replaces SiftGPU::SetKeypointList -> SiftPyramid::SetKeypointList (SiftPyramid.cpp:326-355): the
  * NEXT hess_run_* call (one image) skips detection and computes orientation (unless
  * keys_have_orientation) and descriptors for these keypoints (PyramidCU::GenerateFeatureListTex,
- * PyramidCU.cpp:555-718); results come back in input order; the list is cleared afterwards. */
+ * PyramidCU.cpp:555-718); results come back in input order; the list is cleared afterwards.
+ * keys_have_orientation: HESS_KEYS_NONE, HESS_KEYS_ORIENTED (any non-zero value but -1) or HESS_KEYS_RECTANGLES. */
 int hess_set_keypoints(hess_ctx* ctx, const hess_keypoint* keys, int num, int keys_have_orientation);
 /* Replaces SiftGPU::RunSIFT(num, keys, keys_have_orientation) (SiftGPU.cpp:307-315): the same on the
  * CURRENT image (first image of the last run) without rebuilding the pyramid. */
