@@ -264,7 +264,7 @@ void copier_main(hess_ctx* c) {
       size_t done_feats = 0;
       for (int k = 0; k < nparts; k++) {
         if (k > 0 && (e = hipEventSynchronize(k < nparts - 1 ? cp.ev_part[k] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
-        // features of the images so far -- or, of one image's list, the bound the part's launch formed (k_feature.hip, feature_part)
+        // features of the images so far -- or, of one image's list, the bound the part's launch formed (k_feature.hip, desc_image)
         const size_t upto = overflow ? 0 : (k == nparts - 1 ? total : parts.features ? (size_t)((long long)total * (k + 1) / nparts)
                                                                                    : (size_t)hs[parts.end[k]]);
         copy_part(done_feats, upto - done_feats);

@@ -289,23 +289,35 @@ void launch_topk(hipStream_t st, const Geom& g, int K, const RawKey* raw, const 
                  int* overflow);  // overflow[2]: raised when the look-back over the chunk words does not complete
 size_t topk_scratch_bytes(int cap_raw, int batch, int nlev);
 
+// The device buffers of the feature stages (orientation -> feature scan -> descriptors), filled once per batch by
+// enqueue_features and handed to the three launchers below.  Per image of the batch unless said otherwise:
+struct FeatureBuffers {
+  const RawKey* list;     // [cap_list] the keypoint list in (level, row, col) order (raw or top-K selected)
+  const int* list_total;  // its length
+  int cap_list;
+  FRec* recs;             // [cap_list] feature records: written by the orientation kernel (a caller's keys: uploaded)
+  int* ocount;            // [cap_list] orientations per keypoint
+  int* foffset;           // [cap_list] first feature of a keypoint (exclusive scan of ocount)
+  int* fsrc;              // [cap_feat] feature -> keypoint * 4 + orientation rank
+  int* feat_total;        // features kept, and the first of them in fsrc (LimitFeatureCount(1))
+  int* feat_first;
+  int* img_base;          // [batch + 1], one for the batch: packed output offset of every image, and the batch's total
+  HostKeypoint* keys;     // packed output, images back to back
+  float* desc;            // float [..][dim], with DescParams::u8 unsigned char [..][dim]; null: keypoint records only
+  int cap_feat;
+};
+
 // Orientation (ComputeOrientation_Kernel, ProgramCU.cu:1221-1605): one wavefront per keypoint.
-void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const RawKey* list,
-                        const int* list_total, int cap_list, const float* got, FRec* recs,
-                        int* ocount, int batch);
+void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const FeatureBuffers& fb, const float* got,
+                        int batch);
 // Exclusive scan of the per-keypoint orientation counts -> output offsets and feature totals
 // (ReshapeFeatureListCPU, PyramidCU.cpp:720-924; LimitFeatureCount(1)).
-void launch_feature_scan(hipStream_t st, const Geom& g, const LimitParams& lp, int multi, const RawKey* list,
-                         const int* list_total, int cap_list, const int* ocount, int* foffset, int* fsrc,
-                         int* feat_total, int* feat_first, int cap_feat, int* overflow, int* img_base, int* host_small,
-                         int batch);
+void launch_feature_scan(hipStream_t st, const Geom& g, const LimitParams& lp, int multi, const FeatureBuffers& fb,
+                         int* overflow, int* host_small, int batch);
 // Descriptor + normalisation + host keypoint record (ComputeDescriptor_Kernel /
 // NormalizeDescriptor_Kernel, ProgramCU.cu:1650-2054; keypoint unpack PyramidCU.cpp:866-906).
-// desc: float [..][dim], or with dp.u8 unsigned char [..][dim] behind the same pointer.
-void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, const RawKey* list,
-                       int cap_list, const FRec* recs, const int* fsrc, const int* feat_total,
-                       const int* feat_first, const int* img_base, const float* got, HostKeypoint* keys,
-                       float* desc, int cap_feat, int batch, int seen_features = 0);
+void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, const FeatureBuffers& fb, const float* got,
+                       int batch, int seen_features = 0);
 // Exclusive prefix of the per-image feature totals: img_base[0..batch] (packed output layout).
 // Device evaluation of the elementary functions for the parity tests.
 void launch_math_probe(hipStream_t st, int which, const float* a, const float* b, float* out, int n);

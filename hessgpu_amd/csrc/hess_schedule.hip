@@ -1,5 +1,6 @@
 // hess_schedule.hip -- the launch order of one batch on the context's stream (see hess_ctx.h).
 #include "hess_ctx.h"
+#include "hess_devmath.h"  // float_to_fixed
 
 namespace hess {
 
@@ -435,18 +436,19 @@ static int enqueue_detection(hess_ctx* c, int batch, const LimitParams& lp) {
 static int enqueue_features(hess_ctx* c, const LimitParams& lp, int batch, int pixtype, int desc_format, bool user, bool orient) {
   const Geom& g = c->g;
   hipStream_t st = c->st;
-  const RawKey* list = c->d_list;
-  const int* list_total = c->d_list_total;
-  const int cap_list = c->cap_list;
+  FeatureBuffers fb;
+  fb.list = c->d_list; fb.list_total = c->d_list_total; fb.cap_list = c->cap_list;
+  fb.recs = (FRec*)c->recs.p; fb.ocount = (int*)c->ocount.p;
+  fb.foffset = (int*)c->foffset.p; fb.fsrc = (int*)c->fsrc.p;
+  fb.feat_total = (int*)c->feat_total.p; fb.feat_first = (int*)c->feat_first.p; fb.img_base = (int*)c->img_base.p;
+  fb.keys = (HostKeypoint*)c->keys.p; fb.desc = c->dim ? (float*)c->desc.p : nullptr; fb.cap_feat = c->cap_feat;
   const float* got = (const float*)c->got.p;
   if (orient) {
     ProfScope ps(c, HESS_K_ORIENT, 0.0);
-    launch_orientation(st, g, orient_params(c, user), list, list_total, cap_list, got, (FRec*)c->recs.p, (int*)c->ocount.p, batch);
+    launch_orientation(st, g, orient_params(c, user), fb, got, batch);
   }
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[5], st));
-  launch_feature_scan(st, g, lp, (c->multi && !user) ? 1 : 0, list, list_total, cap_list, (const int*)c->ocount.p,
-                      (int*)c->foffset.p, (int*)c->fsrc.p, (int*)c->feat_total.p, (int*)c->feat_first.p, c->cap_feat,
-                      (int*)c->overflow.p, (int*)c->img_base.p, (int*)c->h_small.p, batch);
+  launch_feature_scan(st, g, lp, (c->multi && !user) ? 1 : 0, fb, (int*)c->overflow.p, (int*)c->h_small.p, batch);
   if (c->stage_events) HIP_TRY(c, hipEventRecord(c->ev[6], st));
   DescParams dsp = desc_params(c, pixtype, desc_format, user);
   if (user) c->parts = Parts{};  // one launch
@@ -458,10 +460,7 @@ static int enqueue_features(hess_ctx* c, const LimitParams& lp, int batch, int p
     dsp.first_image = first;
     dsp.part = parts.features ? k : 0;
     dsp.part_den = parts.features ? parts.n : 1;
-    launch_descriptor(st, g, dsp, list, cap_list, (const FRec*)c->recs.p, (const int*)c->fsrc.p,
-                      (const int*)c->feat_total.p, (const int*)c->feat_first.p, (const int*)c->img_base.p, got,
-                      (HostKeypoint*)c->keys.p, c->dim ? (float*)c->desc.p : nullptr, c->cap_feat,
-                      user ? 1 : parts.end[k] - first, user ? 0 : c->seen_features);
+    launch_descriptor(st, g, dsp, fb, got, user ? 1 : parts.end[k] - first, user ? 0 : c->seen_features);
     if (k < parts.n - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
     if (!parts.features) first = parts.end[k];
   }
@@ -485,11 +484,6 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   lp.threshold = c->p.feature_count_threshold;
   if (int rc = enqueue_detection(c, r.batch, lp)) return rc;
   return enqueue_features(c, lp, r.batch, r.pixtype, r.desc_format, false, true);
-}
-
-// FLOAT_TO_FIXED_POINT (config.h:73-74), host version.
-static inline int float_to_fixed_host(float v, int n) {
-  return (int)((double)(v * (float)(1 << n)) + ((v >= 0.0) ? 0.5 : -0.5));
 }
 
 // User-supplied keypoints (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718): bin the keys to
@@ -533,9 +527,9 @@ int enqueue_user(hess_ctx* c, int desc_format) {
           const float fScale = key.s / octave_sigma;
           const float fOrientation = rect ? key.o / octave_sigma : (float)fmod(twopi - key.o, twopi);
           FRec r;
-          r.x = (uint32_t)float_to_fixed_host(fX, 10) & 0x00FFFFFFu;
-          r.y = (uint32_t)float_to_fixed_host(fY, 10) & 0x00FFFFFFu;
-          r.z = (uint32_t)float_to_fixed_host(fScale, 8) & 0x0000FFFFu;
+          r.x = (uint32_t)float_to_fixed(fX, 10) & 0x00FFFFFFu;
+          r.y = (uint32_t)float_to_fixed(fY, 10) & 0x00FFFFFFu;
+          r.z = (uint32_t)float_to_fixed(fScale, 8) & 0x0000FFFFu;
           memcpy(&r.w, &fOrientation, 4);
           RawKey rk;
           memset(&rk, 0, sizeof(rk));

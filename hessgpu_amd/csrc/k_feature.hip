@@ -17,6 +17,16 @@
 //                box per iteration (the reference's scan order); lane (cell, q) owns bins q, q+4 (q = 0 also 8)
 //                of its cell and adds the iteration's samples to them through a per-wavefront LDS coefficient
 //                table (see descriptor_kernel).
+// The three descriptor kernels -- descriptor_kernel (cells), descriptor_pixel[_u8]_kernel (one raster, k_feature_pixel.h) and
+// descriptor_rect_kernel (a caller's rectangles) -- differ in how they sample.  What is not sampling they share, once:
+//   desc_image        the workgroup's image and the range of its features that the launch covers (delivery in parts);
+//   keypoint_records  the host keypoint records of that range;
+//   first_feature     the order in which wavefronts take features (largest first, blocks of the list per XCD);
+//   load_feature      a feature's record, output place and gradient plane (plane_resource: as a buffer resource);
+//   oriented_frame    keypoint, cell pitch and rotation of an oriented feature (record_pos / _scale / _angle unpack);
+//   theta_end         the bound of the bin coordinate (-di);
+//   finish_descriptor normalisation and store of the staged values (finish_values: for the values in registers).
+// launch_descriptor picks one of the ten instantiations from a table; they have one parameter list.
 // Built without the SLP vectoriser (hessgpu_amd/build.py): packed FP32 issues at half rate on gfx950.
 #include <algorithm>
 #include <cstdlib>
@@ -35,10 +45,6 @@ __device__ __forceinline__ float rl(float v, int lane) {
   return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), lane));
 }
 __device__ __forceinline__ int rli(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-__device__ __forceinline__ int float_to_fixed(float v, int n) {  // FLOAT_TO_FIXED_POINT, config.h:73-74
-  return (int)((double)(v * (float)(1 << n)) + ((v >= 0.0) ? 0.5 : -0.5));
-}
 
 __device__ __forceinline__ void level_of(const Geom& g, int li, int* o, int* l) {
   *o = li / g.dog;
@@ -506,12 +512,6 @@ __global__ __launch_bounds__(256) void orientation_kernel(Geom g, OrientParams o
 constexpr int DC_BINS = 12;
 constexpr int DC_BIN_PITCH = 80;
 constexpr int DC_ROWS = DC_BINS * DC_BIN_PITCH;
-// Dynamic LDS requested at launch on top of the static 17 KB.  Rounds 1-2 padded a workgroup to 36 KB so that at most
-// four fit a CU (the kernel then measured 5-30 % slower at 5-8 wavefronts per SIMD).  With the all-miss skip and the
-// features taken largest first that no longer holds: without padding (five workgroups per CU, the register limit)
-// the launch takes 0.372 ms per 8 images against 0.405 ms with it, same box (profiles/r03_desc_pad.txt), and the
-// unpadded workgroups leave LDS to the kernels of the other contexts.
-constexpr int DC_LDS_PAD_BYTES = 0;
 
 typedef const __attribute__((address_space(1))) char* GlobalBytes;  // byte pointer into global memory (HBM)
 typedef float dfloat2 __attribute__((ext_vector_type(2)));
@@ -536,24 +536,140 @@ __device__ __forceinline__ void quad_fma(float& acc, float coef, float w) {
   acc = fmaf(coef, wb, acc);
 }
 
+// ---- shared by the descriptor kernels (descriptor_kernel, descriptor_pixel[_u8]_kernel, descriptor_rect_kernel) ----
+// What a kernel does once per workgroup or once per feature: which features it takes and in what order, the feature's
+// record and gradient plane, the oriented frame, and the normalisation and store of the finished descriptor.  The sample
+// loops between are each kernel's own.
+
+constexpr float rpi = (float)(4.0 / kPI);  // orientation bins per radian
+
+// Position (14.10 fixed point in the low 24 bits of FRec::x, y) and scale (8.8 in the low 16 bits of z) of a feature
+// record (ProgramCU.cu:1246-1278).
+__device__ __forceinline__ float record_pos(uint32_t xy) { return (float)(xy & 0x00FFFFFFu) / 1024.0f; }
+__device__ __forceinline__ float record_scale(uint32_t z) { return (float)(z & 0x0000FFFFu) / 256.0f; }
 // Angle k of a multi-orientation record (PyramidCU.cpp:763-767): four 8-bit angles (multi = 1), or two 16-bit angles of the
 // difference-of-Gaussians build (multi = 2).
 __device__ __forceinline__ float multi_angle(int multi, uint32_t w, int k) {
   return multi == 2 ? (float)((2.0 * kPI / 65535.0) * (double)((w >> (16 * k)) & 0xFFFFu))
                     : (float)((2.0 * kPI / 255.0) * (double)((w >> (8 * k)) & 0xFFu));
 }
-
-// A launch that does only a part of one image's features (a single large image delivered in parts: the copier's DMA copy
-// of part k crosses the host link while part k + 1 is computed): the image's list narrowed to features
-// [n part / den, n (part + 1) / den) -- in list order, which is the order of the packed output, so a part is one contiguous
-// range of keypoint records and descriptors (the copier thread forms the same bounds from the count it reads).
-__device__ __forceinline__ void feature_part(const DescParams& dp, int* ftotal, int* ffirst, long long* obase) {
-  if (dp.part_den > 1) {
-    const int n = *ftotal;
-    const int lo = (int)((long long)n * dp.part / dp.part_den), hi = (int)((long long)n * (dp.part + 1) / dp.part_den);
-    *ffirst += lo; *obase += lo; *ftotal = hi - lo;
-  }
+// The un-mirrored orientation handed to the kernels (PyramidCU.cpp:764,791; A.1 of SURVEY): of rank k, or the record's one
+// float angle.
+__device__ __forceinline__ float record_angle(const DescParams& dp, uint32_t w, int k) {
+  return dp.multi ? multi_angle(dp.multi, w, k) : __uint_as_float(w);
 }
+
+// The workgroup's image and the features of it that the launch covers: features ffirst .. ffirst + ftotal of the image's
+// table, feature m's results at obase + (m - ffirst) of the packed output (images of the batch back to back).
+struct DescImage {
+  int b, ftotal, ffirst;
+  long long obase;
+};
+__device__ __forceinline__ DescImage desc_image(const DescParams& dp, const int* feat_total, const int* feat_first,
+                                                const int* img_base) {
+  DescImage im;
+  im.b = blockIdx.y + dp.first_image;  // (a batch's descriptors may be launched in several parts, see enqueue_features())
+  im.ftotal = feat_total[im.b];
+  im.ffirst = feat_first[im.b];
+  im.obase = img_base[im.b];
+  // A launch that does only a part of one image's features (a single large image delivered in parts: the copier's DMA copy
+  // of part k crosses the host link while part k + 1 is computed): the image's list narrowed to features
+  // [n part / den, n (part + 1) / den) -- in list order, which is the order of the packed output, so a part is one contiguous
+  // range of keypoint records and descriptors (the copier thread forms the same bounds from the count it reads).
+  if (dp.part_den > 1) {
+    const int n = im.ftotal;
+    const int lo = (int)((long long)n * dp.part / dp.part_den), hi = (int)((long long)n * (dp.part + 1) / dp.part_den);
+    im.ffirst += lo; im.obase += lo; im.ftotal = hi - lo;
+  }
+  return im;
+}
+
+// Work order.  Wavefront wv of the workgroup takes places mw = first_feature(dp, wv), + 4 gridDim.x, ... below ftotal, and
+// place mw is feature m = ffirst + ftotal - 1 - mw: the list is taken from its END backwards.  It is ordered by (octave,
+// level), most features belong to octave 0, and within an octave the footprint grows with the level, so the launch's last
+// wavefronts -- its tail -- get the smallest features (octave 0, level 1) instead of a mixture.
+// With dp.xcd_block (64; 0: the plain order, when the grid does not divide or the features are a caller's few
+// rectangles, see launch_descriptor) the places go out in blocks of that many consecutive ones per XCD: workgroups are dealt
+// round-robin over the eight XCDs, each with its own L2, while features that are neighbours in the list are neighbours in
+// the image (raster order within a level) and read overlapping footprints -- so a block of the list goes to the
+// workgroups of ONE XCD instead of being spread over all eight L2s.
+__device__ __forceinline__ int first_feature(const DescParams& dp, int wv) {
+  int mw0 = blockIdx.x * 4 + wv;
+  if (dp.xcd_block) {
+    const int xcd = blockIdx.x & 7, wx = (int)(blockIdx.x >> 3) * 4 + wv;  // wavefront index inside the XCD
+    mw0 = ((wx / dp.xcd_block) * 8 + xcd) * dp.xcd_block + wx % dp.xcd_block;
+  }
+  return mw0;
+}
+
+// The (gradient, theta) plane of level l of octave o, image b, as a buffer resource.  The feature, and with it the plane,
+// is the same in all lanes: the plane's address is kept in scalar registers and a gather is `resource + 32-bit byte
+// offset` -- no 64-bit address arithmetic per sample, and an offset outside the plane reads 0 instead of faulting.  (A
+// generic pointer here made the compiler emit flat_load, which also counts as an LDS operation: every wait for LDS then
+// waited for the gathers too.)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_resource(const Geom& g, const OctGeom& og, const float* got, int l, int b) {
+  const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
+                                                      ((long long)(l - 1) * g.B + b) * og.plane);
+  const GlobalBytes gp = (GlobalBytes)(
+      ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
+      (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8),
+                                           0x00020000 /* raw 32-bit data, gfx9 family */);
+}
+
+// Feature m of the image's table: its record, its place in the packed output and the plane it samples.
+struct Feature {
+  FRec rec;
+  int k;               // orientation rank inside the record
+  int oidx;            // m - ffirst
+  int width, height;   // of the plane
+  __amdgpu_buffer_rsrc_t grsrc;
+};
+__device__ __forceinline__ Feature load_feature(const Geom& g, const DescImage& im, int m, const RawKey* list, int cap_list,
+                                                const FRec* recs, const int* fsrc, int cap_feat, const float* got) {
+  Feature f;
+  const int src = fsrc[(long long)im.b * cap_feat + m];
+  const int i = src >> 2;
+  f.k = src & 3;
+  f.oidx = m - im.ffirst;
+  f.rec = recs[(long long)im.b * cap_list + i];
+  const int li = list[(long long)im.b * cap_list + i].level_index;
+  int o, l;
+  level_of(g, li, &o, &l);
+  const OctGeom& og = g.o[o];
+  f.grsrc = plane_resource(g, og, got, l, im.b);
+  f.width = og.wa;
+  f.height = og.h;
+  return f;
+}
+
+// The keypoint frame of an oriented feature (ProgramCU.cu:1692-1702): cell pitch spt in pixels, rotation by the angle.
+struct OrientedFrame {
+  float kx, ky;        // the keypoint, in pixels of the plane
+  float spt, anglef;
+  float cspt, sspt;    // keypoint frame -> pixels
+  float crspt, srspt;  // pixels -> keypoint frame
+  float bsz;           // half extent of a cell's bounding box
+};
+__device__ __forceinline__ OrientedFrame oriented_frame(const DescParams& dp, const Feature& f) {
+  OrientedFrame fr;
+  fr.kx = record_pos(f.rec.x);
+  fr.ky = record_pos(f.rec.y);
+  const float kw = record_angle(dp, f.rec.w, f.k);
+  fr.spt = fabsf(record_scale(f.rec.z) * dp.window_factor);
+  float s, c;
+  dm_sincosf(kw, &s, &c);  // __sincosf, ProgramCU.cu:1698
+  fr.anglef = (kw > kPI) ? (float)(kw - (2.0 * kPI)) : kw;
+  fr.cspt = c * fr.spt; fr.sspt = s * fr.spt;
+  fr.crspt = c / fr.spt; fr.srspt = s / fr.spt;
+  fr.bsz = fabsf(fr.cspt) + fabsf(fr.sspt);
+  return fr;
+}
+
+// A bin coordinate theta counts while 0 <= theta < 8.0f, with dynamic_indexing (-di) while theta <= 8.0f: as ONE unsigned
+// compare of the bit patterns against this bound (negative values and NaNs have larger patterns than any non-negative
+// bound).
+__device__ __forceinline__ uint32_t theta_end(const DescParams& dp) { return dp.dynamic_indexing ? 0x41000001u : 0x41000000u; }
 
 // Host keypoint records (PyramidCU.cpp:866-906 / :1097-1137, host arithmetic) of one image, by the whole workgroup: one
 // thread per feature, 256 per pass, staged in LDS (`kst`: 256 x 24 bytes, not otherwise in use yet) and stored as
@@ -561,22 +677,18 @@ __device__ __forceinline__ void feature_part(const DescParams& dp, int* ftotal, 
 // mirror as as many small PCIe writes and cost the kernel as much as the 512-byte descriptors did.
 // (by the launch's LAST workgroups: the first ones hold the largest features and are the launch's critical path)
 template <bool HOST_MIRROR>
-__device__ __forceinline__ void keypoint_records(const DescParams& dp, uint32_t* const kst, const RawKey* list, int cap_list,
-                                                 const FRec* recs, const int* fsrc, int cap_feat, int b, int ftotal, int ffirst,
-                                                 long long obase, HostKeypoint* keys) {
-  for (int f0 = (gridDim.x - 1 - blockIdx.x) * 256; f0 < ftotal; f0 += gridDim.x * 256) {  // (uniform over the workgroup)
-    const int nrec = min(256, ftotal - f0);
+__device__ __forceinline__ void keypoint_records(const DescParams& dp, uint32_t* const kst, const DescImage& im, const RawKey* list,
+                                                 int cap_list, const FRec* recs, const int* fsrc, int cap_feat, HostKeypoint* keys) {
+  for (int f0 = (gridDim.x - 1 - blockIdx.x) * 256; f0 < im.ftotal; f0 += gridDim.x * 256) {  // (uniform over the workgroup)
+    const int nrec = min(256, im.ftotal - f0);
     if ((int)threadIdx.x < nrec) {
-      const int m = ffirst + f0 + threadIdx.x;
-      const int src = fsrc[(long long)b * cap_feat + m];
+      const int m = im.ffirst + f0 + threadIdx.x;
+      const int src = fsrc[(long long)im.b * cap_feat + m];
       const int i = src >> 2, k = src & 3;
-      const FRec rec = recs[(long long)b * cap_list + i];
-      const int li = list[(long long)b * cap_list + i].level_index;
-      const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
-                                : __uint_as_float(rec.w);
-      const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
-      const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
-      const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
+      const FRec rec = recs[(long long)im.b * cap_list + i];
+      const int li = list[(long long)im.b * cap_list + i].level_index;
+      const float kw = record_angle(dp, rec.w, k);
+      const float kx = record_pos(rec.x), ky = record_pos(rec.y), kz = record_scale(rec.z);
       const float oss = dp.octave_sigma * (float)(1 << (li / dp.dog));
       const float offset = dp.lowe_origin ? 0.0f : 0.5f;
       HostKeypoint hk;
@@ -591,8 +703,8 @@ __device__ __forceinline__ void keypoint_records(const DescParams& dp, uint32_t*
     }
     __syncthreads();
     const uint2* const k2 = reinterpret_cast<const uint2*>(kst);
-    uint2* const out = reinterpret_cast<uint2*>(keys + obase + f0);
-    uint2* const hout = (HOST_MIRROR && dp.hkeys) ? reinterpret_cast<uint2*>(dp.hkeys + obase + f0) : nullptr;
+    uint2* const out = reinterpret_cast<uint2*>(keys + im.obase + f0);
+    uint2* const hout = (HOST_MIRROR && dp.hkeys) ? reinterpret_cast<uint2*>(dp.hkeys + im.obase + f0) : nullptr;
     for (int j = threadIdx.x; j < 3 * nrec; j += 256) {
       const uint2 v = k2[j];
       out[j] = v;
@@ -616,64 +728,71 @@ __device__ __forceinline__ float* desc_at(void* base, long long o, int dim, bool
   return u8 ? reinterpret_cast<float*>(static_cast<char*>(base) + o * dim) : static_cast<float*>(base) + o * dim;
 }
 
-// Normalisation with the reference's 32-lane tree (NormalizeDescriptor_Kernel + ND_WarpReduction, ProgramCU.cu:1950-2054)
-// and the 512-byte (256-byte) coalesced store of one descriptor; lanes 0..31 hold four (two) consecutive values each.
-// u8 (HESS_DESC_FORMAT_U8; uniform over the launch -- dp.u8 in descriptor_kernel, a template parameter of
-// descriptor_pixel_kernel): the same values after the same normalisation go out as bytes, desc_pack4 / desc_byte of
-// hess_dev.h -- 128 (64) contiguous bytes per feature; dout / hout then address the feature's bytes (desc_at).
-template <bool HOST_MIRROR>
-__device__ __forceinline__ void finish_descriptor128(const DescParams& dp, bool u8, int lane, float4 v, float* dout, float* hout) {
+// The end of a feature.  Lanes 0..31 hold N = four (-half: two) consecutive values of the descriptor each: normalisation with
+// the reference's 32-lane tree (NormalizeDescriptor_Kernel + ND_WarpReduction, ProgramCU.cu:1950-2054) and the 512-byte
+// (256-byte) coalesced store at dout and, mirrored, at hout.
+// u8 (HESS_DESC_FORMAT_U8; uniform over the launch -- dp.u8, or a template parameter of descriptor_pixel_kernel): the same
+// values after the same normalisation go out as bytes, desc_pack4 / desc_byte of hess_dev.h -- 128 (64) contiguous bytes
+// per feature; dout / hout then address the feature's bytes (desc_at).
+// (One template over N for what were two functions.  The values are a vector type on purpose: written over float2 / float4
+// members the kernels without a host mirror need one scalar register less, but the byte form of descriptor_pixel_kernel
+// a 72nd vector register, profiles/r14_desc_helpers.txt.)
+template <int N>
+using DescValues = float __attribute__((ext_vector_type(N)));
+template <bool HOST_MIRROR, int N>
+__device__ __forceinline__ void finish_values(const DescParams& dp, bool u8, int lane, DescValues<N> v, float* dout, float* hout) {
   if (dp.normalize) {
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
-      float part = fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.y, v.y, v.x * v.x)));
+      float part = v[0] * v[0];
+#pragma unroll
+      for (int i = 1; i < N; i++) part = fmaf(v[i], v[i], part);
 #pragma unroll
       for (int d = 16; d >= 1; d >>= 1) part += __shfl_down(part, d);
       const float nrm = 1.0f / sqrtf(rl(part, 0));
-      if (pass == 0) {
-        v.x = fminf(0.2f, v.x * nrm); v.y = fminf(0.2f, v.y * nrm);
-        v.z = fminf(0.2f, v.z * nrm); v.w = fminf(0.2f, v.w * nrm);
-      } else { v.x *= nrm; v.y *= nrm; v.z *= nrm; v.w *= nrm; }
-    }
-  }
-  if (u8) {  // one dword per lane: bytes 4 lane .. 4 lane + 3
-    const uint32_t q = desc_pack4(v.x, v.y, v.z, v.w);
-    const int at = 4 * unhoisted(lane);
-    if (lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + at) = q;
-    if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + at) = q;
-    return;
-  }
-  if (lane < 32) *reinterpret_cast<float4*>(dout + lane * 4) = v;
-  // (streaming stores for the mirror were measured: 0.341 - 0.346 against 0.333 - 0.339 ms per single image, same call)
-  if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<float4*>(hout + lane * 4) = v;
-}
-template <bool HOST_MIRROR>
-__device__ __forceinline__ void finish_descriptor64(const DescParams& dp, bool u8, int lane, float2 v, float* dout, float* hout) {
-  if (dp.normalize) {
 #pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-      float part = fmaf(v.y, v.y, v.x * v.x);
-#pragma unroll
-      for (int d = 16; d >= 1; d >>= 1) part += __shfl_down(part, d);
-      const float nrm = 1.0f / sqrtf(rl(part, 0));
-      if (pass == 0) { v.x = fminf(0.2f, v.x * nrm); v.y = fminf(0.2f, v.y * nrm); }
-      else { v.x *= nrm; v.y *= nrm; }
+      for (int i = 0; i < N; i++) v[i] = (pass == 0) ? fminf(0.2f, v[i] * nrm) : v[i] * nrm;
     }
   }
   if (u8) {
-    // a lane's two bytes, and those of its odd neighbour by a DPP quad permute (lanes [1,1,3,3] of the quad: no LDS, and
-    // executed by all lanes): the 16 even lanes below 32 store one dword each, bytes 2 lane .. 2 lane + 3
-    const uint32_t h = desc_byte(v.x) | (desc_byte(v.y) << 8);
-    const uint32_t nb = (uint32_t)__builtin_amdgcn_mov_dpp((int)h, 0xF5 /* quad_perm:[1,1,3,3] */, 0xF, 0xF, true);
-    const uint32_t q = h | (nb << 16);
-    const int l = unhoisted(lane);
-    const bool mine = l < 32 && !(l & 1);
-    if (mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + 2 * l) = q;
-    if (HOST_MIRROR && hout && mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + 2 * l) = q;
+    if constexpr (N == 4) {  // one dword per lane: bytes 4 lane .. 4 lane + 3
+      const uint32_t q = desc_pack4(v[0], v[1], v[2], v[3]);
+      const int at = 4 * unhoisted(lane);
+      if (lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + at) = q;
+      if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + at) = q;
+    } else {
+      // a lane's two bytes, and those of its odd neighbour by a DPP quad permute (lanes [1,1,3,3] of the quad: no LDS, and
+      // executed by all lanes): the 16 even lanes below 32 store one dword each, bytes 2 lane .. 2 lane + 3
+      const uint32_t h = desc_byte(v[0]) | (desc_byte(v[1]) << 8);
+      const uint32_t nb = (uint32_t)__builtin_amdgcn_mov_dpp((int)h, 0xF5 /* quad_perm:[1,1,3,3] */, 0xF, 0xF, true);
+      const uint32_t q = h | (nb << 16);
+      const int l = unhoisted(lane);
+      const bool mine = l < 32 && !(l & 1);
+      if (mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dout) + 2 * l) = q;
+      if (HOST_MIRROR && hout && mine) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hout) + 2 * l) = q;
+    }
     return;
   }
-  if (lane < 32) *reinterpret_cast<float2*>(dout + lane * 2) = v;
-  if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<float2*>(hout + lane * 2) = v;
+  if (lane < 32) *reinterpret_cast<DescValues<N>*>(dout + lane * N) = v;
+  // (streaming stores for the mirror were measured: 0.341 - 0.346 against 0.333 - 0.339 ms per single image, same call)
+  if (HOST_MIRROR && hout && lane < 32) *reinterpret_cast<DescValues<N>*>(hout + lane * N) = v;
+}
+// The lane's N values of a descriptor staged in the wavefront's own LDS in descriptor order.
+template <int N>
+__device__ __forceinline__ DescValues<N> staged_values(const float* staged, int lane) {
+  DescValues<N> v = 0.0f;
+  if (lane < 32) v = *reinterpret_cast<const DescValues<N>*>(staged + lane * N);
+  return v;
+}
+// ... from the 128 staged values (-half: the 64 folded ones) to feature `o` of the packed output.
+template <bool HOST_MIRROR>
+__device__ __forceinline__ void finish_descriptor(const DescParams& dp, bool u8, int lane, const float* staged, void* desc,
+                                                  long long o) {
+  const int dim = dp.half_sift ? 64 : 128;
+  float* const dout = desc_at(desc, o, dim, u8);
+  float* const hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, o, dim, u8) : nullptr;
+  if (dp.half_sift) finish_values<HOST_MIRROR, 2>(dp, u8, lane, staged_values<2>(staged, lane), dout, hout);
+  else finish_values<HOST_MIRROR, 4>(dp, u8, lane, staged_values<4>(staged, lane), dout, hout);
 }
 
 // One wavefront per feature.  Lane = cell*4 + sub.
@@ -690,8 +809,10 @@ __device__ __forceinline__ void finish_descriptor64(const DescParams& dp, bool u
 //          for the two bins that are touched and `+= 0 * weight` (no change: weights and sums are finite and
 //          non-negative) for the others.  Per bin the additions therefore happen in the reference's order.
 // No sample lists, no compaction: per iteration a lane does two 2-dword LDS stores (set, clear) and three 16-byte loads.
-// Occupancy: five workgroups (= five wavefronts per SIMD) per CU by the register count (see DC_LDS_PAD_BYTES for the
-// history: rounds 1-2 held it at four through the LDS footprint).
+// Occupancy: five workgroups (= five wavefronts per SIMD) per CU by the register count (rounds 1-2 held it at four through
+// the LDS footprint, see launch_descriptor).
+// Which features the workgroup takes, the feature's record, plane and frame, and its end are the shared helpers above
+// (desc_image .. finish_descriptor); the kernel's own part is the scan and the ordered accumulation.
 // HOST_MIRROR: the packed results are also stored into their pinned host mirrors (dp.hkeys / dp.hdesc); a template
 // parameter so that the two forms carry different names in profiles (alone on the device the mirroring form waits
 // for PCIe).
@@ -705,85 +826,33 @@ __global__ __launch_bounds__(256) void descriptor_kernel(Geom g, DescParams dp, 
   __shared__ __attribute__((aligned(16))) float dl[4][128];
   __shared__ __attribute__((aligned(16))) float crow[4][DC_ROWS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.y + dp.first_image;  // (a batch's descriptors may be launched in two halves, see enqueue())
-  int ftotal = feat_total[b], ffirst = feat_first[b];
-  long long obase = img_base[b];  // packed output: images of the batch back to back
-  feature_part(dp, &ftotal, &ffirst, &obase);
-  const int nwaves = gridDim.x * 4;
-  const float rpi = (float)(4.0 / kPI);
-  const int dim = dp.half_sift ? 64 : 128;
+  const DescImage im = desc_image(dp, feat_total, feat_first, img_base);
   const int mycell = lane >> 2, sub = lane & 3;
   float* const rows = &crow[wv][0];
 
   static_assert(sizeof(HostKeypoint) == 24 && 4 * DC_ROWS * 4 >= 256 * 24, "record staging fits the table");
-  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&crow[0][0]), list, cap_list, recs, fsrc, cap_feat, b, ftotal, ffirst, obase, keys);
+  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&crow[0][0]), im, list, cap_list, recs, fsrc, cap_feat, keys);
   if (!desc) return;
   for (int i = lane; i < DC_ROWS; i += 64) rows[i] = 0.0f;
   float* const mycol = rows + mycell * 4 + sub;  // + DC_BIN_PITCH*bin: the column this lane fills (cell, slot `sub`)
   const float* const rdbin = rows + sub * DC_BIN_PITCH + mycell * 4;  // + 4*DC_BIN_PITCH*k: bins sub, sub+4, sub+8
-  const uint32_t theta_end_bits = dp.dynamic_indexing ? 0x41000001u : 0x41000000u;  // 8.0f, or the next float (admits theta == 8)
+  const uint32_t theta_end_bits = theta_end(dp);
 
-  // Features are taken from the END of the list backwards: the list is ordered by (octave, level), most features
-  // belong to octave 0, and within an octave the footprint grows with the level, so the launch's last wavefronts --
-  // its tail -- get the smallest features (octave 0, level 1) instead of a mixture.
-  // ... and in blocks of 64 consecutive features per XCD: workgroups are dealt round-robin over the eight XCDs, each with
-  // its own L2, while features that are neighbours in the list are neighbours in the image (raster order within a
-  // level) and read overlapping footprints -- so a block of the list goes to the workgroups of ONE XCD instead of
-  // being spread over all eight L2s (dp.xcd_block: 64, or 0 for the plain order when the grid does not divide).
-  int mw0 = blockIdx.x * 4 + wv;
-  if (dp.xcd_block) {
-    const int xcd = blockIdx.x & 7, wx = (int)(blockIdx.x >> 3) * 4 + wv;  // wavefront index inside the XCD
-    mw0 = ((wx / dp.xcd_block) * 8 + xcd) * dp.xcd_block + wx % dp.xcd_block;
-  }
-  for (int mw = mw0; mw < ftotal; mw += nwaves) {
-    const int m = ffirst + ftotal - 1 - mw;
-    const int src = fsrc[(long long)b * cap_feat + m];
-    const int i = src >> 2, k = src & 3;
-    const int oidx = m - ffirst;
-    const FRec rec = recs[(long long)b * cap_list + i];
-    const int li = list[(long long)b * cap_list + i].level_index;
-    int o, l;
-    level_of(g, li, &o, &l);
-    const OctGeom& og = g.o[o];
-    // the feature, and with it the gradient plane, is the same in all lanes: keep the plane's address in scalar
-    // registers so that a gather is `scalar base + 32-bit lane offset`
-    const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
-                                                        ((long long)(l - 1) * g.B + b) * og.plane);
-    // and gather through a buffer resource over the plane: `resource + 32-bit byte offset`, no 64-bit address
-    // arithmetic per sample, and an offset outside the plane reads 0 instead of faulting.  (A generic pointer here
-    // made the compiler emit flat_load, which also counts as an LDS operation: every wait for the coefficient
-    // table then waited for the gathers too.)
-    const GlobalBytes gp = (GlobalBytes)(
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
-        (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
-    const int width = og.wa, height = og.h;
-
-    // un-mirrored orientation handed to the kernel (PyramidCU.cpp:764,791; A.1 of SURVEY)
-    const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
-                              : __uint_as_float(rec.w);
-    const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
-    const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
-    const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
-
-
-    const float spt = fabsf(kz * dp.window_factor);
-    float s, c;
-    dm_sincosf(kw, &s, &c);  // __sincosf, ProgramCU.cu:1698
-    const float anglef = (kw > kPI) ? (float)(kw - (2.0 * kPI)) : kw;
-    const float cspt = c * spt, sspt = s * spt;
-    const float crspt = c / spt, srspt = s / spt;
-    const float bsz = fabsf(cspt) + fabsf(sspt);
+  for (int mw = first_feature(dp, wv); mw < im.ftotal; mw += gridDim.x * 4) {
+    const Feature f = load_feature(g, im, im.ffirst + im.ftotal - 1 - mw, list, cap_list, recs, fsrc, cap_feat, got);
+    const OrientedFrame fr = oriented_frame(dp, f);
+    const __amdgpu_buffer_rsrc_t grsrc = f.grsrc;
+    const int width = f.width;
+    const float crspt = fr.crspt, srspt = fr.srspt, anglef = fr.anglef;
 
     // Cell geometry (ProgramCU.cu:1692-1716), every lane for its own cell.
     const float offx = (mycell & 3) - 1.5f, offy = (mycell >> 2) - 1.5f;
-    const float ptx = fmaf(cspt, offx, -(sspt * offy)) + kx;
-    const float pty = fmaf(cspt, offy, sspt * offx) + ky;
-    const float xmin = fmaxf(1.5f, floorf(ptx - bsz) + 0.5f);
-    const float ymin = fmaxf(1.5f, floorf(pty - bsz) + 0.5f);
-    const float xmax = fminf(width - 1.5f, floorf(ptx + bsz) + 0.5f);
-    const float ymax = fminf(height - 1.5f, floorf(pty + bsz) + 0.5f);
+    const float ptx = fmaf(fr.cspt, offx, -(fr.sspt * offy)) + fr.kx;
+    const float pty = fmaf(fr.cspt, offy, fr.sspt * offx) + fr.ky;
+    const float xmin = fmaxf(1.5f, floorf(ptx - fr.bsz) + 0.5f);
+    const float ymin = fmaxf(1.5f, floorf(pty - fr.bsz) + 0.5f);
+    const float xmax = fminf(width - 1.5f, floorf(ptx + fr.bsz) + 0.5f);
+    const float ymax = fminf(f.height - 1.5f, floorf(pty + fr.bsz) + 0.5f);
     const int nxs = (xmax >= xmin) ? (int)(xmax - xmin) + 1 : 0;
     const int nys = (ymax >= ymin) ? (int)(ymax - ymin) + 1 : 0;
     const int total = nxs * nys;
@@ -942,17 +1011,7 @@ __global__ __launch_bounds__(256) void descriptor_kernel(Geom g, DescParams dp, 
     }
     // same wavefront wrote dl[wv]; LDS operations of one wavefront complete in order
     __builtin_amdgcn_wave_barrier();
-    float* dout = desc_at(desc, obase + oidx, dim, dp.u8 != 0);
-    float* hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, obase + oidx, dim, dp.u8 != 0) : nullptr;
-    if (dp.half_sift) {
-      float2 v = make_float2(0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float2*>(&dl[wv][lane * 2]);
-      finish_descriptor64<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
-    } else {
-      float4 v = make_float4(0, 0, 0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
-      finish_descriptor128<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
-    }
+    finish_descriptor<HOST_MIRROR>(dp, dp.u8 != 0, lane, dl[wv], desc, im.obase + f.oidx);
   }
 }
 
@@ -1047,7 +1106,7 @@ typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 //               xlo + 64 k + lane), within a band row by row with y ascending;
 //   over lanes  row r = 8 ix + bin of the cell row: s_h = sequential sum, from 0, over k = 0 .. 31 of the sum of lane
 //               32 h + ((k + r) mod 32), for h = 0, 1; the bin is s_0 + s_1;
-//   half_sift   bin k + bin (k + 4), then the shared normalisation (finish_descriptor128 / 64).
+//   half_sift   bin k + bin (k + 4), then the shared normalisation (finish_descriptor).
 // All of it is a function of the record and the plane: no atomics, nothing depends on which wavefront does the work.
 // LDS per wavefront: [4 ix][8 bins][64 lanes] floats, a lane's own column of it (conflict-free), 8 KB.
 // Bounds: every gathered pixel lies in the clipped boxes, [1, width - 2] x [1, height - 2] of the plane, through a buffer
@@ -1064,48 +1123,22 @@ __global__ __launch_bounds__(256) void descriptor_rect_kernel(Geom g, DescParams
   __shared__ __attribute__((aligned(16))) float dl[4][128];
   __shared__ __attribute__((aligned(16))) float hist[4][RC_WAVE];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.y + dp.first_image;
-  int ftotal = feat_total[b], ffirst = feat_first[b];
-  long long obase = img_base[b];
-  feature_part(dp, &ftotal, &ffirst, &obase);
-  const int nwaves = gridDim.x * 4;
-  const float rpi = (float)(4.0 / kPI);
-  const int dim = dp.half_sift ? 64 : 128;
+  const DescImage im = desc_image(dp, feat_total, feat_first, img_base);
 
   static_assert(sizeof(HostKeypoint) == 24 && 4 * RC_WAVE * 4 >= 256 * 24, "record staging fits the histograms");
-  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), list, cap_list, recs, fsrc, cap_feat, b, ftotal, ffirst, obase, keys);
+  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), im, list, cap_list, recs, fsrc, cap_feat, keys);
   if (!desc) return;
   float* const hw = &hist[wv][0];
   for (int i = lane; i < RC_WAVE; i += 64) hw[i] = 0.0f;
   float* const mine = hw + lane;  // + 64 * (8 ix + bin)
-  const uint32_t theta_end_bits = dp.dynamic_indexing ? 0x41000001u : 0x41000000u;  // 8.0f, or the next float (admits t == 8)
+  const uint32_t theta_end_bits = theta_end(dp);
 
-  // from the end of the list backwards: (octave, level) order, and a level's rectangles grow with the level
-  for (int mw = blockIdx.x * 4 + wv; mw < ftotal; mw += nwaves) {
-    const int m = ffirst + ftotal - 1 - mw;
-    const int src = fsrc[(long long)b * cap_feat + m];
-    const int i = src >> 2;
-    const int oidx = m - ffirst;
-    const FRec rec = recs[(long long)b * cap_list + i];
-    const int li = list[(long long)b * cap_list + i].level_index;
-    int o, l;
-    level_of(g, li, &o, &l);
-    const OctGeom& og = g.o[o];
-    // the plane as a buffer resource, as descriptor_kernel makes it: an offset outside it reads 0
-    const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
-                                                        ((long long)(l - 1) * g.B + b) * og.plane);
-    const GlobalBytes gp = (GlobalBytes)(
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
-        (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
-    const int width = og.wa, height = og.h;
-
-    const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
-    const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
-    const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
-    const float kh = __uint_as_float(rec.w);
-    const float sptx = kz * 0.25f, spty = kh * 0.25f;
+  for (int mw = first_feature(dp, wv); mw < im.ftotal; mw += gridDim.x * 4) {  // (a level's rectangles grow with the level)
+    const Feature f = load_feature(g, im, im.ffirst + im.ftotal - 1 - mw, list, cap_list, recs, fsrc, cap_feat, got);
+    const __amdgpu_buffer_rsrc_t grsrc = f.grsrc;
+    const int width = f.width, height = f.height;
+    const float kx = record_pos(f.rec.x), ky = record_pos(f.rec.y);  // the corner
+    const float sptx = record_scale(f.rec.z) * 0.25f, spty = __uint_as_float(f.rec.w) * 0.25f;  // width / 4, height / 4
 
     // the four cell columns: centre and clipped box in x (ProgramCU.cu:1859-1864)
     float cx[4], bx0[4], bx1[4];
@@ -1223,48 +1256,46 @@ __global__ __launch_bounds__(256) void descriptor_rect_kernel(Geom g, DescParams
       }
       __builtin_amdgcn_wave_barrier();
     }
-    float* dout = desc_at(desc, obase + oidx, dim, dp.u8 != 0);
-    float* hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, obase + oidx, dim, dp.u8 != 0) : nullptr;
-    if (dp.half_sift) {
-      float2 v = make_float2(0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float2*>(&dl[wv][lane * 2]);
-      finish_descriptor64<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
-    } else {
-      float4 v = make_float4(0, 0, 0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
-      finish_descriptor128<HOST_MIRROR>(dp, dp.u8 != 0, lane, v, dout, hout);
-    }
+    finish_descriptor<HOST_MIRROR>(dp, dp.u8 != 0, lane, dl[wv], desc, im.obase + f.oidx);
   }
 }
 
 }  // namespace
 
-void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const RawKey* list,
-                        const int* list_total, int cap_list, const float* got, FRec* recs, int* ocount,
+void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const FeatureBuffers& fb, const float* got,
                         int batch) {
-  int blocks = (cap_list + 3) / 4;
+  int blocks = (fb.cap_list + 3) / 4;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(orientation_kernel, dim3(blocks, batch), dim3(256), 0, st, g, op, list, list_total, cap_list,
-                     got, recs, ocount);
+  hipLaunchKernelGGL(orientation_kernel, dim3(blocks, batch), dim3(256), 0, st, g, op, fb.list, fb.list_total, fb.cap_list,
+                     got, fb.recs, fb.ocount);
 }
 
-void launch_feature_scan(hipStream_t st, const Geom& g, const LimitParams& lp, int multi, const RawKey* list,
-                         const int* list_total, int cap_list, const int* ocount, int* foffset, int* fsrc,
-                         int* feat_total, int* feat_first, int cap_feat, int* overflow, int* img_base, int* host_small,
-                         int batch) {
+void launch_feature_scan(hipStream_t st, const Geom& g, const LimitParams& lp, int multi, const FeatureBuffers& fb,
+                         int* overflow, int* host_small, int batch) {
   FeatScan fs;
-  fs.lp = lp; fs.multi = multi; fs.foffset = foffset; fs.fsrc = fsrc; fs.feat_total = feat_total; fs.feat_first = feat_first;
-  fs.cap_feat = cap_feat; fs.overflow = overflow; fs.img_base = img_base; fs.host_small = host_small;
+  fs.lp = lp; fs.multi = multi; fs.foffset = fb.foffset; fs.fsrc = fb.fsrc; fs.feat_total = fb.feat_total;
+  fs.feat_first = fb.feat_first; fs.cap_feat = fb.cap_feat; fs.overflow = overflow; fs.img_base = fb.img_base;
+  fs.host_small = host_small;
   // chunks of >= 4096 keypoints of an image's list, one workgroup each (see feature_scan_image)
-  const int nchunk = std::min(16, std::max(1, cap_list / 4096));
-  hipLaunchKernelGGL(feature_scan_kernel, dim3(nchunk, batch), dim3(1024), 0, st, g, fs, list, list_total, cap_list, ocount);
+  const int nchunk = std::min(16, std::max(1, fb.cap_list / 4096));
+  hipLaunchKernelGGL(feature_scan_kernel, dim3(nchunk, batch), dim3(1024), 0, st, g, fs, fb.list, fb.list_total, fb.cap_list,
+                     fb.ocount);
 }
 
-void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, const RawKey* list,
-                       int cap_list, const FRec* recs, const int* fsrc, const int* feat_total,
-                       const int* feat_first, const int* img_base, const float* got, HostKeypoint* keys,
-                       float* desc, int cap_feat, int batch, int seen_features) {
+// The ten descriptor kernels share one parameter list; which one a launch takes:
+using DescKernel = void (*)(Geom, DescParams, const RawKey*, int, const FRec*, const int*, const int*, const int*, const int*,
+                            const float*, HostKeypoint*, float*, int);
+static DescKernel descriptor_kernel_for(bool rect, bool pixel, bool u8, bool sequential, bool mirror) {
+  if (rect) return mirror ? descriptor_rect_kernel<true> : descriptor_rect_kernel<false>;  // whatever the order and format
+  if (pixel && u8) return mirror ? descriptor_pixel_u8_kernel<true> : descriptor_pixel_u8_kernel<false>;
+  if (pixel) return mirror ? descriptor_pixel_kernel<true> : descriptor_pixel_kernel<false>;
+  if (sequential) return mirror ? descriptor_kernel<true, true> : descriptor_kernel<false, true>;
+  return mirror ? descriptor_kernel<true, false> : descriptor_kernel<false, false>;
+}
+
+void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, const FeatureBuffers& fb, const float* got,
+                       int batch, int seen_features) {
   // (dp.first_image: first image of this launch; `batch` images from there)
   // Grid: one wavefront per feature where that is known to fit -- the workgroup dispatcher then hands the features out
   // largest first as wavefront slots free up, which a fixed stride over a smaller grid does not (configs[4], 25 k features
@@ -1278,35 +1309,20 @@ void launch_descriptor(hipStream_t st, const Geom& g, const DescParams& dp, cons
     const long long want = ((long long)seen_features * 5 / 4 / den + 3) / 4;
     blocks = (int)std::min<long long>(16384, std::max<long long>(256, (want + 127) / 128 * 128));
   }
-  const int cap_blocks = (cap_feat / den + 3) / 4;
+  const int cap_blocks = (fb.cap_feat / den + 3) / 4;
   if (blocks > cap_blocks) blocks = cap_blocks;
   if (blocks < 1) blocks = 1;
-  const int lds_pad = DC_LDS_PAD_BYTES;
   DescParams dpx = dp;
   dpx.px_band = std::min(PX_BAND_MAX, std::max(64, dp.px_band > 0 ? dp.px_band : PX_BAND_MAX));
   // the block order needs whole blocks per XCD, and a grid of whole rounds over the eight XCDs (else the map from
-  // (XCD, wavefront in the XCD) to list blocks is not onto: features would be skipped and others computed twice)
-  if (dpx.xcd_block && ((blocks * 4) % (8 * dpx.xcd_block) != 0 || blocks % 8 != 0)) dpx.xcd_block = 0;
-#define HESS_DESC_LAUNCH(MIRROR, SEQ)                                                                                  \
-  hipLaunchKernelGGL((descriptor_kernel<MIRROR, SEQ>), dim3(blocks, batch), dim3(256), lds_pad, st, g, dpx, list, cap_list, \
-                     recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat)
-  const bool mirror = dp.hkeys || dp.hdesc;
-  if (dp.rect) {  // a caller's rectangles: one kernel whatever the pixel type and descriptor_order
-    dpx.xcd_block = 0;
-    if (mirror) hipLaunchKernelGGL((descriptor_rect_kernel<true>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list,
-                                   recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
-    else hipLaunchKernelGGL((descriptor_rect_kernel<false>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list,
-                            recs, fsrc, feat_total, feat_first, img_base, got, keys, desc, cap_feat);
-  } else if (dp.pixel) {
-#define HESS_PIXEL_LAUNCH(KERNEL, MIRROR)                                                                               \
-  hipLaunchKernelGGL((KERNEL<MIRROR>), dim3(blocks, batch), dim3(256), 0, st, g, dpx, list, cap_list, recs, fsrc, feat_total, \
-                     feat_first, img_base, got, keys, desc, cap_feat)
-    if (dp.u8) { if (mirror) HESS_PIXEL_LAUNCH(descriptor_pixel_u8_kernel, true); else HESS_PIXEL_LAUNCH(descriptor_pixel_u8_kernel, false); }
-    else { if (mirror) HESS_PIXEL_LAUNCH(descriptor_pixel_kernel, true); else HESS_PIXEL_LAUNCH(descriptor_pixel_kernel, false); }
-#undef HESS_PIXEL_LAUNCH
-  } else if (dp.sequential) { if (mirror) HESS_DESC_LAUNCH(true, true); else HESS_DESC_LAUNCH(false, true); }
-  else { if (mirror) HESS_DESC_LAUNCH(true, false); else HESS_DESC_LAUNCH(false, false); }
-#undef HESS_DESC_LAUNCH
+  // (XCD, wavefront in the XCD) to list blocks is not onto: features would be skipped and others computed twice);
+  // a caller's rectangles are few: plain order
+  if (dp.rect || (dpx.xcd_block && ((blocks * 4) % (8 * dpx.xcd_block) != 0 || blocks % 8 != 0))) dpx.xcd_block = 0;
+  // (no dynamic LDS: rounds 1-2 padded the cell kernel's workgroups to 36 KB to hold them at four per CU; since round 3 that
+  // measures slower than none, profiles/r03_desc_pad.txt)
+  hipLaunchKernelGGL(descriptor_kernel_for(dp.rect, dp.pixel, dp.u8, dp.sequential, dp.hkeys || dp.hdesc), dim3(blocks, batch),
+                     dim3(256), 0, st, g, dpx, fb.list, fb.cap_list, fb.recs, fb.fsrc, fb.feat_total, fb.feat_first, fb.img_base,
+                     got, fb.keys, fb.desc, fb.cap_feat);
 }
 
 }  // namespace hess

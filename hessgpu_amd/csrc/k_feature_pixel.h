@@ -4,6 +4,8 @@
 // kernel keeps its name (descriptor_pixel_kernel<host mirror>: profiles and bench.py know it by that) AND its code -- with
 // the format as a run-time branch the float form needed 72 registers and 16 - 28 bytes of scratch per lane, through an
 // inlined body 70 - 72 registers in another allocation; this way its instructions are the ones it had (71, no scratch).
+// What is not the raster -- which features, the feature's record, plane and frame, normalisation and store -- are the helpers
+// the three descriptor kernels share (k_feature.hip, "shared by the descriptor kernels").
 // (no include guard: meant to be included more than once; everything it uses is defined above the include)
 template <bool HOST_MIRROR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, PX_WAVES))) void HESS_PIXEL_KERNEL(Geom g, DescParams dp, const RawKey* list,
@@ -17,16 +19,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, P
   __shared__ __attribute__((aligned(16))) unsigned long long hist[4][PX_WAVE_U64];
   __shared__ __attribute__((aligned(16))) uint4 rowtab[4][64];  // per wavefront: the rows of the current raster band
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.y + dp.first_image;
-  int ftotal = feat_total[b], ffirst = feat_first[b];
-  long long obase = img_base[b];
-  feature_part(dp, &ftotal, &ffirst, &obase);
-  const int nwaves = gridDim.x * 4;
-  const float rpi = (float)(4.0 / kPI);
-  const int dim = dp.half_sift ? 64 : 128;
+  const DescImage im = desc_image(dp, feat_total, feat_first, img_base);
 
   static_assert(sizeof(HostKeypoint) == 24 && sizeof(hist) >= 256 * 24, "record staging fits the sums");
-  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), list, cap_list, recs, fsrc, cap_feat, b, ftotal, ffirst, obase, keys);
+  keypoint_records<HOST_MIRROR>(dp, reinterpret_cast<uint32_t*>(&hist[0][0]), im, list, cap_list, recs, fsrc, cap_feat, keys);
   if (!desc) return;
   unsigned long long* const sums = &hist[wv][0];
   {
@@ -35,46 +31,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, P
   }
   // LDS byte address of the lane's copy, as a float (stage B adds the word's offset in floating point)
   const float mycopy_f = (float)(unsigned)(unsigned long long)(lds_u64*)(sums + (lane % PX_COPIES) * PX_COPY_U64);
-  const uint32_t theta_end_bits = dp.dynamic_indexing ? 0x41000001u : 0x41000000u;  // 8.0f, or the next float (admits theta == 8)
+  const uint32_t theta_end_bits = theta_end(dp);
 
-  // feature order: as descriptor_kernel (largest footprints first, blocks of consecutive features per XCD)
-  int mw0 = blockIdx.x * 4 + wv;
-  if (dp.xcd_block) {
-    const int xcd = blockIdx.x & 7, wx = (int)(blockIdx.x >> 3) * 4 + wv;
-    mw0 = ((wx / dp.xcd_block) * 8 + xcd) * dp.xcd_block + wx % dp.xcd_block;
-  }
-  for (int mw = mw0; mw < ftotal; mw += nwaves) {
-    const int m = ffirst + ftotal - 1 - mw;
-    const int src = fsrc[(long long)b * cap_feat + m];
-    const int i = src >> 2, k = src & 3;
-    const int oidx = m - ffirst;
-    const FRec rec = recs[(long long)b * cap_list + i];
-    const int li = list[(long long)b * cap_list + i].level_index;
-    int o, l;
-    level_of(g, li, &o, &l);
-    const OctGeom& og = g.o[o];
-    const unsigned long long gpa = (unsigned long long)(reinterpret_cast<const float2*>(got) + og.got_off +
-                                                        ((long long)(l - 1) * g.B + b) * og.plane);
-    const GlobalBytes gp = (GlobalBytes)(
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gpa >> 32)) << 32) |
-        (unsigned)__builtin_amdgcn_readfirstlane((int)(gpa & 0xFFFFFFFFull)));
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)gp, 0, __builtin_amdgcn_readfirstlane(og.plane * 8), 0x00020000 /* raw 32-bit data, gfx9 family */);
-    const int width = og.wa, height = og.h;
-
-    const float kw = dp.multi ? multi_angle(dp.multi, rec.w, k)
-                              : __uint_as_float(rec.w);
-    const float kx = (float)(rec.x & 0x00FFFFFFu) / 1024.0f;
-    const float ky = (float)(rec.y & 0x00FFFFFFu) / 1024.0f;
-    const float kz = (float)(rec.z & 0x0000FFFFu) / 256.0f;
-    const float spt = fabsf(kz * dp.window_factor);
-    float s, c;
-    dm_sincosf(kw, &s, &c);
-    const float anglef = (kw > kPI) ? (float)(kw - (2.0 * kPI)) : kw;
-    const float cspt = c * spt, sspt = s * spt;
-    const float crspt = c / spt, srspt = s / spt;
-    const float bsz = fabsf(cspt) + fabsf(sspt);
-    const float ext = 2.5f * bsz;  // half extent of the footprint's bounding box
+  for (int mw = first_feature(dp, wv); mw < im.ftotal; mw += gridDim.x * 4) {
+    const Feature f = load_feature(g, im, im.ffirst + im.ftotal - 1 - mw, list, cap_list, recs, fsrc, cap_feat, got);
+    const __amdgpu_buffer_rsrc_t grsrc = f.grsrc;
+    const int width = f.width, height = f.height;
+    const OrientedFrame fr = oriented_frame(dp, f);
+    const float kx = fr.kx, ky = fr.ky;
+    const float spt = fr.spt, crspt = fr.crspt, srspt = fr.srspt, anglef = fr.anglef;
+    const float ext = 2.5f * fr.bsz;  // half extent of the footprint's bounding box
     const float xmin = fmaxf(1.5f, floorf(kx - ext) + 0.5f);
     const float ymin = fmaxf(1.5f, floorf(ky - ext) + 0.5f);
     const float xmax = fminf(width - 1.5f, floorf(kx + ext) + 0.5f);
@@ -247,20 +213,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PX_WAVES, P
       *reinterpret_cast<float2*>(&dl[wv][2 * lane]) = make_float2(f0, f1);
     }
     __builtin_amdgcn_wave_barrier();
-    float* dout = desc_at(desc, obase + oidx, dim, U8);
-    float* hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, obase + oidx, dim, U8) : nullptr;
+    // The end is this kernel's own text on top of finish_values, not finish_descriptor: -half folds des[k] + des[k+4] out of
+    // the unfolded staging layout, and with the folded values handed over through LDS once more (or folded in registers
+    // ahead of the staging) the raster's loops came out with other waits and scalar instructions, the float form with a 72nd
+    // register and scratch (profiles/r14_desc_helpers.txt).
+    const int dim = dp.half_sift ? 64 : 128;
+    float* const dout = desc_at(desc, im.obase + f.oidx, dim, U8);
+    float* const hout = (HOST_MIRROR && dp.hdesc) ? desc_at(dp.hdesc, im.obase + f.oidx, dim, U8) : nullptr;
     if (dp.half_sift) {  // des[k] += des[k+4], ProgramCU.cu:1782-1785: lane < 32 -> cell lane/2, k = 2 (lane & 1) + {0, 1}
-      float2 v = make_float2(0, 0);
+      DescValues<2> v = 0.0f;
       if (lane < 32) {
         const float* cellp = &dl[wv][(lane >> 1) * 8 + (lane & 1) * 2];
         const float2 lo = *reinterpret_cast<const float2*>(cellp), hi = *reinterpret_cast<const float2*>(cellp + 4);
-        v = make_float2(lo.x + hi.x, lo.y + hi.y);
+        v.x = lo.x + hi.x; v.y = lo.y + hi.y;
       }
-      finish_descriptor64<HOST_MIRROR>(dp, U8, lane, v, dout, hout);
+      finish_values<HOST_MIRROR, 2>(dp, U8, lane, v, dout, hout);
     } else {
-      float4 v = make_float4(0, 0, 0, 0);
-      if (lane < 32) v = *reinterpret_cast<const float4*>(&dl[wv][lane * 4]);
-      finish_descriptor128<HOST_MIRROR>(dp, U8, lane, v, dout, hout);
+      finish_values<HOST_MIRROR, 4>(dp, U8, lane, staged_values<4>(dl[wv], lane), dout, hout);
     }
     __builtin_amdgcn_wave_barrier();  // (dl and the sums are rewritten by the next feature)
   }
