@@ -154,6 +154,10 @@ PRODUCT_PROTOTYPES = {
     # 64-d descriptors in the matcher (added during version 5 without a bump)
     "matcher_set_dim": (C.c_int, [C.c_void_p, C.c_int]),
     "matcher_dim": (C.c_int, [C.c_void_p]),
+    # keypoint lists for every image of a batch (added during version 5 without a bump)
+    "set_keypoints_batch": (C.c_int, [_ctx, C.c_void_p, _P(C.c_int), C.c_int, C.c_int]),
+    "run_keypoints_batch": (C.c_int, [_ctx, C.c_void_p, _P(C.c_int), C.c_int, C.c_int]),
+    "key_list_order": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int]),
 }
 
 

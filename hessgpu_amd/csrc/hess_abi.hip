@@ -95,7 +95,7 @@ void hess_destroy(hess_ctx* c) {
   DevBuf* bufs[] = {&c->gauss, &c->deth, &c->got, &c->input_f32, &c->upsampled, &c->stage, &c->zeroed, &c->rowoff,
                     &c->level_count, &c->raw_total, &c->found, &c->task_count, &c->raw, &c->sel, &c->sel_total,
                     &c->recs, &c->ocount, &c->foffset, &c->fsrc, &c->feat_total, &c->feat_first, &c->img_base,
-                    &c->keys, &c->desc, &c->prime_px};
+                    &c->keys, &c->desc, &c->prime_px, &c->d_user, &c->kmember, &c->kmap};
   // A poisoned context (a DMA copy that was lost may still be in flight or land late) deliberately leaks the copy's
   // sources and targets -- result buffers on both sides and the pixel staging area -- rather than hand memory that may
   // still be written back to the allocator; a shared result buffer stays mapped for the same reason.
@@ -105,7 +105,9 @@ void hess_destroy(hess_ctx* c) {
   if (!leak) {
     release(c->h_keys, true);
     release(c->h_desc, true);
+    release(c->h_kmap, true);
   }
+  release(c->h_user, true);
   release(c->h_small, true);
   if (c->share_dir) {
     (void)munmap(c->share_dir, 4096);
@@ -170,7 +172,7 @@ static int prime(hess_ctx* c, int width, int height, int batch) {
   static const bool no_dry = dev_env("HESS_NO_PRIME_BATCH") != nullptr;
   const long long shape = ((long long)width << 40) ^ ((long long)height << 16) ^ batch;
   const bool primed = std::find(std::begin(c->primed_shapes), std::end(c->primed_shapes), shape) != std::end(c->primed_shapes);
-  if (!no_dry && c->batch == 0 && c->user_keys.empty() && !primed) {
+  if (!no_dry && c->batch == 0 && !user_mode(c) && !primed) {
     // The scratch image belongs to the context (grow-only, freed with it): a hipMalloc / hipFree pair per call would
     // synchronise the whole device under the other contexts of a pipelining process.  The dry batch takes the settings of a
     // SUBMITTED batch (what a caller who reserves and then pipelines gets); a caller of hess_run_* with one or two images
@@ -273,6 +275,7 @@ static int begin_submit(hess_ctx* c, const void* pixels, int width, int height, 
                         int format, int pixtype, bool device) {
   if (int rc = check_run_args(c, pixels, width, height, pitch, image_stride, batch, format, pixtype, device)) return rc;
   if (int rc = refuse_pending(c)) return rc;
+  if (int rc = check_user_batch(c, batch)) return rc;  // (before anything is enqueued)
   HIP_TRY(c, hipSetDevice(c->device));
   c->batch = c->pyramid_batch = 0;
   c->accepted_submit = true;
@@ -332,7 +335,7 @@ int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int
                       .pixtype = pixtype, .image_stride = image_stride, .desc_format = c->desc_format};  // (the pixels will be in the staging area)
   hipPointerAttribute_t at;
   const bool pinned = hipPointerGetAttributes(&at, pixels) == hipSuccess && at.type == hipMemoryTypeHost;
-  if (pinned && c->user_keys.empty() && !c->no_host_upload) {
+  if (pinned && !c->no_host_upload) {
     // Pinned pixels of a batch that the copier thread will deliver: the upload goes to an SDMA engine directly and
     // the copier thread enqueues the kernels once it has landed (Copier::upload_first).  A copy command on the
     // context's stream would hold its hardware queue -- shared with other contexts -- for the length of the
@@ -440,10 +443,25 @@ int hess_last_input(hess_ctx* c, void* out, size_t bytes) {
 }
 
 // The caller's key list for the next run (nothing thrown crosses the C ABI).
-static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation, bool on_current) {
+// The keys of `nimg` images, back to back, into the context's pinned block (the copy that the run uploads); a total of 0
+// clears a pending list.  The stream is idle or busy with an earlier batch whose upload is long done: a run that uses the
+// block is waited for before the next list can be set (the batch entries refuse while one is pending).
+static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, const int* counts, int nimg, int keys_have_orientation,
+                           bool on_current) {
+  long long total = 0;
+  int most = 0;
+  for (int b = 0; b < nimg; b++) { total += counts[b]; most = std::max(most, counts[b]); }
+  if (total > (INT_MAX - 8) / 2) { set_err(c, "too many keypoints (%lld)", total); return HESS_ERR_ARG; }
+  clear_user_list(c);
+  if (total == 0) return 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure(c, c->h_user, user_block_bytes((int)total, nimg), true)) return rc;
   try {
-    c->user_keys.assign(keys, keys + num);
-  } catch (...) { c->user_keys.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
+    c->user_counts.assign(counts, counts + nimg);
+  } catch (...) { c->user_counts.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
+  memcpy(c->h_user.p, keys, (size_t)total * sizeof(hess_keypoint));
+  c->user_total = (int)total;
+  c->user_max = most;
   c->user_have_orientation = keys_have_orientation != 0;  // the reference tests the flag's truth (PyramidCU.cpp:522) ...
   c->user_rect = keys_have_orientation == HESS_KEYS_RECTANGLES;  // ... and -1 alone for rectangles (SiftPyramid.cpp:345-354)
   c->user_on_current = on_current;
@@ -452,7 +470,47 @@ static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, int num, int 
 
 int hess_set_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation) {
   if (!c || num < 0 || (num > 0 && !keys)) return HESS_ERR_ARG;
-  return store_user_keys(c, keys, num, keys_have_orientation, false);
+  if (refuse_pending(c)) return HESS_ERR_STATE;  // (hess_wait tells a list run by the pending list, and its upload reads the block)
+  return store_user_keys(c, keys, &num, 1, keys_have_orientation, false);
+}
+
+static int check_key_batch(hess_ctx* c, const hess_keypoint* keys, const int* counts, int nimg) {
+  if (!c) return HESS_ERR_ARG;
+  if (!counts || nimg <= 0) { set_err(c, "keypoint lists: counts of %d images", nimg); return HESS_ERR_ARG; }
+  long long total = 0;
+  for (int b = 0; b < nimg; b++) {
+    if (counts[b] < 0) { set_err(c, "keypoint lists: image %d has a negative count (%d)", b, counts[b]); return HESS_ERR_ARG; }
+    total += counts[b];
+  }
+  if (total > 0 && !keys) { set_err(c, "keypoint lists: no keys"); return HESS_ERR_ARG; }
+  if (refuse_pending(c)) return HESS_ERR_STATE;
+  if (!c->user_levels.empty()) {
+    set_err(c, "a hess_debug_key_levels override is pending: it covers the list of a single image (hess_set_keypoints)");
+    return HESS_ERR_STATE;
+  }
+  return 0;
+}
+
+int hess_set_keypoints_batch(hess_ctx* c, const hess_keypoint* keys, const int* counts, int nimg, int keys_have_orientation) {
+  if (int rc = check_key_batch(c, keys, counts, nimg)) return rc;
+  return store_user_keys(c, keys, counts, nimg, keys_have_orientation, false);
+}
+
+// The pending lists on the current batch's pyramid: `batch` images, no filtering.
+static int run_on_current(hess_ctx* c, int batch) {
+  PendingRun r = c->run;  // geometry of the current image (a local: the stored run keeps its batch)
+  if (r.width <= 0) { clear_user_list(c); set_err(c, "no current image"); return HESS_ERR_STATE; }
+  r.batch = batch; r.t_load_ms = 0.0;
+  r.desc_format = c->desc_format;  // (the list's run takes the format set now, not the image's)
+  const int keep_pyramid = c->pyramid_batch;
+  c->batch = 0;  // results of the run before: gone; the pyramid stays (that is the point of this entry)
+  int rc = submit_impl(c, r);
+  if (rc) { clear_user_list(c); return rc; }
+  rc = wait_impl(c, r);
+  c->pyramid_batch = keep_pyramid;
+  if (rc) clear_user_list(c);
+  else c->run.desc_format = r.desc_format;  // the results the context now holds are this run's
+  return rc;
 }
 
 int hess_run_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys_have_orientation) {
@@ -460,21 +518,30 @@ int hess_run_keypoints(hess_ctx* c, const hess_keypoint* keys, int num, int keys
   if (refuse_poisoned(c)) return HESS_ERR_DEVICE;
   if (!c->planned || c->pyramid_batch < 1) { set_err(c, "no current image: run an image first"); return HESS_ERR_STATE; }
   if (refuse_pending(c)) return HESS_ERR_STATE;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = store_user_keys(c, keys, num, keys_have_orientation, true)) return rc;
-  PendingRun r = c->run;  // geometry of the current image (a local: the stored run keeps its batch)
-  if (r.width <= 0) { c->user_keys.clear(); set_err(c, "no current image"); return HESS_ERR_STATE; }
-  r.batch = 1; r.t_load_ms = 0.0;
-  r.desc_format = c->desc_format;  // (the list's run takes the format set now, not the image's)
-  const int keep_pyramid = c->pyramid_batch;
-  c->batch = 0;  // results of the run before: gone; the pyramid stays (that is the point of this entry)
-  int rc = submit_impl(c, r);
-  if (rc) { c->user_keys.clear(); return rc; }
-  rc = wait_impl(c, r);
-  c->pyramid_batch = keep_pyramid;
-  if (rc) c->user_keys.clear();
-  else c->run.desc_format = r.desc_format;  // the results the context now holds are this run's
-  return rc;
+  if (int rc = store_user_keys(c, keys, &num, 1, keys_have_orientation, true)) return rc;
+  return run_on_current(c, 1);
+}
+
+int hess_run_keypoints_batch(hess_ctx* c, const hess_keypoint* keys, const int* counts, int nimg, int keys_have_orientation) {
+  if (int rc = check_key_batch(c, keys, counts, nimg)) return rc;
+  if (refuse_poisoned(c)) return HESS_ERR_DEVICE;
+  if (!c->planned || c->pyramid_batch < 1) { set_err(c, "no current batch: run a batch first"); return HESS_ERR_STATE; }
+  if (nimg != c->pyramid_batch) {
+    set_err(c, "keypoint lists for %d images, the current batch has %d", nimg, c->pyramid_batch);
+    return HESS_ERR_ARG;
+  }
+  if (int rc = store_user_keys(c, keys, counts, nimg, keys_have_orientation, true)) return rc;
+  if (!user_mode(c)) { set_err(c, "keypoint lists: no keys"); return HESS_ERR_ARG; }
+  return run_on_current(c, nimg);
+}
+
+int hess_key_list_order(hess_ctx* c, int img, int* out, int cap) {
+  if (!c || img < 0 || img >= c->batch || cap < 0 || (cap > 0 && !out)) return HESS_ERR_ARG;
+  if (!c->user_result) { set_err(c, "the last run had no keypoint list"); return HESS_ERR_STATE; }
+  const size_t first = c->offs[img], len = c->offs[img + 1] - first;
+  const size_t m = std::min(len, (size_t)cap);
+  if (m) memcpy(out, c->u_order.data() + first, m * sizeof(int));
+  return (int)len;
 }
 
 int hess_debug_key_levels(hess_ctx* c, const int* levels, int num) {
@@ -505,8 +572,9 @@ static int fetch_as(hess_ctx* c, int format, int img, hess_keypoint* keys, void*
   }
   const size_t n = (size_t)c->counts[img], db = run_desc_bytes(c, format);
   if (c->user_result) {
-    if (keys && n) memcpy(keys, c->u_keys.data(), n * sizeof(hess_keypoint));
-    if (desc && c->dim && n) memcpy(desc, c->u_desc.data(), n * db);
+    const size_t first = c->u_first[img];  // (input order, the images back to back)
+    if (keys && n) memcpy(keys, c->u_keys.data() + first, n * sizeof(hess_keypoint));
+    if (desc && c->dim && n) memcpy(desc, c->u_desc.data() + first * db, n * db);
     return 0;
   }
   if (keys && n) memcpy(keys, (HostKeypoint*)c->h_keys.p + c->offs[img], n * sizeof(HostKeypoint));
@@ -545,7 +613,8 @@ int hess_device_results(hess_ctx* c, const void** keys, const void** desc, int* 
   if (!c || !c->batch) return HESS_ERR_STATE;
   if (keys) *keys = c->keys.p;
   if (desc) *desc = c->dim ? c->desc.p : nullptr;
-  if (capacity) *capacity = (int)c->offs[c->batch];  // records in use; image b starts at sum of counts < b
+  // records in use; image b starts at sum of counts < b (after a keypoint-list run: of the list lengths, hess_key_list_order)
+  if (capacity) *capacity = (int)c->offs[c->batch];
   return 0;
 }
 

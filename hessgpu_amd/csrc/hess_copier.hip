@@ -261,6 +261,31 @@ void copier_main(hess_ctx* c) {
           fail("hipMemcpyAsync(desc)", e);
         if (!rc && (e = hipStreamSynchronize(cp.cs)) != hipSuccess) fail("hipStreamSynchronize(copy stream)", e);
       };
+      if (total && user_mode(c)) {
+        // A caller's keypoint lists: the results are in list order, and hess_wait needs the lists' map to input order beside
+        // them -- key_bin_kernel wrote it before any of the events.  Every image's rows at once: 4 bytes per record.
+        const size_t mb = (size_t)batch * c->cap_list * 4;
+        bool copied = false;
+        if (copier_hsa_setup(c)) {
+          hsa_signal_store_relaxed(cp.sig, 1);
+          if (hsa_amd_memory_async_copy(c->h_kmap.p, cp.cpu_agent, c->kmap.p, cp.gpu_agent, mb, 0, nullptr, cp.sig) == HSA_STATUS_SUCCESS) {
+            hsa_signal_value_t seen = 0;
+            bool real = false;
+            if (const int w = wait_copy_signal(cp.sig, 1, &seen, false, &real)) {
+              snprintf(msg, sizeof(msg), "device->host copy of the keypoint lists' order %s (signal value %lld)",
+                       w == 1 ? "did not complete in time" : "failed", (long long)seen);
+              cp.hsa_ready = false; cp.hsa_failed = true;
+              if (real) c->poisoned.store(true);
+              rc = HESS_ERR_DEVICE;
+            }
+            copied = true;
+          }
+        }
+        if (!copied) {
+          if ((e = hipMemcpyAsync(c->h_kmap.p, c->kmap.p, mb, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess) fail("hipMemcpyAsync(list order)", e);
+          if (!rc && (e = hipStreamSynchronize(cp.cs)) != hipSuccess) fail("hipStreamSynchronize(copy stream)", e);
+        }
+      }
       size_t done_feats = 0;
       for (int k = 0; k < nparts; k++) {
         if (k > 0 && (e = hipEventSynchronize(k < nparts - 1 ? cp.ev_part[k] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
@@ -350,14 +375,20 @@ void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
   cp.cv.notify_all();
 }
 
+// Pending keypoint lists are one per image of the batch that uses them.
+int check_user_batch(hess_ctx* c, int batch) {
+  if (!user_mode(c) || batch == (int)c->user_counts.size()) return 0;
+  if (c->user_counts.size() == 1) set_err(c, "a keypoint list applies to a single image");
+  else set_err(c, "keypoint lists were set for %d images, the batch has %d", (int)c->user_counts.size(), batch);
+  return HESS_ERR_ARG;
+}
+
 // Enqueue the whole path (the per-image counts reach the pinned count block by feature_scan_kernel's own stores);
 // returns without waiting.
 int submit_inner(hess_ctx* c, PendingRun& r) {
-  if (!c->user_keys.empty() && r.batch != 1) {
-    set_err(c, "a keypoint list applies to a single image");
-    return HESS_ERR_ARG;
-  }
-  int rc = plan(c, r.width, r.height, r.batch);
+  int rc = check_user_batch(c, r.batch);
+  if (rc) return rc;
+  rc = plan(c, r.width, r.height, r.batch);
   if (rc) return rc;
   choose_delivery(c, r.batch);
   HIP_TRY(c, hipGetLastError());
@@ -371,7 +402,7 @@ int submit_inner(hess_ctx* c, PendingRun& r) {
   return 0;
 }
 
-// (nothing thrown crosses the C ABI: enqueue_user builds host vectors)
+// (nothing thrown crosses the C ABI: plan() and the profiling scopes grow host vectors)
 int submit_impl(hess_ctx* c, PendingRun& r) {
   try {
     return submit_inner(c, r);
@@ -403,6 +434,10 @@ int wait_inner(hess_ctx* c, PendingRun& r) {
       return HESS_ERR_DEVICE;
     }
     if (!of_raw && !of_feat) break;
+    if (user_mode(c)) {  // (storage for a caller's lists follows from their lengths: growing it would not help)
+      set_err(c, "keypoint lists (%d) exceed the reserved feature storage", of_raw > of_feat ? of_raw : of_feat);
+      return HESS_ERR_NOMEM;
+    }
     if (attempt >= 8) { set_err(c, "feature storage keeps overflowing"); return HESS_ERR_NOMEM; }
     // grow-only reallocation, then run the batch again (reference: SetLevelFeatureNum grows on demand,
     // PyramidCU.cpp:393-397)
@@ -431,28 +466,41 @@ int wait_inner(hess_ctx* c, PendingRun& r) {
     HIP_TRY(c, hipMemcpyAsync(c->h_keys.p, c->keys.p, total * sizeof(HostKeypoint), hipMemcpyDeviceToHost, c->st));
     if (c->dim)
       HIP_TRY(c, hipMemcpyAsync(c->h_desc.p, c->desc.p, total * db, hipMemcpyDeviceToHost, c->st));
+    if (user_mode(c))  // the lists' map to input order travels with the results
+      HIP_TRY(c, hipMemcpyAsync(c->h_kmap.p, c->kmap.p, (size_t)batch * c->cap_list * 4, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
   }
   c->user_result = false;
-  if (!c->user_keys.empty()) {
-    // back to input order (PyramidCU.cpp:537-549,1157-1168); the caller's keypoints are returned
-    // unchanged unless DownloadKeypoints would run (-m 1 / -ofix, SiftPyramid.cpp:160-171)
-    const int num = (int)c->user_keys.size();
-    const int listed = (int)std::min<size_t>(total, (size_t)num);
+  if (user_mode(c)) {
+    // Every image's results back to input order (PyramidCU.cpp:537-549,1157-1168): zeros for a key that is listed nowhere,
+    // the later listing for a key listed twice, and of a list longer than the image's keys only the first `num` entries,
+    // as the reference has it.  The caller's keypoints are returned unchanged unless DownloadKeypoints would run (-m 1 /
+    // -ofix, SiftPyramid.cpp:160-171).  The device records stay in list order (hess_device_results, hess_key_list_order).
     const bool download = !c->user_have_orientation && ((c->p.max_orientation < 2) || c->p.fixed_orientation);
-    c->u_keys = c->user_keys;
-    c->u_desc.assign((size_t)num * (db ? db : 1), 0);
-    for (int i = 0; i < listed; i++) {
-      const int k = c->user_kindex[i];
-      if (download) memcpy(&c->u_keys[k], (HostKeypoint*)c->h_keys.p + i, sizeof(hess_keypoint));
-      if (c->dim) memcpy(&c->u_desc[(size_t)k * db], (const char*)c->h_desc.p + (size_t)i * db, db);
+    const hess_keypoint* const given = (const hess_keypoint*)c->h_user.p;
+    const int* const kmap = (const int*)c->h_kmap.p;
+    c->u_keys.assign(given, given + c->user_total);
+    c->u_desc.assign((size_t)c->user_total * (db ? db : 1), 0);
+    c->u_order.assign(total, 0);
+    c->u_first.assign(batch + 1, 0);
+    for (int b = 0; b < batch; b++) {
+      const int num = c->user_counts[b], len = c->counts[b];
+      const size_t first = c->u_first[b], lfirst = c->offs[b];
+      const int listed = std::min(len, num);
+      for (int i = 0; i < len; i++) {
+        const int k = kmap[(size_t)b * c->cap_list + i];
+        if (k < 0 || k >= num) { set_err(c, "keypoint list of image %d: entry %d names key %d of %d", b, i, k, num); return HESS_ERR_DEVICE; }
+        c->u_order[lfirst + i] = k;
+        if (i >= listed) continue;
+        if (download) memcpy(&c->u_keys[first + k], (HostKeypoint*)c->h_keys.p + lfirst + i, sizeof(hess_keypoint));
+        if (c->dim) memcpy(&c->u_desc[(first + k) * db], (const char*)c->h_desc.p + (lfirst + i) * db, db);
+      }
+      c->u_first[b + 1] = first + (size_t)num;
+      c->counts[b] = num;
     }
-    c->counts[0] = num;
-    c->offs[1] = (size_t)num;
     c->user_result = true;
-    c->user_keys.clear();  // _existing_keypoints = 0 after RunSIFT (SiftPyramid.cpp:182-184)
+    clear_user_list(c);      // _existing_keypoints = 0 after RunSIFT (SiftPyramid.cpp:182-184)
     c->user_levels.clear();  // the parity hook covers one keypoint-list run
-    c->user_on_current = false;
   }
   // stage times from the events of the last enqueue (config.h:17-31 order)
   memset(c->timing, 0, sizeof(c->timing));
@@ -477,7 +525,7 @@ int wait_impl(hess_ctx* c, PendingRun& r) {
   try {
     return wait_inner(c, r);
   } catch (...) {  // the host-side count / keypoint-list vectors
-    c->user_keys.clear();
+    clear_user_list(c);
     set_err(c, "out of host memory while collecting the results");
     return HESS_ERR_NOMEM;
   }

@@ -289,16 +289,25 @@ struct hess_ctx {
   DevBuf prime_px;                 // the dry batch's scratch image (zero pixels)
   PendingRun run;                  // the batch submitted last: pending while run.active, then the current image's geometry (width 0: none)
   bool accepted_submit = false;    // hess_submit_* has accepted a batch at least once (hess_share_results comes before that)
-  // user-supplied keypoint list (SiftPyramid::SetKeypointList): used by the next run, then cleared
-  std::vector<hess_keypoint> user_keys;
+  // user-supplied keypoint lists (SiftPyramid::SetKeypointList), one per image of the next run: used by it, then cleared.
+  // The keys of all images lie back to back at the start of the pinned block h_user since the set call; enqueue_user
+  // appends what else key_bin_kernel reads (UserBlock) and uploads the block to d_user with one copy.
+  DevBuf h_user, d_user;
+  std::vector<int> user_counts;     // keys per image; empty: no list is pending
+  int user_total = 0, user_max = 0; // their sum (> 0 while a list is pending) and the largest of them
   bool user_have_orientation = false;
   bool user_rect = false;           // HESS_KEYS_RECTANGLES: the keys are rectangles (x, y, width, height); implies user_have_orientation
   bool user_on_current = false;     // RunSIFT(num, keys, flag): skip filtering, reuse the resident pyramid
-  std::vector<int> user_kindex;     // list position -> input index (_keypoint_index)
-  std::vector<int> user_levels;     // parity hook: explicit level index per user keypoint (hess_debug_key_levels)
-  bool user_result = false;         // last results are in u_keys / u_desc (input order)
+  std::vector<int> user_levels;     // parity hook: explicit level index per user keypoint (hess_debug_key_levels; one image)
+  DevBuf kmember;                   // key_bin_kernel's scratch: [B][user_max] levels of every key
+  DevBuf kmap, h_kmap;              // [B][cap_list] list position -> input index (_keypoint_index); h_kmap: pinned, filled by
+                                    // the route the results take (the kernel's own stores, the copier thread, hess_wait's copy)
+  bool user_result = false;         // last results are in u_keys / u_desc (input order, the images back to back)
   std::vector<hess_keypoint> u_keys;
-  std::vector<unsigned char> u_desc;  // [num][run_desc_bytes]: floats or bytes, as the run's format says
+  std::vector<unsigned char> u_desc;  // [sum of counts][run_desc_bytes]: floats or bytes, as the run's format says
+  std::vector<size_t> u_first;      // [batch + 1] first key of every image in u_keys / u_desc
+  std::vector<int> u_order;         // the lists of the last keypoint-list run, list position -> input index, the images back to
+                                    // back as the device records are: image b's list is entries [offs[b], offs[b + 1]) (hess_key_list_order)
   const RawKey* d_list = nullptr;  // list fed to the orientation stage in the last run
   const int* d_list_total = nullptr;
   int cap_list = 0;
@@ -325,6 +334,17 @@ void set_err(hess_ctx* c, const char* fmt, ...);
 
 // Bytes of one descriptor of a run in format `format` (HESS_DESC_FORMAT_*): the one place that knows the element size.
 inline size_t run_desc_bytes(const hess_ctx* c, int format) { return desc_bytes(c->dim, format); }
+
+// A caller's keypoint lists are pending for the next run; the records an image's list may take (GenerateFeatureListTex
+// reserves 2 * num + 8, PyramidCU.cpp:575; here for the largest list of the batch: key_level_kernel says why no list gets
+// there); the list is consumed or dropped.
+inline bool user_mode(const hess_ctx* c) { return c->user_total > 0; }
+inline int user_cap(const hess_ctx* c) { return 2 * c->user_max + 8; }
+inline void clear_user_list(hess_ctx* c) {
+  c->user_counts.clear();
+  c->user_total = c->user_max = 0;
+  c->user_on_current = false;
+}
 
 // Environment switches.  The shipped library reads four: HESS_SHARE_DIR (and TMPDIR) -- where node-shared result buffers go
 // when /dev/shm has no room --, HESS_COPY_TIMEOUT_S -- how long a result copy may take before the context is poisoned --
@@ -364,6 +384,7 @@ int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which);
 // hess_schedule.hip
 void drain_profile(hess_ctx* c);
 int enqueue(hess_ctx* c, const PendingRun& r);
+size_t user_block_bytes(int total, int nimg);  // bytes of the pinned block h_user for `total` keys of `nimg` images
 // hess_copier.hip
 void stager_start(Stager& sg);
 void stager_copy(Stager& sg, int k);
@@ -374,6 +395,7 @@ int copier_start(hess_ctx* c);
 void copier_stop(hess_ctx* c);
 void choose_delivery(hess_ctx* c, int batch);
 void copier_post(hess_ctx* c, PendingRun* run, bool upload_first);
+int check_user_batch(hess_ctx* c, int batch);
 int submit_impl(hess_ctx* c, PendingRun& r);
 int wait_impl(hess_ctx* c, PendingRun& r);
 

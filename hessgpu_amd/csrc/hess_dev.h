@@ -295,7 +295,7 @@ struct FeatureBuffers {
   const RawKey* list;     // [cap_list] the keypoint list in (level, row, col) order (raw or top-K selected)
   const int* list_total;  // its length
   int cap_list;
-  FRec* recs;             // [cap_list] feature records: written by the orientation kernel (a caller's keys: uploaded)
+  FRec* recs;             // [cap_list] feature records: written by the orientation kernel (a caller's keys: by key_bin_kernel)
   int* ocount;            // [cap_list] orientations per keypoint
   int* foffset;           // [cap_list] first feature of a keypoint (exclusive scan of ocount)
   int* fsrc;              // [cap_feat] feature -> keypoint * 4 + orientation rank
@@ -306,6 +306,35 @@ struct FeatureBuffers {
   float* desc;            // float [..][dim], with DescParams::u8 unsigned char [..][dim]; null: keypoint records only
   int cap_feat;
 };
+
+// A caller's keypoints binned to levels (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718), the images of a batch in
+// one go: per image the list (level index ascending, then input index ascending), its records, its length and the map from
+// list entry to input index.  A key is listed at every level whose test it passes: normally one, two at a seam where the
+// rounded bounds of neighbouring levels overlap, none with a NaN scale.
+struct KeyLevel {          // one per level index octave * dog + (level - 1); the host forms them (the powf calls stay there)
+  float sigma_min, sigma_max;  // level_sigma / half_step, level_sigma * half_step
+  float octave_sigma;          // 2^octave * first_octave_sigma
+  float level_sigma;           // the scale a key with a given level (hess_debug_key_levels) is tested with
+};
+struct KeyBinJob {
+  const HostKeypoint* keys;  // [total] the images' keys back to back, as the caller gave them
+  const int* first_count;    // [batch][2] first key and number of keys of every image
+  const int* levels;         // [count of image 0] hess_debug_key_levels (a single image), or null
+  const KeyLevel* table;     // [nlev]
+  int total, max_count, nlev;
+  int rect;                  // HESS_KEYS_RECTANGLES: min(s, o) / 12 is binned, the record holds the height o / octave_sigma as a float
+  float origin;              // 0.5, or 0 with lowe_origin
+  int* member;               // [batch][max_count] scratch: the (at most two) levels of every key
+  int* level_count;          // [batch][nlev] scratch, arrives zeroed
+  RawKey* list;              // [batch][cap_list] out: level_index set, the rest zero
+  FRec* recs;                // [batch][cap_list] out
+  int* list_total;           // [batch] out
+  int* kmap;                 // [batch][cap_list] out: list entry -> input index within the image
+  int* host_kmap;            // the same in pinned host memory (results delivered by the kernels' own stores), or null
+  int cap_list;
+  int* overflow;             // word 0 is raised when an image's list would exceed cap_list (or a key passes more than two tests)
+};
+void launch_key_bin(hipStream_t st, const KeyBinJob& job, int batch);
 
 // Orientation (ComputeOrientation_Kernel, ProgramCU.cu:1221-1605): one wavefront per keypoint.
 void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const FeatureBuffers& fb, const float* got,

@@ -16,7 +16,7 @@ __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 
 // FLOAT_TO_FIXED_POINT (config.h:73-74): the n-bit fixed point of the feature records, packed by the orientation kernel
-// and, for a caller's keypoints, by the host (enqueue_user).
+// (a caller's keypoints: key_fixed, k_feature.hip, which keeps the host's result beyond the int range).
 __host__ __device__ __forceinline__ int float_to_fixed(float v, int n) {
   return (int)((double)(v * (float)(1 << n)) + ((v >= 0.0) ? 0.5 : -0.5));
 }

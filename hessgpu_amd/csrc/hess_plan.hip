@@ -176,11 +176,19 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   }
   ws &= ~3;  // TruncateWidthCU
   if (ws < 4 || hs < 1) { set_err(c, "image too small"); return HESS_ERR_ARG; }
+  const int need = user_mode(c) ? user_cap(c) : 0;  // records per image of a caller's lists (the largest of the batch)
   const bool same = c->planned && c->in_w == width && c->in_h == height && batch <= c->g.B &&
-                    (int)(2 * c->user_keys.size() + 8) <= c->cap_sel && (int)(2 * c->user_keys.size() + 8) <= c->cap_feat &&
+                    need <= c->cap_sel && need <= c->cap_feat &&
                     c->planned_format == c->desc_format;  // (the result buffers are sized in bytes of the format)
-  if (same) return 0;
   const int B = (c->planned && c->g.B > batch) ? c->g.B : batch;
+  if (user_mode(c)) {  // what key_bin_kernel reads and writes beside the list buffers (grow-only; most runs have no list)
+    int rc;
+    if ((rc = ensure(c, c->d_user, c->h_user.bytes))) return rc;
+    if ((rc = ensure(c, c->kmember, (size_t)B * c->user_max * 4))) return rc;
+    if ((rc = ensure(c, c->kmap, (size_t)B * need * 4))) return rc;
+    if ((rc = ensure(c, c->h_kmap, (size_t)B * need * 4, true))) return rc;
+  }
+  if (same) return 0;
 
   Geom g;
   memset(&g, 0, sizeof(g));
@@ -227,16 +235,14 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   int cap_raw = (int)(det_px / 32 < 16384 ? 16384 : det_px / 32);
   if (c->cap_init > 0) cap_raw = c->cap_init;  // developer switch: start small so that the grow-and-re-run path is taken
   if (cap_raw < c->cap_raw) cap_raw = c->cap_raw;
-  if (cap_raw < (int)(2 * c->user_keys.size() + 8)) cap_raw = (int)(2 * c->user_keys.size() + 8);
+  if (cap_raw < need) cap_raw = need;
   int cap_sel = c->use_topk ? p.feature_count_threshold : cap_raw;
   if (cap_sel > cap_raw) cap_sel = cap_raw;
   int cap_feat = c->multi ? (c->use_topk ? 4 * cap_sel : cap_sel) : cap_sel;
   if (cap_feat < c->cap_feat) cap_feat = c->cap_feat;
-  if (!c->user_keys.empty()) {  // a keypoint list bypasses top-K: every stage must hold 2*num+8 records
-    const int need = (int)(2 * c->user_keys.size() + 8);
-    if (cap_sel < need) cap_sel = need;
-    if (cap_feat < need) cap_feat = need;
-  }
+  // a keypoint list bypasses top-K: every stage must hold 2*num+8 records
+  if (cap_sel < need) cap_sel = need;
+  if (cap_feat < need) cap_feat = need;
 
   int rc;
   if ((rc = ensure(c, c->gauss, (size_t)lvl * 4))) return rc;

@@ -1,6 +1,5 @@
 // hess_schedule.hip -- the launch order of one batch on the context's stream (see hess_ctx.h).
 #include "hess_ctx.h"
-#include "hess_devmath.h"  // float_to_fixed
 
 namespace hess {
 
@@ -82,7 +81,7 @@ static inline float first_octave_sigma(const hess_ctx* c) {
   return c->ds > 0 ? (float)(1 << c->ds) : (c->ds < 0 ? 1.0f / (float)(1 << (-c->ds)) : 1.0f);
 }
 
-int enqueue_user(hess_ctx* c, int desc_format);
+int enqueue_user(hess_ctx* c, int batch, int desc_format);
 
 // Orientation stage (GetFeatureOrientations).  existing: a caller's keypoints -- position and scale as packed, one angle written.
 static OrientParams orient_params(const hess_ctx* c, bool existing) {
@@ -159,7 +158,7 @@ static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
   float* deth = (float*)c->deth.p;
   float* got = (float*)c->got.p;
   auto plane_ptr = [&](float* base, int o, int l) { return base + g.o[o].lvl_off + (long long)l * g.B * g.o[o].plane; };
-  const bool user_mode = !c->user_keys.empty();
+  const bool user_mode = hess::user_mode(c);
   const bool direct_u8 = (format == HESS_FMT_LUM && pixtype == HESS_PIX_U8 && c->ds == 0 && c->has_taps0 &&
                           (pitch % 4) == 0 && (image_stride % 4) == 0 && ((uintptr_t)dev % 4) == 0);
   const float* src_f = nullptr;
@@ -431,7 +430,7 @@ static int enqueue_detection(hess_ctx* c, int batch, const LimitParams& lp) {
 
 // ---- orientation (GetFeatureOrientations), multi-orientation expansion (ReshapeFeatureListCPU), descriptors
 // (GetFeatureDescriptors) over the list in c->d_list ----
-// user: a caller's keypoints (enqueue_user: one image, no expansion, one descriptor launch over its whole list); orient =
+// user: a caller's keypoints (enqueue_user: no expansion, one descriptor launch over the whole lists of all images); orient =
 // false: they came with their angle.
 static int enqueue_features(hess_ctx* c, const LimitParams& lp, int batch, int pixtype, int desc_format, bool user, bool orient) {
   const Geom& g = c->g;
@@ -460,7 +459,7 @@ static int enqueue_features(hess_ctx* c, const LimitParams& lp, int batch, int p
     dsp.first_image = first;
     dsp.part = parts.features ? k : 0;
     dsp.part_den = parts.features ? parts.n : 1;
-    launch_descriptor(st, g, dsp, fb, got, user ? 1 : parts.end[k] - first, user ? 0 : c->seen_features);
+    launch_descriptor(st, g, dsp, fb, got, user ? batch : parts.end[k] - first, user ? 0 : c->seen_features);
     if (k < parts.n - 1) HIP_TRY(c, hipEventRecord(c->cp.ev_part[k], st));
     if (!parts.features) first = parts.end[k];
   }
@@ -475,10 +474,10 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   // per-kernel profile.  An event record between two kernels leaves the stream idle for about 6 us.
   c->stage_events = (c->p.verbose & 2) != 0;
   HIP_TRY(c, hipEventRecord(c->ev[0], c->st));
-  const bool user_mode = !c->user_keys.empty();
+  const bool user_mode = hess::user_mode(c);
   if (!(user_mode && c->user_on_current))  // SIFT_SKIP_FILTERING: the resident pyramid is reused
     if (int rc = enqueue_pyramid(c, r)) return rc;
-  if (user_mode) return enqueue_user(c, r.desc_format);
+  if (user_mode) return enqueue_user(c, r.batch, r.desc_format);
   LimitParams lp;
   lp.method = c->p.truncate_method;
   lp.threshold = c->p.feature_count_threshold;
@@ -486,83 +485,87 @@ int enqueue(hess_ctx* c, const PendingRun& r) {
   return enqueue_features(c, lp, r.batch, r.pixtype, r.desc_format, false, true);
 }
 
-// User-supplied keypoints (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718): bin the keys to
-// levels by scale, pack fixed-point records on the host, upload, strongest orientation on the device
-// unless supplied, descriptors.  One image.
+// User-supplied keypoints (PyramidCU::GenerateFeatureListTex, PyramidCU.cpp:555-718), one list per image of the batch: the
+// keys go up as the caller gave them (they lie in the pinned block since the set call) together with the per-level table
+// of the scale rule, key_bin_kernel bins them to levels and packs the fixed-point records, then the strongest orientation
+// on the device unless supplied, descriptors.  Nothing here waits for the device.
 // Rectangles (HESS_KEYS_RECTANGLES; IsUsingRectDescription, SiftPyramid.cpp:345-354): (x, y) is the corner, s the width
 // and o the height; the scale that is binned is min(s, o) / 12 (PyramidCU.cpp:598-599), the record holds the width as the
 // scale's 8.8 fixed point and the height o / octave_sigma as it is, a float (:618-622); no orientation pass
 // (PyramidCU.cpp:522), and the descriptor launch is descriptor_rect_kernel's.
-int enqueue_user(hess_ctx* c, int desc_format) {
+size_t user_block_bytes(int total, int nimg) {
+  return (size_t)total * (sizeof(hess_keypoint) + 4) + (size_t)nimg * 8 + 16 + (size_t)kMaxOct * kMaxDog * sizeof(KeyLevel);
+}
+
+int enqueue_user(hess_ctx* c, int batch, int desc_format) {
   const hess_params& p = c->p;
   const Schedule& s = c->sch;
   const Geom& g = c->g;
   hipStream_t st = c->st;
-  const int num = (int)c->user_keys.size();
-  const double twopi = 2.0 * 3.14159265358979323846;
-  const bool rect = c->user_rect;
+  const int total = c->user_total, cap = user_cap(c);
+  static_assert(sizeof(hess_keypoint) == sizeof(HostKeypoint), "keypoint layout");
+  if (cap > c->cap_raw || cap > c->cap_sel || cap > c->cap_feat || c->h_user.bytes < user_block_bytes(total, batch) ||
+      c->d_user.bytes < c->h_user.bytes) {
+    set_err(c, "keypoint lists (%d per image) exceed the reserved feature storage", cap);
+    return HESS_ERR_NOMEM;  // plan() sizes storage for 2*num+8 when a list is set
+  }
+  // the block behind the keys: (first, count) per image, the parity hook's levels (one image), the level table
+  char* const hb = (char*)c->h_user.p;
+  size_t at = (size_t)total * sizeof(hess_keypoint);
+  const size_t o_first = at;
+  int* const fc = (int*)(hb + at);
+  for (int b = 0, first = 0; b < batch; b++) {
+    fc[2 * b] = first;
+    fc[2 * b + 1] = c->user_counts[b];
+    first += c->user_counts[b];
+  }
+  at += (size_t)batch * 8;
+  const bool given = batch == 1 && (int)c->user_levels.size() == total;
+  const size_t o_levels = at;
+  if (given) {
+    memcpy(hb + at, c->user_levels.data(), (size_t)total * 4);
+    at += (size_t)total * 4;
+  }
+  at = (at + 15) & ~(size_t)15;
+  const size_t o_table = at;
+  KeyLevel* const table = (KeyLevel*)(hb + at);
   const float sigma_half_step = powf(2.0f, 0.5f / g.dog);
   float octave_sigma = first_octave_sigma(c);
-  const float offset = p.lowe_origin ? 0.0f : 0.5f;
-  std::vector<RawKey> hl;
-  std::vector<FRec> hr;
-  c->user_kindex.clear();
-  const size_t cap = 2 * (size_t)num + 8;
   for (int octave = 0; octave < g.noct; octave++, octave_sigma *= 2.0f) {
     for (int level = 1; level <= g.dog; level++) {
       const float level_sigma = s.level_sigma[level] * octave_sigma;
-      const float sigma_min = level_sigma / sigma_half_step;
-      const float sigma_max = level_sigma * sigma_half_step;
-      for (int k = 0; k < num && hl.size() < cap; k++) {
-        const hess_keypoint& key = c->user_keys[k];
-        float sigmak = rect ? (key.s < key.o ? key.s : key.o) / 12.0f : key.s;
-        if ((int)c->user_levels.size() == num && c->user_levels[k] >= 0) {  // parity hook: level given, not derived
-          if (c->user_levels[k] != octave * g.dog + (level - 1)) continue;
-          sigmak = level_sigma;
-        }
-        if (((sigmak >= sigma_min) && (sigmak < sigma_max)) || ((sigmak < sigma_min) && (octave == 0) && (level == 1)) ||
-            ((sigmak > sigma_max) && (octave == g.noct - 1) && (level == g.dog))) {
-          const float fX = (key.x - offset) / octave_sigma + 0.5f;
-          const float fY = (key.y - offset) / octave_sigma + 0.5f;
-          const float fScale = key.s / octave_sigma;
-          const float fOrientation = rect ? key.o / octave_sigma : (float)fmod(twopi - key.o, twopi);
-          FRec r;
-          r.x = (uint32_t)float_to_fixed(fX, 10) & 0x00FFFFFFu;
-          r.y = (uint32_t)float_to_fixed(fY, 10) & 0x00FFFFFFu;
-          r.z = (uint32_t)float_to_fixed(fScale, 8) & 0x0000FFFFu;
-          memcpy(&r.w, &fOrientation, 4);
-          RawKey rk;
-          memset(&rk, 0, sizeof(rk));
-          rk.level_index = octave * g.dog + (level - 1);
-          hl.push_back(rk);
-          hr.push_back(r);
-          c->user_kindex.push_back(k);
-        }
-      }
+      table[octave * g.dog + (level - 1)] = KeyLevel{level_sigma / sigma_half_step, level_sigma * sigma_half_step, octave_sigma, level_sigma};
     }
   }
-  const int n = (int)hl.size();
-  if (n > c->cap_raw || n > c->cap_sel || n > c->cap_feat) {
-    set_err(c, "keypoint list (%d) exceeds the reserved feature storage", n);
-    return HESS_ERR_NOMEM;  // plan() sizes storage for 2*num+8 when a list is set
-  }
-  int* hs = (int*)c->h_small.p;
-  hs[3 * g.B + 4] = n;
+  at += (size_t)g.nlev * sizeof(KeyLevel);
+  const char* const db = (const char*)c->d_user.p;
+  HIP_TRY(c, hipMemcpyAsync(c->d_user.p, hb, at, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(c->overflow.p, 0, 64, st));  // overflow words + feature_scan_kernel's arrival counter
-  if (n) {
-    HIP_TRY(c, hipMemcpyAsync(c->raw.p, hl.data(), (size_t)n * sizeof(RawKey), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->recs.p, hr.data(), (size_t)n * sizeof(FRec), hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->raw_total.p, hs + 3 * g.B + 4, 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipStreamSynchronize(st));  // hl/hr are pageable host vectors: finish before they go away
+  HIP_TRY(c, hipMemsetAsync(c->level_count.p, 0, (size_t)batch * g.nlev * 4, st));
   c->d_list = (const RawKey*)c->raw.p;
   c->d_list_total = (const int*)c->raw_total.p;
-  c->cap_list = c->cap_raw;
+  c->cap_list = cap;
+  KeyBinJob job;
+  job.keys = (const HostKeypoint*)db;
+  job.first_count = (const int*)(db + o_first);
+  job.levels = given ? (const int*)(db + o_levels) : nullptr;
+  job.table = (const KeyLevel*)(db + o_table);
+  job.total = total; job.max_count = c->user_max; job.nlev = g.nlev;
+  job.rect = c->user_rect ? 1 : 0;
+  job.origin = p.lowe_origin ? 0.0f : 0.5f;
+  job.member = (int*)c->kmember.p;
+  job.level_count = (int*)c->level_count.p;
+  job.list = (RawKey*)c->raw.p; job.recs = (FRec*)c->recs.p; job.list_total = (int*)c->raw_total.p;
+  job.kmap = (int*)c->kmap.p;
+  job.host_kmap = c->host_direct ? (int*)c->h_kmap.p : nullptr;
+  job.cap_list = cap;
+  job.overflow = (int*)c->overflow.p;
+  launch_key_bin(st, job, batch);
   if (c->stage_events) for (int e = 1; e <= 4; e++) HIP_TRY(c, hipEventRecord(c->ev[e], st));
   LimitParams lp;
   lp.method = 0;
   lp.threshold = -1;  // LimitFeatureCount returns at once for existing keypoints (SiftPyramid.cpp:203)
-  return enqueue_features(c, lp, 1, HESS_PIX_U8, desc_format, true, !c->user_have_orientation);
+  return enqueue_features(c, lp, batch, HESS_PIX_U8, desc_format, true, !c->user_have_orientation);
 }
 
 

@@ -246,6 +246,125 @@ __global__ __launch_bounds__(1024) void feature_scan_kernel(Geom g, FeatScan fs,
   feature_scan_image(g, fs, list, list_total, cap_list, ocount, (int)blockIdx.y, (int)gridDim.y, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// ================================= a caller's keypoints: binning to levels =====================
+
+// (first, count) of image b's keys, held inside [0, total) and to the capacity the scratch arrays were sized for: the block
+// comes from pinned host memory that the caller's next hess_set_keypoints rewrites.
+__device__ __forceinline__ void key_range(const KeyBinJob& j, int b, int* first, int* count) {
+  const int f = min(max(j.first_count[2 * b], 0), j.total);
+  *first = f;
+  *count = min(max(j.first_count[2 * b + 1], 0), min(j.max_count, j.total - f));
+}
+
+// float_to_fixed as the HOST evaluates it.  The records were packed by the host until this kernel took over, and the test
+// oracle still packs them there: a value beyond the int range (a scale of 1e7, an infinite coordinate) or a NaN converts to
+// INT_MIN on the host and saturates (NaN: 0) on the device, and the masked record would differ.
+__device__ __forceinline__ int key_fixed(float v, int n) {
+  const double d = (double)(v * (float)(1 << n)) + ((v >= 0.0) ? 0.5 : -0.5);
+  return (d > -2147483649.0 && d < 2147483648.0) ? (int)d : (int)0x80000000u;
+}
+
+// Pass 1, one thread per key: the levels whose test the key passes (the host loop's test, PyramidCU.cpp:600-603, level by
+// level) as level + 1 in the low and the high half of one word, and the number of keys per (image, level).
+// At most two levels: the ranges [ls / h, ls * h) have ls growing by h^2 >= 2^0.1 per level, so only neighbours can overlap
+// (by the rounding of their bounds); the catch-alls (below the first level's range, above the last one's) exclude each
+// other and, with increasing bounds, every range but their own level's.  That is also why an image's list stays below its
+// capacity 2 * count + 8, and the host loop's cut at that length never applied.  Should a parameter set break the argument,
+// the third hit raises the overflow word instead of being dropped silently.
+__global__ __launch_bounds__(256) void key_level_kernel(KeyBinJob j) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  int first, count;
+  key_range(j, b, &first, &count);
+  if (i >= count) return;
+  const HostKeypoint key = j.keys[first + i];
+  const float s = j.rect ? (key.s < key.o ? key.s : key.o) / 12.0f : key.s;  // PyramidCU.cpp:598-599
+  const int given = j.levels ? j.levels[i] : -1;  // parity hook: level given, not derived
+  int m = 0, hits = 0;
+  for (int lv = 0; lv < j.nlev; lv++) {
+    const KeyLevel t = j.table[lv];
+    float sigmak = s;
+    if (given >= 0) {
+      if (given != lv) continue;
+      sigmak = t.level_sigma;
+    }
+    if (((sigmak >= t.sigma_min) && (sigmak < t.sigma_max)) || ((sigmak < t.sigma_min) && lv == 0) ||
+        ((sigmak > t.sigma_max) && lv == j.nlev - 1)) {
+      if (hits < 2) {
+        m |= (lv + 1) << (16 * hits);
+        atomicAdd(j.level_count + b * j.nlev + lv, 1);
+      }
+      hits++;
+    }
+  }
+  j.member[(long long)b * j.max_count + i] = m;
+  if (hits > 2) atomicMax(j.overflow, j.cap_list + 1);
+}
+
+// Pass 2, one wavefront per (image, level): the level's entries start behind those of the levels below (the counts of
+// pass 1); the wavefront walks the image's keys in input order, 64 at a time, and a key of this level takes the place
+// given by the ballot of the keys before it -- level ascending, then input index ascending, whatever order the
+// wavefronts run in.  The walk is a chain of dependent steps on one wavefront, so it does nothing but compact: it writes
+// the entry's RawKey and its map entry and loads no key; the records are pass 3's.
+__global__ __launch_bounds__(64) void key_bin_kernel(KeyBinJob j) {
+  const int lv = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  int first, count;
+  key_range(j, b, &first, &count);
+  int off = 0;
+  for (int l = lane; l < lv; l += 64) off += j.level_count[b * j.nlev + l];
+  off = __builtin_amdgcn_readlane(wave_inclusive_scan(off), 63);
+  const int* const member = j.member + (long long)b * j.max_count;
+  constexpr int KU = 4;  // steps of 64 keys whose level words are loaded together: the walk is a chain of load latencies
+  for (int base = 0; base < count; base += 64 * KU) {
+    int m[KU];
+#pragma unroll
+    for (int u = 0; u < KU; u++) {
+      const int i = base + u * 64 + lane;
+      m[u] = i < count ? member[i] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < KU; u++) {
+      const bool hit = (m[u] & 0xFFFF) == lv + 1 || (m[u] >> 16) == lv + 1;
+      const unsigned long long hits = __builtin_amdgcn_ballot_w64(hit);
+      const int pos = off + __builtin_popcountll(hits & ((1ull << lane) - 1ull));
+      if (hit && pos < j.cap_list) {
+        const long long at = (long long)b * j.cap_list + pos;
+        const RawKey rk = {lv, 0, 0, 0u, 0.0f, 0.0f, 0.0f, 0u};
+        j.list[at] = rk;
+        j.kmap[at] = base + u * 64 + lane;
+        if (j.host_kmap) j.host_kmap[at] = base + u * 64 + lane;
+      }
+      off += __builtin_popcountll(hits);
+    }
+  }
+  if (lv == j.nlev - 1 && lane == 0) {  // the last level's wavefront knows the image's total
+    if (off > j.cap_list) { atomicMax(j.overflow, off); off = j.cap_list; }
+    j.list_total[b] = off;
+  }
+}
+
+// Pass 3, one thread per list entry: the entry's fixed-point record from its key and its level -- the host loop's
+// expressions (PyramidCU.cpp:605-657), binary32 except the angle.
+__global__ __launch_bounds__(256) void key_record_kernel(KeyBinJob j) {
+  const int b = blockIdx.y, pos = blockIdx.x * 256 + threadIdx.x;
+  int first, count;
+  key_range(j, b, &first, &count);
+  if (pos >= min(j.list_total[b], j.cap_list)) return;
+  const long long at = (long long)b * j.cap_list + pos;
+  const int i = min(max(j.kmap[at], 0), count - 1), lv = min(max(j.list[at].level_index, 0), j.nlev - 1);  // (as written by pass 2)
+  const KeyLevel t = j.table[lv];
+  const HostKeypoint key = j.keys[first + i];
+  const float fX = (key.x - j.origin) / t.octave_sigma + 0.5f;
+  const float fY = (key.y - j.origin) / t.octave_sigma + 0.5f;
+  const float fScale = key.s / t.octave_sigma;
+  const float fOrientation = j.rect ? key.o / t.octave_sigma : (float)fmod(2.0 * kPI - (double)key.o, 2.0 * kPI);
+  FRec r;
+  r.x = (uint32_t)key_fixed(fX, 10) & 0x00FFFFFFu;
+  r.y = (uint32_t)key_fixed(fY, 10) & 0x00FFFFFFu;
+  r.z = (uint32_t)key_fixed(fScale, 8) & 0x0000FFFFu;
+  r.w = __float_as_uint(fOrientation);
+  j.recs[at] = r;
+}
+
 // ================================= orientation ===============================================
 
 // e^x for the Gaussian windows of the orientation and descriptor stages: same operations and results as dm_expf() on -87 <= x <= 88 (there
@@ -1261,6 +1380,14 @@ __global__ __launch_bounds__(256) void descriptor_rect_kernel(Geom g, DescParams
 }
 
 }  // namespace
+
+void launch_key_bin(hipStream_t st, const KeyBinJob& job, int batch) {
+  if (job.max_count > 0)
+    hipLaunchKernelGGL(key_level_kernel, dim3((job.max_count + 255) / 256, batch), dim3(256), 0, st, job);
+  hipLaunchKernelGGL(key_bin_kernel, dim3(job.nlev, batch), dim3(64), 0, st, job);
+  if (job.max_count > 0)
+    hipLaunchKernelGGL(key_record_kernel, dim3((job.cap_list + 255) / 256, batch), dim3(256), 0, st, job);
+}
 
 void launch_orientation(hipStream_t st, const Geom& g, const OrientParams& op, const FeatureBuffers& fb, const float* got,
                         int batch) {

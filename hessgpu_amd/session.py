@@ -169,6 +169,39 @@ class Session:
         self._check(self._f["run_keypoints"](self._h, k.ctypes.data_as(C.c_void_p), len(k), int(have_orientation)))
         return self.count(0)
 
+    @staticmethod
+    def _key_lists(keys_per_image):
+        """A sequence of KEYPOINT_DTYPE arrays, one per image -> (the keys back to back, the counts as a C array)."""
+        lists = [np.ascontiguousarray(k, dtype=_abi.KEYPOINT_DTYPE).reshape(-1) for k in keys_per_image]
+        allk = np.concatenate(lists) if lists else np.zeros(0, dtype=_abi.KEYPOINT_DTYPE)
+        return np.ascontiguousarray(allk), (C.c_int * len(lists))(*[len(k) for k in lists])
+
+    def set_keypoints_batch(self, keys_per_image, have_orientation=True):
+        """hess_set_keypoints_batch: one keypoint list per image of the next run() / submit_*(), whose batch must be
+        len(keys_per_image); an empty list gives that image no results.  have_orientation as for set_keypoints (product
+        only).  Rectangles: rect_keys per image with _abi.KEYS_RECTANGLES."""
+        k, counts = self._key_lists(keys_per_image)
+        self._check(self._f["set_keypoints_batch"](self._h, k.ctypes.data_as(C.c_void_p), counts, len(counts),
+                                                   int(have_orientation)))
+
+    def run_keypoints_batch(self, keys_per_image, have_orientation=True):
+        """hess_run_keypoints_batch: the lists on the current batch (one per image of the last run), without rebuilding its
+        pyramids -> the counts (product only)."""
+        k, counts = self._key_lists(keys_per_image)
+        self._check(self._f["run_keypoints_batch"](self._h, k.ctypes.data_as(C.c_void_p), counts, len(counts),
+                                                   int(have_orientation)))
+        self._batch = len(counts)
+        return [self.count(i) for i in range(len(counts))]
+
+    def key_list_order(self, img=0):
+        """After a keypoint-list run: int32 array, list position -> input index, of image img's list -- the order of its
+        records in device_results() (level, then input index; product only, hess_key_list_order)."""
+        n = self._check(self._f["key_list_order"](self._h, img, None, 0))
+        out = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self._f["key_list_order"](self._h, img, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
     def debug_key_levels(self, levels=None):
         """Parity hook: explicit level index per user keypoint for the following set/run_keypoints (None clears)."""
         if levels is None:

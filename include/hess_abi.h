@@ -41,7 +41,10 @@ extern "C" {
  *    hess_matcher_bank_set_device_u8 (byte descriptors; added during version 5 without a bump: hess_params keeps its
  *    layout, and a context that never calls the setter behaves as before).  hess_matcher_set_dim / hess_matcher_dim
  *    (64-d descriptors of a half_sift run in the matcher; added during version 5 without a bump: a matcher that never
- *    calls the setter is 128-d as before). */
+ *    calls the setter is 128-d as before).  hess_set_keypoints_batch / hess_run_keypoints_batch / hess_key_list_order
+ *    (keypoint lists for every image of a batch; added during version 5 without a bump: hess_set_keypoints and
+ *    hess_run_keypoints are the same calls with one image and answer as before, except that hess_set_keypoints now
+ *    refuses while a submitted batch is pending, where it used to corrupt that batch's results). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -293,11 +296,37 @@ enum { HESS_KEYS_NONE = 0, HESS_KEYS_ORIENTED = 1, HESS_KEYS_RECTANGLES = -1 };
  * NEXT hess_run_* call (one image) skips detection and computes orientation (unless
  * keys_have_orientation) and descriptors for these keypoints (PyramidCU::GenerateFeatureListTex,
  * PyramidCU.cpp:555-718); results come back in input order; the list is cleared afterwards.
+ * HESS_ERR_STATE while a submitted batch is pending.
  * keys_have_orientation: HESS_KEYS_NONE, HESS_KEYS_ORIENTED (any non-zero value but -1) or HESS_KEYS_RECTANGLES. */
 int hess_set_keypoints(hess_ctx* ctx, const hess_keypoint* keys, int num, int keys_have_orientation);
 /* Replaces SiftGPU::RunSIFT(num, keys, keys_have_orientation) (SiftGPU.cpp:307-315): the same on the
  * CURRENT image (first image of the last run) without rebuilding the pyramid. */
 int hess_run_keypoints(hess_ctx* ctx, const hess_keypoint* keys, int num, int keys_have_orientation);
+
+/* Keypoint lists for every image of a batch (no reference counterpart: its list belongs to the one image it holds).
+ * keys: the lists back to back, counts[b] >= 0 keys for image b (0: that image has no results), nimg images.  The NEXT
+ * hess_run_host / hess_run_device / hess_submit_host / hess_submit_device must have batch == nimg: any other batch fails
+ * with HESS_ERR_ARG and a text naming both numbers before anything is enqueued, and the lists stay pending.  The keys are
+ * copied by the call; they are binned to levels on the device (key_bin_kernel, csrc/k_feature.hip: the scale rule of
+ * hess_set_keypoints, the same bits), so a submitted list batch overlaps with the batches of other contexts like any
+ * other.  Per image everything is as after hess_set_keypoints with that image alone: hess_count(b) == counts[b], keys
+ * and descriptors in input order (zeros for a key whose scale is NaN), keys_have_orientation as there
+ * (HESS_KEYS_RECTANGLES included); the lists are cleared by the run.  A total of 0 keys clears pending lists.
+ *   HESS_ERR_ARG    ctx or counts NULL, nimg <= 0, a negative count, keys NULL with a total above 0
+ *   HESS_ERR_STATE  a submitted batch is pending, or a hess_debug_key_levels override is (the hook covers the list of a
+ *                   single image: hess_set_keypoints) */
+int hess_set_keypoints_batch(hess_ctx* ctx, const hess_keypoint* keys, const int* counts, int nimg, int keys_have_orientation);
+/* The same on the CURRENT batch, whose pyramids are resident, without rebuilding them (hess_run_keypoints for every image
+ * of the last run): nimg must equal the batch of the last run (HESS_ERR_ARG otherwise; HESS_ERR_STATE without a current
+ * batch), the total must be above 0.  The descriptor format is the one set now, as for hess_run_keypoints. */
+int hess_run_keypoints_batch(hess_ctx* ctx, const hess_keypoint* keys, const int* counts, int nimg, int keys_have_orientation);
+/* After a keypoint-list run (any of the four calls above): the LIST of image img -- its keys in the order the device holds
+ * their records: level index ascending, then input index ascending; a key is listed once, twice where the rounded bounds
+ * of two neighbouring levels overlap at its scale, or not at all (a NaN scale).  Returns the list's length and writes up
+ * to cap entries of the map list position -> input index (0 .. count - 1 of that image) to out (out may be NULL with
+ * cap == 0).  hess_device_results after such a run hands out list-order records, which this map assigns to the caller's
+ * keys.  HESS_ERR_STATE when the last run had no list. */
+int hess_key_list_order(hess_ctx* ctx, int img, int* out, int cap);
 
 /* Replaces SiftGPU::GetFeatureNum (SiftGPU.cpp:1551-1554) for image `img` of the last batch. */
 int hess_count(hess_ctx* ctx, int img);
@@ -335,6 +364,9 @@ int hess_fetch_u8(hess_ctx* ctx, int img, hess_keypoint* keys, unsigned char* de
  * gather over RCCL): keys = [total] hess_keypoint, desc = [total][dim] float -- unsigned char [total][dim] after a
  * HESS_DESC_FORMAT_U8 run (hess_desc_format tells) --, the images of the
  * batch back to back (image b starts at hess_count(0)+..+hess_count(b-1)); *total = records in use.
+ * After a keypoint-list run the records are in LIST order, not in the caller's: image b starts at the sum of the list
+ * lengths of the images before it, and hess_key_list_order gives each list's length and its map to the caller's keys
+ * (hess_count and hess_fetch speak of the input order).
  * Pointers stay valid until the next run. */
 int hess_device_results(hess_ctx* ctx, const void** keys, const void** desc, int* total);
 
