@@ -150,21 +150,7 @@ static int refuse_poisoned(hess_ctx* c) {
 static int prime(hess_ctx* c, int width, int height, int batch) {
   if (c->run.active) return 0;
   choose_delivery(c, batch);
-  if (c->delivery == kDeliverDma && c->batch == 0 && c->keys.p && c->h_keys.p && c->h_keys.bytes >= 64 && !c->cp.has_job) {
-    Copier& cp = c->cp;
-    if (copier_hsa_setup(c)) {
-      auto tiny = [&](hsa_signal_t sig, void* dst, const void* src) {
-        hsa_signal_store_relaxed(sig, 1);
-        hsa_status_t st = cp.engine
-            ? hsa_amd_memory_async_copy_on_engine(dst, cp.cpu_agent, src, cp.gpu_agent, 64, 0, nullptr, sig,
-                                                  (hsa_amd_sdma_engine_id_t)cp.engine, false)
-            : hsa_amd_memory_async_copy(dst, cp.cpu_agent, src, cp.gpu_agent, 64, 0, nullptr, sig);
-        if (st == HSA_STATUS_SUCCESS && wait_copy_signal(sig, 1, nullptr, false) != 0) { cp.hsa_ready = false; cp.hsa_failed = true; }
-      };
-      tiny(cp.sig, c->h_keys.p, c->keys.p);
-      if (cp.hsa_ready && c->dim && c->desc.p && c->h_desc.p && c->h_desc.bytes >= 64) tiny(cp.sig2, c->h_desc.p, c->desc.p);
-    }
-  }
+  copier_warm_up(c);
   if (c->zeroed.p && c->zeroed.bytes >= 64) {
     HIP_TRY(c, hipMemsetAsync(c->zeroed.p, 0, 64, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
@@ -335,89 +321,12 @@ int hess_submit_host(hess_ctx* c, const void* pixels, int width, int height, int
                       .pixtype = pixtype, .image_stride = image_stride, .desc_format = c->desc_format};  // (the pixels will be in the staging area)
   hipPointerAttribute_t at;
   const bool pinned = hipPointerGetAttributes(&at, pixels) == hipSuccess && at.type == hipMemoryTypeHost;
-  if (pinned && !c->no_host_upload) {
-    // Pinned pixels of a batch that the copier thread will deliver: the upload goes to an SDMA engine directly and
-    // the copier thread enqueues the kernels once it has landed (Copier::upload_first).  A copy command on the
-    // context's stream would hold its hardware queue -- shared with other contexts -- for the length of the
-    // transfer: 15.9 - 16.2 against 17.0 Gpix/s for six pipelined contexts, while the same bytes uploaded on the side
-    // cost nothing (tools/r03/r03_h2d_bg.py).
-    if ((rc = plan(c, width, height, batch))) return rc;
-    choose_delivery(c, batch);
-    Copier& cp = c->cp;
-    hsa_amd_pointer_info_t pi;
-    memset(&pi, 0, sizeof(pi));
-    pi.size = sizeof(pi);
-    if (c->delivery == kDeliverDma && copier_hsa_setup(c) &&
-        hsa_amd_pointer_info(const_cast<void*>(pixels), &pi, nullptr, nullptr, nullptr) == HSA_STATUS_SUCCESS &&
-        pi.type != HSA_EXT_POINTER_TYPE_UNKNOWN &&
-        (cp.have_sig_in || hsa_signal_create(1, 0, nullptr, &cp.sig_in) == HSA_STATUS_SUCCESS)) {
-      cp.have_sig_in = true;
-      hsa_signal_store_relaxed(cp.sig_in, 1);
-      hsa_status_t up = cp.engine_in
-          ? hsa_amd_memory_async_copy_on_engine(c->stage.p, cp.gpu_agent, pixels, pi.agentOwner, bytes, 0, nullptr, cp.sig_in,
-                                                (hsa_amd_sdma_engine_id_t)cp.engine_in, false)
-          : HSA_STATUS_ERROR;
-      if (up != HSA_STATUS_SUCCESS)  // no engine chosen, or busy / not available: let ROCr choose
-        up = hsa_amd_memory_async_copy(c->stage.p, cp.gpu_agent, pixels, pi.agentOwner, bytes, 0, nullptr, cp.sig_in);
-      if (up == HSA_STATUS_SUCCESS) {
-        c->last_input_bytes = bytes;
-        copier_post(c, &c->run, true);
-        c->run.active = true;
-        return 0;
-      }
-    }
-  }
-  HIP_TRY(c, hipEventRecord(c->ev_load[0], c->st));
-  if (pinned) {
-    HIP_TRY(c, hipMemcpyAsync(c->stage.p, pixels, bytes, hipMemcpyHostToDevice, c->st));
-  } else {
-    (void)hipGetLastError();  // an unregistered pointer is reported as an error: not one
-    if ((rc = ensure(c, c->h_stage, bytes, true))) return rc;
-    // Pageable memory: copied into the pinned staging buffer in chunks, each chunk's transfer enqueued as soon as
-    // it is staged, so the copy engine works while the next chunks are being copied (one core copies at about
-    // 17 GB/s, a third of what the link takes: the context's helper threads share the work, see Stager).
-    // 4 MB chunks; a small input (one image) is cut in four so that its transfer, too, overlaps its staging, and is
-    // staged by the calling thread alone: waking the helpers costs more than they save below about 8 MB (one 1080p
-    // image: 0.544 ms per call alone, 0.58 ms with helpers; profiles/r03_host_path.json).
-    // Nothing here allocates or throws once the helpers exist (nothing thrown crosses the C ABI).
-    Stager& sg = c->sg;
-    const size_t chunk = std::min<size_t>((size_t)4 << 20, std::max<size_t>((size_t)256 << 10, ((bytes / 4 + 65535) >> 16) << 16));
-    const int nchunk = (int)((bytes + chunk - 1) / chunk);
-    const bool helped = bytes >= policy::kStagerHelpFrom && nchunk > 1;
-    if (helped) stager_start(sg);
-    try {
-      if ((int)sg.state.size() < nchunk) { std::vector<std::atomic<int>> grown(nchunk); sg.state.swap(grown); }
-    } catch (...) { set_err(c, "out of memory"); return HESS_ERR_NOMEM; }
-    {
-      std::lock_guard<std::mutex> lk(sg.mu);
-      for (int k = 0; k < nchunk; k++) sg.state[k].store(0, std::memory_order_relaxed);
-      sg.src = (const char*)pixels; sg.dst = (char*)c->h_stage.p; sg.bytes = bytes; sg.chunk = chunk; sg.nchunk = nchunk;
-      sg.next_hi.store(helped ? nchunk - 1 : -1, std::memory_order_release);
-      sg.active = helped ? sg.nth : 0;
-      if (helped && sg.nth) sg.gen++;
-    }
-    if (helped && sg.nth) sg.cv_job.notify_all();
-    hipError_t cerr = hipSuccess;
-    for (int k = 0; k < nchunk; k++) {
-      int expect = 0;
-      if (sg.state[k].compare_exchange_strong(expect, 1, std::memory_order_acq_rel)) stager_copy(sg, k);
-      else if (sg.state[k].load(std::memory_order_acquire) != 2) {
-        std::unique_lock<std::mutex> lk(sg.mu);
-        sg.cv_done.wait(lk, [&] { return sg.state[k].load(std::memory_order_acquire) == 2; });
-      }
-      const size_t off = (size_t)k * chunk, len = std::min(chunk, bytes - off);
-      if (cerr == hipSuccess)
-        cerr = hipMemcpyAsync((char*)c->stage.p + off, (const char*)c->h_stage.p + off, len, hipMemcpyHostToDevice, c->st);
-    }
-    {  // the helpers are done with this job's bookkeeping before the next one rewrites it
-      std::unique_lock<std::mutex> lk(sg.mu);
-      sg.cv_done.wait(lk, [&] { return sg.active == 0; });
-    }
-    HIP_TRY(c, cerr);
-  }
-  HIP_TRY(c, hipEventRecord(c->ev_load[1], c->st));
-  c->last_input_bytes = bytes;
-  c->run.timed_load = true;
+  // The route (hess_copier.hip): pinned pixels of a batch the copier thread delivers are uploaded beside the queues, and that
+  // thread submits the batch; everything else crosses on the context's stream, pageable pixels through the stager's threads.
+  bool taken = false;
+  if (pinned && (rc = upload_beside_queues(c, pixels, bytes, &taken))) return rc;
+  if (taken) return 0;
+  if ((rc = upload_on_stream(c, pixels, bytes, pinned))) return rc;
   rc = submit_impl(c, c->run);
   if (rc) return rc;
   c->run.active = true;

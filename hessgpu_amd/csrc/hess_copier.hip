@@ -1,53 +1,7 @@
-// hess_copier.hip -- pixels in, results out: stager threads, the copier thread, submit / wait (see hess_ctx.h).
+// hess_copier.hip -- pixels in, results out: the input routes, the copier thread, submit / wait (see hess_ctx.h).
 #include "hess_ctx.h"
 
 namespace hess {
-
-// ---- staging helpers (hess_submit_host, pageable input) ----
-void stager_copy(Stager& sg, int k) {
-  const size_t off = (size_t)k * sg.chunk, len = std::min(sg.chunk, sg.bytes - off);
-  memcpy(sg.dst + off, sg.src + off, len);
-  { std::lock_guard<std::mutex> lk(sg.mu); sg.state[k].store(2, std::memory_order_release); }
-  sg.cv_done.notify_all();
-}
-
-void stager_main(Stager* sgp) {
-  Stager& sg = *sgp;
-  unsigned long long seen = 0;
-  std::unique_lock<std::mutex> lk(sg.mu);
-  for (;;) {
-    sg.cv_job.wait(lk, [&] { return sg.stop || sg.gen != seen; });
-    if (sg.stop) return;
-    seen = sg.gen;
-    lk.unlock();
-    for (;;) {
-      const int k = sg.next_hi.fetch_sub(1, std::memory_order_acq_rel);
-      if (k < 0) break;
-      int expect = 0;
-      if (sg.state[k].compare_exchange_strong(expect, 1, std::memory_order_acq_rel)) stager_copy(sg, k);
-      else break;  // met the calling thread coming up: everything is claimed
-    }
-    lk.lock();
-    sg.active--;
-    sg.cv_done.notify_all();
-  }
-}
-
-void stager_start(Stager& sg) {
-  if (sg.tried) return;
-  sg.tried = true;
-  for (int t = 0; t < Stager::kHelpers; t++) {
-    try { sg.th[sg.nth] = std::thread(stager_main, &sg); sg.nth++; } catch (...) { break; }  // fewer helpers: the caller copies more
-  }
-}
-
-void stager_stop(Stager& sg) {
-  if (!sg.nth) return;
-  { std::lock_guard<std::mutex> lk(sg.mu); sg.stop = true; }
-  sg.cv_job.notify_all();
-  for (int t = 0; t < sg.nth; t++) sg.th[t].join();
-  sg.nth = 0;
-}
 
 // ---- copier thread (kDeliverDma) ----
 // One job at a time: wait on the host for the event behind the batch's last kernel, read the packed total from the
@@ -56,7 +10,7 @@ std::atomic<int> g_copier_count{0};  // contexts with a copier, for spreading th
 
 // Bind the copier to ROCr: the agents that own the result buffers (from the pointers themselves), an SDMA engine of
 // the set ROCr recommends for device->host on this pair of agents (contexts take turns), a completion signal.
-bool copier_hsa_setup(hess_ctx* c) {
+static bool copier_hsa_setup(hess_ctx* c) {
   Copier& cp = c->cp;
   if (cp.hsa_ready) return true;
   if (cp.hsa_failed) return false;
@@ -108,7 +62,7 @@ bool copier_hsa_setup(hess_ctx* c) {
 // is the signal's own: then the copy may still be in flight and the context is poisoned (HESS_COPIER_FAULT=poisoned
 // reports a timeout as if it were real, after the copy has in fact completed).
 std::atomic<int> g_copier_fault{-1};  // -1: not read yet, 0: none, 1: timeout, 2: error, 3: poisoned (consumed by the first wait)
-int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_value_t* last, bool injectable, bool* real) {
+static int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_value_t* last, bool injectable, bool* real) {
   if (real) *real = false;
   static const double limit_s = [] { const char* e = getenv("HESS_COPY_TIMEOUT_S"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 10.0; }();
   static const uint64_t ticks_per_s = [] {
@@ -146,46 +100,167 @@ int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_valu
   return v < 0 ? 2 : 0;
 }
 
-// keys + descriptors of features [first, first + total) to the pinned host buffers by SDMA.  0: done; 1: ROCr refused
-// to take the copy, use the fallback; 2: a copy was taken and did not complete (timeout or error, `why`): the batch fails.
-int copier_hsa_copy(hess_ctx* c, size_t first, size_t total, char* why, size_t why_len) {
-  Copier& cp = c->cp;
-  const size_t db = run_desc_bytes(c, cp.run->desc_format);
-  hsa_signal_value_t seen = 0;
-  bool real = false;
-  auto lost = [&](int w) {
-    snprintf(why, why_len, "device->host copy of the results %s (signal value %lld, engine 0x%x)",
-             w == 1 ? "did not complete in time" : "failed", (long long)seen, cp.engine);
-    cp.hsa_ready = false; cp.hsa_failed = true;  // later batches take the stream copy; the signals are not reused
-    if (real) c->poisoned.store(true);           // the copy may still land: see hess_ctx::poisoned
-    return 2;
-  };
-  auto one = [&](hsa_signal_t sig, void* dst, const void* src, size_t bytes) {
-    hsa_signal_store_relaxed(sig, 1);
-    hsa_status_t st = cp.engine
-        ? hsa_amd_memory_async_copy_on_engine(dst, cp.cpu_agent, src, cp.gpu_agent, bytes, 0, nullptr, sig,
-                                              (hsa_amd_sdma_engine_id_t)cp.engine, false)
-        : hsa_amd_memory_async_copy(dst, cp.cpu_agent, src, cp.gpu_agent, bytes, 0, nullptr, sig);
-    if (st != HSA_STATUS_SUCCESS && cp.engine)  // engine busy or not available: let ROCr choose
-      st = hsa_amd_memory_async_copy(dst, cp.cpu_agent, src, cp.gpu_agent, bytes, 0, nullptr, sig);
-    return st == HSA_STATUS_SUCCESS;
-  };
-  if (!one(cp.sig, (char*)c->h_keys.p + first * sizeof(HostKeypoint), (const char*)c->keys.p + first * sizeof(HostKeypoint),
-           total * sizeof(HostKeypoint)))
-    return 1;
-  const bool second = c->dim && one(cp.sig2, (char*)c->h_desc.p + first * db, (const char*)c->desc.p + first * db, total * db);
-  // (both copies are in flight on the same engine; each has its own signal)
-  if (const int w = wait_copy_signal(cp.sig, 1, &seen, true, &real)) {
-    if (second) { bool r2 = false; (void)wait_copy_signal(cp.sig2, 1, nullptr, false, &r2); real = real || r2; }
-    return lost(w);
-  }
-  if (c->dim && !second) return 1;  // ROCr took the first copy (done by now) and refused the second: the fallback copies both
-  if (second)
-    if (const int w = wait_copy_signal(cp.sig2, 1, &seen, false, &real)) return lost(w);
-  return 0;
+// ---- one SDMA copy through ROCr: start it, finish it ----
+// Start: arm the copy's own signal with 1 (Copier::sig says why exactly that) and hand the copy to `engine` (0 = let ROCr
+// choose).  Returns whether ROCr took the copy.
+static bool sdma_start(uint32_t engine, void* dst, hsa_agent_t dst_agent, const void* src, hsa_agent_t src_agent, size_t bytes,
+                       hsa_signal_t sig) {
+  hsa_signal_store_relaxed(sig, 1);
+  hsa_status_t st = engine ? hsa_amd_memory_async_copy_on_engine(dst, dst_agent, src, src_agent, bytes, 0, nullptr, sig,
+                                                                 (hsa_amd_sdma_engine_id_t)engine, false)
+                           : HSA_STATUS_ERROR;
+  if (st != HSA_STATUS_SUCCESS)  // no engine chosen, or busy / not available: let ROCr choose
+    st = hsa_amd_memory_async_copy(dst, dst_agent, src, src_agent, bytes, 0, nullptr, sig);
+  return st == HSA_STATUS_SUCCESS;
 }
 
-void copier_main(hess_ctx* c) {
+// What a step of the copier thread returns: a hess_status and, unless that is 0, the message for hess_last_error.
+struct Step {
+  int rc = 0;
+  char msg[256] = "";
+};
+
+static Step hip_failed(const char* what, hipError_t e) {
+  Step s;
+  snprintf(s.msg, sizeof(s.msg), "%s failed: %s (copier)", what, hipGetErrorString(e));
+  s.rc = e == hipErrorOutOfMemory ? HESS_ERR_NOMEM : HESS_ERR_DEVICE;
+  return s;
+}
+
+// Finish: wait for the copy.  0: it is done; 2: it did not complete (timeout or error; `msg` -- a Step's, or null -- says
+// which of `what`, with `detail` behind the signal's value) -- and when that is the signal's own outcome the copy may still
+// land: the context is poisoned (hess_ctx::poisoned).  What else a lost copy costs is the caller's to mark.
+static int sdma_finish(hess_ctx* c, hsa_signal_t sig, const char* what, bool injectable, char* msg, const char* detail = "") {
+  hsa_signal_value_t seen = 0;
+  bool real = false;
+  const int w = wait_copy_signal(sig, 1, &seen, injectable, &real);
+  if (!w) return 0;
+  if (msg) snprintf(msg, sizeof(Step::msg), "%s %s (signal value %lld%s)", what, w == 1 ? "did not complete in time" : "failed", (long long)seen, detail);
+  if (real) c->poisoned.store(true);
+  return 2;
+}
+
+// One or two blocks of device memory that travel together (keypoints and their descriptors; the lists' order).
+struct HostBlock {
+  void* dst;
+  const void* src;
+  size_t bytes;
+  const char* hip_call;  // the name the stream copy fails under
+};
+
+// Bring the blocks to the pinned host buffers: by SDMA -- a copy that was taken and does not complete fails the batch; only
+// the first wait can be `injectable` (HESS_COPIER_FAULT) -- or, where ROCr refuses a copy, by copies on the copy-only stream,
+// which is then waited for.
+static Step bring_to_host(hess_ctx* c, const HostBlock* b, int n, uint32_t engine, const char* what, const char* detail, bool injectable) {
+  Copier& cp = c->cp;
+  Step s;
+  if (copier_hsa_setup(c) && sdma_start(engine, b[0].dst, cp.cpu_agent, b[0].src, cp.gpu_agent, b[0].bytes, cp.sig)) {
+    const bool second = n > 1 && sdma_start(engine, b[1].dst, cp.cpu_agent, b[1].src, cp.gpu_agent, b[1].bytes, cp.sig2);
+    // (both copies are in flight on the same engine; each has its own signal, and the second is waited for whatever the first did)
+    int lost = sdma_finish(c, cp.sig, what, injectable, s.msg, detail);
+    if (second && sdma_finish(c, cp.sig2, what, false, lost ? nullptr : s.msg, detail)) lost = 2;
+    if (lost) {
+      cp.hsa_ready = false; cp.hsa_failed = true;  // later batches take the stream copy; the signals are not reused
+      s.rc = HESS_ERR_DEVICE;
+    }
+    if (lost || n == 1 || second) return s;  // failed, or the blocks are in host memory
+    // ROCr took the first copy (done by now) and refused the second: the fallback copies both
+  }
+  hipError_t e;
+  for (int i = 0; i < n; i++)
+    if ((e = hipMemcpyAsync(b[i].dst, b[i].src, b[i].bytes, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess) return hip_failed(b[i].hip_call, e);
+  if ((e = hipStreamSynchronize(cp.cs)) != hipSuccess) return hip_failed("hipStreamSynchronize(copy stream)", e);
+  return s;
+}
+
+// hess_reserve: the SDMA engine's queue is created by a 64-byte copy into each result buffer now, not by the first batch
+// (only while the context holds no results and no job is posted).
+void copier_warm_up(hess_ctx* c) {
+  Copier& cp = c->cp;
+  if (c->delivery != kDeliverDma || c->batch != 0 || !c->keys.p || !c->h_keys.p || c->h_keys.bytes < 64 || cp.has_job) return;
+  if (!copier_hsa_setup(c)) return;
+  auto tiny = [&](hsa_signal_t sig, void* dst, const void* src) {
+    if (sdma_start(cp.engine, dst, cp.cpu_agent, src, cp.gpu_agent, 64, sig) && sdma_finish(c, sig, "", false, nullptr)) {
+      cp.hsa_ready = false; cp.hsa_failed = true;
+    }
+  };
+  tiny(cp.sig, c->h_keys.p, c->keys.p);
+  if (cp.hsa_ready && c->dim && c->desc.p && c->h_desc.p && c->h_desc.bytes >= 64) tiny(cp.sig2, c->h_desc.p, c->desc.p);
+}
+
+// ---- the copier thread's steps (none touches cp.mu: copier_main holds the job between its unlock and lock) ----
+// A batch whose pixels are still on their way (Copier::upload_first): wait for them on the host, then enqueue the batch.
+static Step await_upload_and_enqueue(hess_ctx* c) {
+  Copier& cp = c->cp;
+  Step s;
+  const auto t0 = std::chrono::steady_clock::now();
+  // (a lost upload may still write the staging area: hess_ctx::poisoned)
+  if (sdma_finish(c, cp.sig_in, "host->device upload of the pixels", true, s.msg)) {
+    // the pixels never arrived (or arrived wrong): the kernels are NOT run on them
+    snprintf(s.msg + strlen(s.msg), sizeof(s.msg) - strlen(s.msg), " (copier)");
+    s.rc = HESS_ERR_DEVICE;
+    cp.have_sig_in = false;  // (a signal that may still be written is left alone, not reused)
+  }
+  PendingRun& r = *cp.run;
+  r.t_load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (s.rc) return s;
+  try {
+    s.rc = enqueue(c, r);
+  } catch (...) { s.rc = HESS_ERR_NOMEM; snprintf(s.msg, sizeof(s.msg), "out of host memory (copier)"); }
+  if (!s.rc) {
+    const hipError_t e = hipEventRecord(cp.ev_done, c->st);
+    if (e != hipSuccess) return hip_failed("hipEventRecord", e);
+  }
+  if (s.rc && !s.msg[0]) snprintf(s.msg, sizeof(s.msg), "%s", c->err.c_str());
+  return s;
+}
+
+// Room for `total` records in the pinned buffers (they hold the worst case unless that exceeds 512 MB: then they grow here, rarely).
+static Step make_room(hess_ctx* c, size_t total, size_t db) {
+  Step s;
+  DevBuf &hk = c->h_keys, &hd = c->h_desc;
+  if (hk.bytes >= total * sizeof(HostKeypoint) && (!c->dim || hd.bytes >= total * db)) return s;
+  if (ensure(c, hk, total * sizeof(HostKeypoint), true) || (c->dim && ensure(c, hd, total * db, true))) {
+    snprintf(s.msg, sizeof(s.msg), "pinned result buffers: %s (copier)", c->err.empty() ? "allocation failed" : c->err.c_str());
+    s.rc = HESS_ERR_NOMEM;
+  }
+  return s;
+}
+
+// A caller's keypoint lists: the results are in list order, and hess_wait needs the lists' map to input order beside
+// them -- key_bin_kernel wrote it before any of the events.  Every image's rows at once: 4 bytes per record.
+static Step deliver_list_order(hess_ctx* c, int batch) {
+  const HostBlock b{c->h_kmap.p, c->kmap.p, (size_t)batch * c->cap_list * 4, "hipMemcpyAsync(list order)"};
+  return bring_to_host(c, &b, 1, 0, "device->host copy of the keypoint lists' order", "", false);
+}
+
+// The results, part by part as the parts' events arrive; `s` is the status so far: a batch that has failed copies nothing
+// more, but its events are still waited for.  The first wait of a part's copies is the injectable one.
+static Step deliver_parts(hess_ctx* c, size_t total, bool overflow, size_t db, Step s) {
+  Copier& cp = c->cp;
+  const Parts& parts = c->parts;
+  const int* hs = (const int*)c->h_small.p;
+  const size_t kb = sizeof(HostKeypoint);
+  char engine[32];
+  snprintf(engine, sizeof(engine), ", engine 0x%x", cp.engine);
+  size_t done_feats = 0;
+  for (int k = 0; k < parts.n; k++) {
+    hipError_t e;
+    if (k > 0 && (e = hipEventSynchronize(k < parts.n - 1 ? cp.ev_part[k] : cp.ev_done)) != hipSuccess) s = hip_failed("hipEventSynchronize", e);
+    // features of the images so far -- or, of one image's list, the bound the part's launch formed (k_feature.hip, desc_image)
+    const size_t upto = overflow ? 0 : (k == parts.n - 1 ? total : parts.features ? (size_t)((long long)total * (k + 1) / parts.n)
+                                                                                  : (size_t)hs[parts.end[k]]);
+    const size_t first = done_feats, n = upto - done_feats;
+    done_feats = upto;
+    if (s.rc || !n) continue;
+    const HostBlock b[2] = {{(char*)c->h_keys.p + first * kb, (const char*)c->keys.p + first * kb, n * kb, "hipMemcpyAsync(keys)"},
+                            {(char*)c->h_desc.p + first * db, (const char*)c->desc.p + first * db, n * db, "hipMemcpyAsync(desc)"}};
+    s = bring_to_host(c, b, c->dim ? 2 : 1, cp.engine, "device->host copy of the results", engine, true);
+  }
+  return s;
+}
+
+static void copier_main(hess_ctx* c) {
   Copier& cp = c->cp;
   (void)hipSetDevice(c->device);
   std::unique_lock<std::mutex> lk(cp.mu);
@@ -195,111 +270,29 @@ void copier_main(hess_ctx* c) {
     const int batch = cp.run->batch;
     const size_t db = run_desc_bytes(c, cp.run->desc_format);  // (plan() ran before the job was posted)
     lk.unlock();
-    int rc = 0;
     bool overflow = false;
-    char msg[256] = "";
-    auto fail = [&](const char* what, hipError_t e) {
-      snprintf(msg, sizeof(msg), "%s failed: %s (copier)", what, hipGetErrorString(e));
-      rc = e == hipErrorOutOfMemory ? HESS_ERR_NOMEM : HESS_ERR_DEVICE;
-    };
-    hipError_t e = hipSuccess;
-    if (cp.upload_first) {  // wait for the pixels on the host, then enqueue the batch
-      const auto t0 = std::chrono::steady_clock::now();
-      hsa_signal_value_t seen = 0;
-      bool real = false;
-      if (const int w = wait_copy_signal(cp.sig_in, 1, &seen, true, &real)) {
-        if (real) c->poisoned.store(true);  // the upload may still write the staging area: see hess_ctx::poisoned
-        // the pixels never arrived (or arrived wrong): the kernels are NOT run on them
-        snprintf(msg, sizeof(msg), "host->device upload of the pixels %s (signal value %lld) (copier)",
-                 w == 1 ? "did not complete in time" : "failed", (long long)seen);
-        rc = HESS_ERR_DEVICE;
-        cp.have_sig_in = false;  // (a signal that may still be written is left alone, not reused)
-      }
-      PendingRun& r = *cp.run;
-      r.t_load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      if (!rc) {
-        try {
-          rc = enqueue(c, r);
-        } catch (...) { rc = HESS_ERR_NOMEM; snprintf(msg, sizeof(msg), "out of host memory (copier)"); }
-        if (!rc && (e = hipEventRecord(cp.ev_done, c->st)) != hipSuccess) fail("hipEventRecord", e);
-        if (rc && !msg[0]) snprintf(msg, sizeof(msg), "%s", c->err.c_str());
-      }
-    }
+    Step s;
+    if (cp.upload_first) s = await_upload_and_enqueue(c);
     // Several parts when the batch's descriptors were launched in groups of images (nparts > 1): a group's results
     // cross while the next group is computed; else one part behind the last kernel.  The counts (and the overflow
     // words) are in the pinned count block since feature_scan_kernel, i.e. before any of the events.
     // (hess_ctx::parts says why no lock is needed; after a failed upload or a half-run enqueue rc is set: no parts to wait for)
-    const Parts& parts = c->parts;
-    const int nparts = parts.n;
-    if (!rc && (e = hipEventSynchronize(nparts > 1 ? cp.ev_part[0] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
-    if (!rc) {
+    if (!s.rc) {
+      const hipError_t e = hipEventSynchronize(c->parts.n > 1 ? cp.ev_part[0] : cp.ev_done);
+      if (e != hipSuccess) s = hip_failed("hipEventSynchronize", e);
+    }
+    if (!s.rc) {
       const int* hs = (const int*)c->h_small.p;
       overflow = hs[batch + 1] != 0 || hs[batch + 2] != 0 || hs[batch + 3] != 0;  // (word 3: a device-side error, nothing to copy)
       const size_t total = overflow ? 0 : (size_t)hs[batch];
-      DevBuf *hk = &c->h_keys, *hd = &c->h_desc;
-      if (total) {
-        // (the pinned buffers hold the worst case unless that exceeds 512 MB: then they grow here, rarely)
-        if (hk->bytes < total * sizeof(HostKeypoint) || (c->dim && hd->bytes < total * db)) {
-          if (ensure(c, *hk, total * sizeof(HostKeypoint), true) || (c->dim && ensure(c, *hd, total * db, true))) {
-            snprintf(msg, sizeof(msg), "pinned result buffers: %s (copier)", c->err.empty() ? "allocation failed" : c->err.c_str());
-            rc = HESS_ERR_NOMEM;
-          }
-        }
-      }
-      auto copy_part = [&](size_t first, size_t n) {
-        if (rc || !n) return;
-        if (copier_hsa_setup(c)) {
-          const int hr = copier_hsa_copy(c, first, n, msg, sizeof(msg));
-          if (hr == 0) return;  // both blocks are in host memory
-          if (hr == 2) { rc = HESS_ERR_DEVICE; return; }
-        }
-        const size_t kb = sizeof(HostKeypoint);
-        if ((e = hipMemcpyAsync((char*)hk->p + first * kb, (const char*)c->keys.p + first * kb, n * kb, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess)
-          fail("hipMemcpyAsync(keys)", e);
-        if (!rc && c->dim &&
-            (e = hipMemcpyAsync((char*)hd->p + first * db, (const char*)c->desc.p + first * db, n * db, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess)
-          fail("hipMemcpyAsync(desc)", e);
-        if (!rc && (e = hipStreamSynchronize(cp.cs)) != hipSuccess) fail("hipStreamSynchronize(copy stream)", e);
-      };
-      if (total && user_mode(c)) {
-        // A caller's keypoint lists: the results are in list order, and hess_wait needs the lists' map to input order beside
-        // them -- key_bin_kernel wrote it before any of the events.  Every image's rows at once: 4 bytes per record.
-        const size_t mb = (size_t)batch * c->cap_list * 4;
-        bool copied = false;
-        if (copier_hsa_setup(c)) {
-          hsa_signal_store_relaxed(cp.sig, 1);
-          if (hsa_amd_memory_async_copy(c->h_kmap.p, cp.cpu_agent, c->kmap.p, cp.gpu_agent, mb, 0, nullptr, cp.sig) == HSA_STATUS_SUCCESS) {
-            hsa_signal_value_t seen = 0;
-            bool real = false;
-            if (const int w = wait_copy_signal(cp.sig, 1, &seen, false, &real)) {
-              snprintf(msg, sizeof(msg), "device->host copy of the keypoint lists' order %s (signal value %lld)",
-                       w == 1 ? "did not complete in time" : "failed", (long long)seen);
-              cp.hsa_ready = false; cp.hsa_failed = true;
-              if (real) c->poisoned.store(true);
-              rc = HESS_ERR_DEVICE;
-            }
-            copied = true;
-          }
-        }
-        if (!copied) {
-          if ((e = hipMemcpyAsync(c->h_kmap.p, c->kmap.p, mb, hipMemcpyDeviceToHost, cp.cs)) != hipSuccess) fail("hipMemcpyAsync(list order)", e);
-          if (!rc && (e = hipStreamSynchronize(cp.cs)) != hipSuccess) fail("hipStreamSynchronize(copy stream)", e);
-        }
-      }
-      size_t done_feats = 0;
-      for (int k = 0; k < nparts; k++) {
-        if (k > 0 && (e = hipEventSynchronize(k < nparts - 1 ? cp.ev_part[k] : cp.ev_done)) != hipSuccess) fail("hipEventSynchronize", e);
-        // features of the images so far -- or, of one image's list, the bound the part's launch formed (k_feature.hip, desc_image)
-        const size_t upto = overflow ? 0 : (k == nparts - 1 ? total : parts.features ? (size_t)((long long)total * (k + 1) / nparts)
-                                                                                   : (size_t)hs[parts.end[k]]);
-        copy_part(done_feats, upto - done_feats);
-        done_feats = upto;
-      }
+      if (total) s = make_room(c, total, db);
+      if (!s.rc && total && user_mode(c)) s = deliver_list_order(c, batch);
+      s = deliver_parts(c, total, overflow, db, s);
     }
     lk.lock();
-    cp.rc = rc;
+    cp.rc = s.rc;
     cp.overflow = overflow;
-    snprintf(cp.err, sizeof(cp.err), "%s", msg);
+    snprintf(cp.err, sizeof(cp.err), "%s", s.msg);
     cp.has_job = false;
     cp.done = true;
     cp.cv.notify_all();
@@ -365,7 +358,7 @@ void choose_delivery(hess_ctx* c, int batch) {
 
 // The one hand-off to the copier thread: `run` (which outlives the job: hess_ctx::run, or a local of a caller that waits
 // before it returns) and whether the thread is to wait for the pixels' upload and enqueue the batch itself.
-void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
+static void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
   Copier& cp = c->cp;
   std::lock_guard<std::mutex> lk(cp.mu);
   cp.run = run;
@@ -373,6 +366,71 @@ void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
   cp.done = false;
   cp.has_job = true;
   cp.cv.notify_all();
+}
+
+// ---- input routes (hess_submit_host: the pixels into the staging area c->stage, c->run describes them) ----
+// Pinned pixels of a batch that the copier thread will deliver: the upload goes to an SDMA engine directly and
+// the copier thread enqueues the kernels once it has landed (Copier::upload_first).  A copy command on the
+// context's stream would hold its hardware queue -- shared with other contexts -- for the length of the
+// transfer: 15.9 - 16.2 against 17.0 Gpix/s for six pipelined contexts, while the same bytes uploaded on the side
+// cost nothing (tools/r03/r03_h2d_bg.py).  *taken: the batch is submitted; else nothing is in flight, take the stream.
+int upload_beside_queues(hess_ctx* c, const void* pixels, size_t bytes, bool* taken) {
+  *taken = false;
+  if (c->no_host_upload) return 0;
+  if (int rc = plan(c, c->run.width, c->run.height, c->run.batch)) return rc;
+  choose_delivery(c, c->run.batch);
+  Copier& cp = c->cp;
+  hsa_amd_pointer_info_t pi;
+  memset(&pi, 0, sizeof(pi));
+  pi.size = sizeof(pi);
+  if (c->delivery != kDeliverDma || !copier_hsa_setup(c) ||
+      hsa_amd_pointer_info(const_cast<void*>(pixels), &pi, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS ||
+      pi.type == HSA_EXT_POINTER_TYPE_UNKNOWN ||
+      !(cp.have_sig_in || hsa_signal_create(1, 0, nullptr, &cp.sig_in) == HSA_STATUS_SUCCESS))
+    return 0;
+  cp.have_sig_in = true;
+  if (!sdma_start(cp.engine_in, c->stage.p, cp.gpu_agent, pixels, pi.agentOwner, bytes, cp.sig_in)) return 0;
+  c->last_input_bytes = bytes;
+  copier_post(c, &c->run, true);
+  c->run.active = true;
+  *taken = true;
+  return 0;
+}
+
+// Pageable memory: copied into the pinned staging buffer in chunks, each chunk's transfer enqueued as soon as
+// it is staged, so the copy engine works while the next chunks are being copied (one core copies at about
+// 17 GB/s, a third of what the link takes: the context's helper threads share the work, see Stager).
+// 4 MB chunks; a small input (one image) is cut in four so that its transfer, too, overlaps its staging, and is
+// staged by the calling thread alone: waking the helpers costs more than they save below about 8 MB (one 1080p
+// image: 0.544 ms per call alone, 0.58 ms with helpers; profiles/r03_host_path.json).
+// Nothing here allocates or throws once the helpers exist (nothing thrown crosses the C ABI).
+static int upload_staged(hess_ctx* c, const void* pixels, size_t bytes) {
+  if (int rc = ensure(c, c->h_stage, bytes, true)) return rc;
+  const size_t chunk = std::min<size_t>((size_t)4 << 20, std::max<size_t>((size_t)256 << 10, ((bytes / 4 + 65535) >> 16) << 16));
+  hipError_t cerr = hipSuccess;  // the first one
+  const bool ran = stager_run(c->sg, pixels, c->h_stage.p, bytes, chunk, bytes >= policy::kStagerHelpFrom, [&](size_t off, size_t len) {
+    if (cerr == hipSuccess)
+      cerr = hipMemcpyAsync((char*)c->stage.p + off, (const char*)c->h_stage.p + off, len, hipMemcpyHostToDevice, c->st);
+  });
+  if (!ran) { set_err(c, "out of memory"); return HESS_ERR_NOMEM; }
+  HIP_TRY(c, cerr);
+  return 0;
+}
+
+// One asynchronous host->device transfer on the context's stream, between the two load events: pinned pixels are read by
+// the copy engine directly, pageable ones go through the pinned staging buffer.
+int upload_on_stream(hess_ctx* c, const void* pixels, size_t bytes, bool pinned) {
+  HIP_TRY(c, hipEventRecord(c->ev_load[0], c->st));
+  if (pinned) {
+    HIP_TRY(c, hipMemcpyAsync(c->stage.p, pixels, bytes, hipMemcpyHostToDevice, c->st));
+  } else {
+    (void)hipGetLastError();  // an unregistered pointer is reported as an error: not one
+    if (int rc = upload_staged(c, pixels, bytes)) return rc;
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_load[1], c->st));
+  c->last_input_bytes = bytes;
+  c->run.timed_load = true;
+  return 0;
 }
 
 // Pending keypoint lists are one per image of the batch that uses them.

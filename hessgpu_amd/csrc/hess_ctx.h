@@ -6,7 +6,8 @@
 //                      FitPyramid, PyramidCU.cpp:113-489; CuTexImage::InitTexture)
 //   hess_schedule.hip  the launch order of one batch on the context's stream (SiftPyramid::RunSIFT, SiftPyramid.cpp:53-198, and
 //                      the PyramidCU stages under it), the table of its thresholds, per-kernel hipEvent profiling
-//   hess_copier.hip    pixels in / results out: stager threads, the copier thread + SDMA delivery, submit / wait
+//   hess_copier.hip    pixels in / results out: the input routes of hess_submit_host, the copier thread + SDMA delivery, submit / wait
+//   hess_stager.cpp    the helper threads that stage pageable pixels (hess_stager.h; standard headers only)
 //   hess_shared.hip    result buffers in node-shared memory (hess_share_results)
 //   hess_abi.hip       the extern "C" entry points
 #pragma once
@@ -39,6 +40,7 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_dev.h"
+#include "hess_stager.h"
 
 namespace hess {
 
@@ -173,28 +175,6 @@ struct Parts {
   bool features = false;
 };
 
-// Persistent helper threads that copy pageable input pixels into the context's pinned staging buffer
-// (hess_submit_host).  The calling thread walks the chunks in ascending order -- staging the ones nobody has claimed,
-// enqueueing every chunk's transfer as soon as it is staged -- while the helpers claim chunks from the END, so the
-// early chunks are ready first.  Started at the first pageable submission, reused afterwards: starting threads per
-// call cost more than staging one image.
-struct Stager {
-  static constexpr int kHelpers = 3;
-  std::thread th[kHelpers];
-  int nth = 0;
-  bool tried = false;
-  std::mutex mu;
-  std::condition_variable cv_job, cv_done;
-  bool stop = false;
-  unsigned long long gen = 0;
-  const char* src = nullptr;
-  char* dst = nullptr;
-  size_t bytes = 0, chunk = 0;
-  int nchunk = 0, active = 0;
-  std::vector<std::atomic<int>> state;  // per chunk: 0 free, 1 claimed, 2 staged
-  std::atomic<int> next_hi{-1};
-};
-
 struct hess_ctx {
   int device = 0;
   hipStream_t st = nullptr;
@@ -279,7 +259,7 @@ struct hess_ctx {
   int desc_px_band = 4096;         // HESS_PX_BAND: pixels per raster band of descriptor_pixel_kernel (test hook: small bands at ordinary footprints)
   int desc_xcd_block = 64;         // HESS_DESC_XCD: features per XCD block of the descriptor launch (0: plain order; A/B switch)
   Copier cp;
-  Stager sg;
+  Stager sg;                       // hess_stager.h
   // A DMA copy that did not complete in time (or that ROCr reported as failed) may still be in flight, or land later:
   // its targets -- the pinned result buffers, the pixel staging area -- must neither be reused nor freed.  The context
   // refuses every further run (HESS_ERR_DEVICE) and hess_destroy leaves those buffers and the signals alone.
@@ -386,15 +366,12 @@ void drain_profile(hess_ctx* c);
 int enqueue(hess_ctx* c, const PendingRun& r);
 size_t user_block_bytes(int total, int nimg);  // bytes of the pinned block h_user for `total` keys of `nimg` images
 // hess_copier.hip
-void stager_start(Stager& sg);
-void stager_copy(Stager& sg, int k);
-void stager_stop(Stager& sg);
-bool copier_hsa_setup(hess_ctx* c);
-int wait_copy_signal(hsa_signal_t sig, hsa_signal_value_t below, hsa_signal_value_t* last, bool injectable = true, bool* real = nullptr);
+int upload_beside_queues(hess_ctx* c, const void* pixels, size_t bytes, bool* taken);
+int upload_on_stream(hess_ctx* c, const void* pixels, size_t bytes, bool pinned);
+void copier_warm_up(hess_ctx* c);
 int copier_start(hess_ctx* c);
 void copier_stop(hess_ctx* c);
 void choose_delivery(hess_ctx* c, int batch);
-void copier_post(hess_ctx* c, PendingRun* run, bool upload_first);
 int check_user_batch(hess_ctx* c, int batch);
 int submit_impl(hess_ctx* c, PendingRun& r);
 int wait_impl(hess_ctx* c, PendingRun& r);

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import pytest
 
+import fixtures
 import keybatch_cases as kc
 from hessgpu_amd import _abi
 from hessgpu_amd.session import HessError
@@ -182,6 +183,70 @@ def test_two_contexts_alternate(gpu_ctx_factory):
             ls = sets[(step + i) % 2]
             for b in range(4):
                 _check_image(g, b, ls[b], want[(step + i) % 2][b] if len(ls[b]) else None, f"step {step} context {i} image {b}")
+
+
+PINNED_W, PINNED_H = 320, 240
+
+
+@functools.lru_cache(maxsize=None)
+def _pinned_case():
+    """-> (four 320 x 240 images, one list per image): case A's lists (image 0 has none), image 2's with one key listed twice.
+    "Twice" is an exact repeat in the caller's list: no scale belongs to two levels (in binary32 a level's sigma_max never
+    exceeds the next one's sigma_min: kc.level_table), so that is the only way a key comes twice."""
+    imgs = np.stack([fixtures.synthetic_blobs(PINNED_W, PINNED_H, i) for i in range(4)])
+    imgs.setflags(write=False)
+    lists = list(kc.case_a())
+    lists[2] = np.concatenate([lists[2], lists[2][5:6]])
+    return imgs, tuple(lists)
+
+
+@functools.lru_cache(maxsize=None)
+def _pinned_expected(flag):
+    """The oracle's single-image runs of _pinned_case()."""
+    imgs, lists = _pinned_case()
+    o = _oracle("default")
+    out = []
+    for b, keys in enumerate(lists):
+        if not len(keys):
+            out.append(None)
+            continue
+        o.run(imgs[b][None])
+        assert o.run_keypoints(keys, flag) == len(keys)
+        out.append(o.fetch(0))
+    return out
+
+
+@pytest.mark.parametrize("flag", [1, 0])
+@pytest.mark.parametrize("side", [True, False])
+def test_lists_on_pinned_pixels(gpu_ctx_factory, monkeypatch, side, flag):
+    """set_keypoints_batch + submit_host of PINNED pixels + wait: a submitted batch of four is delivered by the copier thread,
+    so the lists' order crosses by its copy -- behind the side upload (the thread enqueues the batch itself), or behind a copy
+    on the stream (HESS_NO_SIDE_UPLOAD=1).  Same counts, bytes and list order as run_keypoints_batch on the same pixels from
+    pageable memory on a second context, and as the oracle."""
+    import torch
+    imgs, lists = _pinned_case()
+    assert len(lists[0]) == 0 and lists[2][-1].tobytes() == lists[2][5].tobytes()
+    if not side:
+        monkeypatch.setenv("HESS_NO_SIDE_UPLOAD", "1")
+    g = gpu_ctx_factory(dev_switches=True)
+    monkeypatch.delenv("HESS_NO_SIDE_UPLOAD", raising=False)
+    ref = _context(gpu_ctx_factory, "default")
+    ref.run(np.array(imgs))
+    assert ref.run_keypoints_batch(lists, flag) == [len(k) for k in lists]
+    pinned = torch.from_numpy(np.array(imgs)).pin_memory()
+    g.set_keypoints_batch(lists, flag)
+    g.submit_host(ptr=pinned.data_ptr(), batch=4, height=PINNED_H, width=PINNED_W)
+    g.wait()
+    want = _pinned_expected(flag)
+    table = kc.level_table(noct=kc.octaves(PINNED_W, PINNED_H))
+    for b, keys in enumerate(lists):
+        what = f"pinned pixels, side upload {side}, flag {flag}, image {b}"
+        assert g.count(b) == ref.count(b) == len(keys), what
+        (gk, gd), (rk, rd) = g.fetch(b), ref.fetch(b)
+        assert gk.tobytes() == rk.tobytes() and gd.tobytes() == rd.tobytes(), what
+        assert np.array_equal(g.key_list_order(b), ref.key_list_order(b)), what
+        assert np.array_equal(g.key_list_order(b), kc.list_order(keys, flag, table)), what
+        _check_image(g, b, keys, want[b], what)
 
 
 def test_errors(gpu_ctx_factory):
