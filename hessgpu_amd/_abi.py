@@ -158,6 +158,10 @@ PRODUCT_PROTOTYPES = {
     "set_keypoints_batch": (C.c_int, [_ctx, C.c_void_p, _P(C.c_int), C.c_int, C.c_int]),
     "run_keypoints_batch": (C.c_int, [_ctx, C.c_void_p, _P(C.c_int), C.c_int, C.c_int]),
     "key_list_order": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int]),
+    # feature types in the matcher (added during version 5 without a bump)
+    "matcher_set_types": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "matcher_bank_set_types": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "matcher_bank_set_types_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 
 

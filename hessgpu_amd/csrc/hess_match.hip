@@ -16,6 +16,10 @@
 //                          the same launch, the per-row-block (max, index, second) column partials in ascending row order
 //                          (match_col_kernel: the same for the small / guided path);
 //   match_pairs_compact_kernel  each pair's matches compacted on the device (a single pair is compacted on the host).
+// Feature types (hess_matcher_set_types, _bank_set_types; no reference counterpart): a typed set is stored grouped by class
+// and a gated pair is one job of the same tables per class, the two kernels above unchanged --
+//   type_classify_kernel / type_place_kernel / bank_gather_kernel   class and stable position of every row, its place, the move;
+//   match_types_compact_kernel  the compaction in ORIGINAL row order through the maps; see the comment at type_classify_kernel.
 // Small unguided match and guided match (GetGuidedSiftMatch: per-pair homography / fundamental-matrix gates,
 // per-8-row-block rule) --
 //   match_dot_kernel       64x64 tile of the dot-product matrix per workgroup, descriptor panels in LDS,
@@ -544,6 +548,160 @@ __global__ __launch_bounds__(256) void bank_build_kernel(const void* src, const 
   }
 }
 
+// ---- feature types (hess_matcher_set_types / _bank_set_types): sets stored grouped by class ---------------------------
+// Class of a feature = type & 3 (dark, bright, saddle, none).  A typed set is stored as four class groups, each in
+// ascending original order and padded to whole 256-row blocks like a set, so the gated match of a pair is the ungated
+// match of up to four (group of set 1, group of set 2) jobs of the same tables: match_mfma_kernel and match_finish_kernel
+// see smaller sets and nothing else.  fwd[original row] = stored row, inv[stored row] = original row of its set (-1: padding).
+//
+// One workgroup per set: pos[original row] = (position within its class) << 2 | class and counts[set][class].  Ballots
+// and prefix counts in row order: the positions do not depend on scheduling.  sets[s] = (first value of the caller's
+// array, rows kept, first original row).
+__global__ __launch_bounds__(256) void type_classify_kernel(const uint8_t* types, size_t stride, const int3* sets, int* pos,
+                                                            int* counts) {
+  __shared__ int wsum[4][4];
+  const int3 S = sets[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+  for (int base = 0; base < S.y; base += 256) {
+    const int i = base + tid;
+    int cls = 4;
+    if (i < S.y) cls = *reinterpret_cast<const uint16_t*>(types + ((size_t)S.x + i) * stride) & 3;
+    int before = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const unsigned long long bal = __ballot(cls == c);
+      if (lane == 0) wsum[wv][c] = __popcll(bal);
+      if (cls == c) before = __popcll(bal & ((1ull << lane) - 1));
+    }
+    __syncthreads();
+    int t[4], mine = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      t[c] = wsum[0][c] + wsum[1][c] + wsum[2][c] + wsum[3][c];
+      int w = 0;
+      for (int k = 0; k < wv; k++) w += wsum[k][c];
+      const int start = c == 0 ? n0 : c == 1 ? n1 : c == 2 ? n2 : n3;
+      if (cls == c) mine = start + w + before;
+    }
+    if (i < S.y) pos[S.z + i] = mine << 2 | cls;
+    n0 += t[0]; n1 += t[1]; n2 += t[2]; n3 += t[3];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    counts[4 * blockIdx.x] = n0; counts[4 * blockIdx.x + 1] = n1;
+    counts[4 * blockIdx.x + 2] = n2; counts[4 * blockIdx.x + 3] = n3;
+  }
+}
+
+// One thread per original row: where it is stored now (old_fwd, or its set's plain order without one) and where it goes
+// (its class group by pos, or the plain order without one).  tab[s] = {first original row, first padded row of the plain
+// order, first row of each class group}.  src and inv arrive filled with -1 (padding).
+struct TypeSet { int first, off, grp[4]; };
+__global__ __launch_bounds__(256) void type_place_kernel(const TypeSet* tab, int nsets, int total, const int* pos,
+                                                         const int* old_fwd, int* fwd, int* inv, int* src) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  int lo = 0, hi = nsets - 1;  // the last set starting at or before idx (empty sets share their successor's start)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].first <= idx) lo = mid;
+    else hi = mid - 1;
+  }
+  const TypeSet S = tab[lo];
+  const int i = idx - S.first;
+  int to = S.off + i;
+  if (pos) {
+    const int p = pos[idx];
+    to = S.grp[p & 3] + (p >> 2);
+  }
+  src[to] = old_fwd ? old_fwd[idx] : S.off + i;
+  if (fwd) { fwd[idx] = to; inv[to] = i; }
+}
+
+// The sets in another order: row g and its score offsets from row src[g] of the old storage, zero (bank_build_kernel's
+// padding) where src[g] < 0.  KD / 16 lanes x 16 bytes per descriptor.
+template <int KD>
+__global__ __launch_bounds__(256) void bank_gather_kernel(const uint8_t* orows, const int* orfix, const int* ocfix,
+                                                          const int* src, int total, uint8_t* rows, int* rfix, int* cfix) {
+  constexpr int LPD = KD / 16;
+  const int g = blockIdx.x * (256 / LPD) + threadIdx.x / LPD, l = threadIdx.x % LPD;
+  if (g >= total) return;
+  const int s = src[g];
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (s >= 0) v = *reinterpret_cast<const uint4*>(orows + (size_t)s * KD + 16 * l);
+  *reinterpret_cast<uint4*>(rows + (size_t)g * KD + 16 * l) = v;
+  if (l == 0) {
+    cfix[g] = s >= 0 ? ocfix[s] : 0;
+    rfix[g] = s >= 0 ? orfix[s] : -128 * 128 * KD;
+  }
+}
+
+// match_pairs_compact_kernel for typed sets.  Pair blockIdx.x is jobs[4 x + class] (a job without work has n1 = 0);
+// orig[x] = (first original row of its set 1, rows of that set).  The ORIGINAL rows in ascending order: each row's
+// decision is looked up through fwd in the job of its class, its column mapped back through inv, so the first max_match
+// kept are those of the definition.
+__global__ __launch_bounds__(256) void match_types_compact_kernel(const PairJob* jobs, const int2* orig, const int* fwd1,
+                                                                  const int* inv2, const int* rowm, const int* colm,
+                                                                  int mutual_best, int max_match, int* counts, int* pairs) {
+  __shared__ int wsum[4];
+  const PairJob* const J4 = jobs + 4 * blockIdx.x;
+  const int2 O = orig[blockIdx.x];
+  int* out = pairs + (size_t)blockIdx.x * max_match * 2;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // a row's answer is a chain of four dependent loads (fwd, row decision, column decision, inv) and a pair has one
+  // workgroup: four 256-row steps are looked up at once, stage by stage and without branches (a row without an answer
+  // reads element 0 and drops it), so that their chains are in flight together; then they are placed in order
+  constexpr int U = 4;
+  int n = 0;
+  const bool work = (J4[0].n1 | J4[1].n1 | J4[2].n1 | J4[3].n1) != 0;  // (else set 2 may have no inv at all)
+  for (int base = 0; work && base < O.y && n < max_match; base += 256 * U) {
+    int jv[U], g[U], r[U], n2[U], cm[U], b[U], jj[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) g[u] = fwd1[O.x + min(base + 256 * u + tid, O.y - 1)];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      int rm = 0;
+      ok[u] = false;
+      r[u] = n2[u] = cm[u] = b[u] = 0;
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const PairJob& J = J4[c];
+        const int rr = g[u] - J.a;
+        const bool in = rr >= 0 && rr < J.n1;
+        ok[u] = ok[u] || in;
+        r[u] = in ? rr : r[u]; rm = in ? J.rm : rm; n2[u] = in ? J.n2 : n2[u]; cm[u] = in ? J.cm : cm[u]; b[u] = in ? J.b : b[u];
+      }
+      ok[u] = ok[u] && base + 256 * u + tid < O.y;
+      jj[u] = rowm[ok[u] ? rm + r[u] : 0];
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      ok[u] = ok[u] && jj[u] >= 0 && jj[u] < n2[u];
+      if (mutual_best) ok[u] = (colm[ok[u] ? cm[u] + jj[u] : 0] == r[u]) && ok[u];  // (uniform)
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int v = inv2[ok[u] ? b[u] + jj[u] : 0];
+      jv[u] = ok[u] ? v : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int i = base + 256 * u + tid, j = jv[u];
+      const unsigned long long bal = __ballot(j >= 0);
+      if (lane == 0) wsum[wv] = __popcll(bal);
+      __syncthreads();
+      int pos = n + __popcll(bal & ((1ull << lane) - 1));
+      for (int k = 0; k < wv; k++) pos += wsum[k];
+      if (j >= 0 && pos < max_match) { out[2 * pos] = i; out[2 * pos + 1] = j; }
+      n += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+      __syncthreads();
+    }
+  }
+  if (tid == 0) counts[blockIdx.x] = min(n, max_match);
+}
+
 // One workgroup per pair: the rows i in ascending order with rowm[i] >= 0 (and, for mutual best, colm[rowm[i]] == i),
 // the first max_match of them.  out: [MP_PAIRS] counts, then [pair][max_match][2].
 __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob* jobs, const int* rowm, const int* colm,
@@ -580,7 +738,13 @@ struct DescSets {
   int dim = 128;  // bytes per row (the matcher's dim when the sets were built)
   uint8_t* rows = nullptr;
   int *rfix = nullptr, *cfix = nullptr;  // one allocation: cfix = rfix + padded rows
-  std::vector<int> off, num;             // first padded row and stored descriptors of each set
+  std::vector<int> off, num;             // first padded row and stored descriptors of each set (in the caller's order)
+  std::vector<int> cnt, first;           // descriptors the caller counted per set (before max_sift); first original row
+  bool built = false;                    // descriptors were loaded (possibly none)
+  // feature types (hess_matcher_set_types, _bank_set_types): the rows are stored by class instead
+  bool typed = false;
+  std::vector<int> goff, gnum;           // [set][class]: first stored row and rows of the class group
+  int *fwd = nullptr, *inv = nullptr;    // original row (first[s] + i) -> stored row; stored row -> i, -1 for padding
   int count(int s) const { return s < (int)num.size() ? num[s] : 0; }
 };
 
@@ -665,6 +829,15 @@ void sets_clear(DescSets& s) {
   s.rfix = s.cfix = nullptr;
   s.off.clear();
   s.num.clear();
+  s.cnt.clear();
+  s.first.clear();
+  s.built = false;
+  (void)hipFree(s.fwd);
+  (void)hipFree(s.inv);
+  s.fwd = s.inv = nullptr;
+  s.typed = false;
+  s.goff.clear();
+  s.gnum.clear();
 }
 
 template <int KD>
@@ -683,12 +856,14 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
   const size_t KD = (size_t)m->dim;
   s.dim = m->dim;
   std::vector<int3> sets((size_t)nsets);
-  std::vector<int> off((size_t)nsets), num((size_t)nsets);
-  size_t padded = 0, srow = 0;
+  std::vector<int> off((size_t)nsets), num((size_t)nsets), first((size_t)nsets);
+  size_t padded = 0, srow = 0, orow = 0;
   for (int k = 0; k < nsets; k++) {
     const int n = counts[k] > m->max_sift ? m->max_sift : counts[k];
     off[k] = (int)padded;
     num[k] = n;
+    first[k] = (int)orow;
+    orow += (size_t)n;
     sets[k] = make_int3((int)padded, (int)srow, n);
     padded += ((size_t)n + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
     srow += (size_t)counts[k];
@@ -716,6 +891,9 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
   }
   s.off.swap(off);
   s.num.swap(num);
+  s.first.swap(first);
+  s.cnt.assign(counts, counts + nsets);
+  s.built = true;
   return 0;
 }
 
@@ -734,6 +912,131 @@ int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const 
   (void)hipFree(staging);
   if (rc) sets_clear(s);
   return rc;
+}
+
+template <int KD>
+void launch_bank_gather(hipStream_t st, size_t padded, const DescSets& o, const int* src, uint8_t* rows, int* rfix, int* cfix) {
+  const dim3 grid((unsigned)((padded + 4096 / KD - 1) / (4096 / KD)));
+  hipLaunchKernelGGL(bank_gather_kernel<KD>, grid, dim3(256), 0, st, o.rows, o.rfix, o.cfix, src, (int)padded, rows, rfix, cfix);
+}
+
+// Device buffers of one sets_regroup, freed when it returns.
+struct Scratch {
+  std::vector<void*> p;
+  ~Scratch() { for (void* q : p) (void)hipFree(q); }
+  template <class T> hipError_t get(T*& out, size_t n) {
+    out = nullptr;
+    const hipError_t e = hipMalloc(&out, (n ? n : 1) * sizeof(T));
+    if (e == hipSuccess) p.push_back(out);
+    return e;
+  }
+  void keep(void* q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
+};
+
+// Stores the rows of `s` grouped by the class of dev_types (device memory: one u16 per descriptor the caller counted,
+// `stride` bytes apart), or back in the caller's order for dev_types == NULL.  The rows move from the present storage,
+// typed or not; `s` changes only when everything succeeded.  Returns after the sets are ready.
+int sets_regroup(hess_matcher* m, DescSets& s, const void* dev_types, size_t stride) {
+  if (!dev_types && !s.typed) return 0;
+  const int nsets = (int)s.num.size();
+  const size_t KD = (size_t)s.dim;
+  const size_t total = nsets ? (size_t)s.first[nsets - 1] + s.num[nsets - 1] : 0;
+  std::vector<int> goff, gnum;
+  Scratch tmp;
+  int *pos = nullptr, *fwd = nullptr, *inv = nullptr, *src = nullptr, *rfix = nullptr;
+  uint8_t* rows = nullptr;
+  size_t padded = 0;
+  std::vector<TypeSet> tab((size_t)nsets);
+  for (int k = 0; k < nsets; k++) tab[k] = TypeSet{s.first[k], s.off[k], {0, 0, 0, 0}};
+  if (dev_types) {
+    goff.assign((size_t)nsets * 4, 0);
+    gnum.assign((size_t)nsets * 4, 0);
+    if (total) {
+      std::vector<int3> sets((size_t)nsets);
+      size_t srow = 0;
+      for (int k = 0; k < nsets; k++) {
+        sets[k] = make_int3((int)srow, s.num[k], s.first[k]);
+        srow += (size_t)s.cnt[k];
+      }
+      int3* dsets = nullptr;
+      int* dcounts = nullptr;
+      M_TRY(m, tmp.get(pos, total));
+      M_TRY(m, tmp.get(dsets, (size_t)nsets));
+      M_TRY(m, tmp.get(dcounts, (size_t)nsets * 4));
+      M_TRY(m, hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st));
+      hipLaunchKernelGGL(type_classify_kernel, dim3(nsets), dim3(256), 0, m->st, static_cast<const uint8_t*>(dev_types), stride,
+                         dsets, pos, dcounts);
+      M_TRY(m, hipGetLastError());
+      M_TRY(m, hipMemcpyAsync(gnum.data(), dcounts, gnum.size() * sizeof(int), hipMemcpyDeviceToHost, m->st));
+      M_TRY(m, hipStreamSynchronize(m->st));
+    }
+    for (int k = 0; k < nsets; k++)
+      for (int c = 0; c < 4; c++) {
+        goff[4 * k + c] = tab[k].grp[c] = (int)padded;
+        padded += ((size_t)gnum[4 * k + c] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+        if (padded > (size_t)INT32_MAX / KD) { m->err = "set_types: bank too large"; return HESS_ERR_TOO_BIG; }
+      }
+  } else {
+    for (int k = 0; k < nsets; k++) padded = (size_t)s.off[k] + ((size_t)s.num[k] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+  }
+  if (total) {
+    TypeSet* dtab = nullptr;
+    M_TRY(m, tmp.get(rows, padded * KD));
+    M_TRY(m, tmp.get(rfix, 2 * padded));
+    M_TRY(m, tmp.get(src, padded));
+    M_TRY(m, tmp.get(dtab, (size_t)nsets));
+    M_TRY(m, hipMemsetAsync(src, 0xff, padded * sizeof(int), m->st));
+    if (dev_types) {
+      M_TRY(m, tmp.get(fwd, total));
+      M_TRY(m, tmp.get(inv, padded));
+      M_TRY(m, hipMemsetAsync(inv, 0xff, padded * sizeof(int), m->st));
+    }
+    M_TRY(m, hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(TypeSet), hipMemcpyHostToDevice, m->st));
+    hipLaunchKernelGGL(type_place_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st, dtab, nsets, (int)total,
+                       pos, s.typed ? s.fwd : nullptr, fwd, inv, src);
+    if (s.dim == 128) launch_bank_gather<128>(m->st, padded, s, src, rows, rfix, rfix + padded);
+    else launch_bank_gather<64>(m->st, padded, s, src, rows, rfix, rfix + padded);
+    M_TRY(m, hipGetLastError());
+    M_TRY(m, hipStreamSynchronize(m->st));
+    tmp.keep(rows); tmp.keep(rfix); tmp.keep(fwd); tmp.keep(inv);
+    (void)hipFree(s.rows); (void)hipFree(s.rfix);
+    s.rows = rows;
+    s.rfix = rfix;
+    s.cfix = rfix + padded;
+  }
+  (void)hipFree(s.fwd); (void)hipFree(s.inv);
+  s.fwd = fwd;
+  s.inv = inv;
+  s.typed = dev_types != nullptr;
+  s.goff.swap(goff);
+  s.gnum.swap(gnum);
+  return 0;
+}
+
+// The strided host values of a types argument, packed and staged on the device, then sets_regroup.
+int sets_types_host(hess_matcher* m, DescSets& s, const uint16_t* types, size_t stride) {
+  if (!types) return sets_regroup(m, s, nullptr, 0);
+  size_t n = 0;
+  for (int c : s.cnt) n += (size_t)c;
+  std::vector<uint16_t> h(n ? n : 1);
+  for (size_t i = 0; i < n; i++) memcpy(&h[i], reinterpret_cast<const char*>(types) + i * stride, 2);
+  uint16_t* d = nullptr;
+  M_TRY(m, hipMalloc(&d, h.size() * 2));
+  hipError_t e = hipMemcpy(d, h.data(), h.size() * 2, hipMemcpyHostToDevice);
+  const int rc = e == hipSuccess ? sets_regroup(m, s, d, 2) : 0;
+  (void)hipFree(d);
+  M_TRY(m, e);
+  return rc;
+}
+
+// What every types setter refuses: `what` names the entry point in the error text.
+int types_args(hess_matcher* m, const DescSets& s, const void* types, size_t stride, const char* what) {
+  if (!s.built) { m->err = std::string(what) + ": load the descriptors before their types"; return HESS_ERR_STATE; }
+  if (types && (stride < 2 || stride % 2)) {
+    m->err = std::string(what) + ": stride_bytes must be even and at least 2, not " + std::to_string(stride);
+    return HESS_ERR_ARG;
+  }
+  return 0;
 }
 
 // Host floats quantised as the reference does, int(512*d + 0.5) into a byte (SiftMatchCU.cpp:88-100): set k is counts[k]
@@ -774,11 +1077,41 @@ void pair_seg(int nsuper, int sps, int& nseg, int& psps) {
 
 // Jobs [p0, p1) of one multiply and one finish launch, with segments of at most sps super tiles; the scratch they use (row
 // states, column partials, row and column decisions) and the entries of the two work tables.
+// Typed sets (jpp = 4): four jobs per pair, one per class, and behind the work tables one (first original row, rows) of
+// set 1 per pair for match_types_compact_kernel.
 struct Chunk {
   int p0, p1, sps;
   size_t rs, cp, rm, cm, nwg, nfin;
-  size_t plan_bytes() const { return (size_t)(p1 - p0) * sizeof(PairJob) + (nwg + nfin) * sizeof(int2); }
+  int jpp = 1;  // jobs per pair
+  size_t norig() const { return jpp == 4 ? (size_t)(p1 - p0) / 4 : 0; }
+  size_t plan_bytes() const { return (size_t)(p1 - p0) * sizeof(PairJob) + (nwg + nfin + norig()) * sizeof(int2); }
 };
+
+// Super tiles per segment for `work` (256-row block, super tile) units in one launch: whole rounds of workgroups over the
+// 256 CUs as in hess_matcher_match (two per CU when that leaves each at least four super tiles), at most
+// MM_MAX_TILES / 4 super tiles per segment.
+int chunk_sps(size_t work) {
+  const size_t target = work >= 512 * 4 ? 512 : 256;
+  const size_t sps = (work + target - 1) / target;
+  return sps < 1 ? 1 : (sps > MM_MAX_TILES / 4 ? MM_MAX_TILES / 4 : (int)sps);
+}
+
+size_t job_work(const PairJob& J) {
+  return J.n1 ? (size_t)((J.n1 + MM_ROWS - 1) / MM_ROWS) * ((J.n2 + MM_SUPER - 1) / MM_SUPER) : 0;
+}
+
+// The class jobs of typed sets s1[sa] x s2[sb]: one per class present on both sides (n1 = n2 = 0 otherwise).
+void type_jobs(const DescSets& s1, int sa, const DescSets& s2, int sb, PairJob* J4) {
+  for (int c = 0; c < 4; c++) {
+    PairJob& J = J4[c];
+    J = PairJob{};
+    J.a = s1.goff[4 * sa + c];
+    J.b = s2.goff[4 * sb + c];
+    J.n1 = s1.gnum[4 * sa + c];
+    J.n2 = s2.gnum[4 * sb + c];
+    if (J.n1 == 0 || J.n2 == 0) J.n1 = J.n2 = 0;
+  }
+}
 
 // Plans c's jobs (a, b, n1, n2 given, n1 = n2 = 0 for a pair without work): shapes, segments and offsets into the scratch;
 // and c's totals.  Returns the scratch bytes.
@@ -805,7 +1138,8 @@ size_t plan_chunk(PairJob* jobs, Chunk& c, int mutual_best) {
 // block)) into the pinned slot hp and up to m->plan, then `start`, the multiply and the finish.  s1, s2: the sets the
 // jobs' a, b index.  The caller has grown every buffer to c's size.
 hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Chunk& c,
-                     uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax) {
+                     uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
+                     const int2* orig = nullptr) {
   const int np = c.p1 - c.p0;
   memcpy(hp, jobs + c.p0, np * sizeof(PairJob));
   int2* const work = reinterpret_cast<int2*>(hp + np * sizeof(PairJob));
@@ -819,6 +1153,7 @@ hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, co
     const int nfb = (J.n1 + 255) / 256 + (mutual_best ? (J.n2 + 31) / 32 : 0);
     for (int b = 0; b < nfb; b++) fin[jf++] = make_int2(q, b);
   }
+  if (c.norig()) memcpy(fin + c.nfin, orig + c.p0 / 4, c.norig() * sizeof(int2));
   const PairJob* djobs = reinterpret_cast<const PairJob*>(m->plan);
   const int2* dwork = reinterpret_cast<const int2*>(m->plan + np * sizeof(PairJob));
   const hipError_t e = hipMemcpyAsync(m->plan, hp, c.plan_bytes(), hipMemcpyHostToDevice, m->st);
@@ -948,11 +1283,53 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
                        float ratiomax, float hdistmax, float fdistmax, int mutual_best) {
   if (!m || !pairs || max_match < 0) return HESS_ERR_ARG;
   const int n1 = m->slot[0].count(0), n2 = m->slot[1].count(0);
-  if (n1 <= 0 || n2 <= 0) return 0;
   const bool guided = (H != nullptr) || (F != nullptr);
+  const bool typed = m->slot[0].typed && m->slot[1].typed;
+  if (guided && (m->slot[0].typed || m->slot[1].typed)) {
+    m->err = "match: guided matching (H, F) with feature types is not built; remove the types (set_types NULL) first";
+    return HESS_ERR_UNSUPPORTED;
+  }
+  if (m->slot[0].typed != m->slot[1].typed) {
+    m->err = std::string("match: slot ") + (m->slot[0].typed ? "1" : "0") + " has no types and the other has (set_types both, or NULL both)";
+    return HESS_ERR_STATE;
+  }
+  if (n1 <= 0 || n2 <= 0) return 0;
   if (guided && (!H || !F)) { m->err = "guided matching needs both H and F"; return HESS_ERR_ARG; }
   if (guided && (!m->have_loc[0] || !m->have_loc[1])) return 0;  // SiftMatchCU.cpp:131
   M_TRY(m, hipSetDevice(m->device));
+  if (typed) {
+    // the gated pair: its class jobs through the job tables at any size (bank pairs take them below the 3 Mi switch too),
+    // compacted on the device in original row order
+    PairJob jobs[4];
+    type_jobs(m->slot[0], 0, m->slot[1], 0, jobs);
+    size_t work = 0;
+    for (const PairJob& J : jobs) work += job_work(J);
+    Chunk c{0, 4, chunk_sps(work), 0, 0, 0, 0, 0, 0, 4};
+    plan_chunk(jobs, c, mutual_best);
+    const int2 orig = make_int2(0, n1);
+    const int mm = std::min(n1, max_match);
+    const size_t outn = (size_t)MP_PAIRS + (size_t)mm * 2;
+    M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, std::max<size_t>(c.rs, 1)));
+    M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, std::max<size_t>(c.cp, 1)));
+    M_TRY(m, grow_device(m->rowm, m->rowm_cap, std::max<size_t>(c.rm, 1)));
+    M_TRY(m, grow_device(m->colm, m->colm_cap, std::max<size_t>(c.cm, 1)));
+    M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, outn));
+    M_TRY(m, grow_device(m->plan, m->plan_cap, c.plan_bytes()));
+    M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, c.plan_bytes()));
+    M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, outn));
+    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], jobs, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax, &orig));
+    hipLaunchKernelGGL(match_types_compact_kernel, dim3(1), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
+                       reinterpret_cast<const int2*>(m->plan + c.plan_bytes()) - 1, m->slot[0].fwd, m->slot[1].inv, m->rowm,
+                       m->colm, mutual_best ? 1 : 0, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    (void)hipEventRecord(m->e1, m->st);
+    M_TRY(m, hipGetLastError());
+    M_TRY(m, hipMemcpyAsync(m->mp_hout[0], m->mp_out, outn * sizeof(int), hipMemcpyDeviceToHost, m->st));
+    M_TRY(m, hipStreamSynchronize(m->st));
+    (void)hipEventElapsedTime(&m->last_ms, m->e0, m->e1);
+    const int nmatch = m->mp_hout[0][0];
+    memcpy(pairs, m->mp_hout[0] + MP_PAIRS, (size_t)nmatch * 2 * sizeof(int));
+    return nmatch;
+  }
   M_TRY(m, grow_device(m->rowm, m->rowm_cap, (size_t)n1));
   M_TRY(m, grow_device(m->colm, m->colm_cap, (size_t)n2));
   // small problems (three launches of latency) stay on the one-pass dot kernel: 1024 x 1024 0.026 vs 0.033 ms
@@ -1035,7 +1412,31 @@ int hess_matcher_bank_set_f32(hess_matcher* m, int nsets, const int* counts, con
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   std::vector<int> kept((size_t)nsets);
   std::vector<unsigned char> q = quantise(des, (size_t)m->dim, nsets, counts, m->max_sift, kept.data());
-  return hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
+  const int rc = hess_matcher_bank_set(m, nsets, kept.data(), q.empty() ? nullptr : q.data());
+  if (rc == 0) m->bank.cnt.assign(counts, counts + nsets);  // (types are indexed as the caller counted)
+  return rc;
+}
+
+// `bytes` from p on must be device memory of the matcher's device and lie within one allocation: HESS_ERR_ARG otherwise.
+static int device_range(hess_matcher* m, const void* p, size_t bytes, const char* what, const char* noun) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != m->device) {
+    (void)hipGetLastError();
+    m->err = std::string(what) + ": the " + noun + " are not device memory of device " + std::to_string(m->device);
+    return HESS_ERR_ARG;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
+      (const char*)p + bytes > (const char*)base + size) {
+    (void)hipGetLastError();
+    m->err = std::string(what) + ": the counts reach past the end of the " + noun + "' allocation";
+    return HESS_ERR_ARG;
+  }
+  (void)hipGetLastError();
+  return 0;
 }
 
 // The bank from descriptors in device memory, float (quantised by bank_build_kernel<true>) or bytes (<false>: stored as they
@@ -1050,23 +1451,7 @@ static int bank_set_device(hess_matcher* m, int nsets, const int* counts, const 
       m->err = "bank_set_device: the descriptors must be " + std::to_string(align) + "-byte aligned";
       return HESS_ERR_ARG;
     }
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    const hipError_t e = hipPointerGetAttributes(&at, dev_desc);
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != m->device) {
-      (void)hipGetLastError();
-      m->err = "bank_set_device: the descriptors are not device memory of device " + std::to_string(m->device);
-      return HESS_ERR_ARG;
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dev_desc) != hipSuccess ||
-        (const char*)dev_desc + rows * (size_t)m->dim * esz > (const char*)base + size) {
-      (void)hipGetLastError();
-      m->err = "bank_set_device: the counts reach past the end of the descriptors' allocation";
-      return HESS_ERR_ARG;
-    }
-    (void)hipGetLastError();
+    if (const int rc = device_range(m, dev_desc, rows * (size_t)m->dim * esz, "bank_set_device", "descriptors")) return rc;
   }
   sets_clear(m->bank);
   const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, f32);
@@ -1092,9 +1477,50 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
   if (out && n) {
     M_TRY(m, hipSetDevice(m->device));
     const size_t KD = (size_t)m->bank.dim;
-    M_TRY(m, hipMemcpy(out, m->bank.rows + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
+    if (m->bank.typed) {  // the set's four class groups, then the caller's order through fwd
+      const int g0 = m->bank.goff[4 * set];
+      size_t ext = 0;
+      for (int c = 0; c < 4; c++) ext += ((size_t)m->bank.gnum[4 * set + c] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+      std::vector<unsigned char> grp(ext * KD);
+      std::vector<int> fwd((size_t)n);
+      M_TRY(m, hipMemcpy(grp.data(), m->bank.rows + (size_t)g0 * KD, ext * KD, hipMemcpyDeviceToHost));
+      M_TRY(m, hipMemcpy(fwd.data(), m->bank.fwd + m->bank.first[set], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+      for (int i = 0; i < n; i++) memcpy(out + (size_t)i * KD, grp.data() + (size_t)(fwd[i] - g0) * KD, KD);
+    } else {
+      M_TRY(m, hipMemcpy(out, m->bank.rows + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
+    }
   }
   return n;
+}
+
+// ---- feature types: see the comment at type_classify_kernel ----------------------------------------------------------
+
+int hess_matcher_set_types(hess_matcher* m, int index, const uint16_t* types, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  if (index < 0 || index > 1) { m->err = "set_types: index must be 0 or 1, not " + std::to_string(index); return HESS_ERR_ARG; }
+  if (const int rc = types_args(m, m->slot[index], types, stride_bytes, "set_types")) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  return sets_types_host(m, m->slot[index], types, stride_bytes);
+}
+
+int hess_matcher_bank_set_types(hess_matcher* m, const uint16_t* types, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  if (const int rc = types_args(m, m->bank, types, stride_bytes, "bank_set_types")) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  return sets_types_host(m, m->bank, types, stride_bytes);
+}
+
+int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  if (const int rc = types_args(m, m->bank, dev_types, stride_bytes, "bank_set_types_device")) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  size_t rows = 0;
+  for (int c : m->bank.cnt) rows += (size_t)c;
+  if (dev_types && rows) {
+    if ((uintptr_t)dev_types % 2) { m->err = "bank_set_types_device: dev_types must be 2-byte aligned"; return HESS_ERR_ARG; }
+    if (const int rc = device_range(m, dev_types, (rows - 1) * stride_bytes + 2, "bank_set_types_device", "types")) return rc;
+  }
+  return sets_regroup(m, m->bank, dev_types, stride_bytes);
 }
 
 int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
@@ -1115,36 +1541,44 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
   M_TRY(m, hipSetDevice(m->device));
   mutual_best = mutual_best ? 1 : 0;
 
-  std::vector<PairJob> jobs((size_t)npairs);
+  // one job per pair, or with types on the bank one per pair and class (jobs jpp p .. jpp p + jpp - 1 are pair p's)
+  const bool typed = m->bank.typed;
+  const int jpp = typed ? 4 : 1;
+  std::vector<PairJob> jobs((size_t)npairs * jpp);
+  std::vector<int2> orig(typed ? (size_t)npairs : 0);
   for (int p = 0; p < npairs; p++) {
+    const int sa = pairs_ab[2 * p], sb = pairs_ab[2 * p + 1];
+    if (typed) {
+      type_jobs(m->bank, sa, m->bank, sb, &jobs[(size_t)p * 4]);
+      orig[p] = make_int2(m->bank.first[sa], m->bank.num[sa]);
+      continue;
+    }
     PairJob& J = jobs[p];
-    J.a = m->bank.off[pairs_ab[2 * p]];
-    J.b = m->bank.off[pairs_ab[2 * p + 1]];
-    J.n1 = m->bank.num[pairs_ab[2 * p]];
-    J.n2 = m->bank.num[pairs_ab[2 * p + 1]];
+    J.a = m->bank.off[sa];
+    J.b = m->bank.off[sb];
+    J.n1 = m->bank.num[sa];
+    J.n2 = m->bank.num[sb];
     if (J.n1 == 0 || J.n2 == 0) J.n1 = J.n2 = 0;  // a pair with an empty side has no work and no matches
   }
-  // Segments per pair from the whole chunk's grid: whole rounds of workgroups over the 256 CUs as in hess_matcher_match
-  // (two per CU when that leaves each at least four super tiles), at most MM_MAX_TILES / 4 super tiles per segment.
-  auto chunk_sps = [](size_t work) {
-    const size_t target = work >= 512 * 4 ? 512 : 256;
-    const size_t sps = (work + target - 1) / target;
-    return sps < 1 ? 1 : (sps > MM_MAX_TILES / 4 ? MM_MAX_TILES / 4 : (int)sps);
-  };
+  // Segments per pair from the whole chunk's grid: chunk_sps.
   std::vector<Chunk> chunks;
   int mm = 0;  // matches kept per pair: max_match, at most the rows of its set 1
-  for (int p0 = 0; p0 < npairs;) {
-    Chunk c{p0, p0, 1, 0, 0, 0, 0, 0, 0};
+  for (int p0 = 0; p0 < npairs;) {  // (p0 and `pairs` count pairs, the chunk's p0 and p1 jobs)
+    Chunk c{p0 * jpp, p0 * jpp, 1, 0, 0, 0, 0, 0, 0, jpp};
     size_t work = 0;
-    while (c.p1 < npairs && c.p1 - p0 < MP_PAIRS) {
-      const int n1 = jobs[c.p1].n1, n2 = jobs[c.p1].n2;
-      const size_t w = n1 ? (size_t)((n1 + MM_ROWS - 1) / MM_ROWS) * ((n2 + MM_SUPER - 1) / MM_SUPER) : 0;
+    int pairs = 0;
+    while (p0 + pairs < npairs && pairs < MP_PAIRS) {
+      const int sa = pairs_ab[2 * (p0 + pairs)], sb = pairs_ab[2 * (p0 + pairs) + 1];
+      const int n1 = m->bank.num[sb] ? m->bank.num[sa] : 0;
+      size_t w = 0;
+      for (int k = 0; k < jpp; k++) w += job_work(jobs[c.p1 + k]);
       Chunk t = c;
-      t.p1++;
+      t.p1 += jpp;
       t.sps = chunk_sps(work + w);
-      if (c.p1 > p0 && plan_chunk(jobs.data(), t, mutual_best) > MP_SCRATCH) break;
+      if (pairs > 0 && plan_chunk(jobs.data(), t, mutual_best) > MP_SCRATCH) break;
       c = t;
       work += w;
+      pairs++;
       mm = std::max(mm, std::min(n1, max_match));
     }
     plan_chunk(jobs.data(), c, mutual_best);  // (the plan of the chunk as it ends)
@@ -1153,13 +1587,13 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
       return HESS_ERR_TOO_BIG;
     }
     chunks.push_back(c);
-    p0 = c.p1;
+    p0 += pairs;
   }
   size_t rs = 1, cp = 1, rm = 1, cm = 1, plan = 0, outn = 0;
   for (const Chunk& c : chunks) {
     rs = std::max(rs, c.rs); cp = std::max(cp, c.cp); rm = std::max(rm, c.rm); cm = std::max(cm, c.cm);
     plan = std::max(plan, c.plan_bytes());
-    outn = std::max(outn, (size_t)MP_PAIRS + (size_t)(c.p1 - c.p0) * mm * 2);
+    outn = std::max(outn, (size_t)MP_PAIRS + (size_t)(c.p1 - c.p0) / jpp * mm * 2);
   }
   M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, rs));
   M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, cp));
@@ -1185,22 +1619,28 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
     if (e != hipSuccess) return e;
     total_ms += ms;
     const int* h = m->mp_hout[k & 1];
-    for (int p = c.p0; p < c.p1; p++) {
-      const int n = h[p - c.p0];
+    const int q0 = c.p0 / jpp, q1 = c.p1 / jpp;
+    for (int p = q0; p < q1; p++) {
+      const int n = h[p - q0];
       out_counts[p] = n;
-      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - c.p0) * mm * 2, (size_t)n * 2 * sizeof(int));
+      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - q0) * mm * 2, (size_t)n * 2 * sizeof(int));
     }
     return hipSuccess;
   };
   hipError_t err = hipSuccess;
   for (size_t k = 0; k < chunks.size() && err == hipSuccess; k++) {
     const Chunk& c = chunks[k];
-    const int np = c.p1 - c.p0;
+    const int np = (c.p1 - c.p0) / jpp;
     hipEvent_t* ev = m->mp_ev[k & 1];
-    err = run_chunk(m, m->bank, m->bank, jobs.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax);
+    err = run_chunk(m, m->bank, m->bank, jobs.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax, orig.data());
     if (err != hipSuccess) break;
-    hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
-                       m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    if (typed)
+      hipLaunchKernelGGL(match_types_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
+                         reinterpret_cast<const int2*>(m->plan + c.plan_bytes()) - c.norig(), m->bank.fwd, m->bank.inv, m->rowm,
+                         m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    else
+      hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
+                         m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
     (void)hipEventRecord(ev[1], m->st);
     err = hipGetLastError();
     if (err != hipSuccess) break;

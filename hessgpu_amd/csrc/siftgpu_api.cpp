@@ -963,6 +963,14 @@ int SiftMatchGPU::GetGuidedSiftMatch(int max_match, int match_buffer[][2], float
                                    distmax, ratiomax, H ? hdistmax : ti, F ? fdistmax : ti, mbm);
   return n < 0 ? 0 : n;
 }
+int SiftMatchGPU::SetFeatureTypes(int index, const SiftGPU::SiftKeypoint* keys) {
+  return SetFeatureTypes(index, keys ? &keys->type : nullptr, (int)sizeof(SiftGPU::SiftKeypoint)) == 0;
+}
+int SiftMatchGPU::SetFeatureTypes(int index, const unsigned short* types, int stride_bytes) {
+  if (!_VerifyContextGL()) return HESS_ERR_DEVICE;
+  return hess_matcher_set_types(MH(__matcher), index > 1 ? 1 : (index < 0 ? 0 : index), types,
+                                stride_bytes < 0 ? 0 : (size_t)stride_bytes);
+}
 void* SiftMatchGPU::operator new(size_t size) {
   void* p = malloc(size);
   if (!p) throw std::bad_alloc();
@@ -1016,6 +1024,9 @@ int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const f
   if (F) memcpy(f, F, sizeof(f));
   return m->GetGuidedSiftMatch(max_match, reinterpret_cast<int(*)[2]>(buf), H ? h : nullptr, F ? f : nullptr, distmax,
                                ratiomax, hdistmax, fdistmax, mbm);
+}
+int siftmatch_set_types(SiftMatchGPU* m, int index, const unsigned short* types, int stride_bytes) {
+  return m ? m->SetFeatureTypes(index, types, stride_bytes) : HESS_ERR_ARG;
 }
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { return s->RunSIFT(num, keys, have_orientation); }
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { s->SetKeypointList(num, keys, have_orientation); }

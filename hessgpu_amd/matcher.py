@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import load_library
+from . import _abi, load_library
 from .session import HessError
 
 _bound = False
@@ -33,6 +33,9 @@ def _lib():
         L.hess_matcher_bank_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hess_matcher_match_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_float, C.c_float, C.c_int]
+        L.hess_matcher_set_types.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.hess_matcher_bank_set_types.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.hess_matcher_bank_set_types_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.hess_matcher_last_ms.restype = C.c_float
         L.hess_matcher_last_ms.argtypes = [C.c_void_p]
         L.hess_matcher_last_error.restype = C.c_char_p
@@ -128,6 +131,36 @@ class Matcher:
         a = np.ascontiguousarray(loc, dtype=np.float32)
         self._check(self.L.hess_matcher_set_locations(self.h, index, a.ctypes.data, gap))
 
+    @staticmethod
+    def _types(types):
+        """-> (array that owns the memory, address, stride in bytes) of one u16 per feature.  A structured key array
+        (HessContext.fetch) is read in place through its "type" field."""
+        a = np.asarray(types)
+        if a.dtype.names and "type" in a.dtype.names:
+            a = a["type"]
+        if a.dtype != np.uint16:
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"feature types are integers (hess_keypoint.type), not {a.dtype}")
+            a = (a.astype(np.int64) & 0xffff).astype(np.uint16)
+        if a.ndim != 1:
+            raise ValueError(f"feature types must be one value per feature, not an array of shape {a.shape}")
+        if len(a) > 1 and (a.strides[0] < 2 or a.strides[0] % 2):
+            a = np.ascontiguousarray(a)
+        return a, a.ctypes.data, (a.strides[0] if len(a) > 1 else 2)
+
+    def set_types(self, index, types):
+        """The feature types (hess_keypoint.type: class = type & 3) of slot `index`, one per descriptor loaded there: with
+        both slots typed, match() (unguided) pairs features of the same class only -- best, second best, ratio test and
+        mutual best within the class.  None removes them; set_descriptors on the slot removes them too."""
+        if types is None:
+            self._check(self.L.hess_matcher_set_types(self.h, int(index), None, 2))
+            return
+        a, ptr, stride = self._types(types)
+        if not len(a):
+            a = np.zeros(1, np.uint16)      # (an address for a slot without descriptors: nothing is read)
+            ptr = a.ctypes.data
+        self._check(self.L.hess_matcher_set_types(self.h, int(index), ptr, stride))
+
     def match(self, max_match=4096, H=None, F=None, distmax=0.7, ratiomax=0.8, hdistmax=32.0, fdistmax=16.0,
               mutual_best=True):
         out = np.zeros((max(max_match, 1), 2), dtype=np.int32)
@@ -169,18 +202,37 @@ class Matcher:
         self._check(fn(self.h, len(c), c.ctypes.data, ptr))
         self._bank_sets = len(c)
 
-    def set_bank_from_session(self, session):
+    def set_bank_types(self, types):
+        """types: one array per bank set (as passed to set_bank, before truncation to max_sift), or None to remove the
+        types.  With types on the bank match_pairs returns the gated match of every pair (see set_types)."""
+        if types is None:
+            self._check(self.L.hess_matcher_bank_set_types(self.h, None, 2))
+            return
+        parts = [self._types(t)[0] for t in types]
+        flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.uint16), dtype=np.uint16)
+        if not len(flat):
+            flat = np.zeros(1, np.uint16)   # (an address for a bank without descriptors: nothing is read)
+        self._check(self.L.hess_matcher_bank_set_types(self.h, flat.ctypes.data, 2))
+
+    def set_bank_types_device(self, ptr, stride):
+        """ptr: device address of the first u16 type on the matcher's device, one per descriptor `stride` bytes apart."""
+        self._check(self.L.hess_matcher_bank_set_types_device(self.h, ptr, int(stride)))
+
+    def set_bank_from_session(self, session, types=False):
         """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,
         without leaving the device -- floats or bytes, whichever the run made.  The context's descriptor length must be the
-        matcher's: Matcher(dim=64) for a half_sift context."""
+        matcher's: Matcher(dim=64) for a half_sift context.  types=True also takes the type field of the device key records,
+        so that match_pairs gates by feature type (set_bank_types), again without a host round trip."""
         dim = session.desc_dim()
         if dim != self.dim:
             raise ValueError(f"the matcher takes {self.dim}-d descriptors; this context's are {dim}-d (-half / -sd)")
-        _, desc, total = session.device_results()
+        keys, desc, total = session.device_results()
         counts = [session.count(i) for i in range(session._batch)]
         if sum(counts) != total:
             raise ValueError(f"the context's counts ({sum(counts)}) do not cover its device results ({total})")
         self.set_bank_device(desc, counts, dtype=np.uint8 if session.desc_format() == "u8" else np.float32)
+        if types:
+            self.set_bank_types_device((keys or 0) + _abi.KEYPOINT_DTYPE.fields["type"][1], _abi.KEYPOINT_DTYPE.itemsize)
 
     def bank(self, i):
         """The stored bytes of set i: [n, dim] u8."""

@@ -156,6 +156,15 @@ class SiftMatchGPU {
                                  float distmax = 0.7, float ratiomax = 0.8, float hdistmax = 32,
                                  float fdistmax = 16, int mutual_best_match = 1);
   void* operator new(size_t size);
+  // Not in the reference, and NOT virtual (declared after the virtual functions: layout and vtable are the reference's).
+  // The feature types of the descriptors in slot `index` (keys[i].type, one per descriptor set there; NULL removes them).
+  // With types on both slots GetSiftMatch pairs features of the same class (type & 3: dark, bright, saddle, none) only:
+  // best, second best, the ratio test and mutual best within the class (hess_matcher_set_types, hess_abi.h).  SetDescriptors
+  // on a slot removes its types.  GetGuidedSiftMatch with a matrix is not built for typed slots and returns 0 matches.
+  // Returns 1, or 0 when the types were refused (no descriptors in the slot yet, no matcher).
+  int SetFeatureTypes(int index, const SiftGPU::SiftKeypoint* keys);
+  // the same for any array of types, one every stride_bytes (2: packed); returns the hess_status (0, or negative)
+  int SetFeatureTypes(int index, const unsigned short* types, int stride_bytes);
 };
 
 typedef SiftGPU::SiftKeypoint SiftKeypoint;
@@ -195,6 +204,8 @@ void siftmatch_set_locations(SiftMatchGPU* m, int index, const float* loc, int g
 // H, F: 3x3 row-major or NULL (GetGuidedSiftMatch's rule for a missing matrix)
 int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const float* H, const float* F, float distmax,
                                float ratiomax, float hdistmax, float fdistmax, int mbm);
+// SetFeatureTypes(index, types, stride_bytes): NULL removes the types; returns the hess_status
+int siftmatch_set_types(SiftMatchGPU* m, int index, const unsigned short* types, int stride_bytes);
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 // The resolved hess_params of the instance (what ParseParam did), for tests.

@@ -44,7 +44,9 @@ extern "C" {
  *    calls the setter is 128-d as before).  hess_set_keypoints_batch / hess_run_keypoints_batch / hess_key_list_order
  *    (keypoint lists for every image of a batch; added during version 5 without a bump: hess_set_keypoints and
  *    hess_run_keypoints are the same calls with one image and answer as before, except that hess_set_keypoints now
- *    refuses while a submitted batch is pending, where it used to corrupt that batch's results). */
+ *    refuses while a submitted batch is pending, where it used to corrupt that batch's results).
+ *    hess_matcher_set_types / _bank_set_types / _bank_set_types_device (the feature-type gate of the matcher; added
+ *    during version 5 without a bump: a matcher that never calls them matches as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -477,6 +479,35 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out);
  * negative hess_status; hess_matcher_last_ms: device time of all the call's kernels. */
 int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
                              int* out_counts, float distmax, float ratiomax, int mutual_best);
+
+/* Feature types (no reference counterpart in the matcher; the detector's README: "features of different types should
+ * not be considered for a correspondence").  Class of a feature = type & 3 (hess_keypoint.type: 0 dark, 1 bright,
+ * 2 saddle, 3 none; higher bits are ignored).  With types on both single-pair slots hess_matcher_match (H = F = NULL),
+ * and with types on the bank hess_matcher_match_pairs, return the GATED match G of a pair:
+ *   1. per class c, the ungated match (same thresholds, no limit) of the rows of set 1 of class c against the rows of
+ *      set 2 of class c, each in ascending original order;
+ *   2. the indices mapped back to the original rows, the union in ascending row of set 1;
+ *   3. the first max_match of them.
+ * Best, second best, the ratio test and mutual best see same-class features only, and the reference's tie order applies
+ * to a column's position within its class subset.  This is not what discarding mixed pairs from the ungated result
+ * gives.  A typed set is stored grouped by class on the device; hess_matcher_bank_read returns the caller's order.
+ *
+ * types: one value per descriptor, stride_bytes apart (&keys[0].type with sizeof(hess_keypoint), or a packed array with
+ * 2), as the caller counted them when the descriptors were loaded: for the bank the sets back to back, each truncated
+ * to max_sift as its descriptors were.  NULL removes the types (results are the ungated ones again).  Loading
+ * descriptors (hess_matcher_set_descriptors* on a slot, hess_matcher_bank_set* on the bank) removes that slot's or the
+ * bank's types; hess_matcher_set_dim to the other length removes everything.  A matcher that never calls these
+ * behaves as before.  The device form takes device memory of the matcher's device, 2-byte aligned, with the pointer
+ * check and error of hess_matcher_bank_set_device -- meant for (const char*)keys + offsetof(hess_keypoint, type) of
+ * hess_device_results with stride sizeof(hess_keypoint).  All three return when the sets are ready.
+ *   HESS_ERR_STATE        types before the descriptors they belong to; hess_matcher_match with exactly one slot typed
+ *   HESS_ERR_ARG          stride_bytes odd or below 2; index not 0 or 1; a bad device pointer
+ *   HESS_ERR_UNSUPPORTED  hess_matcher_match with H or F while either slot has types: guided matching with types is
+ *                         NOT built (the types are never ignored silently: remove them first)
+ * hess_matcher_last_error names the argument; the matcher is unchanged after an error. */
+int hess_matcher_set_types(hess_matcher* m, int index, const uint16_t* types, size_t stride_bytes);
+int hess_matcher_bank_set_types(hess_matcher* m, const uint16_t* types, size_t stride_bytes);
+int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, size_t stride_bytes);
 float hess_matcher_last_ms(hess_matcher* m);   /* device time of the last match's kernels */
 const char* hess_matcher_last_error(hess_matcher* m);
 
