@@ -26,7 +26,7 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
 # loaded side by side by the tests; without it the second one's internal calls would resolve to the first one's code.
 LINK_LIBS = ["-lhsa-runtime64", "-lrt", "-Wl,-Bsymbolic"]
 KERNEL_SOURCES = ["k_gauss.hip", "k_detect.hip", "k_feature.hip", "hess_plan.hip", "hess_schedule.hip", "hess_copier.hip",
-                  "hess_stager.cpp", "hess_shared.hip", "hess_abi.hip", "hess_match.hip"]  # (hess_stager.cpp: host code, standard headers only)
+                  "hess_stager.cpp", "hess_shared.hip", "hess_abi.hip", "hess_match.hip", "hess_geom.hip"]  # (hess_stager.cpp: host code, standard headers only)
 DEV_SWITCH_SOURCES = ("hess_abi.hip", "hess_copier.hip", "hess_shared.hip")  # the files that call dev_env()
 # Per-file flags.  k_feature.hip: the SLP vectoriser turns pairs of FP32 operations into packed
 # instructions (v_pk_add/mul/fma_f32), which on gfx950 issue at half rate (tools/micro/README.md) and need

@@ -1,0 +1,820 @@
+// hess_geom.hip -- two-view geometry from matches on the matcher's device: a deterministic, fixed-budget RANSAC for a
+// homography or a fundamental matrix (hess_matcher_estimate, hess_matcher_estimate_pairs; the rule is stated in
+// include/hess_abi.h).  No reference counterpart: SiftMatchGPU's callers do this step on the host.
+//
+//   geom_score_kernel    one workgroup per (pair, block of 256 hypotheses) of a work table, one hypothesis per lane: sample
+//                        (geom_sample), solve in registers (geom_null_vector: fully unrolled Gauss-Jordan, pivots by
+//                        selects), then count the pair's correspondences that pass the gate -- gathered once per workgroup
+//                        into LDS as float4 (x1, y1, x2, y2), 2048 at a time, every lane reading the same address
+//                        (a broadcast) -- and store the block's best (score, lowest t, matrix);
+//   geom_finish_kernel   one workgroup per pair: arg-max over the block entries (score, then lowest t), rank 2 for F and
+//                        unit norm in double (one thread), then the inlier mask with the guided gate's own formulas
+//                        (match_dot_kernel, hess_match.hip) and its count;
+//   geom_loc_gather_kernel  bank locations from strided records into the caller's row order of the kept rows.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/hess_abi.h"
+#include "hess_matcher_int.h"
+
+namespace {
+
+constexpr int GEOM_CHUNK = 2048;        // correspondences in LDS at a time: 32 KB
+constexpr int GEOM_DEFAULT_T = 2048;
+constexpr int GEOM_MAX_T = 65536;       // 256 blocks of 256 hypotheses: one finish thread per block
+constexpr int GEOM_PAIRS = 256;         // pairs per chunk (one set of launches), and
+constexpr size_t GEOM_MATCHES = (size_t)4 << 20;  // correspondences per chunk (a pair above it is a chunk of its own)
+
+constexpr int geom_k(int model) { return model == HESS_GEOM_HOMOGRAPHY ? 4 : 8; }
+
+__host__ __device__ inline uint32_t geom_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+
+// The sampling rule (hess_abi.h, step 1): k <= 8 distinct indices below n in draw order.  Compile-time indices only: with
+// a constant k everything stays in registers.
+__host__ __device__ inline void geom_sample(uint32_t seed, int t, int k, int n, int (&out)[8]) {
+  const uint32_t h = geom_mix(geom_mix(seed ^ 0x9E3779B9u) + (uint32_t)t);
+  int sorted[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    out[j] = 0;
+    sorted[j] = 0;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    if (j < k) {
+      int c = (int)(((uint64_t)geom_mix(h + (uint32_t)j) * (uint32_t)(n - j)) >> 32);
+#pragma unroll
+      for (int i = 0; i < j; i++) c += sorted[i] <= c ? 1 : 0;  // the earlier draws in ascending value
+      out[j] = c;
+#pragma unroll
+      for (int i = j; i >= 0; i--) {  // insert c: sorted[0..j] ascending
+        const int a = i < j ? sorted[i] : INT32_MAX, b = i > 0 ? sorted[i - 1] : -1;
+        sorted[i] = a < c ? a : (b < c ? c : b);
+      }
+    }
+  }
+}
+
+// The unit null vector direction x of the 8 x 9 matrix a (destroyed): Gauss-Jordan elimination with complete pivoting.
+// Rows and columns are never moved: a pivot is the largest remaining |a[r][c]| over the unused rows and columns, found,
+// read and applied through selects on compile-time indices, so the 72 entries stay in registers.  After eight steps one
+// column f is left: x[f] = 1 and row r gives x[its pivot column] = -a[r][f] / a[r][pivot column].  A singular system
+// divides by zero: the caller's finiteness test drops the hypothesis.
+__host__ __device__ inline void geom_null_vector(float (&a)[8][9], float (&x)[9]) {
+  unsigned rused = 0, cused = 0;
+  int pcol[8];
+#pragma unroll
+  for (int r = 0; r < 8; r++) pcol[r] = 0;
+#pragma unroll
+  for (int step = 0; step < 8; step++) {
+    float best = -1.0f;
+    int pr = 0, pc = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const bool rfree = !((rused >> r) & 1u);
+#pragma unroll
+      for (int c = 0; c < 9; c++) {
+        const float v = fabsf(a[r][c]);
+        const bool take = rfree && !((cused >> c) & 1u) && v > best;
+        best = take ? v : best;
+        pr = take ? r : pr;
+        pc = take ? c : pc;
+      }
+    }
+    rused |= 1u << pr;
+    cused |= 1u << pc;
+    float prow[9], piv = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 9; c++) {
+      float v = a[0][c];
+#pragma unroll
+      for (int r = 1; r < 8; r++) v = pr == r ? a[r][c] : v;
+      prow[c] = v;
+      piv = pc == c ? v : piv;
+    }
+    const float inv = 1.0f / piv;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      float f = a[r][0];
+#pragma unroll
+      for (int c = 1; c < 9; c++) f = pc == c ? a[r][c] : f;
+      f = pr == r ? 0.0f : f * inv;
+      pcol[r] = pr == r ? pc : pcol[r];
+#pragma unroll
+      for (int c = 0; c < 9; c++) a[r][c] = fmaf(-f, prow[c], a[r][c]);
+    }
+  }
+  int fc = 0;
+#pragma unroll
+  for (int c = 0; c < 9; c++) fc = ((cused >> c) & 1u) ? fc : c;
+#pragma unroll
+  for (int c = 0; c < 9; c++) x[c] = fc == c ? 1.0f : 0.0f;
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    float num = a[r][0], den = a[r][0];
+#pragma unroll
+    for (int c = 1; c < 9; c++) {
+      num = fc == c ? a[r][c] : num;
+      den = pcol[r] == c ? a[r][c] : den;
+    }
+    const float v = -num / den;
+#pragma unroll
+    for (int c = 0; c < 9; c++) x[c] = pcol[r] == c ? v : x[c];
+  }
+}
+
+// Hartley normalisation of K points: centre and scale s with mean distance sqrt 2, p_n = s (p - c).
+template <int K>
+__host__ __device__ inline void geom_normalise(float (&x)[K], float (&y)[K], float& cx, float& cy, float& s) {
+  float sx = 0.0f, sy = 0.0f;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    sx += x[i];
+    sy += y[i];
+  }
+  cx = sx * (1.0f / K);
+  cy = sy * (1.0f / K);
+  float d = 0.0f;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    x[i] -= cx;
+    y[i] -= cy;
+    d += sqrtf(fmaf(x[i], x[i], y[i] * y[i]));
+  }
+  s = 1.41421356237f * K / d;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    x[i] *= s;
+    y[i] *= s;
+  }
+}
+
+// The hypothesis of geom_k(MODEL) correspondences (x1, y1) -> (x2, y2) in pixel coordinates (destroyed); false: not finite.
+template <int MODEL>
+__host__ __device__ inline bool geom_hypothesis(float (&x1)[geom_k(MODEL)], float (&y1)[geom_k(MODEL)],
+                                                float (&x2)[geom_k(MODEL)], float (&y2)[geom_k(MODEL)], float (&M)[9]) {
+  constexpr int K = geom_k(MODEL);
+  float c1x, c1y, s1, c2x, c2y, s2;
+  geom_normalise<K>(x1, y1, c1x, c1y, s1);
+  geom_normalise<K>(x2, y2, c2x, c2y, s2);
+  float a[8][9];
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    const float x = x1[i], y = y1[i], u = x2[i], v = y2[i];
+    if (MODEL == HESS_GEOM_HOMOGRAPHY) {  // u (h6 x + h7 y + h8) = h0 x + h1 y + h2, and the same for v
+      float(&r0)[9] = a[(2 * i) & 7];
+      float(&r1)[9] = a[(2 * i + 1) & 7];
+      r0[0] = x; r0[1] = y; r0[2] = 1.0f; r0[3] = 0.0f; r0[4] = 0.0f; r0[5] = 0.0f; r0[6] = -u * x; r0[7] = -u * y; r0[8] = -u;
+      r1[0] = 0.0f; r1[1] = 0.0f; r1[2] = 0.0f; r1[3] = x; r1[4] = y; r1[5] = 1.0f; r1[6] = -v * x; r1[7] = -v * y; r1[8] = -v;
+    } else {                              // (u, v, 1) F (x, y, 1)^T = 0
+      float(&r)[9] = a[i & 7];
+      r[0] = u * x; r[1] = u * y; r[2] = u; r[3] = v * x; r[4] = v * y; r[5] = v; r[6] = x; r[7] = y; r[8] = 1.0f;
+    }
+  }
+  float h[9];
+  geom_null_vector(a, h);
+  // G = h T1, T1 = [s1 0 -s1 c1x; 0 s1 -s1 c1y; 0 0 1]
+  float G[9];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    G[3 * r] = h[3 * r] * s1;
+    G[3 * r + 1] = h[3 * r + 1] * s1;
+    G[3 * r + 2] = h[3 * r + 2] - s1 * fmaf(h[3 * r], c1x, h[3 * r + 1] * c1y);
+  }
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (MODEL == HESS_GEOM_HOMOGRAPHY) {  // H = T2^-1 G, T2^-1 = [1/s2 0 c2x; 0 1/s2 c2y; 0 0 1]
+      M[c] = fmaf(c2x, G[6 + c], G[c] / s2);
+      M[3 + c] = fmaf(c2y, G[6 + c], G[3 + c] / s2);
+      M[6 + c] = G[6 + c];
+    } else {                              // F = T2^T G, T2^T = [s2 0 0; 0 s2 0; -s2 c2x  -s2 c2y  1]
+      M[c] = s2 * G[c];
+      M[3 + c] = s2 * G[3 + c];
+      M[6 + c] = G[6 + c] - s2 * fmaf(c2x, G[c], c2y * G[3 + c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 9; c++) ok = ok && fabsf(M[c]) <= 3.0e38f;  // (false for NaN and infinity)
+  return ok;
+}
+
+// Scoring test of a hypothesis: the gate's inequalities multiplied through by their (positive) denominators.
+template <int MODEL>
+__host__ __device__ inline bool geom_pass(const float (&M)[9], const float4 p, float bound) {
+  if (MODEL == HESS_GEOM_HOMOGRAPHY) {
+    const float x0 = fmaf(M[0], p.x, M[1] * p.y) + M[2];
+    const float x1 = fmaf(M[3], p.x, M[4] * p.y) + M[5];
+    const float x2 = fmaf(M[6], p.x, M[7] * p.y) + M[8];
+    const float lim = bound * fabsf(x2);
+    return fabsf(fmaf(-x2, p.z, x0)) < lim && fabsf(fmaf(-x2, p.w, x1)) < lim;
+  } else {
+    const float fx0 = fmaf(M[0], p.x, M[1] * p.y) + M[2];
+    const float fx1 = fmaf(M[3], p.x, M[4] * p.y) + M[5];
+    const float fx2 = fmaf(M[6], p.x, M[7] * p.y) + M[8];
+    const float ft0 = fmaf(M[0], p.z, M[3] * p.w) + M[6];
+    const float ft1 = fmaf(M[1], p.z, M[4] * p.w) + M[7];
+    const float s = fmaf(p.z, fx0, p.w * fx1) + fx2;
+    return s * s < bound * fmaf(ft1, ft1, fmaf(ft0, ft0, fmaf(fx0, fx0, fx1 * fx1)));
+  }
+}
+
+// The guided gate itself, as match_dot_kernel (hess_match.hip) evaluates it: the mask's decision.
+template <int MODEL>
+__host__ __device__ inline bool geom_gate(const float (&M)[9], const float2 l1, const float2 l2, float bound) {
+  if (MODEL == HESS_GEOM_HOMOGRAPHY) {
+    const float x0 = fmaf(M[0], l1.x, M[1] * l1.y) + M[2];
+    const float x1 = fmaf(M[3], l1.x, M[4] * l1.y) + M[5];
+    const float x2 = fmaf(M[6], l1.x, M[7] * l1.y) + M[8];
+    const float d0 = fabsf(x0 / x2 - l2.x), d1 = fabsf(x1 / x2 - l2.y);
+    return d0 < bound && d1 < bound;
+  } else {
+    const float fx0 = fmaf(M[0], l1.x, M[1] * l1.y) + M[2];
+    const float fx1 = fmaf(M[3], l1.x, M[4] * l1.y) + M[5];
+    const float fx2 = fmaf(M[6], l1.x, M[7] * l1.y) + M[8];
+    const float ft0 = fmaf(M[0], l2.x, M[3] * l2.y) + M[6];
+    const float ft1 = fmaf(M[1], l2.x, M[4] * l2.y) + M[7];
+    const float x2fx1 = fmaf(l2.x, fx0, l2.y * fx1) + fx2;
+    const float se = (x2fx1 * x2fx1) / fmaf(ft1, ft1, fmaf(ft0, ft0, fmaf(fx0, fx0, fx1 * fx1)));
+    return se < bound;
+  }
+}
+
+// One rotation of the one-sided Jacobi SVD: makes columns P and Q of w orthogonal, v collects the rotations.
+template <int P, int Q>
+__host__ __device__ inline bool geom_rotate(double (&w)[9], double (&v)[9]) {
+  double al = 0.0, be = 0.0, ga = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    al = fma(w[3 * r + P], w[3 * r + P], al);
+    be = fma(w[3 * r + Q], w[3 * r + Q], be);
+    ga = fma(w[3 * r + P], w[3 * r + Q], ga);
+  }
+  if (ga == 0.0 || fabs(ga) <= 1.0e-17 * sqrt(al * be)) return false;
+  const double ze = (be - al) / (2.0 * ga);
+  const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
+  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const double wp = w[3 * r + P], wq = w[3 * r + Q], vp = v[3 * r + P], vq = v[3 * r + Q];
+    w[3 * r + P] = c * wp - s * wq;
+    w[3 * r + Q] = s * wp + c * wq;
+    v[3 * r + P] = c * vp - s * vq;
+    v[3 * r + Q] = s * vp + c * vq;
+  }
+  return true;
+}
+
+// The winner's matrix as returned: for F the nearest rank-2 matrix (A V = W with orthogonal columns, the shortest column of
+// W zeroed, A' = W' V^T), then unit Frobenius norm.
+__host__ __device__ inline void geom_finalise(int model, double (&m)[9]) {
+  if (model == HESS_GEOM_FUNDAMENTAL) {
+    double v[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < 30; sweep++) {
+      const bool r01 = geom_rotate<0, 1>(m, v), r02 = geom_rotate<0, 2>(m, v), r12 = geom_rotate<1, 2>(m, v);
+      if (!(r01 || r02 || r12)) break;
+    }
+    double n[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) n[c] = m[c] * m[c] + m[3 + c] * m[3 + c] + m[6 + c] * m[6 + c];
+    const int z = n[0] <= n[1] && n[0] <= n[2] ? 0 : (n[1] <= n[2] ? 1 : 2);
+    double a[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) s += (k == z ? 0.0 : m[3 * r + k]) * v[3 * c + k];
+        a[3 * r + c] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < 9; i++) m[i] = a[i];
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 9; i++) s += m[i] * m[i];
+  s = 1.0 / sqrt(s);
+#pragma unroll
+  for (int i = 0; i < 9; i++) m[i] *= s;
+}
+
+// One pair of a launch: the locations of its two sets, its matches (and mask bytes) from moff on, its block entries from boff.
+struct GeomJob {
+  const float2 *l1, *l2;
+  int moff, n;
+  uint32_t seed;
+  int boff, nblk, pad;
+};
+// The best hypothesis of one block of 256.
+struct GeomBest {
+  int score, t;
+  float M[9];
+  int pad;
+};
+
+__device__ __forceinline__ unsigned long long geom_key(int score, int t) {  // larger score, then lower t
+  return ((unsigned long long)(unsigned)(score + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)t);
+}
+
+__device__ __forceinline__ unsigned long long geom_block_max(unsigned long long key, unsigned long long* wmax) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(key, d);
+    key = o > key ? o : key;
+  }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = key;
+  __syncthreads();
+  const unsigned long long a = wmax[0] > wmax[1] ? wmax[0] : wmax[1], b = wmax[2] > wmax[3] ? wmax[2] : wmax[3];
+  return a > b ? a : b;
+}
+
+// work[blockIdx.x] = (job, block of hypotheses); only jobs with n >= k have work.
+template <int MODEL>
+__global__ __launch_bounds__(256) void geom_score_kernel(const GeomJob* jobs, const int2* work, const int2* matches, int T,
+                                                         float bound, GeomBest* best) {
+  constexpr int K = geom_k(MODEL);
+  __shared__ float4 pts[GEOM_CHUNK];
+  __shared__ unsigned long long wmax[4];
+  const int2 w = work[blockIdx.x];
+  const GeomJob J = jobs[w.x];
+  const int2* const mt = matches + J.moff;
+  const int tid = threadIdx.x, t = w.y * 256 + tid;
+  float M[9];
+  bool live = t < T;
+  {
+    int idx[8];
+    geom_sample(J.seed, live ? t : 0, K, J.n, idx);
+    float x1[K], y1[K], x2[K], y2[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const int2 m = mt[idx[j]];
+      const float2 a = J.l1[m.x], b = J.l2[m.y];
+      x1[j] = a.x; y1[j] = a.y; x2[j] = b.x; y2[j] = b.y;
+    }
+    const bool finite = geom_hypothesis<MODEL>(x1, y1, x2, y2, M);
+    if (!finite) {  // scores 0
+#pragma unroll
+      for (int c = 0; c < 9; c++) M[c] = 0.0f;
+    }
+  }
+  int score = 0;
+  for (int base = 0; base < J.n; base += GEOM_CHUNK) {
+    const int cnt = min(GEOM_CHUNK, J.n - base);
+    if (base) __syncthreads();  // every lane is done with the chunk before
+    for (int i = tid; i < cnt; i += 256) {
+      const int2 m = mt[base + i];
+      const float2 a = J.l1[m.x], b = J.l2[m.y];
+      pts[i] = make_float4(a.x, a.y, b.x, b.y);
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int i = 0; i < cnt; i++) score += geom_pass<MODEL>(M, pts[i], bound) ? 1 : 0;
+  }
+  const unsigned long long key = live ? geom_key(score, t) : 0ull;
+  const unsigned long long top = geom_block_max(key, wmax);
+  if (live && key == top) {
+    GeomBest e;
+    e.score = score;
+    e.t = t;
+#pragma unroll
+    for (int c = 0; c < 9; c++) e.M[c] = M[c];
+    e.pad = 0;
+    best[J.boff + w.y] = e;
+  }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void geom_finish_kernel(const GeomJob* jobs, const int2* matches, const GeomBest* best,
+                                                          float bound, hess_geom_result* results, unsigned char* mask) {
+  constexpr int K = geom_k(MODEL);
+  __shared__ unsigned long long wmax[4];
+  __shared__ float sM[9];
+  __shared__ int wcnt[4];
+  const GeomJob J = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  GeomBest e;
+  e.score = -1;
+  e.t = 0;
+  unsigned long long key = 0ull;
+  if (tid < J.nblk) {
+    e = best[J.boff + tid];
+    key = geom_key(e.score, e.t);
+  }
+  const unsigned long long top = geom_block_max(key, wmax);
+  const int score = (int)(top >> 32) - 1;
+  unsigned char* const mk = mask + J.moff;
+  hess_geom_result* const R = results + blockIdx.x;
+  if (J.n < K || score < K) {  // no model (workgroup-uniform)
+    for (int i = tid; i < J.n; i += 256) mk[i] = 0;
+    if (tid < 9) R->M[tid] = 0.0f;
+    if (tid == 0) {
+      R->inliers = 0;
+      R->hypothesis = -1;
+      R->reserved[0] = R->reserved[1] = 0;
+    }
+    return;
+  }
+  if (key == top) {  // one thread: the keys of a pair are distinct
+    double m[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) m[c] = (double)e.M[c];
+    geom_finalise(MODEL, m);
+#pragma unroll
+    for (int c = 0; c < 9; c++) sM[c] = (float)m[c];
+  }
+  __syncthreads();
+  float M[9];
+#pragma unroll
+  for (int c = 0; c < 9; c++) M[c] = sM[c];
+  const int2* const mt = matches + J.moff;
+  int cnt = 0;
+  for (int i = tid; i < J.n; i += 256) {
+    const int2 q = mt[i];
+    const bool in = geom_gate<MODEL>(M, J.l1[q.x], J.l2[q.y], bound);
+    mk[i] = in ? 1 : 0;
+    cnt += in ? 1 : 0;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+  if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid < 9) R->M[tid] = M[tid];
+  if (tid == 0) {
+    R->inliers = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    R->hypothesis = (int)(0xFFFFFFFFu - (unsigned)(top & 0xFFFFFFFFull));
+    R->reserved[0] = R->reserved[1] = 0;
+  }
+}
+
+// out[first kept row of set + i] = the (x, y) at record (first record of the set + i) of src, records `stride` bytes apart.
+// sets[s] = (first kept row, first record, rows kept) in ascending kept rows.
+__global__ __launch_bounds__(256) void geom_loc_gather_kernel(const unsigned char* src, size_t stride, const int3* sets,
+                                                              int nsets, int total, float2* out) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  int lo = 0, hi = nsets - 1;  // the last set starting at or before g (empty sets share their successor's start)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sets[mid].x <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  const int3 S = sets[lo];
+  const float* p = reinterpret_cast<const float*>(src + ((size_t)S.y + (size_t)(g - S.x)) * stride);
+  out[g] = make_float2(p[0], p[1]);
+}
+
+template <class T>
+hipError_t geom_grow(T*& p, size_t& cap, size_t n) {
+  if (n <= cap) return hipSuccess;
+  (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const hipError_t e = hipMalloc(&p, n * sizeof(T));
+  if (e == hipSuccess) cap = n;
+  return e;
+}
+
+}  // namespace
+
+struct hess_geom_state {
+  float2* bank_loc = nullptr;  // [kept rows of the bank] in the caller's order (DescSets::first)
+  bool have_bank_loc = false;
+  // one chunk's plan (jobs, work table), matches, block entries, results and masks
+  unsigned char* plan = nullptr;
+  int2* matches = nullptr;
+  GeomBest* best = nullptr;
+  hess_geom_result* results = nullptr;
+  unsigned char* mask = nullptr;
+  size_t plan_cap = 0, matches_cap = 0, best_cap = 0, results_cap = 0, mask_cap = 0;
+};
+
+void hess_geom_drop_bank_locations(hess_geom_state* g) {
+  if (!g) return;
+  (void)hipFree(g->bank_loc);
+  g->bank_loc = nullptr;
+  g->have_bank_loc = false;
+}
+
+void hess_geom_state_destroy(hess_geom_state* g) {
+  if (!g) return;
+  (void)hipFree(g->bank_loc);
+  (void)hipFree(g->plan);
+  (void)hipFree(g->matches);
+  (void)hipFree(g->best);
+  (void)hipFree(g->results);
+  (void)hipFree(g->mask);
+  delete g;
+}
+
+#define G_TRY(v, expr)                                                                       \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      *(v).err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                   \
+      return HESS_ERR_DEVICE;                                                                \
+    }                                                                                        \
+  } while (0)
+
+namespace {
+
+hess_geom_state* geom_state(hess_matcher_view& v) {
+  if (!*v.geom) *v.geom = new (std::nothrow) hess_geom_state();
+  return *v.geom;
+}
+
+// One pair as the caller gave it: the locations and sizes of its two sets, its n matches (i of set 1, j of set 2).
+struct GeomPair {
+  const float2 *l1, *l2;
+  int n1, n2;
+  const int* matches;
+  int n;
+  uint32_t seed;
+};
+
+int geom_params_check(hess_matcher_view& v, const hess_geom_params* P, const char* what) {
+  const std::string w = what;
+  if (!P) { *v.err = w + ": params is NULL"; return HESS_ERR_ARG; }
+  if (P->model != HESS_GEOM_HOMOGRAPHY && P->model != HESS_GEOM_FUNDAMENTAL) {
+    *v.err = w + ": params.model must be HESS_GEOM_HOMOGRAPHY (1) or HESS_GEOM_FUNDAMENTAL (2), not " + std::to_string(P->model);
+    return HESS_ERR_ARG;
+  }
+  if (P->hypotheses < 0 || P->hypotheses > GEOM_MAX_T) {
+    *v.err = w + ": params.hypotheses must lie in 0..65536, not " + std::to_string(P->hypotheses);
+    return HESS_ERR_ARG;
+  }
+  for (int k = 0; k < 4; k++)
+    if (P->reserved[k]) { *v.err = w + ": params.reserved[" + std::to_string(k) + "] must be zero"; return HESS_ERR_ARG; }
+  if (!(P->bound > 0.0f) || !std::isfinite(P->bound)) {
+    *v.err = w + ": params.bound must be finite and greater than 0";
+    return HESS_ERR_ARG;
+  }
+  return 0;
+}
+
+// Every index of every pair lies in its set, or HESS_ERR_ARG naming the first that does not.
+int geom_matches_check(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const char* what) {
+  for (size_t p = 0; p < pairs.size(); p++) {
+    const GeomPair& G = pairs[p];
+    for (int i = 0; i < G.n; i++) {
+      const int a = G.matches[2 * i], b = G.matches[2 * i + 1];
+      if (a < 0 || a >= G.n1 || b < 0 || b >= G.n2) {
+        *v.err = std::string(what) + ": match " + std::to_string(i) + " of pair " + std::to_string(p) + " is (" + std::to_string(a) +
+                 ", " + std::to_string(b) + "), outside its sets of " + std::to_string(G.n1) + " and " + std::to_string(G.n2);
+        return HESS_ERR_ARG;
+      }
+    }
+  }
+  return 0;
+}
+
+template <int MODEL>
+hipError_t geom_launch(hipStream_t st, hess_geom_state* g, int np, size_t nwork, int T, float bound) {
+  const GeomJob* djobs = reinterpret_cast<const GeomJob*>(g->plan);
+  const int2* dwork = reinterpret_cast<const int2*>(g->plan + (size_t)np * sizeof(GeomJob));
+  if (nwork)
+    hipLaunchKernelGGL(geom_score_kernel<MODEL>, dim3((unsigned)nwork), dim3(256), 0, st, djobs, dwork, g->matches, T, bound,
+                       g->best);
+  hipLaunchKernelGGL(geom_finish_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, g->matches, g->best, bound,
+                     g->results, g->mask);
+  return hipGetLastError();
+}
+
+// The checked pairs in chunks: per chunk one upload (jobs, work table, matches), the two launches, one download (results,
+// masks).  inlier: pair p's bytes at inlier + p * pitch, or NULL.
+int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hess_geom_params& P, hess_geom_result* out,
+             unsigned char* inlier, size_t pitch) {
+  hess_geom_state* const g = geom_state(v);
+  if (!g) { *v.err = "estimate: out of memory"; return HESS_ERR_NOMEM; }
+  const int K = geom_k(P.model), T = P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T, nblk = (T + 255) / 256;
+  *v.last_ms = 0.0f;
+  float total_ms = 0.0f;
+  std::vector<unsigned char> hplan, hmask;
+  std::vector<int> hmatch;
+  std::vector<hess_geom_result> hres;
+  for (size_t p0 = 0; p0 < pairs.size();) {
+    size_t p1 = p0, nm = 0;
+    while (p1 < pairs.size() && p1 - p0 < (size_t)GEOM_PAIRS && (p1 == p0 || nm + (size_t)pairs[p1].n <= GEOM_MATCHES))
+      nm += (size_t)pairs[p1++].n;
+    const int np = (int)(p1 - p0);
+    size_t nwork = 0;
+    for (size_t p = p0; p < p1; p++) nwork += pairs[p].n >= K ? (size_t)nblk : 0;
+    hplan.assign((size_t)np * sizeof(GeomJob) + nwork * sizeof(int2), 0);
+    hmatch.resize(nm * 2);
+    GeomJob* const jobs = reinterpret_cast<GeomJob*>(hplan.data());
+    int2* const work = reinterpret_cast<int2*>(hplan.data() + (size_t)np * sizeof(GeomJob));
+    size_t moff = 0, boff = 0;
+    for (int q = 0; q < np; q++) {
+      const GeomPair& G = pairs[p0 + q];
+      GeomJob& J = jobs[q];
+      J.l1 = G.l1;
+      J.l2 = G.l2;
+      J.moff = (int)moff;
+      J.n = G.n;
+      J.seed = G.seed;
+      J.boff = (int)boff;
+      J.nblk = G.n >= K ? nblk : 0;
+      if (G.n) memcpy(&hmatch[moff * 2], G.matches, (size_t)G.n * 2 * sizeof(int));
+      for (int b = 0; b < J.nblk; b++) work[boff + b] = make_int2(q, b);
+      moff += (size_t)G.n;
+      boff += (size_t)J.nblk;
+    }
+    G_TRY(v, geom_grow(g->plan, g->plan_cap, hplan.size()));
+    G_TRY(v, geom_grow(g->matches, g->matches_cap, std::max<size_t>(nm, 1)));
+    G_TRY(v, geom_grow(g->best, g->best_cap, std::max<size_t>(nwork, 1)));
+    G_TRY(v, geom_grow(g->results, g->results_cap, (size_t)np));
+    G_TRY(v, geom_grow(g->mask, g->mask_cap, std::max<size_t>(nm, 1)));
+    G_TRY(v, hipMemcpyAsync(g->plan, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
+    if (nm) G_TRY(v, hipMemcpyAsync(g->matches, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
+    (void)hipEventRecord(v.e0, v.st);
+    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, g, np, nwork, T, P.bound)
+                                             : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, g, np, nwork, T, P.bound));
+    (void)hipEventRecord(v.e1, v.st);
+    hres.resize((size_t)np);
+    hmask.resize(std::max<size_t>(nm, 1));
+    G_TRY(v, hipMemcpyAsync(hres.data(), g->results, (size_t)np * sizeof(hess_geom_result), hipMemcpyDeviceToHost, v.st));
+    if (nm && inlier) G_TRY(v, hipMemcpyAsync(hmask.data(), g->mask, nm, hipMemcpyDeviceToHost, v.st));
+    G_TRY(v, hipStreamSynchronize(v.st));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, v.e0, v.e1);
+    total_ms += ms;
+    for (int q = 0; q < np; q++) {
+      out[p0 + q] = hres[q];
+      if (inlier && jobs[q].n) memcpy(inlier + (p0 + q) * pitch, hmask.data() + jobs[q].moff, (size_t)jobs[q].n);
+    }
+    p0 = p1;
+  }
+  *v.last_ms = total_ms;
+  return 0;
+}
+
+// The bank's locations from `rows` records in device memory (checked), `stride` bytes apart.
+int geom_bank_locations(hess_matcher_view& v, const void* dev, size_t stride) {
+  hess_geom_state* const g = geom_state(v);
+  if (!g) { *v.err = "bank_set_locations: out of memory"; return HESS_ERR_NOMEM; }
+  const int nsets = (int)v.bank_num->size();
+  std::vector<int3> sets((size_t)nsets);
+  size_t srow = 0, total = 0;
+  for (int k = 0; k < nsets; k++) {
+    sets[k] = make_int3((*v.bank_first)[k], (int)srow, (*v.bank_num)[k]);
+    srow += (size_t)(*v.bank_cnt)[k];
+    total = (size_t)(*v.bank_first)[k] + (size_t)(*v.bank_num)[k];
+  }
+  float2* loc = nullptr;
+  if (total) {
+    int3* dsets = nullptr;
+    G_TRY(v, hipMalloc(&loc, total * sizeof(float2)));
+    hipError_t e = hipMalloc(&dsets, sets.size() * sizeof(int3));
+    if (e == hipSuccess) e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, v.st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(geom_loc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v.st,
+                         static_cast<const unsigned char*>(dev), stride, dsets, nsets, (int)total, loc);
+      e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(v.st);
+    (void)hipFree(dsets);
+    if (e != hipSuccess || es != hipSuccess) (void)hipFree(loc);
+    G_TRY(v, e);
+    G_TRY(v, es);
+  }
+  (void)hipFree(g->bank_loc);
+  g->bank_loc = loc;
+  g->have_bank_loc = true;
+  return 0;
+}
+
+// What both bank_set_locations forms refuse.  rows: the records the caller counted.
+int geom_bank_locations_args(hess_matcher_view& v, size_t stride, const char* what, size_t* rows) {
+  if (!v.bank_built) {
+    *v.err = std::string(what) + ": load the bank's descriptors before their locations";
+    return HESS_ERR_STATE;
+  }
+  if (stride < 8 || stride % 4) {
+    *v.err = std::string(what) + ": stride_bytes must be a multiple of 4 and at least 8, not " + std::to_string(stride);
+    return HESS_ERR_ARG;
+  }
+  size_t n = 0;
+  for (int c : *v.bank_cnt) n += (size_t)c;
+  *rows = n;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hess_geom_sample(uint32_t seed, int t, int k, int n, int* out) {
+  if (!out || t < 0 || k < 1 || k > 8 || n < k) return HESS_ERR_ARG;
+  int idx[8];
+  geom_sample(seed, t, k, n, idx);
+  for (int j = 0; j < k; j++) out[j] = idx[j];
+  return 0;
+}
+
+int hess_matcher_estimate(hess_matcher* m, int nmatch, const int* pairs, const hess_geom_params* params,
+                          hess_geom_result* out, unsigned char* inlier) {
+  if (!m) return HESS_ERR_ARG;
+  hess_matcher_view v = hess_matcher_view_of(m);
+  if (const int rc = geom_params_check(v, params, "estimate")) return rc;
+  if (!out) { *v.err = "estimate: out is NULL"; return HESS_ERR_ARG; }
+  if (nmatch < 0 || (nmatch > 0 && !pairs)) { *v.err = "estimate: nmatch < 0 or pairs NULL"; return HESS_ERR_ARG; }
+  for (int k = 0; k < 2; k++)
+    if (v.nloc[k] < 0) {
+      *v.err = "estimate: slot " + std::to_string(k) + " has no locations (hess_matcher_set_locations after its descriptors)";
+      return HESS_ERR_STATE;
+    }
+  std::vector<GeomPair> one(1);
+  one[0] = GeomPair{v.loc[0], v.loc[1], v.nloc[0], v.nloc[1], pairs, nmatch, params->seed};
+  if (const int rc = geom_matches_check(v, one, "estimate")) return rc;
+  G_TRY(v, hipSetDevice(v.device));
+  return geom_run(v, one, *params, out, inlier, 0);
+}
+
+int hess_matcher_bank_set_locations(hess_matcher* m, const float* loc, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  hess_matcher_view v = hess_matcher_view_of(m);
+  if (!loc) { hess_geom_drop_bank_locations(*v.geom); return 0; }
+  size_t rows = 0;
+  if (const int rc = geom_bank_locations_args(v, stride_bytes, "bank_set_locations", &rows)) return rc;
+  G_TRY(v, hipSetDevice(v.device));
+  // the (x, y) pairs packed on the host, staged on the device, then the device form's gather
+  std::vector<float2> h(rows ? rows : 1);
+  for (size_t i = 0; i < rows; i++) memcpy(&h[i], reinterpret_cast<const char*>(loc) + i * stride_bytes, sizeof(float2));
+  float2* d = nullptr;
+  G_TRY(v, hipMalloc(&d, h.size() * sizeof(float2)));
+  const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
+  const int rc = e == hipSuccess ? geom_bank_locations(v, d, sizeof(float2)) : 0;
+  (void)hipFree(d);
+  G_TRY(v, e);
+  return rc;
+}
+
+int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  hess_matcher_view v = hess_matcher_view_of(m);
+  if (!dev_loc) { hess_geom_drop_bank_locations(*v.geom); return 0; }
+  size_t rows = 0;
+  if (const int rc = geom_bank_locations_args(v, stride_bytes, "bank_set_locations_device", &rows)) return rc;
+  G_TRY(v, hipSetDevice(v.device));
+  if (rows) {
+    if ((uintptr_t)dev_loc % 4) { *v.err = "bank_set_locations_device: dev_loc must be 4-byte aligned"; return HESS_ERR_ARG; }
+    if (const int rc = hess_matcher_device_range(m, dev_loc, (rows - 1) * stride_bytes + 8, "bank_set_locations_device", "locations"))
+      return rc;
+  }
+  return geom_bank_locations(v, dev_loc, stride_bytes);
+}
+
+int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* matches,
+                                const int* counts, const hess_geom_params* params, hess_geom_result* out,
+                                unsigned char* inlier) {
+  if (!m) return HESS_ERR_ARG;
+  hess_matcher_view v = hess_matcher_view_of(m);
+  if (const int rc = geom_params_check(v, params, "estimate_pairs")) return rc;
+  if (npairs < 0 || max_match < 0 || (npairs > 0 && (!pairs_ab || !counts || !out))) {
+    *v.err = "estimate_pairs: npairs or max_match < 0, or pairs_ab, counts or out is NULL";
+    return HESS_ERR_ARG;
+  }
+  const hess_geom_state* const g = *v.geom;
+  if (!g || !g->have_bank_loc) {
+    *v.err = "estimate_pairs: the bank has no locations (hess_matcher_bank_set_locations after its descriptors)";
+    return HESS_ERR_STATE;
+  }
+  const int nsets = (int)v.bank_num->size();
+  std::vector<GeomPair> pairs((size_t)npairs);
+  for (int p = 0; p < npairs; p++) {
+    const int a = pairs_ab[2 * p], b = pairs_ab[2 * p + 1];
+    if (a < 0 || a >= nsets || b < 0 || b >= nsets) {
+      *v.err = "estimate_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
+      return HESS_ERR_ARG;
+    }
+    if (counts[p] < 0 || counts[p] > max_match) {
+      *v.err = "estimate_pairs: counts[" + std::to_string(p) + "] = " + std::to_string(counts[p]) + " lies outside 0..max_match";
+      return HESS_ERR_ARG;
+    }
+    if (counts[p] > 0 && !matches) { *v.err = "estimate_pairs: matches is NULL"; return HESS_ERR_ARG; }
+    pairs[p] = GeomPair{g->bank_loc + (*v.bank_first)[a], g->bank_loc + (*v.bank_first)[b], (*v.bank_num)[a], (*v.bank_num)[b],
+                        matches ? matches + (size_t)p * max_match * 2 : nullptr, counts[p], params->seed + (uint32_t)p};
+  }
+  if (const int rc = geom_matches_check(v, pairs, "estimate_pairs")) return rc;
+  *v.last_ms = 0.0f;
+  if (npairs == 0) return 0;
+  G_TRY(v, hipSetDevice(v.device));
+  if (inlier) memset(inlier, 0, (size_t)npairs * max_match);
+  return geom_run(v, pairs, *params, out, inlier, (size_t)max_match);
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_dev.h"
+#include "hess_matcher_int.h"
 
 namespace {
 
@@ -757,6 +758,7 @@ struct hess_matcher {
   DescSets bank, slot[2];  // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
   float2* loc[2] = {nullptr, nullptr};
   int have_loc[2] = {0, 0};
+  hess_geom_state* geom = nullptr;  // hess_geom.hip: the bank's locations and the estimator's buffers
   // small / guided path: score matrix and column partials per 64-row tile
   int3* cpart = nullptr;
   int* dotm = nullptr;
@@ -1202,6 +1204,7 @@ void hess_matcher_destroy(hess_matcher* m) {
   (void)hipFree(m->cpart); (void)hipFree(m->dotm);
   (void)hipFree(m->mm_rstate); (void)hipFree(m->mm_cpart); (void)hipFree(m->plan);
   (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out);
+  hess_geom_state_destroy(m->geom);
   for (int k = 0; k < 2; k++) {
     (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]);
     for (int q = 0; q < 3; q++)
@@ -1231,6 +1234,7 @@ int hess_matcher_set_dim(hess_matcher* m, int dim) {
   M_TRY(m, hipSetDevice(m->device));
   M_TRY(m, hipStreamSynchronize(m->st));
   sets_clear(m->bank);
+  hess_geom_drop_bank_locations(m->geom);
   for (int k = 0; k < 2; k++) {
     sets_clear(m->slot[k]);
     (void)hipFree(m->loc[k]);
@@ -1403,6 +1407,7 @@ int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const u
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   M_TRY(m, hipSetDevice(m->device));
+  hess_geom_drop_bank_locations(m->geom);
   return sets_load(m, m->bank, nsets, counts, des, rows);
 }
 
@@ -1454,6 +1459,7 @@ static int bank_set_device(hess_matcher* m, int nsets, const int* counts, const 
     if (const int rc = device_range(m, dev_desc, rows * (size_t)m->dim * esz, "bank_set_device", "descriptors")) return rc;
   }
   sets_clear(m->bank);
+  hess_geom_drop_bank_locations(m->geom);
   const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, f32);
   if (rc) sets_clear(m->bank);
   return rc;
@@ -1664,3 +1670,29 @@ float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }
 const char* hess_matcher_last_error(hess_matcher* m) { return m ? m->err.c_str() : "null matcher"; }
 
 }  // extern "C"
+
+// ---- hess_matcher_int.h: the estimator's (hess_geom.hip) access to a matcher ------------------------------------------
+
+int hess_matcher_device_range(hess_matcher* m, const void* p, size_t bytes, const char* what, const char* noun) {
+  return device_range(m, p, bytes, what, noun);
+}
+
+hess_matcher_view hess_matcher_view_of(hess_matcher* m) {
+  hess_matcher_view v;
+  v.device = m->device;
+  v.st = m->st;
+  v.e0 = m->e0;
+  v.e1 = m->e1;
+  v.err = &m->err;
+  v.last_ms = &m->last_ms;
+  for (int k = 0; k < 2; k++) {
+    v.loc[k] = m->loc[k];
+    v.nloc[k] = m->have_loc[k] ? m->slot[k].count(0) : -1;
+  }
+  v.bank_built = m->bank.built;
+  v.bank_num = &m->bank.num;
+  v.bank_cnt = &m->bank.cnt;
+  v.bank_first = &m->bank.first;
+  v.geom = &m->geom;
+  return v;
+}

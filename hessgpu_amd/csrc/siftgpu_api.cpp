@@ -971,6 +971,22 @@ int SiftMatchGPU::SetFeatureTypes(int index, const unsigned short* types, int st
   return hess_matcher_set_types(MH(__matcher), index > 1 ? 1 : (index < 0 ? 0 : index), types,
                                 stride_bytes < 0 ? 0 : (size_t)stride_bytes);
 }
+int SiftMatchGPU::EstimateGeometry(int model, int nmatch, const int match_buffer[][2], float M[3][3], float bound,
+                                   unsigned char* inlier, int hypotheses, unsigned seed) {
+  if (M) memset(&M[0][0], 0, 9 * sizeof(float));
+  if (!__matcher || !M) return 0;
+  hess_geom_params p;
+  memset(&p, 0, sizeof(p));
+  p.model = model;
+  p.hypotheses = hypotheses;
+  p.seed = seed;
+  p.bound = bound;
+  hess_geom_result r;
+  memset(&r, 0, sizeof(r));
+  if (hess_matcher_estimate(MH(__matcher), nmatch, match_buffer ? &match_buffer[0][0] : nullptr, &p, &r, inlier) != 0) return 0;
+  memcpy(&M[0][0], r.M, 9 * sizeof(float));
+  return r.inliers;
+}
 void* SiftMatchGPU::operator new(size_t size) {
   void* p = malloc(size);
   if (!p) throw std::bad_alloc();
@@ -1027,6 +1043,12 @@ int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const f
 }
 int siftmatch_set_types(SiftMatchGPU* m, int index, const unsigned short* types, int stride_bytes) {
   return m ? m->SetFeatureTypes(index, types, stride_bytes) : HESS_ERR_ARG;
+}
+int siftmatch_estimate(SiftMatchGPU* m, int model, int nmatch, const int* matches, float* M, float bound, unsigned char* inlier,
+                       int hypotheses, unsigned seed) {
+  return m ? m->EstimateGeometry(model, nmatch, reinterpret_cast<const int(*)[2]>(matches), reinterpret_cast<float(*)[3]>(M), bound,
+                                 inlier, hypotheses, seed)
+           : 0;
 }
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { return s->RunSIFT(num, keys, have_orientation); }
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { s->SetKeypointList(num, keys, have_orientation); }

@@ -36,6 +36,12 @@ def _lib():
         L.hess_matcher_set_types.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.hess_matcher_bank_set_types.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.hess_matcher_bank_set_types_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.hess_geom_sample.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hess_matcher_estimate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hess_matcher_bank_set_locations.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.hess_matcher_bank_set_locations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.hess_matcher_estimate_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
         L.hess_matcher_last_ms.restype = C.c_float
         L.hess_matcher_last_ms.argtypes = [C.c_void_p]
         L.hess_matcher_last_error.restype = C.c_char_p
@@ -71,6 +77,29 @@ def check_pairs(pairs):
 
 
 DIMS = (128, 64)
+
+# hess_geom_params / hess_geom_result (include/hess_abi.h)
+GEOM_MODELS = {"H": 1, "F": 2, "homography": 1, "fundamental": 2, 1: 1, 2: 2}
+GEOM_PARAMS_DTYPE = np.dtype([("model", "<i4"), ("hypotheses", "<i4"), ("seed", "<u4"), ("bound", "<f4"), ("reserved", "<i4", 4)])
+GEOM_RESULT_DTYPE = np.dtype([("M", "<f4", 9), ("inliers", "<i4"), ("hypothesis", "<i4"), ("reserved", "<i4", 2)])
+assert GEOM_PARAMS_DTYPE.itemsize == 32 and GEOM_RESULT_DTYPE.itemsize == 52
+
+
+def geom_sample(seed, t, k, n):
+    """The sampling rule of the estimator on the host (hess_geom_sample): the k indices of hypothesis t among n matches."""
+    out = np.zeros(max(int(k), 1), dtype=np.int32)
+    rc = _lib().hess_geom_sample(int(seed) & 0xffffffff, int(t), int(k), int(n), out.ctypes.data)
+    if rc < 0:
+        raise HessError(rc, f"hess_geom_sample refuses t = {t}, k = {k}, n = {n}")
+    return out[:k].copy()
+
+
+def _geom_params(model, bound, hypotheses, seed):
+    if model not in GEOM_MODELS:
+        raise ValueError(f"model is 'H' or 'F', not {model!r}")
+    p = np.zeros(1, dtype=GEOM_PARAMS_DTYPE)
+    p["model"], p["hypotheses"], p["seed"], p["bound"] = GEOM_MODELS[model], int(hypotheses), int(seed) & 0xffffffff, bound
+    return p
 
 
 class Matcher:
@@ -218,11 +247,61 @@ class Matcher:
         """ptr: device address of the first u16 type on the matcher's device, one per descriptor `stride` bytes apart."""
         self._check(self.L.hess_matcher_bank_set_types_device(self.h, ptr, int(stride)))
 
-    def set_bank_from_session(self, session, types=False):
+    # ---- two-view geometry from matches (hess_matcher_estimate*, the rule is stated in include/hess_abi.h) ----
+    def estimate(self, matches, model, bound, hypotheses=0, seed=0):
+        """H ("H") or F ("F") from matches [n, 2] of the two single-pair slots (what match() returned), both located by
+        set_locations -> (M [3, 3] float32 of unit norm, mask bool [n], hypothesis).  No model: zeros, no inliers and -1.
+        M and `bound` are what match(H=M, hdistmax=bound) / match(F=M, fdistmax=bound) take; mask is that gate's decision."""
+        mt = check_pairs(matches)
+        p = _geom_params(model, bound, hypotheses, seed)
+        res = np.zeros(1, dtype=GEOM_RESULT_DTYPE)
+        mask = np.zeros(max(len(mt), 1), dtype=np.uint8)
+        self._check(self.L.hess_matcher_estimate(self.h, len(mt), mt.ctypes.data, p.ctypes.data, res.ctypes.data, mask.ctypes.data))
+        return res["M"][0].reshape(3, 3).copy(), mask[:len(mt)].astype(bool), int(res["hypothesis"][0])
+
+    def set_bank_locations(self, locs):
+        """locs: one [n_i, 2] array of (x, y) per bank set (as passed to set_bank, before truncation to max_sift), or None to
+        remove the locations.  Loading the bank again removes them too."""
+        if locs is None:
+            self._check(self.L.hess_matcher_bank_set_locations(self.h, None, 8))
+            return
+        parts = [np.asarray(a, dtype=np.float32).reshape(-1, 2) for a in locs]
+        flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2), np.float32), dtype=np.float32)
+        if not len(flat):
+            flat = np.zeros((1, 2), np.float32)   # (an address for a bank without descriptors: nothing is read)
+        self._check(self.L.hess_matcher_bank_set_locations(self.h, flat.ctypes.data, 8))
+
+    def set_bank_locations_device(self, ptr, stride):
+        """ptr: device address of the first (x, y) float pair on the matcher's device, one per descriptor `stride` bytes apart."""
+        self._check(self.L.hess_matcher_bank_set_locations_device(self.h, ptr, int(stride)))
+
+    def estimate_pairs(self, pairs, matches_list, model, bound, hypotheses=0, seed=0):
+        """For every (a, b) of pairs and its matches (match_pairs' list): what estimate() returns for that pair with seed +
+        its position -> list of (M, mask, hypothesis).  The bank needs locations (set_bank_locations*)."""
+        ab = check_pairs(pairs)
+        if len(matches_list) != len(ab):
+            raise ValueError(f"{len(ab)} pairs but {len(matches_list)} match lists")
+        mts = [check_pairs(m) for m in matches_list]
+        n = len(ab)
+        mm = max([len(m) for m in mts] + [1])
+        buf = np.zeros((max(n, 1), mm, 2), dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        for k, m in enumerate(mts):
+            buf[k, :len(m)] = m
+            cnt[k] = len(m)
+        p = _geom_params(model, bound, hypotheses, seed)
+        res = np.zeros(max(n, 1), dtype=GEOM_RESULT_DTYPE)
+        mask = np.zeros((max(n, 1), mm), dtype=np.uint8)
+        self._check(self.L.hess_matcher_estimate_pairs(self.h, n, ab.ctypes.data, mm, buf.ctypes.data, cnt.ctypes.data,
+                                                       p.ctypes.data, res.ctypes.data, mask.ctypes.data))
+        return [(res["M"][k].reshape(3, 3).copy(), mask[k, :cnt[k]].astype(bool), int(res["hypothesis"][k])) for k in range(n)]
+
+    def set_bank_from_session(self, session, types=False, locations=False):
         """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,
         without leaving the device -- floats or bytes, whichever the run made.  The context's descriptor length must be the
         matcher's: Matcher(dim=64) for a half_sift context.  types=True also takes the type field of the device key records,
-        so that match_pairs gates by feature type (set_bank_types), again without a host round trip."""
+        so that match_pairs gates by feature type (set_bank_types), again without a host round trip; locations=True takes
+        their x, y for estimate_pairs (set_bank_locations_device)."""
         dim = session.desc_dim()
         if dim != self.dim:
             raise ValueError(f"the matcher takes {self.dim}-d descriptors; this context's are {dim}-d (-half / -sd)")
@@ -233,6 +312,8 @@ class Matcher:
         self.set_bank_device(desc, counts, dtype=np.uint8 if session.desc_format() == "u8" else np.float32)
         if types:
             self.set_bank_types_device((keys or 0) + _abi.KEYPOINT_DTYPE.fields["type"][1], _abi.KEYPOINT_DTYPE.itemsize)
+        if locations:
+            self.set_bank_locations_device((keys or 0) + _abi.KEYPOINT_DTYPE.fields["x"][1], _abi.KEYPOINT_DTYPE.itemsize)
 
     def bank(self, i):
         """The stored bytes of set i: [n, dim] u8."""

@@ -165,6 +165,13 @@ class SiftMatchGPU {
   int SetFeatureTypes(int index, const SiftGPU::SiftKeypoint* keys);
   // the same for any array of types, one every stride_bytes (2: packed); returns the hess_status (0, or negative)
   int SetFeatureTypes(int index, const unsigned short* types, int stride_bytes);
+  // Not in the reference, and NOT virtual either: the step between GetSiftMatch and GetGuidedSiftMatch.  H (model 1) or F
+  // (model 2) from the nmatch matches of match_buffer (GetSiftMatch's output) and the locations of both slots
+  // (SetFeatureLocation), by the deterministic fixed-budget RANSAC of hess_matcher_estimate (hess_abi.h): M of unit norm and
+  // `bound` are what GetGuidedSiftMatch takes as (H, hdistmax) or (F, fdistmax); inlier[i] (nmatch bytes, or NULL) is that
+  // gate's decision on match i.  hypotheses 0: 2048.  Returns the inlier count; 0 without a model (M all zero) or on an error.
+  int EstimateGeometry(int model, int nmatch, const int match_buffer[][2], float M[3][3], float bound,
+                       unsigned char* inlier = NULL, int hypotheses = 0, unsigned seed = 0);
 };
 
 typedef SiftGPU::SiftKeypoint SiftKeypoint;
@@ -206,6 +213,9 @@ int siftmatch_get_guided_match(SiftMatchGPU* m, int max_match, int* buf, const f
                                float ratiomax, float hdistmax, float fdistmax, int mbm);
 // SetFeatureTypes(index, types, stride_bytes): NULL removes the types; returns the hess_status
 int siftmatch_set_types(SiftMatchGPU* m, int index, const unsigned short* types, int stride_bytes);
+// EstimateGeometry: matches [nmatch][2], M [9] row-major, inlier [nmatch] or NULL; returns the inlier count
+int siftmatch_estimate(SiftMatchGPU* m, int model, int nmatch, const int* matches, float* M, float bound, unsigned char* inlier,
+                       int hypotheses, unsigned seed);
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 // The resolved hess_params of the instance (what ParseParam did), for tests.

@@ -46,7 +46,9 @@ extern "C" {
  *    hess_run_keypoints are the same calls with one image and answer as before, except that hess_set_keypoints now
  *    refuses while a submitted batch is pending, where it used to corrupt that batch's results).
  *    hess_matcher_set_types / _bank_set_types / _bank_set_types_device (the feature-type gate of the matcher; added
- *    during version 5 without a bump: a matcher that never calls them matches as before). */
+ *    during version 5 without a bump: a matcher that never calls them matches as before).
+ *    hess_geom_sample, hess_matcher_estimate / _estimate_pairs, hess_matcher_bank_set_locations(_device) (H or F from
+ *    matches on the device; added during version 5 without a bump: a matcher that never calls them behaves as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -508,6 +510,72 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
 int hess_matcher_set_types(hess_matcher* m, int index, const uint16_t* types, size_t stride_bytes);
 int hess_matcher_bank_set_types(hess_matcher* m, const uint16_t* types, size_t stride_bytes);
 int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, size_t stride_bytes);
+
+/* ---- Two-view geometry from matches (no reference counterpart): the step between GetSiftMatch and GetGuidedSiftMatch.
+ * A deterministic RANSAC with a fixed budget of T hypotheses for a homography H or a fundamental matrix F, on the
+ * matcher's device and stream.  The result is a function of the inputs alone (locations, matches, params):
+ *   1 sample   mix(x) on uint32: x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16.
+ *              base = mix(seed ^ 0x9E3779B9), h_t = mix(base + t).  Draw j (0 <= j < k) of hypothesis t from n matches:
+ *              c = (uint64(mix(h_t + j)) * (n - j)) >> 32, then for every earlier draw in ascending value: c++ if it is
+ *              <= c.  k distinct indices into the match list, in draw order; k = 4 for H, 8 for F.  hess_geom_sample is this
+ *              rule on the host (the kernel calls the same function).
+ *   2 solve    in float32 from the k correspondences in Hartley-normalised coordinates (centroid to the origin, mean
+ *              distance sqrt 2, per image): the null vector of the 8 x 9 DLT (H) or 8-point (F) matrix by Gauss-Jordan
+ *              elimination with complete pivoting, then back to pixel coordinates.  A hypothesis with a non-finite entry
+ *              scores 0.
+ *   3 score    the number of the pair's correspondences (x1, y1) -> (x2, y2) that pass the guided gate of
+ *              hess_matcher_match with the hypothesis and `bound` (a division-free form of the same inequalities):
+ *              H: x = H (x1, y1, 1), |x0 / x2 - x2| < bound and |x1 / x2 - y2| < bound;
+ *              F: Sampson error (p2^T F p1)^2 / ((F p1)_0^2 + (F p1)_1^2 + (F^T p2)_0^2 + (F^T p2)_1^2) < bound.
+ *   4 winner   the largest score, among equal scores the lowest t.  A largest score below k, or n < k (an empty pair
+ *              included): no model -- hypothesis -1, inliers 0, M and the mask all zero, and the call still returns 0.
+ *   5 result   M: the winner's matrix, for F first made rank 2 (its smallest singular value zeroed, in double), scaled to
+ *              unit Frobenius norm.  inlier[i] = 1 exactly when correspondence i passes the gate's own formulas (with the
+ *              division, in float32) on the returned M: the decision hess_matcher_match makes with M and `bound` as
+ *              (H, hdistmax) or (F, fdistmax).  inliers counts the mask.  No refit on the inliers, no early termination.
+ * Added during version 5 without a bump: a matcher that never calls these behaves as before. */
+enum { HESS_GEOM_HOMOGRAPHY = 1, HESS_GEOM_FUNDAMENTAL = 2 };
+typedef struct hess_geom_params {
+  int32_t model;        /* HESS_GEOM_* */
+  int32_t hypotheses;   /* T, 1..65536; 0 = 2048 */
+  uint32_t seed;
+  float bound;          /* HOMOGRAPHY: hdistmax of the guided gate; FUNDAMENTAL: fdistmax */
+  int32_t reserved[4];  /* zero */
+} hess_geom_params;
+typedef struct hess_geom_result {
+  float M[9];           /* row-major, unit Frobenius norm; all zero when there is no model */
+  int32_t inliers;      /* set bytes of the mask */
+  int32_t hypothesis;   /* index t of the winner, -1: no model */
+  int32_t reserved[2];
+} hess_geom_result;
+
+/* Host only: the k (1..8) indices of hypothesis t (>= 0) among n (>= k) matches into out[k].  0, or HESS_ERR_ARG. */
+int hess_geom_sample(uint32_t seed, int t, int k, int n, int* out);
+/* The two single-pair slots: pairs[i] = (row of slot 0, row of slot 1) as hess_matcher_match writes them, located by
+ * hess_matcher_set_locations of both slots.  out: one result; inlier: nmatch bytes or NULL. */
+int hess_matcher_estimate(hess_matcher* m, int nmatch, const int* pairs, const hess_geom_params* params,
+                          hess_geom_result* out, unsigned char* inlier);
+/* Locations of the bank's descriptors: one (x, y) float pair per descriptor, stride_bytes apart (a multiple of 4, at
+ * least 8), the sets back to back as the caller counted them at load; each set is truncated to max_sift like its
+ * descriptors.  They are kept in the caller's row order whatever hess_matcher_bank_set_types does to the storage: match
+ * indices are the caller's.  The _device form reads device memory of the matcher's device (the key records of
+ * hess_device_results with stride sizeof(hess_keypoint)) under the pointer check of hess_matcher_bank_set_device.
+ * NULL removes them; so do hess_matcher_bank_set* and hess_matcher_set_dim to the other length. */
+int hess_matcher_bank_set_locations(hess_matcher* m, const float* loc, size_t stride_bytes);
+int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc, size_t stride_bytes);
+/* Many pairs of the bank per call: pairs_ab[p] = (a, b), matches [npairs][max_match][2] and counts [npairs] exactly as
+ * hess_matcher_match_pairs wrote them for those pairs.  Pair p uses seed + p (mod 2^32): out[p] and inlier[p][0..counts[p])
+ * are what hess_matcher_estimate returns for that pair's locations, matches and seed; the rest of inlier[p] is zero.
+ * One set of launches per chunk of pairs.
+ *   HESS_ERR_STATE  a slot or the bank has no locations; bank locations before the bank's descriptors are loaded
+ *   HESS_ERR_ARG    NULL params or out; an unknown model; hypotheses outside 0..65536; non-zero reserved words; bound not
+ *                   greater than 0 or not finite; a match index outside its set; a set index outside the bank; counts[p]
+ *                   outside 0..max_match; a bad stride or device pointer
+ * Nothing is launched on an error, the matcher is unchanged and hess_matcher_last_error names the argument.
+ * hess_matcher_last_ms: device time of the call's kernels. */
+int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* matches,
+                                const int* counts, const hess_geom_params* params, hess_geom_result* out,
+                                unsigned char* inlier);
 float hess_matcher_last_ms(hess_matcher* m);   /* device time of the last match's kernels */
 const char* hess_matcher_last_error(hess_matcher* m);
 
