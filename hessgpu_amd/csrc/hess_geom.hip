@@ -3,10 +3,10 @@
 // include/hess_abi.h).  No reference counterpart: SiftMatchGPU's callers do this step on the host.
 //
 //   geom_score_kernel    one workgroup per (pair, block of 256 hypotheses) of a work table, one hypothesis per lane: sample
-//                        (geom_sample), solve in registers (geom_null_vector: fully unrolled Gauss-Jordan, pivots by
-//                        selects), then count the pair's correspondences that pass the gate -- gathered once per workgroup
-//                        into LDS as float4 (x1, y1, x2, y2), 2048 at a time, every lane reading the same address
-//                        (a broadcast) -- and store the block's best (score, lowest t, matrix);
+//                        (geom_sample), solve in registers (geom_null_vector: fully unrolled Gauss-Jordan in double, pivots
+//                        by selects), then count the pair's correspondences that pass the gate -- gathered once per
+//                        workgroup into LDS as float4 (x1, y1, x2, y2), 2048 at a time, every lane reading the same
+//                        address (a broadcast) -- and store the block's best (score, lowest t, matrix);
 //   geom_finish_kernel   one workgroup per pair: arg-max over the block entries (score, then lowest t), rank 2 for F and
 //                        unit norm in double (one thread), then the inlier mask with the guided gate's own formulas
 //                        (match_dot_kernel, hess_match.hip) and its count;
@@ -73,22 +73,24 @@ __host__ __device__ inline void geom_sample(uint32_t seed, int t, int k, int n, 
 // Rows and columns are never moved: a pivot is the largest remaining |a[r][c]| over the unused rows and columns, found,
 // read and applied through selects on compile-time indices, so the 72 entries stay in registers.  After eight steps one
 // column f is left: x[f] = 1 and row r gives x[its pivot column] = -a[r][f] / a[r][pivot column].  A singular system
-// divides by zero: the caller's finiteness test drops the hypothesis.
-__host__ __device__ inline void geom_null_vector(float (&a)[8][9], float (&x)[9]) {
+// divides by zero: the caller's finiteness test drops the hypothesis.  In double: in float32 the eight updates of every
+// entry put the null vector up to 22 x (kappa 2^-24) from the exact one where a float32 SVD stays within 2 x
+// (profiles/r18_estimate_tests.txt); the points around it stay float32.
+__host__ __device__ inline void geom_null_vector(double (&a)[8][9], double (&x)[9]) {
   unsigned rused = 0, cused = 0;
   int pcol[8];
 #pragma unroll
   for (int r = 0; r < 8; r++) pcol[r] = 0;
 #pragma unroll
   for (int step = 0; step < 8; step++) {
-    float best = -1.0f;
+    double best = -1.0;
     int pr = 0, pc = 0;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
       const bool rfree = !((rused >> r) & 1u);
 #pragma unroll
       for (int c = 0; c < 9; c++) {
-        const float v = fabsf(a[r][c]);
+        const double v = fabs(a[r][c]);
         const bool take = rfree && !((cused >> c) & 1u) && v > best;
         best = take ? v : best;
         pr = take ? r : pr;
@@ -97,41 +99,41 @@ __host__ __device__ inline void geom_null_vector(float (&a)[8][9], float (&x)[9]
     }
     rused |= 1u << pr;
     cused |= 1u << pc;
-    float prow[9], piv = 0.0f;
+    double prow[9], piv = 0.0;
 #pragma unroll
     for (int c = 0; c < 9; c++) {
-      float v = a[0][c];
+      double v = a[0][c];
 #pragma unroll
       for (int r = 1; r < 8; r++) v = pr == r ? a[r][c] : v;
       prow[c] = v;
       piv = pc == c ? v : piv;
     }
-    const float inv = 1.0f / piv;
+    const double inv = 1.0 / piv;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-      float f = a[r][0];
+      double f = a[r][0];
 #pragma unroll
       for (int c = 1; c < 9; c++) f = pc == c ? a[r][c] : f;
-      f = pr == r ? 0.0f : f * inv;
+      f = pr == r ? 0.0 : f * inv;
       pcol[r] = pr == r ? pc : pcol[r];
 #pragma unroll
-      for (int c = 0; c < 9; c++) a[r][c] = fmaf(-f, prow[c], a[r][c]);
+      for (int c = 0; c < 9; c++) a[r][c] = fma(-f, prow[c], a[r][c]);
     }
   }
   int fc = 0;
 #pragma unroll
   for (int c = 0; c < 9; c++) fc = ((cused >> c) & 1u) ? fc : c;
 #pragma unroll
-  for (int c = 0; c < 9; c++) x[c] = fc == c ? 1.0f : 0.0f;
+  for (int c = 0; c < 9; c++) x[c] = fc == c ? 1.0 : 0.0;
 #pragma unroll
   for (int r = 0; r < 8; r++) {
-    float num = a[r][0], den = a[r][0];
+    double num = a[r][0], den = a[r][0];
 #pragma unroll
     for (int c = 1; c < 9; c++) {
       num = fc == c ? a[r][c] : num;
       den = pcol[r] == c ? a[r][c] : den;
     }
-    const float v = -num / den;
+    const double v = -num / den;
 #pragma unroll
     for (int c = 0; c < 9; c++) x[c] = pcol[r] == c ? v : x[c];
   }
@@ -171,22 +173,25 @@ __host__ __device__ inline bool geom_hypothesis(float (&x1)[geom_k(MODEL)], floa
   float c1x, c1y, s1, c2x, c2y, s2;
   geom_normalise<K>(x1, y1, c1x, c1y, s1);
   geom_normalise<K>(x2, y2, c2x, c2y, s2);
-  float a[8][9];
+  double a[8][9];
 #pragma unroll
   for (int i = 0; i < K; i++) {
-    const float x = x1[i], y = y1[i], u = x2[i], v = y2[i];
+    const double x = x1[i], y = y1[i], u = x2[i], v = y2[i];
     if (MODEL == HESS_GEOM_HOMOGRAPHY) {  // u (h6 x + h7 y + h8) = h0 x + h1 y + h2, and the same for v
-      float(&r0)[9] = a[(2 * i) & 7];
-      float(&r1)[9] = a[(2 * i + 1) & 7];
-      r0[0] = x; r0[1] = y; r0[2] = 1.0f; r0[3] = 0.0f; r0[4] = 0.0f; r0[5] = 0.0f; r0[6] = -u * x; r0[7] = -u * y; r0[8] = -u;
-      r1[0] = 0.0f; r1[1] = 0.0f; r1[2] = 0.0f; r1[3] = x; r1[4] = y; r1[5] = 1.0f; r1[6] = -v * x; r1[7] = -v * y; r1[8] = -v;
+      double(&r0)[9] = a[(2 * i) & 7];
+      double(&r1)[9] = a[(2 * i + 1) & 7];
+      r0[0] = x; r0[1] = y; r0[2] = 1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0; r0[6] = -u * x; r0[7] = -u * y; r0[8] = -u;
+      r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = x; r1[4] = y; r1[5] = 1.0; r1[6] = -v * x; r1[7] = -v * y; r1[8] = -v;
     } else {                              // (u, v, 1) F (x, y, 1)^T = 0
-      float(&r)[9] = a[i & 7];
-      r[0] = u * x; r[1] = u * y; r[2] = u; r[3] = v * x; r[4] = v * y; r[5] = v; r[6] = x; r[7] = y; r[8] = 1.0f;
+      double(&r)[9] = a[i & 7];
+      r[0] = u * x; r[1] = u * y; r[2] = u; r[3] = v * x; r[4] = v * y; r[5] = v; r[6] = x; r[7] = y; r[8] = 1.0;
     }
   }
+  double hd[9];
+  geom_null_vector(a, hd);
   float h[9];
-  geom_null_vector(a, h);
+#pragma unroll
+  for (int c = 0; c < 9; c++) h[c] = (float)hd[c];
   // G = h T1, T1 = [s1 0 -s1 c1x; 0 s1 -s1 c1y; 0 0 1]
   float G[9];
 #pragma unroll

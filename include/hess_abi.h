@@ -521,8 +521,8 @@ int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, s
  *              rule on the host (the kernel calls the same function).
  *   2 solve    in float32 from the k correspondences in Hartley-normalised coordinates (centroid to the origin, mean
  *              distance sqrt 2, per image): the null vector of the 8 x 9 DLT (H) or 8-point (F) matrix by Gauss-Jordan
- *              elimination with complete pivoting, then back to pixel coordinates.  A hypothesis with a non-finite entry
- *              scores 0.
+ *              elimination with complete pivoting (the elimination alone in double), then back to pixel coordinates.  A
+ *              hypothesis with a non-finite entry scores 0.
  *   3 score    the number of the pair's correspondences (x1, y1) -> (x2, y2) that pass the guided gate of
  *              hess_matcher_match with the hypothesis and `bound` (a division-free form of the same inequalities):
  *              H: x = H (x1, y1, 1), |x0 / x2 - x2| < bound and |x1 / x2 - y2| < bound;

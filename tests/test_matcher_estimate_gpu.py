@@ -59,7 +59,10 @@ def test_planted_model_is_found(name):
     M = res["M"][0].reshape(3, 3)
     hyp, inl = int(res["hypothesis"][0]), int(res["inliers"][0])
     print(f"{name}: hypothesis {hyp}, inliers {inl} of planted {int(c.planted.sum())}")
-    assert hyp in c.allin, (name, hyp, c.allin[:8])
+    if name in g.FIRST_NOT_PINNED:                       # (its first all-inlier sample is badly conditioned in float32)
+        assert hyp in c.allin, (name, hyp, c.allin[:8])
+    else:
+        assert hyp == c.allin[0], (name, hyp, c.allin[:8])
     assert inl == int(c.planted.sum()) == int(mask.sum())
     assert np.array_equal(mask.astype(bool), c.planted) and set(np.unique(mask)) <= {0, 1}
     assert abs(np.linalg.norm(M.astype(np.float64)) - 1.0) <= 1e-6
