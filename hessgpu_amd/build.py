@@ -26,7 +26,7 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
 # loaded side by side by the tests; without it the second one's internal calls would resolve to the first one's code.
 LINK_LIBS = ["-lhsa-runtime64", "-lrt", "-Wl,-Bsymbolic"]
 KERNEL_SOURCES = ["k_gauss.hip", "k_detect.hip", "k_feature.hip", "hess_plan.hip", "hess_schedule.hip", "hess_copier.hip",
-                  "hess_stager.cpp", "hess_shared.hip", "hess_abi.hip", "hess_match.hip", "hess_geom.hip"]  # (hess_stager.cpp: host code, standard headers only)
+                  "hess_stager.cpp", "hess_shared.hip", "hess_abi.hip", "hess_match.hip", "hess_match_plan.cpp", "hess_geom.hip"]  # (hess_stager.cpp, hess_match_plan.cpp: host code, standard headers only)
 DEV_SWITCH_SOURCES = ("hess_abi.hip", "hess_copier.hip", "hess_shared.hip")  # the files that call dev_env()
 # Per-file flags.  k_feature.hip: the SLP vectoriser turns pairs of FP32 operations into packed
 # instructions (v_pk_add/mul/fma_f32), which on gfx950 issue at half rate (tools/micro/README.md) and need
@@ -38,7 +38,7 @@ FILE_FLAGS = {"k_feature.hip": ["-fno-slp-vectorize"], "hess_match.hip": ["-mllv
 
 
 def sources_digest():
-    """First 16 hex digits of the SHA-256 over the sources of libhessgpu.so (csrc/*.hip, *.h, hess_stager.cpp, sorted by name) and the
+    """First 16 hex digits of the SHA-256 over the sources of libhessgpu.so (csrc/*.hip, *.h, the .cpp files of KERNEL_SOURCES, sorted by name) and the
     compiler flags: what a committed profile (profiles/*.json, `kernel_sources_sha16`) was measured on.  bench.py compares it
     with the sources it runs and marks numbers copied from a profile of other sources as stale."""
     import hashlib

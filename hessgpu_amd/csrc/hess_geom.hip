@@ -483,17 +483,6 @@ __global__ __launch_bounds__(256) void geom_loc_gather_kernel(const unsigned cha
   out[g] = make_float2(p[0], p[1]);
 }
 
-template <class T>
-hipError_t geom_grow(T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return hipSuccess;
-  (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const hipError_t e = hipMalloc(&p, n * sizeof(T));
-  if (e == hipSuccess) cap = n;
-  return e;
-}
-
 }  // namespace
 
 struct hess_geom_state {
@@ -638,11 +627,11 @@ int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hes
       moff += (size_t)G.n;
       boff += (size_t)J.nblk;
     }
-    G_TRY(v, geom_grow(g->plan, g->plan_cap, hplan.size()));
-    G_TRY(v, geom_grow(g->matches, g->matches_cap, std::max<size_t>(nm, 1)));
-    G_TRY(v, geom_grow(g->best, g->best_cap, std::max<size_t>(nwork, 1)));
-    G_TRY(v, geom_grow(g->results, g->results_cap, (size_t)np));
-    G_TRY(v, geom_grow(g->mask, g->mask_cap, std::max<size_t>(nm, 1)));
+    G_TRY(v, grow_device(g->plan, g->plan_cap, hplan.size()));
+    G_TRY(v, grow_device(g->matches, g->matches_cap, std::max<size_t>(nm, 1)));
+    G_TRY(v, grow_device(g->best, g->best_cap, std::max<size_t>(nwork, 1)));
+    G_TRY(v, grow_device(g->results, g->results_cap, (size_t)np));
+    G_TRY(v, grow_device(g->mask, g->mask_cap, std::max<size_t>(nm, 1)));
     G_TRY(v, hipMemcpyAsync(g->plan, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
     if (nm) G_TRY(v, hipMemcpyAsync(g->matches, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
     (void)hipEventRecord(v.e0, v.st);

@@ -25,6 +25,12 @@
 //   match_dot_kernel       64x64 tile of the dot-product matrix per workgroup, descriptor panels in LDS,
 //                          v_dot4_u32_u8, gates per pair, score matrix written for
 //   match_row_kernel       one wavefront per row over the matrix (same tie order), and match_col_kernel.
+// Host side.  What the kernels are launched on is decided in hess_match_plan.h / .cpp, without HIP: the layout of the sets,
+// the segments of a pair (two rules: single_sps for the untyped single pair, chunk_sps for a pair list), the chunks of a
+// list, the scratch offsets and the tables of the plan buffer.  Here: grow_for (the buffers of a plan), run_chunk (upload,
+// multiply, finish) and run_pairs (a pair list planned, its chunks run double buffered and compacted on the device), which serves
+// hess_matcher_match_pairs with (bank, bank) and the typed single pair with (slot 0, slot 1) and a list of one;
+// hess_matcher_match otherwise plans one job and compacts on the host, or takes match_small.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,7 +46,11 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_dev.h"
+#include "hess_match_plan.h"
 #include "hess_matcher_int.h"
+
+using namespace hess::match_plan;  // the constants MM_*, MP_*, PairJob, the plan of a pair list and of the plan buffer
+static_assert(sizeof(Entry) == sizeof(int2) && alignof(Entry) == alignof(int2), "the kernels read the plan's tables as int2");
 
 namespace {
 
@@ -54,6 +64,12 @@ struct GeoParams {
   float H[9], F[9];
   float hdistmax, fdistmax;
 };
+
+// ColMatch_Kernel's merge of two column partials (max, row, second): strict '<', so the earlier rows keep a tie.
+__device__ __forceinline__ void col_merge(int3& a, const int3& b) {  // a: earlier rows, b: later rows
+  if (a.x < b.x) a = make_int3(b.x, b.y, max(a.x, b.z));
+  else a.z = max(a.z, b.x);
+}
 
 // dotm[i][j] = what RowMatch reads (clamped at 0 in guided mode).  cpart[tile_row][j] = (max, index,
 // second) of the reference's unclamped `results` over the tile's 64 rows in ascending order -- the
@@ -154,11 +170,7 @@ __global__ __launch_bounds__(256) void match_dot_kernel(const uint8_t* des1, int
     __syncthreads();
     if (tid < TN && j0 + tid < num2) {
       int3 t = cp[0][tid];
-      for (int q = 1; q < TM / 4; q++) {  // merge the 16 four-row partials in row order (ColMatch_Kernel's rule)
-        const int3 u = cp[q][tid];
-        if (t.x < u.x) t = make_int3(u.x, u.y, max(t.x, u.z));
-        else t.z = max(t.z, u.x);
-      }
+      for (int q = 1; q < TM / 4; q++) col_merge(t, cp[q][tid]);  // the 16 four-row partials in row order
       cpart[(size_t)blockIdx.y * num2 + j0 + tid] = t;
     }
   }
@@ -217,19 +229,11 @@ __device__ __forceinline__ void match_col_block(int block, const int3* cpart, in
   const int q0 = ch * per, q1 = min(q0 + per, ntile);
   int3 t = make_int3(0, -1, 0);  // neutral: the per-block partials start from the same state
   if (j < num2)
-    for (int q = q0; q < q1; q++) {
-      const int3 u = cpart[(size_t)q * num2 + j];
-      if (t.x < u.x) t = make_int3(u.x, u.y, max(t.x, u.z));
-      else t.z = max(t.z, u.x);
-    }
+    for (int q = q0; q < q1; q++) col_merge(t, cpart[(size_t)q * num2 + j]);
   part[ch][c] = t;
   __syncthreads();
   if (ch == 0 && j < num2) {
-    for (int k = 1; k < 8; k++) {
-      const int3 u = part[k][c];
-      if (t.x < u.x) t = make_int3(u.x, u.y, max(t.x, u.z));
-      else t.z = max(t.z, u.x);
-    }
+    for (int k = 1; k < 8; k++) col_merge(t, part[k][c]);
     colm[j] = decide(t.x, t.z, t.y, distmax, ratiomax);
   }
 }
@@ -274,26 +278,18 @@ __global__ __launch_bounds__(256) void match_col_kernel(const int3* cpart, int n
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int MM_ROWS = 256;            // rows of set 1 per workgroup (64 per wavefront)
-constexpr int MM_SUPER = 128;           // columns per super tile
 // LDS bytes per staged descriptor: KD + 16, i.e. 36 dwords (128-d) or 20 (64-d).  A 16-byte read is served in groups of 16
 // lanes whose columns are distinct mod 16 (0-3, 12-15, 20-27 | 4-11, 16-19, 28-31), each lane taking 4 consecutive banks of
 // 64: the group is conflict-free exactly when pitch / 16 bytes is odd (9, 5), a bijection of the columns mod 16 onto the 16
 // four-bank slots.  The unpadded 64 bytes (4) would be 4-way.  (Staging stores at 64-d: 8 lanes write two columns, 20 dwords
 // apart over 32 banks: one of their 8 pieces meets a busy bank.)
 template <int KD> constexpr int mm_pitch() { return KD + 16; }
-constexpr int MM_MAX_TILES = 60;        // tiles per segment: the tile index shares 6 key bits with "none"
 constexpr int MM_RS_PITCH = 33;         // row-state exchange: 8-byte entries per row (32 classes + 1 pad)
 constexpr int MM_RS_BYTES = 4 * 32 * MM_RS_PITCH * 8;
 // One of the two descriptor buffers: a super tile, and half of the row-state exchange that reuses both at the end (at 64-d
 // the exchange, 33 792 B, is larger than two staged super tiles, 20 480 B)
 template <int KD> constexpr int mm_buf_bytes() {
   return MM_SUPER * mm_pitch<KD>() > MM_RS_BYTES / 2 ? MM_SUPER * mm_pitch<KD>() : MM_RS_BYTES / 2;
-}
-
-__device__ __forceinline__ void col_merge(int3& a, const int3& b) {  // a: earlier rows, b: later rows
-  if (a.x < b.x) a = make_int3(b.x, b.y, max(a.x, b.z));
-  else a.z = max(a.z, b.x);
 }
 
 // median of three (v_med3_i32: the compiler does not form it from min/max of three variables)
@@ -303,17 +299,7 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
   return d;
 }
 
-// One pair of a launch.  a, b: first row of set 1 in the rows (and rfix) passed as set 1, of set 2 in those passed as set 2
-// -- the bank twice for a bank pair, the two single-pair slots (a = b = 0) for hess_matcher_match; rs, cp, rm, cm: offsets
-// of its row states, column partials, row and column decisions in the scratch.
-struct PairJob {
-  int a, b, n1, n2;
-  int nrb, nsuper, nseg, sps;
-  int rs, cp, rm, cm;
-  int pad[4];
-};
-
-// The work of one workgroup: work[blockIdx.x] = (job, rb | sg << 16), row block rb of the job's set 1 against its column
+// The work of one workgroup (PairJob, the tables: hess_match_plan.h): work[blockIdx.x] = (job, rb | sg << 16), row block rb of the job's set 1 against its column
 // segment sg of set 2.
 template <bool COLS, int KD>
 __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, const int* rfix, const uint8_t* rows2,
@@ -638,6 +624,20 @@ __global__ __launch_bounds__(256) void bank_gather_kernel(const uint8_t* orows, 
   }
 }
 
+// One 256-row step of a compaction, by the whole workgroup: row i's match (i, j) goes to place n + (the rows before it in
+// the step with j >= 0) of out if that is below max_match; n counts on.  wsum: four ints of LDS.
+__device__ __forceinline__ void compact_step(int i, int j, int& n, int max_match, int* out, int* wsum) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(j >= 0);
+  if (lane == 0) wsum[wv] = __popcll(bal);
+  __syncthreads();
+  int pos = n + __popcll(bal & ((1ull << lane) - 1));
+  for (int k = 0; k < wv; k++) pos += wsum[k];
+  if (j >= 0 && pos < max_match) { out[2 * pos] = i; out[2 * pos + 1] = j; }
+  n += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  __syncthreads();
+}
+
 // match_pairs_compact_kernel for typed sets.  Pair blockIdx.x is jobs[4 x + class] (a job without work has n1 = 0);
 // orig[x] = (first original row of its set 1, rows of that set).  The ORIGINAL rows in ascending order: each row's
 // decision is looked up through fwd in the job of its class, its column mapped back through inv, so the first max_match
@@ -649,7 +649,7 @@ __global__ __launch_bounds__(256) void match_types_compact_kernel(const PairJob*
   const PairJob* const J4 = jobs + 4 * blockIdx.x;
   const int2 O = orig[blockIdx.x];
   int* out = pairs + (size_t)blockIdx.x * max_match * 2;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   // a row's answer is a chain of four dependent loads (fwd, row decision, column decision, inv) and a pair has one
   // workgroup: four 256-row steps are looked up at once, stage by stage and without branches (a row without an answer
   // reads element 0 and drops it), so that their chains are in flight together; then they are placed in order
@@ -689,15 +689,7 @@ __global__ __launch_bounds__(256) void match_types_compact_kernel(const PairJob*
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      const int i = base + 256 * u + tid, j = jv[u];
-      const unsigned long long bal = __ballot(j >= 0);
-      if (lane == 0) wsum[wv] = __popcll(bal);
-      __syncthreads();
-      int pos = n + __popcll(bal & ((1ull << lane) - 1));
-      for (int k = 0; k < wv; k++) pos += wsum[k];
-      if (j >= 0 && pos < max_match) { out[2 * pos] = i; out[2 * pos + 1] = j; }
-      n += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-      __syncthreads();
+      compact_step(base + 256 * u + tid, jv[u], n, max_match, out, wsum);
     }
   }
   if (tid == 0) counts[blockIdx.x] = min(n, max_match);
@@ -713,7 +705,7 @@ __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob*
   const int* rm = rowm + J.rm;
   const int* cm = colm + J.cm;
   int* out = pairs + (size_t)blockIdx.x * max_match * 2;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   int n = 0;
   for (int base = 0; base < J.n1 && n < max_match; base += 256) {
     const int i = base + tid;
@@ -722,14 +714,7 @@ __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob*
       j = rm[i];
       if (j >= J.n2 || (j >= 0 && mutual_best && cm[j] != i)) j = -1;
     }
-    const unsigned long long bal = __ballot(j >= 0);
-    if (lane == 0) wsum[wv] = __popcll(bal);
-    __syncthreads();
-    int pos = n + __popcll(bal & ((1ull << lane) - 1));
-    for (int k = 0; k < wv; k++) pos += wsum[k];
-    if (j >= 0 && pos < max_match) { out[2 * pos] = i; out[2 * pos + 1] = j; }
-    n += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
+    compact_step(i, j, n, max_match, out, wsum);
   }
   if (tid == 0) counts[blockIdx.x] = min(n, max_match);
 }
@@ -747,6 +732,7 @@ struct DescSets {
   std::vector<int> goff, gnum;           // [set][class]: first stored row and rows of the class group
   int *fwd = nullptr, *inv = nullptr;    // original row (first[s] + i) -> stored row; stored row -> i, -1 for padding
   int count(int s) const { return s < (int)num.size() ? num[s] : 0; }
+  SetsLayout layout() const { return {off.data(), num.data(), first.data(), typed ? goff.data() : nullptr, typed ? gnum.data() : nullptr}; }
 };
 
 }  // namespace
@@ -783,12 +769,6 @@ struct hess_matcher {
   hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
 };
 
-// Pairs of one match_pairs chunk, and the device scratch one chunk may use (row states n1 x nseg and, for mutual best,
-// column partials nrb x n2 per pair, then row and column decisions).  A pair whose scratch alone exceeds the budget is
-// a chunk of its own.
-constexpr int MP_PAIRS = 64;
-constexpr size_t MP_SCRATCH = (size_t)256 << 20;
-
 #define M_TRY(m, expr)                                                                       \
   do {                                                                                       \
     hipError_t e_ = (expr);                                                                  \
@@ -799,17 +779,6 @@ constexpr size_t MP_SCRATCH = (size_t)256 << 20;
   } while (0)
 
 namespace {
-
-template <class T>
-hipError_t grow_device(T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return hipSuccess;
-  (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const hipError_t e = hipMalloc(&p, n * sizeof(T));
-  if (e == hipSuccess) cap = n;
-  return e;
-}
 
 template <class T>
 hipError_t grow_pinned(T* (&p)[2], size_t& cap, size_t n) {
@@ -858,22 +827,13 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
   const size_t KD = (size_t)m->dim;
   s.dim = m->dim;
   std::vector<int3> sets((size_t)nsets);
-  std::vector<int> off((size_t)nsets), num((size_t)nsets), first((size_t)nsets);
-  size_t padded = 0, srow = 0, orow = 0;
-  for (int k = 0; k < nsets; k++) {
-    const int n = counts[k] > m->max_sift ? m->max_sift : counts[k];
-    off[k] = (int)padded;
-    num[k] = n;
-    first[k] = (int)orow;
-    orow += (size_t)n;
-    sets[k] = make_int3((int)padded, (int)srow, n);
-    padded += ((size_t)n + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
-    srow += (size_t)counts[k];
-    if (padded > (size_t)INT32_MAX / KD || srow > (size_t)INT32_MAX) {
-      m->err = "bank too large";
-      return HESS_ERR_TOO_BIG;
-    }
+  std::vector<int> off((size_t)nsets), num((size_t)nsets), first((size_t)nsets), srow((size_t)nsets);
+  size_t padded = 0;
+  if (!set_layout(nsets, counts, m->max_sift, KD, off.data(), num.data(), first.data(), srow.data(), &padded)) {
+    m->err = "bank too large";
+    return HESS_ERR_TOO_BIG;
   }
+  for (int k = 0; k < nsets; k++) sets[k] = make_int3(off[k], srow[k], num[k]);
   if (padded) {
     M_TRY(m, hipMalloc(&s.rows, padded * KD));
     M_TRY(m, hipMalloc(&s.rfix, 2 * padded * sizeof(int)));
@@ -972,14 +932,10 @@ int sets_regroup(hess_matcher* m, DescSets& s, const void* dev_types, size_t str
       M_TRY(m, hipMemcpyAsync(gnum.data(), dcounts, gnum.size() * sizeof(int), hipMemcpyDeviceToHost, m->st));
       M_TRY(m, hipStreamSynchronize(m->st));
     }
-    for (int k = 0; k < nsets; k++)
-      for (int c = 0; c < 4; c++) {
-        goff[4 * k + c] = tab[k].grp[c] = (int)padded;
-        padded += ((size_t)gnum[4 * k + c] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
-        if (padded > (size_t)INT32_MAX / KD) { m->err = "set_types: bank too large"; return HESS_ERR_TOO_BIG; }
-      }
-  } else {
-    for (int k = 0; k < nsets; k++) padded = (size_t)s.off[k] + ((size_t)s.num[k] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+    if (!group_layout(4 * nsets, gnum.data(), KD, goff.data(), &padded)) { m->err = "set_types: bank too large"; return HESS_ERR_TOO_BIG; }
+    for (int k = 0; k < nsets; k++) memcpy(tab[k].grp, &goff[4 * k], sizeof(tab[k].grp));
+  } else if (nsets) {
+    padded = (size_t)s.off[nsets - 1] + pad_rows((size_t)s.num[nsets - 1]);
   }
   if (total) {
     TypeSet* dtab = nullptr;
@@ -1069,108 +1025,144 @@ int bank_args(hess_matcher* m, int nsets, const int* counts, const void* des, si
   return 0;
 }
 
-// Segments of a pair of nsuper super tiles: at most sps super tiles each (the tile index shares six key bits, so
-// sps <= MM_MAX_TILES / 4), as many as that needs, balanced: psps <= sps.
-void pair_seg(int nsuper, int sps, int& nseg, int& psps) {
-  nseg = (nsuper + sps - 1) / sps;
-  psps = (nsuper + nseg - 1) / nseg;
-  nseg = (nsuper + psps - 1) / psps;
+// Grows the matcher's buffers to what a plan needs; for compacted output (n.outn) also its device buffer, the two pinned
+// slots and their events.
+int grow_for(hess_matcher* m, const PlanNeed& n) {
+  M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, n.rs));
+  M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, n.cp));
+  M_TRY(m, grow_device(m->rowm, m->rowm_cap, n.rm));
+  M_TRY(m, grow_device(m->colm, m->colm_cap, n.cm));
+  M_TRY(m, grow_device(m->plan, m->plan_cap, n.plan_bytes));
+  M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, n.plan_bytes));
+  if (!n.outn) return 0;
+  M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, n.outn));
+  M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, n.outn));
+  for (int k = 0; k < 2; k++)
+    for (int q = 0; q < 3; q++)
+      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
+  return 0;
 }
 
-// Jobs [p0, p1) of one multiply and one finish launch, with segments of at most sps super tiles; the scratch they use (row
-// states, column partials, row and column decisions) and the entries of the two work tables.
-// Typed sets (jpp = 4): four jobs per pair, one per class, and behind the work tables one (first original row, rows) of
-// set 1 per pair for match_types_compact_kernel.
-struct Chunk {
-  int p0, p1, sps;
-  size_t rs, cp, rm, cm, nwg, nfin;
-  int jpp = 1;  // jobs per pair
-  size_t norig() const { return jpp == 4 ? (size_t)(p1 - p0) / 4 : 0; }
-  size_t plan_bytes() const { return (size_t)(p1 - p0) * sizeof(PairJob) + (nwg + nfin + norig()) * sizeof(int2); }
-};
-
-// Super tiles per segment for `work` (256-row block, super tile) units in one launch: whole rounds of workgroups over the
-// 256 CUs as in hess_matcher_match (two per CU when that leaves each at least four super tiles), at most
-// MM_MAX_TILES / 4 super tiles per segment.
-int chunk_sps(size_t work) {
-  const size_t target = work >= 512 * 4 ? 512 : 256;
-  const size_t sps = (work + target - 1) / target;
-  return sps < 1 ? 1 : (sps > MM_MAX_TILES / 4 ? MM_MAX_TILES / 4 : (int)sps);
-}
-
-size_t job_work(const PairJob& J) {
-  return J.n1 ? (size_t)((J.n1 + MM_ROWS - 1) / MM_ROWS) * ((J.n2 + MM_SUPER - 1) / MM_SUPER) : 0;
-}
-
-// The class jobs of typed sets s1[sa] x s2[sb]: one per class present on both sides (n1 = n2 = 0 otherwise).
-void type_jobs(const DescSets& s1, int sa, const DescSets& s2, int sb, PairJob* J4) {
-  for (int c = 0; c < 4; c++) {
-    PairJob& J = J4[c];
-    J = PairJob{};
-    J.a = s1.goff[4 * sa + c];
-    J.b = s2.goff[4 * sb + c];
-    J.n1 = s1.gnum[4 * sa + c];
-    J.n2 = s2.gnum[4 * sb + c];
-    if (J.n1 == 0 || J.n2 == 0) J.n1 = J.n2 = 0;
-  }
-}
-
-// Plans c's jobs (a, b, n1, n2 given, n1 = n2 = 0 for a pair without work): shapes, segments and offsets into the scratch;
-// and c's totals.  Returns the scratch bytes.
-size_t plan_chunk(PairJob* jobs, Chunk& c, int mutual_best) {
-  c.rs = c.cp = c.rm = c.cm = c.nwg = c.nfin = 0;
-  for (int p = c.p0; p < c.p1; p++) {
-    PairJob& J = jobs[p];
-    if (!J.n1) continue;
-    J.nrb = (J.n1 + MM_ROWS - 1) / MM_ROWS;
-    J.nsuper = (J.n2 + MM_SUPER - 1) / MM_SUPER;
-    pair_seg(J.nsuper, c.sps, J.nseg, J.sps);
-    J.rs = (int)c.rs; J.cp = (int)c.cp; J.rm = (int)c.rm; J.cm = (int)c.cm;
-    c.rs += (size_t)J.n1 * J.nseg;
-    c.cp += mutual_best ? (size_t)J.nrb * J.n2 : 0;
-    c.rm += J.n1;
-    c.cm += mutual_best ? J.n2 : 0;
-    c.nwg += (size_t)J.nrb * J.nseg;
-    c.nfin += (J.n1 + 255) / 256 + (mutual_best ? (J.n2 + 31) / 32 : 0);
-  }
-  return sizeof(int3) * (c.rs + c.cp) + sizeof(int) * (c.rm + c.cm);
-}
-
-// Enqueues planned chunk c on m->st: its jobs and work tables (multiply: (job, row block | segment << 16); finish: (job,
-// block)) into the pinned slot hp and up to m->plan, then `start`, the multiply and the finish.  s1, s2: the sets the
-// jobs' a, b index.  The caller has grown every buffer to c's size.
-hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Chunk& c,
-                     uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
-                     const int2* orig = nullptr) {
-  const int np = c.p1 - c.p0;
-  memcpy(hp, jobs + c.p0, np * sizeof(PairJob));
-  int2* const work = reinterpret_cast<int2*>(hp + np * sizeof(PairJob));
-  int2* const fin = work + c.nwg;
-  size_t iw = 0, jf = 0;
-  for (int q = 0; q < np; q++) {
-    const PairJob& J = jobs[c.p0 + q];
-    if (!J.n1) continue;
-    for (int sg = 0; sg < J.nseg; sg++)
-      for (int rb = 0; rb < J.nrb; rb++) work[iw++] = make_int2(q, rb | sg << 16);
-    const int nfb = (J.n1 + 255) / 256 + (mutual_best ? (J.n2 + 31) / 32 : 0);
-    for (int b = 0; b < nfb; b++) fin[jf++] = make_int2(q, b);
-  }
-  if (c.norig()) memcpy(fin + c.nfin, orig + c.p0 / 4, c.norig() * sizeof(int2));
-  const PairJob* djobs = reinterpret_cast<const PairJob*>(m->plan);
-  const int2* dwork = reinterpret_cast<const int2*>(m->plan + np * sizeof(PairJob));
-  const hipError_t e = hipMemcpyAsync(m->plan, hp, c.plan_bytes(), hipMemcpyHostToDevice, m->st);
+// Enqueues planned chunk c on m->st: its plan buffer (plan_fill) into the pinned slot hp and up to m->plan, then `start`,
+// the multiply and the finish.  s1, s2: the sets the jobs' a, b index.  The caller has grown every buffer to c's size.
+hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Entry* orig,
+                     const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax) {
+  const PlanLayout L = plan_layout(c);
+  plan_fill(hp, jobs, orig, c, mutual_best);
+  const hipError_t e = hipMemcpyAsync(m->plan, hp, L.bytes, hipMemcpyHostToDevice, m->st);
   if (e != hipSuccess) return e;
   (void)hipEventRecord(start, m->st);
   if (c.nwg) {
     if (s1.dim != s2.dim || !dim_ok(s1.dim)) return hipErrorInvalidValue;  // (set_dim empties every set: not reached)
+    const PairJob* djobs = plan_ptr<PairJob>(m->plan, L.jobs);
     auto* const kern = s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128> : match_mfma_kernel<false, 128>)
                                      : (mutual_best ? match_mfma_kernel<true, 64> : match_mfma_kernel<false, 64>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs, dwork,
-                       m->mm_cpart, m->mm_rstate);
-    hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, dwork + c.nwg,
+    hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs,
+                       plan_ptr<int2>(m->plan, L.work), m->mm_cpart, m->mm_rstate);
+    hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(m->plan, L.fin),
                        m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
   }
   return hipGetLastError();
+}
+
+// Plans the pair list pairs_ab of sets s1 x s2 (plan_pairs), runs it and delivers every pair's matches compacted on the device:
+// out_counts[p] and out_pairs[p][max_match][2] (in the pinned slot the pairs are P.mm apart).  Chunk k is enqueued into slot k & 1; its results
+// are read on the host while chunk k + 1 runs.  m->last_ms: the sum of the chunks' kernel intervals (multiply, finish,
+// compaction).  `what` names the entry point in the text of a device error, after which the stream is synchronised.
+int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npairs, const int* pairs_ab, int max_match,
+              int* out_pairs, int* out_counts, float distmax, float ratiomax, int mutual_best, const char* what) {
+  PairPlan P;
+  if (!plan_pairs(s1.layout(), s2.layout(), npairs, pairs_ab, max_match, mutual_best, P)) {
+    m->err = std::string(what) + ": a pair needs more scratch than one launch can address";
+    return HESS_ERR_TOO_BIG;
+  }
+  if (const int rc = grow_for(m, P.need)) return rc;
+  const int mm = P.mm;
+  // A list of one chunk (the typed single pair) waits for the stream and records no third event: the event after the copy
+  // and the wait for it cost 7 us per call, a tenth of that pair's wall time.  Behind the last of several chunks the
+  // stream wait is the slower one (profiles/r19_matcher_plan.txt).
+  const bool one_chunk = P.chunks.size() == 1;
+  float total_ms = 0.0f;
+  auto collect = [&](size_t k) -> hipError_t {
+    const Chunk& c = P.chunks[k];
+    hipEvent_t* ev = m->mp_ev[k & 1];
+    hipError_t e = one_chunk ? hipStreamSynchronize(m->st) : hipEventSynchronize(ev[2]);
+    if (e != hipSuccess) return e;
+    float ms = 0.0f;
+    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e != hipSuccess) return e;
+    total_ms += ms;
+    const int* h = m->mp_hout[k & 1];
+    const int q0 = c.p0 / c.jpp, q1 = c.p1 / c.jpp;
+    for (int p = q0; p < q1; p++) {
+      const int n = h[p - q0];
+      out_counts[p] = n;
+      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - q0) * mm * 2, (size_t)n * 2 * sizeof(int));
+    }
+    return hipSuccess;
+  };
+  hipError_t err = hipSuccess;
+  for (size_t k = 0; k < P.chunks.size() && err == hipSuccess; k++) {
+    const Chunk& c = P.chunks[k];
+    const PlanLayout L = plan_layout(c);
+    hipEvent_t* ev = m->mp_ev[k & 1];
+    err = run_chunk(m, s1, s2, P.jobs.data(), P.orig.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax);
+    if (err != hipSuccess) break;
+    if (P.jpp == 4)
+      hipLaunchKernelGGL(match_types_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan, L.jobs),
+                         plan_ptr<int2>(m->plan, L.orig), s1.fwd, s2.inv, m->rowm, m->colm, mutual_best, mm, m->mp_out,
+                         m->mp_out + MP_PAIRS);
+    else
+      hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan, L.jobs),
+                         m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
+    (void)hipEventRecord(ev[1], m->st);
+    err = hipGetLastError();
+    if (err != hipSuccess) break;
+    err = hipMemcpyAsync(m->mp_hout[k & 1], m->mp_out, (MP_PAIRS + (size_t)c.pairs() * mm * 2) * sizeof(int),
+                         hipMemcpyDeviceToHost, m->st);
+    if (err != hipSuccess) break;
+    if (!one_chunk) (void)hipEventRecord(ev[2], m->st);
+    if (k > 0) err = collect(k - 1);
+  }
+  if (err == hipSuccess) err = collect(P.chunks.size() - 1);
+  if (err != hipSuccess) {
+    (void)hipStreamSynchronize(m->st);
+    m->err = std::string(what) + ": " + hipGetErrorString(err);
+    return HESS_ERR_DEVICE;
+  }
+  m->last_ms = total_ms;
+  return 0;
+}
+
+// The small unguided and the guided single pair, from m->e0 on: the score matrix (match_dot_kernel, gates per pair), the row
+// decisions and, for mutual best, the column decisions.
+int match_small(hess_matcher* m, int n1, int n2, const float* H, const float* F, float distmax, float ratiomax,
+                float hdistmax, float fdistmax, int mutual_best) {
+  M_TRY(m, grow_device(m->rowm, m->rowm_cap, (size_t)n1));
+  M_TRY(m, grow_device(m->colm, m->colm_cap, (size_t)n2));
+  const size_t need = (size_t)n1 * n2;
+  if (need > m->mat_cap) {
+    (void)hipFree(m->cpart); (void)hipFree(m->dotm);
+    m->cpart = nullptr;
+    m->dotm = nullptr;
+    M_TRY(m, hipMalloc(&m->cpart, (size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift * sizeof(int3)));
+    M_TRY(m, hipMalloc(&m->dotm, need * sizeof(int)));
+    m->mat_cap = need;
+  }
+  GeoParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.guided = H ? 1 : 0;
+  if (gp.guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
+  (void)hipEventRecord(m->e0, m->st);
+  hipLaunchKernelGGL(m->dim == 128 ? match_dot_kernel<128> : match_dot_kernel<64>, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM),
+                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp,
+                     mutual_best ? m->cpart : nullptr, m->dotm);
+  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
+                     m->rowm);
+  if (mutual_best)
+    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart, (n1 + TM - 1) / TM, n2,
+                       distmax, ratiomax, m->colm);
+  return 0;
 }
 
 }  // namespace
@@ -1302,85 +1294,22 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
   if (guided && (!m->have_loc[0] || !m->have_loc[1])) return 0;  // SiftMatchCU.cpp:131
   M_TRY(m, hipSetDevice(m->device));
   if (typed) {
-    // the gated pair: its class jobs through the job tables at any size (bank pairs take them below the 3 Mi switch too),
-    // compacted on the device in original row order
-    PairJob jobs[4];
-    type_jobs(m->slot[0], 0, m->slot[1], 0, jobs);
-    size_t work = 0;
-    for (const PairJob& J : jobs) work += job_work(J);
-    Chunk c{0, 4, chunk_sps(work), 0, 0, 0, 0, 0, 0, 4};
-    plan_chunk(jobs, c, mutual_best);
-    const int2 orig = make_int2(0, n1);
-    const int mm = std::min(n1, max_match);
-    const size_t outn = (size_t)MP_PAIRS + (size_t)mm * 2;
-    M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, std::max<size_t>(c.rs, 1)));
-    M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, std::max<size_t>(c.cp, 1)));
-    M_TRY(m, grow_device(m->rowm, m->rowm_cap, std::max<size_t>(c.rm, 1)));
-    M_TRY(m, grow_device(m->colm, m->colm_cap, std::max<size_t>(c.cm, 1)));
-    M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, outn));
-    M_TRY(m, grow_device(m->plan, m->plan_cap, c.plan_bytes()));
-    M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, c.plan_bytes()));
-    M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, outn));
-    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], jobs, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax, &orig));
-    hipLaunchKernelGGL(match_types_compact_kernel, dim3(1), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
-                       reinterpret_cast<const int2*>(m->plan + c.plan_bytes()) - 1, m->slot[0].fwd, m->slot[1].inv, m->rowm,
-                       m->colm, mutual_best ? 1 : 0, mm, m->mp_out, m->mp_out + MP_PAIRS);
-    (void)hipEventRecord(m->e1, m->st);
-    M_TRY(m, hipGetLastError());
-    M_TRY(m, hipMemcpyAsync(m->mp_hout[0], m->mp_out, outn * sizeof(int), hipMemcpyDeviceToHost, m->st));
-    M_TRY(m, hipStreamSynchronize(m->st));
-    (void)hipEventElapsedTime(&m->last_ms, m->e0, m->e1);
-    const int nmatch = m->mp_hout[0][0];
-    memcpy(pairs, m->mp_hout[0] + MP_PAIRS, (size_t)nmatch * 2 * sizeof(int));
-    return nmatch;
+    // the gated pair: a list of one through the job tables at any size (bank pairs take them below the switch too), compacted
+    // on the device in original row order
+    const int ab[2] = {0, 0};
+    int nmatch = 0;
+    const int rc = run_pairs(m, m->slot[0], m->slot[1], 1, ab, max_match, pairs, &nmatch, distmax, ratiomax, mutual_best ? 1 : 0, "match");
+    return rc ? rc : nmatch;
   }
-  M_TRY(m, grow_device(m->rowm, m->rowm_cap, (size_t)n1));
-  M_TRY(m, grow_device(m->colm, m->colm_cap, (size_t)n2));
-  // small problems (three launches of latency) stay on the one-pass dot kernel: 1024 x 1024 0.026 vs 0.033 ms
-  if (!guided && (size_t)n1 * n2 > ((size_t)3 << 20)) {
-    // matrix-core path, the pair as a chunk of one job: (256-row block, column segment) workgroups, at least two per CU
-    // where the problem allows.  Workgroups: whole rounds over the 256 CUs -- two per CU (what the registers allow) when
-    // that leaves a workgroup at least four super tiles, else one per CU with twice the tiles (its prologue and the merge
-    // of the row states at its end cost about as much as two super tiles).  Same call, 4096^2 / 8192^2, TMAC/s: 256
-    // workgroups 91 / 193, 384: 91 / 176, 512: 81 / 211, 768: 81 / 180 (profiles/r06_experiments/matcher.txt).
-    const int nrb = (n1 + MM_ROWS - 1) / MM_ROWS, nsuper = (n2 + MM_SUPER - 1) / MM_SUPER;
-    const int target_wgs = (long long)nrb * nsuper >= 512 * 4 ? 512 : 256;
-    int nseg = (target_wgs + nrb - 1) / nrb;
-    nseg = nseg < 1 ? 1 : (nseg > nsuper ? nsuper : nseg);
-    const int sps = std::min((nsuper + nseg - 1) / nseg, MM_MAX_TILES / 4);
-    PairJob job{};
-    job.n1 = n1;
-    job.n2 = n2;
-    Chunk c{0, 1, sps, 0, 0, 0, 0, 0, 0};
+  if (!guided && (size_t)n1 * n2 > MM_SINGLE_ABOVE) {
+    // matrix cores, the pair as a chunk of one job with the segments of single_sps
+    PairJob job{0, 0, n1, n2};
+    Chunk c{0, 1, single_sps(n1, n2), 0, 0, 0, 0, 0, 0, 1};
     plan_chunk(&job, c, mutual_best);
-    M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, c.rs));
-    M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, c.cp));
-    M_TRY(m, grow_device(m->plan, m->plan_cap, c.plan_bytes()));
-    M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, c.plan_bytes()));
-    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], &job, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax));
-  } else {
-  const size_t need = (size_t)n1 * n2;
-  if (need > m->mat_cap) {
-    (void)hipFree(m->cpart); (void)hipFree(m->dotm);
-    m->cpart = nullptr;
-    m->dotm = nullptr;
-    M_TRY(m, hipMalloc(&m->cpart, (size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift * sizeof(int3)));
-    M_TRY(m, hipMalloc(&m->dotm, need * sizeof(int)));
-    m->mat_cap = need;
-  }
-  GeoParams gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.guided = guided ? 1 : 0;
-  if (guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
-  (void)hipEventRecord(m->e0, m->st);
-  hipLaunchKernelGGL(m->dim == 128 ? match_dot_kernel<128> : match_dot_kernel<64>, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM),
-                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp,
-                     mutual_best ? m->cpart : nullptr, m->dotm);
-  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
-                     m->rowm);
-  if (mutual_best)
-    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart, (n1 + TM - 1) / TM, n2,
-                       distmax, ratiomax, m->colm);
+    if (const int rc = grow_for(m, PlanNeed{c.rs, c.cp, c.rm, c.cm, plan_layout(c).bytes, 0})) return rc;  // (0: compacted on the host, below)
+    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], &job, nullptr, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax));
+  } else if (const int rc = match_small(m, n1, n2, H, F, distmax, ratiomax, hdistmax, fdistmax, mutual_best)) {
+    return rc;
   }
   (void)hipEventRecord(m->e1, m->st);
   m->hrow.resize(n1);
@@ -1486,7 +1415,7 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
     if (m->bank.typed) {  // the set's four class groups, then the caller's order through fwd
       const int g0 = m->bank.goff[4 * set];
       size_t ext = 0;
-      for (int c = 0; c < 4; c++) ext += ((size_t)m->bank.gnum[4 * set + c] + MM_ROWS - 1) / MM_ROWS * MM_ROWS;
+      for (int c = 0; c < 4; c++) ext += pad_rows((size_t)m->bank.gnum[4 * set + c]);
       std::vector<unsigned char> grp(ext * KD);
       std::vector<int> fwd((size_t)n);
       M_TRY(m, hipMemcpy(grp.data(), m->bank.rows + (size_t)g0 * KD, ext * KD, hipMemcpyDeviceToHost));
@@ -1547,123 +1476,7 @@ int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, i
   M_TRY(m, hipSetDevice(m->device));
   mutual_best = mutual_best ? 1 : 0;
 
-  // one job per pair, or with types on the bank one per pair and class (jobs jpp p .. jpp p + jpp - 1 are pair p's)
-  const bool typed = m->bank.typed;
-  const int jpp = typed ? 4 : 1;
-  std::vector<PairJob> jobs((size_t)npairs * jpp);
-  std::vector<int2> orig(typed ? (size_t)npairs : 0);
-  for (int p = 0; p < npairs; p++) {
-    const int sa = pairs_ab[2 * p], sb = pairs_ab[2 * p + 1];
-    if (typed) {
-      type_jobs(m->bank, sa, m->bank, sb, &jobs[(size_t)p * 4]);
-      orig[p] = make_int2(m->bank.first[sa], m->bank.num[sa]);
-      continue;
-    }
-    PairJob& J = jobs[p];
-    J.a = m->bank.off[sa];
-    J.b = m->bank.off[sb];
-    J.n1 = m->bank.num[sa];
-    J.n2 = m->bank.num[sb];
-    if (J.n1 == 0 || J.n2 == 0) J.n1 = J.n2 = 0;  // a pair with an empty side has no work and no matches
-  }
-  // Segments per pair from the whole chunk's grid: chunk_sps.
-  std::vector<Chunk> chunks;
-  int mm = 0;  // matches kept per pair: max_match, at most the rows of its set 1
-  for (int p0 = 0; p0 < npairs;) {  // (p0 and `pairs` count pairs, the chunk's p0 and p1 jobs)
-    Chunk c{p0 * jpp, p0 * jpp, 1, 0, 0, 0, 0, 0, 0, jpp};
-    size_t work = 0;
-    int pairs = 0;
-    while (p0 + pairs < npairs && pairs < MP_PAIRS) {
-      const int sa = pairs_ab[2 * (p0 + pairs)], sb = pairs_ab[2 * (p0 + pairs) + 1];
-      const int n1 = m->bank.num[sb] ? m->bank.num[sa] : 0;
-      size_t w = 0;
-      for (int k = 0; k < jpp; k++) w += job_work(jobs[c.p1 + k]);
-      Chunk t = c;
-      t.p1 += jpp;
-      t.sps = chunk_sps(work + w);
-      if (pairs > 0 && plan_chunk(jobs.data(), t, mutual_best) > MP_SCRATCH) break;
-      c = t;
-      work += w;
-      pairs++;
-      mm = std::max(mm, std::min(n1, max_match));
-    }
-    plan_chunk(jobs.data(), c, mutual_best);  // (the plan of the chunk as it ends)
-    if (c.rs + c.cp > (size_t)INT32_MAX || c.nwg > (size_t)INT32_MAX) {
-      m->err = "match_pairs: a pair needs more scratch than one launch can address";
-      return HESS_ERR_TOO_BIG;
-    }
-    chunks.push_back(c);
-    p0 += pairs;
-  }
-  size_t rs = 1, cp = 1, rm = 1, cm = 1, plan = 0, outn = 0;
-  for (const Chunk& c : chunks) {
-    rs = std::max(rs, c.rs); cp = std::max(cp, c.cp); rm = std::max(rm, c.rm); cm = std::max(cm, c.cm);
-    plan = std::max(plan, c.plan_bytes());
-    outn = std::max(outn, (size_t)MP_PAIRS + (size_t)(c.p1 - c.p0) / jpp * mm * 2);
-  }
-  M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, rs));
-  M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, cp));
-  M_TRY(m, grow_device(m->rowm, m->rowm_cap, rm));
-  M_TRY(m, grow_device(m->colm, m->colm_cap, cm));
-  M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, outn));
-  M_TRY(m, grow_device(m->plan, m->plan_cap, plan));
-  M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, plan));
-  M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, outn));
-  for (int k = 0; k < 2; k++)
-    for (int q = 0; q < 3; q++)
-      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
-
-  // chunk k is enqueued into slot k & 1; its results are read on the host while chunk k + 1 runs
-  float total_ms = 0.0f;
-  auto collect = [&](size_t k) -> hipError_t {
-    const Chunk& c = chunks[k];
-    hipEvent_t* ev = m->mp_ev[k & 1];
-    hipError_t e = hipEventSynchronize(ev[2]);
-    if (e != hipSuccess) return e;
-    float ms = 0.0f;
-    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e != hipSuccess) return e;
-    total_ms += ms;
-    const int* h = m->mp_hout[k & 1];
-    const int q0 = c.p0 / jpp, q1 = c.p1 / jpp;
-    for (int p = q0; p < q1; p++) {
-      const int n = h[p - q0];
-      out_counts[p] = n;
-      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - q0) * mm * 2, (size_t)n * 2 * sizeof(int));
-    }
-    return hipSuccess;
-  };
-  hipError_t err = hipSuccess;
-  for (size_t k = 0; k < chunks.size() && err == hipSuccess; k++) {
-    const Chunk& c = chunks[k];
-    const int np = (c.p1 - c.p0) / jpp;
-    hipEvent_t* ev = m->mp_ev[k & 1];
-    err = run_chunk(m, m->bank, m->bank, jobs.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax, orig.data());
-    if (err != hipSuccess) break;
-    if (typed)
-      hipLaunchKernelGGL(match_types_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
-                         reinterpret_cast<const int2*>(m->plan + c.plan_bytes()) - c.norig(), m->bank.fwd, m->bank.inv, m->rowm,
-                         m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
-    else
-      hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(np), dim3(256), 0, m->st, reinterpret_cast<const PairJob*>(m->plan),
-                         m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
-    (void)hipEventRecord(ev[1], m->st);
-    err = hipGetLastError();
-    if (err != hipSuccess) break;
-    err = hipMemcpyAsync(m->mp_hout[k & 1], m->mp_out, (MP_PAIRS + (size_t)np * mm * 2) * sizeof(int), hipMemcpyDeviceToHost,
-                         m->st);
-    if (err != hipSuccess) break;
-    (void)hipEventRecord(ev[2], m->st);
-    if (k > 0) err = collect(k - 1);
-  }
-  if (err == hipSuccess) err = collect(chunks.size() - 1);
-  if (err != hipSuccess) {
-    (void)hipStreamSynchronize(m->st);
-    m->err = std::string("match_pairs: ") + hipGetErrorString(err);
-    return HESS_ERR_DEVICE;
-  }
-  m->last_ms = total_ms;
-  return 0;
+  return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best, "match_pairs");
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }

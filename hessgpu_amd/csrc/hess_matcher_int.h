@@ -32,4 +32,16 @@ int hess_matcher_device_range(hess_matcher* m, const void* p, size_t bytes, cons
 void hess_geom_drop_bank_locations(hess_geom_state* g);
 void hess_geom_state_destroy(hess_geom_state* g);
 
+// A device buffer of at least n elements: kept when it is large enough, else replaced (its contents are not carried over).
+template <class T>
+hipError_t grow_device(T*& p, size_t& cap, size_t n) {
+  if (n <= cap) return hipSuccess;
+  (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const hipError_t e = hipMalloc(&p, n * sizeof(T));
+  if (e == hipSuccess) cap = n;
+  return e;
+}
+
 #endif  // HESS_MATCHER_INT_H
