@@ -10,6 +10,9 @@
 //   geom_finish_kernel   one workgroup per pair: arg-max over the block entries (score, then lowest t), rank 2 for F and
 //                        unit norm in double (one thread), then the inlier mask with the guided gate's own formulas
 //                        (match_dot_kernel, hess_match.hip) and its count;
+//   geom_refit_kernel    only when params.refit > 0, one workgroup per pair after the finish kernel: up to `refit` times the
+//                        least-squares DLT on the inliers (hess_abi.h, step 6) -- moment sums over the mask, the serial
+//                        solve of hess_geom_refit.h on one lane, the candidate's mask into a second buffer, accept or stop;
 //   geom_loc_gather_kernel  bank locations from strided records into the caller's row order of the kept rows.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +25,7 @@
 #include <vector>
 
 #include "../../include/hess_abi.h"
+#include "hess_geom_refit.h"
 #include "hess_matcher_int.h"
 
 namespace {
@@ -31,6 +35,9 @@ constexpr int GEOM_DEFAULT_T = 2048;
 constexpr int GEOM_MAX_T = 65536;       // 256 blocks of 256 hypotheses: one finish thread per block
 constexpr int GEOM_PAIRS = 256;         // pairs per chunk (one set of launches), and
 constexpr size_t GEOM_MATCHES = (size_t)4 << 20;  // correspondences per chunk (a pair above it is a chunk of its own)
+
+constexpr int GEOM_MAX_REFIT = 8;
+static_assert(GEOM_MODEL_H == HESS_GEOM_HOMOGRAPHY && GEOM_MODEL_F == HESS_GEOM_FUNDAMENTAL, "hess_geom_refit.h names the models");
 
 constexpr int geom_k(int model) { return model == HESS_GEOM_HOMOGRAPHY ? 4 : 8; }
 
@@ -259,65 +266,6 @@ __host__ __device__ inline bool geom_gate(const float (&M)[9], const float2 l1, 
   }
 }
 
-// One rotation of the one-sided Jacobi SVD: makes columns P and Q of w orthogonal, v collects the rotations.
-template <int P, int Q>
-__host__ __device__ inline bool geom_rotate(double (&w)[9], double (&v)[9]) {
-  double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    al = fma(w[3 * r + P], w[3 * r + P], al);
-    be = fma(w[3 * r + Q], w[3 * r + Q], be);
-    ga = fma(w[3 * r + P], w[3 * r + Q], ga);
-  }
-  if (ga == 0.0 || fabs(ga) <= 1.0e-17 * sqrt(al * be)) return false;
-  const double ze = (be - al) / (2.0 * ga);
-  const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const double wp = w[3 * r + P], wq = w[3 * r + Q], vp = v[3 * r + P], vq = v[3 * r + Q];
-    w[3 * r + P] = c * wp - s * wq;
-    w[3 * r + Q] = s * wp + c * wq;
-    v[3 * r + P] = c * vp - s * vq;
-    v[3 * r + Q] = s * vp + c * vq;
-  }
-  return true;
-}
-
-// The winner's matrix as returned: for F the nearest rank-2 matrix (A V = W with orthogonal columns, the shortest column of
-// W zeroed, A' = W' V^T), then unit Frobenius norm.
-__host__ __device__ inline void geom_finalise(int model, double (&m)[9]) {
-  if (model == HESS_GEOM_FUNDAMENTAL) {
-    double v[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    for (int sweep = 0; sweep < 30; sweep++) {
-      const bool r01 = geom_rotate<0, 1>(m, v), r02 = geom_rotate<0, 2>(m, v), r12 = geom_rotate<1, 2>(m, v);
-      if (!(r01 || r02 || r12)) break;
-    }
-    double n[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) n[c] = m[c] * m[c] + m[3 + c] * m[3 + c] + m[6 + c] * m[6 + c];
-    const int z = n[0] <= n[1] && n[0] <= n[2] ? 0 : (n[1] <= n[2] ? 1 : 2);
-    double a[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (k == z ? 0.0 : m[3 * r + k]) * v[3 * c + k];
-        a[3 * r + c] = s;
-      }
-#pragma unroll
-    for (int i = 0; i < 9; i++) m[i] = a[i];
-  }
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < 9; i++) s += m[i] * m[i];
-  s = 1.0 / sqrt(s);
-#pragma unroll
-  for (int i = 0; i < 9; i++) m[i] *= s;
-}
-
 // One pair of a launch: the locations of its two sets, its matches (and mask bytes) from moff on, its block entries from boff.
 struct GeomJob {
   const float2 *l1, *l2;
@@ -466,6 +414,174 @@ __global__ __launch_bounds__(256) void geom_finish_kernel(const GeomJob* jobs, c
   }
 }
 
+// Sums of a workgroup in one fixed order: xor butterflies over the 64 lanes of a wavefront (a + b = b + a: every lane holds
+// the same bits), then (w0 + w1) + (w2 + w3) over the four wavefronts.  red: [4][NV] in LDS.  Every thread gets the totals.
+template <int NV>
+__device__ __forceinline__ void geom_block_sum(double (&v)[NV], double* red) {
+#pragma unroll
+  for (int j = 0; j < NV; j++) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v[j] += __shfl_xor(v[j], d);
+  }
+  __syncthreads();  // the totals of the sum before have been read
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int j = 0; j < NV; j++) red[(threadIdx.x >> 6) * NV + j] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NV; j++) v[j] = (red[j] + red[NV + j]) + (red[2 * NV + j] + red[3 * NV + j]);
+}
+
+// The refit of hess_abi.h, step 6: blockIdx.x = the pair of the chunk, after geom_finish_kernel wrote its result and mask.
+// Order of every sum over the inliers (it depends on the match list and the mask alone): lane l of 256 adds the inliers
+// i = l, l + 256, l + 512, ... in ascending i (the LDS chunk of 2048 is a multiple of 256), then geom_block_sum's tree.
+// Per iteration three passes over the correspondences (centroid sums; distances to the centroids; the moment sums of
+// geom_refit_moments in normalised coordinates, all in double from the float32 locations), the serial solve on thread 0 with
+// its two 9 x 9 matrices in LDS, and the gate pass that writes the candidate's mask to cand[] and counts it.  A list of at
+// most GEOM_CHUNK correspondences is staged in LDS once, a longer one chunk by chunk in every pass.  Every mask byte is
+// read and written by the thread that owns its index modulo 256: no ordering between threads is needed on mask or cand.
+template <int MODEL>
+__global__ __launch_bounds__(256) void geom_refit_kernel(const GeomJob* jobs, const int2* matches, float bound, int refit,
+                                                         hess_geom_result* results, unsigned char* mask, unsigned char* cand) {
+  constexpr int K = geom_k(MODEL), NS = geom_refit_sums(MODEL);
+  __shared__ float4 pts[GEOM_CHUNK];
+  __shared__ double red[4 * NS];
+  __shared__ double sS[NS], sA[81], sV[81];
+  __shared__ float sC[9];
+  __shared__ int sok;
+  __shared__ int wcnt[8];
+  const GeomJob J = jobs[blockIdx.x];
+  hess_geom_result* const R = results + blockIdx.x;
+  if (R->hypothesis < 0) return;  // no model (workgroup-uniform; R is written at the end only)
+  const int tid = threadIdx.x, n = J.n;
+  const int2* const mt = matches + J.moff;
+  unsigned char* const mk = mask + J.moff;
+  unsigned char* const cd = cand + J.moff;
+  float M[9];
+#pragma unroll
+  for (int c = 0; c < 9; c++) M[c] = R->M[c];
+  const int first = R->inliers;
+  int inl = first, refits = 0;
+  const bool one = n <= GEOM_CHUNK;
+  auto stage = [&](int base, int cnt) {
+    __syncthreads();  // every lane is done with the chunk before
+    for (int i = tid; i < cnt; i += 256) {
+      const int2 m = mt[base + i];
+      const float2 a = J.l1[m.x], b = J.l2[m.y];
+      pts[i] = make_float4(a.x, a.y, b.x, b.y);
+    }
+    __syncthreads();
+  };
+  if (one) stage(0, n);
+  for (int r = 0; r < refit; r++) {
+    if (inl < K) break;
+    GeomRefitNorm nm;
+    {  // centroids
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int base = 0; base < n; base += GEOM_CHUNK) {
+        const int cnt = min(GEOM_CHUNK, n - base);
+        if (!one) stage(base, cnt);
+        for (int i = tid; i < cnt; i += 256)
+          if (mk[base + i]) {
+            const float4 p = pts[i];
+            s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z; s[3] += (double)p.w;
+          }
+      }
+      geom_block_sum<4>(s, red);
+      nm.c1x = s[0] / inl; nm.c1y = s[1] / inl; nm.c2x = s[2] / inl; nm.c2y = s[3] / inl;
+    }
+    {  // mean distances
+      double s[2] = {0.0, 0.0};
+      for (int base = 0; base < n; base += GEOM_CHUNK) {
+        const int cnt = min(GEOM_CHUNK, n - base);
+        if (!one) stage(base, cnt);
+        for (int i = tid; i < cnt; i += 256)
+          if (mk[base + i]) {
+            const float4 p = pts[i];
+            const double x = (double)p.x - nm.c1x, y = (double)p.y - nm.c1y, u = (double)p.z - nm.c2x, v = (double)p.w - nm.c2y;
+            s[0] += sqrt(fma(x, x, y * y));
+            s[1] += sqrt(fma(u, u, v * v));
+          }
+      }
+      geom_block_sum<2>(s, red);
+      if (!geom_refit_scales(inl, s[0], s[1], nm.s1, nm.s2)) break;  // (the same bits in every thread)
+    }
+    {  // moment sums, then the solve on one lane
+      double acc[NS];
+#pragma unroll
+      for (int j = 0; j < NS; j++) acc[j] = 0.0;
+      for (int base = 0; base < n; base += GEOM_CHUNK) {
+        const int cnt = min(GEOM_CHUNK, n - base);
+        if (!one) stage(base, cnt);
+        for (int i = tid; i < cnt; i += 256)
+          if (mk[base + i]) {
+            const float4 p = pts[i];
+            geom_refit_moments<MODEL>(nm.s1 * ((double)p.x - nm.c1x), nm.s1 * ((double)p.y - nm.c1y),
+                                      nm.s2 * ((double)p.z - nm.c2x), nm.s2 * ((double)p.w - nm.c2y), acc);
+          }
+      }
+      geom_block_sum<NS>(acc, red);
+      if (tid == 0) {
+#pragma unroll
+        for (int j = 0; j < NS; j++) sS[j] = acc[j];
+        geom_refit_normal(MODEL, sS, sA);
+        double x[9];
+        geom_refit_eigen(sA, sV, x);
+        float C[9];
+        sok = geom_refit_candidate(MODEL, x, nm, M, C) ? 1 : 0;
+#pragma unroll
+        for (int c = 0; c < 9; c++) sC[c] = C[c];
+      }
+      __syncthreads();
+    }
+    if (!sok) break;
+    float C[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) C[c] = sC[c];
+    int cnt_in = 0, differ = 0;
+    for (int base = 0; base < n; base += GEOM_CHUNK) {
+      const int cnt = min(GEOM_CHUNK, n - base);
+      if (!one) stage(base, cnt);
+      for (int i = tid; i < cnt; i += 256) {
+        const float4 p = pts[i];
+        const bool in = geom_gate<MODEL>(C, make_float2(p.x, p.y), make_float2(p.z, p.w), bound);
+        cd[base + i] = in ? 1 : 0;
+        cnt_in += in ? 1 : 0;
+        differ += (in ? 1 : 0) != (int)mk[base + i] ? 1 : 0;
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      cnt_in += __shfl_xor(cnt_in, d);
+      differ += __shfl_xor(differ, d);
+    }
+    __syncthreads();  // sok, sC and wcnt of the iteration before have been read
+    if ((tid & 63) == 0) {
+      wcnt[tid >> 6] = cnt_in;
+      wcnt[4 + (tid >> 6)] = differ;
+    }
+    __syncthreads();
+    cnt_in = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    differ = wcnt[4] + wcnt[5] + wcnt[6] + wcnt[7];
+    const int what = geom_refit_decide(inl, cnt_in, differ);
+    if (what == GEOM_REFIT_DISCARD) break;
+    for (int i = tid; i < n; i += 256) mk[i] = cd[i];
+#pragma unroll
+    for (int c = 0; c < 9; c++) M[c] = C[c];
+    inl = cnt_in;
+    refits++;
+    if (what == GEOM_REFIT_ACCEPT_AND_STOP) break;
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int c = 0; c < 9; c++) R->M[c] = M[c];
+    R->inliers = inl;
+    R->refits = refits;
+    R->ransac_inliers = first;
+  }
+}
+
 // out[first kept row of set + i] = the (x, y) at record (first record of the set + i) of src, records `stride` bytes apart.
 // sets[s] = (first kept row, first record, rows kept) in ascending kept rows.
 __global__ __launch_bounds__(256) void geom_loc_gather_kernel(const unsigned char* src, size_t stride, const int3* sets,
@@ -494,7 +610,8 @@ struct hess_geom_state {
   GeomBest* best = nullptr;
   hess_geom_result* results = nullptr;
   unsigned char* mask = nullptr;
-  size_t plan_cap = 0, matches_cap = 0, best_cap = 0, results_cap = 0, mask_cap = 0;
+  unsigned char* cand = nullptr;  // the refit's candidate masks (only with params.refit > 0)
+  size_t plan_cap = 0, matches_cap = 0, best_cap = 0, results_cap = 0, mask_cap = 0, cand_cap = 0;
 };
 
 void hess_geom_drop_bank_locations(hess_geom_state* g) {
@@ -512,6 +629,7 @@ void hess_geom_state_destroy(hess_geom_state* g) {
   (void)hipFree(g->best);
   (void)hipFree(g->results);
   (void)hipFree(g->mask);
+  (void)hipFree(g->cand);
   delete g;
 }
 
@@ -551,7 +669,11 @@ int geom_params_check(hess_matcher_view& v, const hess_geom_params* P, const cha
     *v.err = w + ": params.hypotheses must lie in 0..65536, not " + std::to_string(P->hypotheses);
     return HESS_ERR_ARG;
   }
-  for (int k = 0; k < 4; k++)
+  if (P->refit < 0 || P->refit > GEOM_MAX_REFIT) {
+    *v.err = w + ": params.refit must lie in 0..8, not " + std::to_string(P->refit);
+    return HESS_ERR_ARG;
+  }
+  for (int k = 1; k < 4; k++)
     if (P->reserved[k]) { *v.err = w + ": params.reserved[" + std::to_string(k) + "] must be zero"; return HESS_ERR_ARG; }
   if (!(P->bound > 0.0f) || !std::isfinite(P->bound)) {
     *v.err = w + ": params.bound must be finite and greater than 0";
@@ -577,7 +699,7 @@ int geom_matches_check(hess_matcher_view& v, const std::vector<GeomPair>& pairs,
 }
 
 template <int MODEL>
-hipError_t geom_launch(hipStream_t st, hess_geom_state* g, int np, size_t nwork, int T, float bound) {
+hipError_t geom_launch(hipStream_t st, hess_geom_state* g, int np, size_t nwork, int T, float bound, int refit) {
   const GeomJob* djobs = reinterpret_cast<const GeomJob*>(g->plan);
   const int2* dwork = reinterpret_cast<const int2*>(g->plan + (size_t)np * sizeof(GeomJob));
   if (nwork)
@@ -585,11 +707,14 @@ hipError_t geom_launch(hipStream_t st, hess_geom_state* g, int np, size_t nwork,
                        g->best);
   hipLaunchKernelGGL(geom_finish_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, g->matches, g->best, bound,
                      g->results, g->mask);
+  if (refit > 0)
+    hipLaunchKernelGGL(geom_refit_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, g->matches, bound, refit, g->results,
+                       g->mask, g->cand);
   return hipGetLastError();
 }
 
-// The checked pairs in chunks: per chunk one upload (jobs, work table, matches), the two launches, one download (results,
-// masks).  inlier: pair p's bytes at inlier + p * pitch, or NULL.
+// The checked pairs in chunks: per chunk one upload (jobs, work table, matches), the two launches (three with a refit), one
+// download (results, masks).  inlier: pair p's bytes at inlier + p * pitch, or NULL.
 int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hess_geom_params& P, hess_geom_result* out,
              unsigned char* inlier, size_t pitch) {
   hess_geom_state* const g = geom_state(v);
@@ -632,11 +757,12 @@ int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hes
     G_TRY(v, grow_device(g->best, g->best_cap, std::max<size_t>(nwork, 1)));
     G_TRY(v, grow_device(g->results, g->results_cap, (size_t)np));
     G_TRY(v, grow_device(g->mask, g->mask_cap, std::max<size_t>(nm, 1)));
+    if (P.refit > 0) G_TRY(v, grow_device(g->cand, g->cand_cap, std::max<size_t>(nm, 1)));
     G_TRY(v, hipMemcpyAsync(g->plan, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
     if (nm) G_TRY(v, hipMemcpyAsync(g->matches, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
     (void)hipEventRecord(v.e0, v.st);
-    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, g, np, nwork, T, P.bound)
-                                             : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, g, np, nwork, T, P.bound));
+    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, g, np, nwork, T, P.bound, P.refit)
+                                             : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, g, np, nwork, T, P.bound, P.refit));
     (void)hipEventRecord(v.e1, v.st);
     hres.resize((size_t)np);
     hmask.resize(std::max<size_t>(nm, 1));

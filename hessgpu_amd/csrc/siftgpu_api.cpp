@@ -972,7 +972,7 @@ int SiftMatchGPU::SetFeatureTypes(int index, const unsigned short* types, int st
                                 stride_bytes < 0 ? 0 : (size_t)stride_bytes);
 }
 int SiftMatchGPU::EstimateGeometry(int model, int nmatch, const int match_buffer[][2], float M[3][3], float bound,
-                                   unsigned char* inlier, int hypotheses, unsigned seed) {
+                                   unsigned char* inlier, int hypotheses, unsigned seed, int refit) {
   if (M) memset(&M[0][0], 0, 9 * sizeof(float));
   if (!__matcher || !M) return 0;
   hess_geom_params p;
@@ -981,6 +981,7 @@ int SiftMatchGPU::EstimateGeometry(int model, int nmatch, const int match_buffer
   p.hypotheses = hypotheses;
   p.seed = seed;
   p.bound = bound;
+  p.refit = refit;
   hess_geom_result r;
   memset(&r, 0, sizeof(r));
   if (hess_matcher_estimate(MH(__matcher), nmatch, match_buffer ? &match_buffer[0][0] : nullptr, &p, &r, inlier) != 0) return 0;
@@ -1048,6 +1049,12 @@ int siftmatch_estimate(SiftMatchGPU* m, int model, int nmatch, const int* matche
                        int hypotheses, unsigned seed) {
   return m ? m->EstimateGeometry(model, nmatch, reinterpret_cast<const int(*)[2]>(matches), reinterpret_cast<float(*)[3]>(M), bound,
                                  inlier, hypotheses, seed)
+           : 0;
+}
+int siftmatch_estimate_refit(SiftMatchGPU* m, int model, int nmatch, const int* matches, float* M, float bound, unsigned char* inlier,
+                             int hypotheses, unsigned seed, int refit) {
+  return m ? m->EstimateGeometry(model, nmatch, reinterpret_cast<const int(*)[2]>(matches), reinterpret_cast<float(*)[3]>(M), bound,
+                                 inlier, hypotheses, seed, refit)
            : 0;
 }
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation) { return s->RunSIFT(num, keys, have_orientation); }

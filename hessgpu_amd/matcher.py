@@ -78,7 +78,8 @@ def check_pairs(pairs):
 
 DIMS = (128, 64)
 
-# hess_geom_params / hess_geom_result (include/hess_abi.h)
+# hess_geom_params / hess_geom_result (include/hess_abi.h).  Word 0 of the params' reserved[] is `refit`; words 0 and 1 of the
+# result's reserved[] are `refits` and `ransac_inliers` (the field names stay those of the arrays).
 GEOM_MODELS = {"H": 1, "F": 2, "homography": 1, "fundamental": 2, 1: 1, 2: 2}
 GEOM_PARAMS_DTYPE = np.dtype([("model", "<i4"), ("hypotheses", "<i4"), ("seed", "<u4"), ("bound", "<f4"), ("reserved", "<i4", 4)])
 GEOM_RESULT_DTYPE = np.dtype([("M", "<f4", 9), ("inliers", "<i4"), ("hypothesis", "<i4"), ("reserved", "<i4", 2)])
@@ -94,12 +95,17 @@ def geom_sample(seed, t, k, n):
     return out[:k].copy()
 
 
-def _geom_params(model, bound, hypotheses, seed):
+def _geom_params(model, bound, hypotheses, seed, refit=0):
     if model not in GEOM_MODELS:
         raise ValueError(f"model is 'H' or 'F', not {model!r}")
     p = np.zeros(1, dtype=GEOM_PARAMS_DTYPE)
     p["model"], p["hypotheses"], p["seed"], p["bound"] = GEOM_MODELS[model], int(hypotheses), int(seed) & 0xffffffff, bound
+    p["reserved"][0, 0] = int(refit)
     return p
+
+
+def _geom_info(res, k):
+    return {"inliers": int(res["inliers"][k]), "refits": int(res["reserved"][k, 0]), "ransac_inliers": int(res["reserved"][k, 1])}
 
 
 class Matcher:
@@ -248,16 +254,20 @@ class Matcher:
         self._check(self.L.hess_matcher_bank_set_types_device(self.h, ptr, int(stride)))
 
     # ---- two-view geometry from matches (hess_matcher_estimate*, the rule is stated in include/hess_abi.h) ----
-    def estimate(self, matches, model, bound, hypotheses=0, seed=0):
+    def estimate(self, matches, model, bound, hypotheses=0, seed=0, refit=0, info=False):
         """H ("H") or F ("F") from matches [n, 2] of the two single-pair slots (what match() returned), both located by
         set_locations -> (M [3, 3] float32 of unit norm, mask bool [n], hypothesis).  No model: zeros, no inliers and -1.
-        M and `bound` are what match(H=M, hdistmax=bound) / match(F=M, fdistmax=bound) take; mask is that gate's decision."""
+        M and `bound` are what match(H=M, hdistmax=bound) / match(F=M, fdistmax=bound) take; mask is that gate's decision.
+        refit (0..8): at most so many least-squares refits of the RANSAC winner on its inliers (hess_abi.h, step 6); the
+        inlier count never falls below refit=0's.  info=True appends a dict: inliers, refits (accepted), ransac_inliers
+        (the count before any refit; 0 with refit=0)."""
         mt = check_pairs(matches)
-        p = _geom_params(model, bound, hypotheses, seed)
+        p = _geom_params(model, bound, hypotheses, seed, refit)
         res = np.zeros(1, dtype=GEOM_RESULT_DTYPE)
         mask = np.zeros(max(len(mt), 1), dtype=np.uint8)
         self._check(self.L.hess_matcher_estimate(self.h, len(mt), mt.ctypes.data, p.ctypes.data, res.ctypes.data, mask.ctypes.data))
-        return res["M"][0].reshape(3, 3).copy(), mask[:len(mt)].astype(bool), int(res["hypothesis"][0])
+        out = (res["M"][0].reshape(3, 3).copy(), mask[:len(mt)].astype(bool), int(res["hypothesis"][0]))
+        return out + (_geom_info(res, 0),) if info else out
 
     def set_bank_locations(self, locs):
         """locs: one [n_i, 2] array of (x, y) per bank set (as passed to set_bank, before truncation to max_sift), or None to
@@ -275,9 +285,10 @@ class Matcher:
         """ptr: device address of the first (x, y) float pair on the matcher's device, one per descriptor `stride` bytes apart."""
         self._check(self.L.hess_matcher_bank_set_locations_device(self.h, ptr, int(stride)))
 
-    def estimate_pairs(self, pairs, matches_list, model, bound, hypotheses=0, seed=0):
+    def estimate_pairs(self, pairs, matches_list, model, bound, hypotheses=0, seed=0, refit=0, info=False):
         """For every (a, b) of pairs and its matches (match_pairs' list): what estimate() returns for that pair with seed +
-        its position -> list of (M, mask, hypothesis).  The bank needs locations (set_bank_locations*)."""
+        its position and the same refit -> list of (M, mask, hypothesis), with info=True of (M, mask, hypothesis, dict).  The
+        bank needs locations (set_bank_locations*)."""
         ab = check_pairs(pairs)
         if len(matches_list) != len(ab):
             raise ValueError(f"{len(ab)} pairs but {len(matches_list)} match lists")
@@ -289,12 +300,13 @@ class Matcher:
         for k, m in enumerate(mts):
             buf[k, :len(m)] = m
             cnt[k] = len(m)
-        p = _geom_params(model, bound, hypotheses, seed)
+        p = _geom_params(model, bound, hypotheses, seed, refit)
         res = np.zeros(max(n, 1), dtype=GEOM_RESULT_DTYPE)
         mask = np.zeros((max(n, 1), mm), dtype=np.uint8)
         self._check(self.L.hess_matcher_estimate_pairs(self.h, n, ab.ctypes.data, mm, buf.ctypes.data, cnt.ctypes.data,
                                                        p.ctypes.data, res.ctypes.data, mask.ctypes.data))
-        return [(res["M"][k].reshape(3, 3).copy(), mask[k, :cnt[k]].astype(bool), int(res["hypothesis"][k])) for k in range(n)]
+        out = [(res["M"][k].reshape(3, 3).copy(), mask[k, :cnt[k]].astype(bool), int(res["hypothesis"][k])) for k in range(n)]
+        return [o + (_geom_info(res, k),) for k, o in enumerate(out)] if info else out
 
     def set_bank_from_session(self, session, types=False, locations=False):
         """The descriptors of a HessContext's last batch (run / run_device, or submit_* and wait), one set per image,

@@ -169,9 +169,11 @@ class SiftMatchGPU {
   // (model 2) from the nmatch matches of match_buffer (GetSiftMatch's output) and the locations of both slots
   // (SetFeatureLocation), by the deterministic fixed-budget RANSAC of hess_matcher_estimate (hess_abi.h): M of unit norm and
   // `bound` are what GetGuidedSiftMatch takes as (H, hdistmax) or (F, fdistmax); inlier[i] (nmatch bytes, or NULL) is that
-  // gate's decision on match i.  hypotheses 0: 2048.  Returns the inlier count; 0 without a model (M all zero) or on an error.
+  // gate's decision on match i.  hypotheses 0: 2048.  refit (0..8): at most so many least-squares refits of the winner on its
+  // inliers (hess_abi.h, step 6); the count never falls below refit 0's.  Returns the inlier count; 0 without a model (M all
+  // zero) or on an error.
   int EstimateGeometry(int model, int nmatch, const int match_buffer[][2], float M[3][3], float bound,
-                       unsigned char* inlier = NULL, int hypotheses = 0, unsigned seed = 0);
+                       unsigned char* inlier = NULL, int hypotheses = 0, unsigned seed = 0, int refit = 0);
 };
 
 typedef SiftGPU::SiftKeypoint SiftKeypoint;
@@ -216,6 +218,9 @@ int siftmatch_set_types(SiftMatchGPU* m, int index, const unsigned short* types,
 // EstimateGeometry: matches [nmatch][2], M [9] row-major, inlier [nmatch] or NULL; returns the inlier count
 int siftmatch_estimate(SiftMatchGPU* m, int model, int nmatch, const int* matches, float* M, float bound, unsigned char* inlier,
                        int hypotheses, unsigned seed);
+// the same with EstimateGeometry's trailing refit
+int siftmatch_estimate_refit(SiftMatchGPU* m, int model, int nmatch, const int* matches, float* M, float bound, unsigned char* inlier,
+                             int hypotheses, unsigned seed, int refit);
 int siftgpu_run_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 void siftgpu_set_keys(SiftGPU* s, int num, const SiftGPU::SiftKeypoint* keys, int have_orientation);
 // The resolved hess_params of the instance (what ParseParam did), for tests.

@@ -48,7 +48,9 @@ extern "C" {
  *    hess_matcher_set_types / _bank_set_types / _bank_set_types_device (the feature-type gate of the matcher; added
  *    during version 5 without a bump: a matcher that never calls them matches as before).
  *    hess_geom_sample, hess_matcher_estimate / _estimate_pairs, hess_matcher_bank_set_locations(_device) (H or F from
- *    matches on the device; added during version 5 without a bump: a matcher that never calls them behaves as before). */
+ *    matches on the device; added during version 5 without a bump: a matcher that never calls them behaves as before).
+ *    hess_geom_params.refit, hess_geom_result.refits / .ransac_inliers (the least-squares refit on the inliers, words
+ *    of the reserved arrays; added during version 5 without a bump: `refit` 0 behaves as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -532,21 +534,56 @@ int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, s
  *   5 result   M: the winner's matrix, for F first made rank 2 (its smallest singular value zeroed, in double), scaled to
  *              unit Frobenius norm.  inlier[i] = 1 exactly when correspondence i passes the gate's own formulas (with the
  *              division, in float32) on the returned M: the decision hess_matcher_match makes with M and `bound` as
- *              (H, hdistmax) or (F, fdistmax).  inliers counts the mask.  No refit on the inliers, no early termination.
- * Added during version 5 without a bump: a matcher that never calls these behaves as before. */
+ *              (H, hdistmax) or (F, fdistmax).  inliers counts the mask.  No early termination.
+ *   6 refit    only with params.refit > 0 and a model: a least-squares refit on the inliers, at most `refit` times.  Let
+ *              M0, S0 be the matrix and the mask of step 5.  For r = 1 .. refit:
+ *              a. |S(r-1)| < k: stop.
+ *              b. normalise: per image, over the correspondences of S(r-1), the centroid and the mean distance d to it;
+ *                 the scale is sqrt 2 / d.  All in double from the float32 locations.  Either d zero or not finite: stop.
+ *              c. N (9 x 9, symmetric, double) = the sum over S(r-1) of a a^T for the DLT rows of step 2 in these
+ *                 normalised coordinates: H two rows per correspondence (x, y) -> (u, v), [x y 1 0 0 0 -ux -uy -u] and
+ *                 [0 0 0 x y 1 -vx -vy -v]; F one row, [ux uy u vx vy v x y 1].
+ *              d. candidate C: the unit eigenvector of N's smallest eigenvalue (in double), back in pixel coordinates
+ *                 (T2^-1 X T1 for H, T2^T X T1 for F), made rank 2 (F) and of unit norm as in step 5, with the sign for
+ *                 which sum_i C_i M(r-1)_i >= 0, rounded to float32.  A non-finite entry: stop.
+ *              e. Sc = the gate's own decision on C (the formulas of step 5).  |Sc| < |S(r-1)|: C is discarded, stop.
+ *                 Otherwise M(r) = C, S(r) = Sc; if Sc = S(r-1) as a set, stop after accepting (a further refit would
+ *                 repeat it).
+ *              The call returns the last accepted M and S: inliers counts that mask and is never below what refit = 0
+ *              returns for the same inputs; hypothesis stays the RANSAC winner's index; the mask is still exactly what
+ *              hess_matcher_match decides with the returned M and `bound`.  refits = the accepted refits, ransac_inliers
+ *              = |S0|; both are zero with refit = 0 or without a model.  No floating-point atomics: every sum over the
+ *              inliers is taken in one fixed order that depends on the match list and the mask alone, so the same inputs
+ *              give the same bytes, run to run, alone or as a pair of a list.  Against exact arithmetic the candidate is
+ *              promised within 8 x 2^-24 in Frobenius norm where lambda_9 / (lambda_2 - lambda_1) of N is at most 1e6;
+ *              the bits of a particular order of summation are not part of the ABI.
+ * Added during version 5 without a bump: a matcher that never calls these behaves as before.  `refit`, `refits` and
+ * `ransac_inliers` were added during version 5 without a bump: `refit` 0 behaves as before. */
 enum { HESS_GEOM_HOMOGRAPHY = 1, HESS_GEOM_FUNDAMENTAL = 2 };
 typedef struct hess_geom_params {
   int32_t model;        /* HESS_GEOM_* */
   int32_t hypotheses;   /* T, 1..65536; 0 = 2048 */
   uint32_t seed;
   float bound;          /* HOMOGRAPHY: hdistmax of the guided gate; FUNDAMENTAL: fdistmax */
-  int32_t reserved[4];  /* zero */
+  union {
+    int32_t reserved[4];  /* words 1..3 must be zero */
+    struct {
+      int32_t refit;      /* 0..8 refits on the inliers at the most (step 6; word 0 of reserved[]); 0: steps 1-5 alone */
+      int32_t reserved_tail[3];
+    };
+  };
 } hess_geom_params;
 typedef struct hess_geom_result {
   float M[9];           /* row-major, unit Frobenius norm; all zero when there is no model */
   int32_t inliers;      /* set bytes of the mask */
   int32_t hypothesis;   /* index t of the winner, -1: no model */
-  int32_t reserved[2];
+  union {
+    int32_t reserved[2];
+    struct {
+      int32_t refits;          /* accepted refits (word 0 of reserved[]) */
+      int32_t ransac_inliers;  /* the inliers of step 5, before any refit (word 1); 0 with refit = 0 */
+    };
+  };
 } hess_geom_result;
 
 /* Host only: the k (1..8) indices of hypothesis t (>= 0) among n (>= k) matches into out[k].  0, or HESS_ERR_ARG. */
@@ -568,9 +605,9 @@ int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc,
  * are what hess_matcher_estimate returns for that pair's locations, matches and seed; the rest of inlier[p] is zero.
  * One set of launches per chunk of pairs.
  *   HESS_ERR_STATE  a slot or the bank has no locations; bank locations before the bank's descriptors are loaded
- *   HESS_ERR_ARG    NULL params or out; an unknown model; hypotheses outside 0..65536; non-zero reserved words; bound not
- *                   greater than 0 or not finite; a match index outside its set; a set index outside the bank; counts[p]
- *                   outside 0..max_match; a bad stride or device pointer
+ *   HESS_ERR_ARG    NULL params or out; an unknown model; hypotheses outside 0..65536; refit outside 0..8; non-zero
+ *                   reserved words; bound not greater than 0 or not finite; a match index outside its set; a set index
+ *                   outside the bank; counts[p] outside 0..max_match; a bad stride or device pointer
  * Nothing is launched on an error, the matcher is unchanged and hess_matcher_last_error names the argument.
  * hess_matcher_last_ms: device time of the call's kernels. */
 int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* matches,

@@ -6,7 +6,8 @@ Banks: the two of tools/bench_match_pairs.py (16 sets x 4096 descriptors, all 12
 location per descriptor: every pool row has a point in a reference image, and set k sees it through a mild homography of
 its own, so the matches of a pair fit a homography (and the run finds it).  The budget is fixed, so the time depends on the
 number of matches and T only, not on how good the matches are; the "full lists" rows feed every pair a list of
-max_match identity matches, the most a pair can have.  Forms alternate `--reps` times; medians and ranges of device time
+max_match identity matches, the most a pair can have.  --refit R [R ...] adds a row per form and R with at most R least-squares
+refits on the inliers (hess_geom_params.refit) and reports the refits that were accepted.  Forms alternate `--reps` times; medians and ranges of device time
 (hipEvents around the call's kernels: last_ms) are reported.  Prints a text table; --out also writes it to a file."""
 import argparse
 import os
@@ -37,7 +38,7 @@ def make_bank(nsets, n, seed, size=4096.0):
     return sets, locs
 
 
-def run(name, reps, T, lines):
+def run(name, reps, T, lines, refits=()):
     nsets, n, w = WORKLOADS[name]
     sets, locs = make_bank(nsets, n, seed=nsets)
     pairs = all_pairs(nsets) if w is None else window_pairs(nsets, w)
@@ -46,29 +47,31 @@ def run(name, reps, T, lines):
     m.set_bank_locations(locs)
     matches = m.match_pairs(pairs, max_match=n)
     full = [np.stack([np.arange(n), np.arange(n)], 1).astype(np.int32)] * len(pairs)
-    forms = [("match_pairs", None, None)] + [(f"estimate_pairs {md}, {kind}", md, lst) for lst, kind in
-                                             ((matches, "match_pairs' lists"), (full, "full lists")) for md in ("H", "F")]
+    forms = [("match_pairs", None, None, 0)] + [(f"estimate_pairs {md}, {kind}" + (f", refit {r}" if r else ""), md, lst, r)
+                                                for lst, kind in ((matches, "match_pairs' lists"), (full, "full lists"))
+                                                for md in ("H", "F") for r in (0,) + tuple(refits)]
     times = {f[0]: [] for f in forms}
     found = {}
     for rep in range(reps + 1):                      # the first round warms up
-        for label, md, lst in forms:
+        for label, md, lst, refit in forms:
             if md is None:
                 m.match_pairs(pairs, max_match=n)
             else:
-                out = m.estimate_pairs(pairs, lst, md, BOUND[md], hypotheses=T, seed=1)
-                found[label] = (sum(int(o[1].sum()) for o in out), sum(o[2] >= 0 for o in out))
+                out = m.estimate_pairs(pairs, lst, md, BOUND[md], hypotheses=T, seed=1, refit=refit, info=True)
+                found[label] = (sum(int(o[1].sum()) for o in out), sum(o[2] >= 0 for o in out), sum(o[3]["refits"] for o in out))
             if rep:
                 times[label].append(m.last_ms() / len(pairs))
     m.close()
     mean = float(np.mean([len(x) for x in matches]))
     lines.append(f"{name}: {len(pairs)} pairs, {mean:.0f} matches per pair on average (full lists: {n}), T = {T}, reps = {reps}")
-    for label, md, lst in forms:
+    for label, md, lst, refit in forms:
         t = times[label]
         extra = ""
         if md is not None:
             per = mean if lst is matches else n
             extra = f"   {per * T / (np.median(t) * 1e-3) / 1e9:8.1f} G gate evaluations/s   models {found[label][1]}, inliers {found[label][0]}"
-        lines.append(f"  {label:44s} {np.median(t):9.5f} ms/pair  [{min(t):.5f}, {max(t):.5f}]{extra}")
+            extra += f", accepted refits {found[label][2]}" if refit else ""
+        lines.append(f"  {label:54s} {np.median(t):9.5f} ms/pair  [{min(t):.5f}, {max(t):.5f}]{extra}")
 
 
 def main():
@@ -76,11 +79,12 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["all"], default="all")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--hypotheses", type=int, default=2048)
+    ap.add_argument("--refit", type=int, nargs="*", default=[], help="also time the calls with these values of refit (1..8)")
     ap.add_argument("--out", help="also write the table here")
     args = ap.parse_args()
     lines = ["tools/bench_estimate.py: device time per pair (hipEvents around the call's kernels), median [min, max]"]
     for nm in (sorted(WORKLOADS) if args.workload == "all" else [args.workload]):
-        run(nm, args.reps, args.hypotheses, lines)
+        run(nm, args.reps, args.hypotheses, lines, args.refit)
     text = "\n".join(lines)
     print(text)
     if args.out:
