@@ -9,7 +9,7 @@
 //                        address (a broadcast) -- and store the block's best (score, lowest t, matrix);
 //   geom_finish_kernel   one workgroup per pair: arg-max over the block entries (score, then lowest t), rank 2 for F and
 //                        unit norm in double (one thread), then the inlier mask with the guided gate's own formulas
-//                        (match_dot_kernel, hess_match.hip) and its count;
+//                        (hess_guided_gate.h, the matcher's) and its count;
 //   geom_refit_kernel    only when params.refit > 0, one workgroup per pair after the finish kernel: up to `refit` times the
 //                        least-squares DLT on the inliers (hess_abi.h, step 6) -- moment sums over the mask, the serial
 //                        solve of hess_geom_refit.h on one lane, the candidate's mask into a second buffer, accept or stop;
@@ -26,6 +26,7 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_geom_refit.h"
+#include "hess_guided_gate.h"
 #include "hess_matcher_int.h"
 
 namespace {
@@ -245,24 +246,16 @@ __host__ __device__ inline bool geom_pass(const float (&M)[9], const float4 p, f
   }
 }
 
-// The guided gate itself, as match_dot_kernel (hess_match.hip) evaluates it: the mask's decision.
+// The guided gate itself (hess_guided_gate.h, the matcher's own): the mask's decision.
 template <int MODEL>
 __host__ __device__ inline bool geom_gate(const float (&M)[9], const float2 l1, const float2 l2, float bound) {
+  hess::GuidedRow R;
   if (MODEL == HESS_GEOM_HOMOGRAPHY) {
-    const float x0 = fmaf(M[0], l1.x, M[1] * l1.y) + M[2];
-    const float x1 = fmaf(M[3], l1.x, M[4] * l1.y) + M[5];
-    const float x2 = fmaf(M[6], l1.x, M[7] * l1.y) + M[8];
-    const float d0 = fabsf(x0 / x2 - l2.x), d1 = fabsf(x1 / x2 - l2.y);
-    return d0 < bound && d1 < bound;
+    hess::guided_row_h(M, l1.x, l1.y, R);
+    return hess::guided_box(R, l2.x, l2.y, bound);
   } else {
-    const float fx0 = fmaf(M[0], l1.x, M[1] * l1.y) + M[2];
-    const float fx1 = fmaf(M[3], l1.x, M[4] * l1.y) + M[5];
-    const float fx2 = fmaf(M[6], l1.x, M[7] * l1.y) + M[8];
-    const float ft0 = fmaf(M[0], l2.x, M[3] * l2.y) + M[6];
-    const float ft1 = fmaf(M[1], l2.x, M[4] * l2.y) + M[7];
-    const float x2fx1 = fmaf(l2.x, fx0, l2.y * fx1) + fx2;
-    const float se = (x2fx1 * x2fx1) / fmaf(ft1, ft1, fmaf(ft0, ft0, fmaf(fx0, fx0, fx1 * fx1)));
-    return se < bound;
+    hess::guided_row_f(M, l1.x, l1.y, R);
+    return hess::guided_sampson(R, hess::guided_col(M, l2.x, l2.y), bound);
   }
 }
 
@@ -619,6 +612,12 @@ void hess_geom_drop_bank_locations(hess_geom_state* g) {
   (void)hipFree(g->bank_loc);
   g->bank_loc = nullptr;
   g->have_bank_loc = false;
+}
+
+bool hess_geom_bank_locations(const hess_geom_state* g, const float2** loc) {
+  if (!g || !g->have_bank_loc) return false;
+  *loc = g->bank_loc;
+  return true;
 }
 
 void hess_geom_state_destroy(hess_geom_state* g) {

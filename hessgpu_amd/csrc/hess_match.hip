@@ -16,6 +16,9 @@
 //                          the same launch, the per-row-block (max, index, second) column partials in ascending row order
 //                          (match_col_kernel: the same for the small / guided path);
 //   match_pairs_compact_kernel  each pair's matches compacted on the device (a single pair is compacted on the host).
+// Guided match of a pair list (hess_matcher_match_pairs_guided, no reference counterpart): the same kernels, match_mfma_kernel
+// in its GUIDED form -- the gate of hess_guided_gate.h per pair and the per-8-row-block rule applied to the scores before the
+// folds; see the comment at the kernel.
 // Feature types (hess_matcher_set_types, _bank_set_types; no reference counterpart): a typed set is stored grouped by class
 // and a gated pair is one job of the same tables per class, the two kernels above unchanged --
 //   type_classify_kernel / type_place_kernel / bank_gather_kernel   class and stable position of every row, its place, the move;
@@ -46,6 +49,7 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_dev.h"
+#include "hess_guided_gate.h"
 #include "hess_match_plan.h"
 #include "hess_matcher_int.h"
 
@@ -123,19 +127,11 @@ __global__ __launch_bounds__(256) void match_dot_kernel(const uint8_t* des1, int
         int v = -262144;
         if (i < num1 && j < num2) {
           const float2 l1 = loc1[i], l2 = loc2[j];
-          const float x0 = fmaf(gp.H[0], l1.x, gp.H[1] * l1.y) + gp.H[2];
-          const float x1 = fmaf(gp.H[3], l1.x, gp.H[4] * l1.y) + gp.H[5];
-          const float x2 = fmaf(gp.H[6], l1.x, gp.H[7] * l1.y) + gp.H[8];
-          const float d0 = fabsf(x0 / x2 - l2.x), d1 = fabsf(x1 / x2 - l2.y);
-          if (d0 < gp.hdistmax && d1 < gp.hdistmax) {
-            const float fx0 = fmaf(gp.F[0], l1.x, gp.F[1] * l1.y) + gp.F[2];
-            const float fx1 = fmaf(gp.F[3], l1.x, gp.F[4] * l1.y) + gp.F[5];
-            const float fx2 = fmaf(gp.F[6], l1.x, gp.F[7] * l1.y) + gp.F[8];
-            const float ft0 = fmaf(gp.F[0], l2.x, gp.F[3] * l2.y) + gp.F[6];
-            const float ft1 = fmaf(gp.F[1], l2.x, gp.F[4] * l2.y) + gp.F[7];
-            const float x2fx1 = fmaf(l2.x, fx0, l2.y * fx1) + fx2;
-            const float se = (x2fx1 * x2fx1) / fmaf(ft1, ft1, fmaf(ft0, ft0, fmaf(fx0, fx0, fx1 * fx1)));
-            v = se < gp.fdistmax ? 0 : -262144;
+          hess::GuidedRow R;
+          hess::guided_row_h(gp.H, l1.x, l1.y, R);
+          if (hess::guided_box(R, l2.x, l2.y, gp.hdistmax)) {
+            hess::guided_row_f(gp.F, l1.x, l1.y, R);
+            v = hess::guided_sampson(R, hess::guided_col(gp.F, l2.x, l2.y), gp.fdistmax) ? 0 : -262144;
           }
         }
         base[r][c] = v;
@@ -299,16 +295,41 @@ __device__ __forceinline__ int med3i(int a, int b, int c) {
   return d;
 }
 
+// One pair's geometry on the device (hess_matcher_match_pairs_guided): hess_guided_pair and where the locations of its two
+// sets start in the bank's locations (DescSets::first: the caller's row order, not padded).  A matrix with a non-finite
+// entry arrives as zeros: nothing passes.
+struct GuidedGeo {
+  float H[9], F[9];
+  float hdistmax, fdistmax;
+  int la, lb;
+};
+static_assert(sizeof(hess_guided_pair) == 80, "hess_guided_pair is ABI");
+
 // The work of one workgroup (PairJob, the tables: hess_match_plan.h): work[blockIdx.x] = (job, rb | sg << 16), row block rb of the job's set 1 against its column
 // segment sg of set 2.
-template <bool COLS, int KD>
+//
+// GUIDED (hess_matcher_match_pairs_guided): the score that enters the folds is the one MultiplyDescriptorG_Kernel stores
+// (match_dot_kernel above): the dot product where (row, column) passes the gate of geo[job] (hess_guided_gate.h), the dot
+// product - 2^18 clamped at 0 where it fails but a row of its 8-row block passes with that column (`good_count`), else 0.
+// A lane's 16 accumulator registers are 16 consecutive rows from a multiple of 16 (set starts are 256-row aligned), i.e.
+// two whole 8-row blocks, so `good_count > 0` is a lane-local OR of eight pass bits.  The row terms of the workgroup's 256
+// rows are computed once into LDS (rowh, rowf; a half-wave reads one address), the column terms of a super tile beside cfix
+// (bufG).  Locations are not padded: a row >= n1 or a column >= n2 reads none and holds NaN, which fails the box test --
+// a padded row that passed would switch on the block rule for the real rows of a ragged last block.
+template <bool COLS, int KD, bool GUIDED>
 __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, const int* rfix, const uint8_t* rows2,
                                                          const int* cfix, const PairJob* jobs, const int2* work,
-                                                         int3* cpart, int3* rstate) {
+                                                         int3* cpart, int3* rstate, const GuidedGeo* geo, const float2* loc) {
   constexpr int MM_PITCH = mm_pitch<KD>(), KK = KD / 32;  // MFMAs (32 bytes of every descriptor each) per block and tile
   __shared__ __attribute__((aligned(16))) uint8_t bufB[2][mm_buf_bytes<KD>()];
   __shared__ int bufC[2][MM_SUPER];
   __shared__ int3 cp[2][4][MM_SUPER];  // the four wavefronts' column partials of a super tile, merged after its barrier
+  // GUIDED, per row of the workgroup: (px, py), (fx0, fx1, fx2, rr), and the row's score offset, which the other form keeps
+  // in registers as the MFMA's C operand (32 of them: the gate needs the room)
+  __shared__ float2 rowh[GUIDED ? MM_ROWS : 1];
+  __shared__ float4 rowf[GUIDED ? MM_ROWS : 1];
+  __shared__ __attribute__((aligned(16))) int rowc[GUIDED ? MM_ROWS : 1];
+  __shared__ float bufG[GUIDED ? 2 : 1][GUIDED ? 4 : 1][GUIDED ? MM_SUPER : 1];              // x, y, ft0, ft1 of a super tile's columns
   static_assert(sizeof(bufB) >= MM_RS_BYTES && mm_buf_bytes<KD>() % 16 == 0, "the row-state exchange reuses the descriptor buffers");
   const int2 w = work[blockIdx.x];
   const PairJob& J = jobs[w.x];
@@ -336,11 +357,13 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
       const uint8_t* pa = des1 + (size_t)(i0 + 32 * blk + prow) * KD + 16 * h;  // (set 1 is padded to whole workgroups)
 #pragma unroll
       for (int kk = 0; kk < KK; kk++) a[blk][kk] = *reinterpret_cast<const v4i*>(pa + kk * 32) ^ (int)0x80808080;
-      const v4i* const pr = reinterpret_cast<const v4i*>(rfix + i0 + 32 * blk + 16 * h);  // (16 consecutive rows: 64-byte aligned)
+      if constexpr (!GUIDED) {
+        const v4i* const pr = reinterpret_cast<const v4i*>(rfix + i0 + 32 * blk + 16 * h);  // (16 consecutive rows: 64-byte aligned)
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const v4i t = pr[q];
-        ra[blk][4 * q] = t.x; ra[blk][4 * q + 1] = t.y; ra[blk][4 * q + 2] = t.z; ra[blk][4 * q + 3] = t.w;
+        for (int q = 0; q < 4; q++) {
+          const v4i t = pr[q];
+          ra[blk][4 * q] = t.x; ra[blk][4 * q + 1] = t.y; ra[blk][4 * q + 2] = t.z; ra[blk][4 * q + 3] = t.w;
+        }
       }
     }
   }
@@ -353,11 +376,45 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
   // staging: thread t copies 16-byte pieces t, t + 256, ... (KD / 32 of them) of a super tile (piece = KD / 16 x column + part)
   v4i st[KK];
   int stc = 0;
+  [[maybe_unused]] float hdm = 0.0f, fdm = 0.0f;
+  [[maybe_unused]] hess::GuidedCol stg = {0.0f, 0.0f, 0.0f, 0.0f};
+  [[maybe_unused]] const float2* loc2 = nullptr;
+  [[maybe_unused]] const float* gF = nullptr;
+  if constexpr (GUIDED) {
+    const GuidedGeo& G = geo[w.x];
+    hdm = G.hdistmax;
+    fdm = G.fdistmax;
+    gF = G.F;
+    loc2 = loc + G.lb;
+    // the row terms of this workgroup's 256 rows, one row per thread (visible after the barrier below)
+    const int gi = (int)rb * MM_ROWS + tid;
+    hess::GuidedRow R;
+    R.px = R.py = __builtin_nanf("");
+    R.fx0 = R.fx1 = R.fx2 = R.rr = 0.0f;
+    if (gi < num1) {
+      const float2 l1 = loc[G.la + gi];
+      hess::guided_row_h(G.H, l1.x, l1.y, R);
+      hess::guided_row_f(G.F, l1.x, l1.y, R);
+    }
+    rowh[tid] = make_float2(R.px, R.py);
+    rowf[tid] = make_float4(R.fx0, R.fx1, R.fx2, R.rr);
+    rowc[tid] = rfix[gi];  // (set 1 is padded to whole workgroups)
+  }
   auto stage_load = [&](int sup) {
     const uint8_t* src = des2 + (size_t)sup * MM_SUPER * KD + (size_t)tid * 16;
 #pragma unroll
     for (int q = 0; q < KK; q++) st[q] = *reinterpret_cast<const v4i*>(src + q * 4096);
     if (tid < MM_SUPER) stc = cfix[sup * MM_SUPER + tid];
+    if constexpr (GUIDED) {
+      if (tid < MM_SUPER) {
+        const int j = sup * MM_SUPER + tid;
+        stg = hess::GuidedCol{__builtin_nanf(""), __builtin_nanf(""), 0.0f, 0.0f};
+        if (j < num2) {
+          const float2 l2 = loc2[j];
+          stg = hess::guided_col(gF, l2.x, l2.y);
+        }
+      }
+    }
   };
   auto stage_store = [&](int buf) {
 #pragma unroll
@@ -367,6 +424,11 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
       *reinterpret_cast<v4i*>(&bufB[buf][(piece >> PS) * MM_PITCH + (piece & (KD / 16 - 1)) * 16]) = st[q] ^ (int)0x80808080;
     }
     if (tid < MM_SUPER) bufC[buf][tid] = stc;
+    if constexpr (GUIDED) {
+      if (tid < MM_SUPER) {
+        bufG[buf][0][tid] = stg.x; bufG[buf][1][tid] = stg.y; bufG[buf][2][tid] = stg.ft0; bufG[buf][3][tid] = stg.ft1;
+      }
+    }
   };
   stage_load(s0);
   stage_store(0);
@@ -387,22 +449,77 @@ __global__ __launch_bounds__(256) void match_mfma_kernel(const uint8_t* rows1, c
 #pragma unroll
       for (int kk = 0; kk < KK; kk++) b[kk] = *reinterpret_cast<const v4i*>(pb + kk * 32);
       const int cbk = (bufC[cur][tt * 32 + r] << 6) | ct;
+      [[maybe_unused]] hess::GuidedCol gc = {0.0f, 0.0f, 0.0f, 0.0f};
+      if constexpr (GUIDED)
+        gc = hess::GuidedCol{bufG[cur][0][tt * 32 + r], bufG[cur][1][tt * 32 + r], bufG[cur][2][tt * 32 + r], bufG[cur][3][tt * 32 + r]};
       int cx = 63, cz = 0;  // column partial over this lane's 32 rows
+      auto fold = [&](int blk, int reg, int k) {  // key k of (row reg of block blk, this lane's column) into both states
+        rnx[blk][reg] = med3i(rmx[blk][reg], k, rnx[blk][reg]);
+        rmx[blk][reg] = max(rmx[blk][reg], k);
+        if (COLS) {
+          const int kc = k + ((62 - (reg + 16 * blk)) - ct);            // low bits: 62 - row in the lane's half
+          cz = med3i(cx, kc, cz);
+          cx = max(cx, kc);
+        }
+      };
 #pragma unroll
       for (int blk = 0; blk < 2; blk++) {
-        v16i c = ra[blk];
+        v16i c;
+        if constexpr (GUIDED) {
+          const v4i* const pr = reinterpret_cast<const v4i*>(&rowc[wv * 64 + 32 * blk + 16 * h]);
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const v4i t = pr[q];
+            c[4 * q] = t.x; c[4 * q + 1] = t.y; c[4 * q + 2] = t.z; c[4 * q + 3] = t.w;
+          }
+        } else {
+          c = ra[blk];
+        }
 #pragma unroll
         for (int kk = 0; kk < KK; kk++) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[blk][kk], b[kk], c, 0, 0, 0);
+        if constexpr (GUIDED) {
+          // an 8-row block at a time: the pass bits of its rows with this lane's column, then the block rule on the scores
+          const int cf = bufC[cur][tt * 32 + r];
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-          const int k = (int)(((unsigned)c[reg] << 6) + (unsigned)cbk);  // (score << 6) | ct: score = c + column offset >= 0
-          rnx[blk][reg] = med3i(rmx[blk][reg], k, rnx[blk][reg]);
-          rmx[blk][reg] = max(rmx[blk][reg], k);
-          if (COLS) {
-            const int kc = k + ((62 - (reg + 16 * blk)) - ct);            // low bits: 62 - row in the lane's half
-            cz = med3i(cx, kc, cz);
-            cx = max(cx, kc);
+          for (int half = 0; half < 2; half++) {
+            const int lr = wv * 64 + 32 * blk + 16 * h + 8 * half;  // the block's first row in the workgroup
+            unsigned pass = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+              const float2 t = rowh[lr + q];
+              hess::GuidedRow R;
+              R.px = t.x;
+              R.py = t.y;
+              pass |= hess::guided_box(R, gc.x, gc.y, hdm) ? 1u << q : 0u;
+            }
+            // (wavefront-uniform.)  Where no lane's block passes the box, every score of the 8 x 64 elements is 0: a key below
+            // "none yet" and below every second best that carries a score, so folding it changes no state that is ever
+            // decoded -- the F part and the folds are skipped, which is most blocks under a real H bound
+            if (__builtin_amdgcn_ballot_w64(pass != 0) != 0) {
+              unsigned pf = 0;
+#pragma unroll
+              for (int q = 0; q < 8; q++) {
+                const float4 t = rowf[lr + q];
+                hess::GuidedRow R;
+                R.fx0 = t.x; R.fx1 = t.y; R.fx2 = t.z; R.rr = t.w;
+                pf |= hess::guided_sampson(R, gc, fdm) ? 1u << q : 0u;
+                // (four divisions in flight, not eight: scheduled as one block the 128-d form with column partials needs
+                // 262 registers and falls to one wavefront per SIMD; with this fence 231, without scratch)
+                if (q == 3) __builtin_amdgcn_sched_barrier(0);
+              }
+              pass &= pf;
+#pragma unroll
+              for (int q = 0; q < 8; q++) {
+                const int sc = c[8 * half + q] + cf;  // the dot product
+                const int sg = (pass >> q) & 1u ? sc : (pass != 0 && sc > 262144 ? sc - 262144 : 0);
+                fold(blk, 8 * half + q, (sg << 6) | ct);
+              }
+            }
           }
+        } else {
+#pragma unroll
+          for (int reg = 0; reg < 16; reg++)
+            fold(blk, reg, (int)(((unsigned)c[reg] << 6) + (unsigned)cbk));  // (score << 6) | ct: score = c + column offset >= 0
         }
       }
       if (COLS) {
@@ -766,6 +883,8 @@ struct hess_matcher {
   int* mp_out = nullptr;
   int* mp_hout[2] = {nullptr, nullptr};
   size_t mp_out_cap = 0, mp_hout_cap = 0;
+  GuidedGeo* geo = nullptr;  // match_pairs_guided: the call's geometry table
+  size_t geo_cap = 0;
   hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
 };
 
@@ -1025,6 +1144,22 @@ int bank_args(hess_matcher* m, int nsets, const int* counts, const void* des, si
   return 0;
 }
 
+// What every pair-list entry point refuses: `what` names it in the error text.
+int pair_list_args(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* out_pairs, const int* out_counts,
+                   const char* what) {
+  if (npairs < 0 || max_match < 0 || (npairs > 0 && (!pairs_ab || !out_counts || (max_match > 0 && !out_pairs)))) {
+    m->err = std::string(what) + ": npairs or max_match < 0, or an array is NULL";
+    return HESS_ERR_ARG;
+  }
+  const int nsets = (int)m->bank.num.size();
+  for (int p = 0; p < npairs; p++)
+    if (pairs_ab[2 * p] < 0 || pairs_ab[2 * p] >= nsets || pairs_ab[2 * p + 1] < 0 || pairs_ab[2 * p + 1] >= nsets) {
+      m->err = std::string(what) + ": pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
+      return HESS_ERR_ARG;
+    }
+  return 0;
+}
+
 // Grows the matcher's buffers to what a plan needs; for compacted output (n.outn) also its device buffer, the two pinned
 // slots and their events.
 int grow_for(hess_matcher* m, const PlanNeed& n) {
@@ -1045,8 +1180,10 @@ int grow_for(hess_matcher* m, const PlanNeed& n) {
 
 // Enqueues planned chunk c on m->st: its plan buffer (plan_fill) into the pinned slot hp and up to m->plan, then `start`,
 // the multiply and the finish.  s1, s2: the sets the jobs' a, b index.  The caller has grown every buffer to c's size.
+// dgeo (guided pair lists only, else NULL): the device geometry of job 0 of the chunk onwards, and loc the bank's locations.
 hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Entry* orig,
-                     const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax) {
+                     const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
+                     const GuidedGeo* dgeo = nullptr, const float2* loc = nullptr) {
   const PlanLayout L = plan_layout(c);
   plan_fill(hp, jobs, orig, c, mutual_best);
   const hipError_t e = hipMemcpyAsync(m->plan, hp, L.bytes, hipMemcpyHostToDevice, m->st);
@@ -1055,10 +1192,13 @@ hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, co
   if (c.nwg) {
     if (s1.dim != s2.dim || !dim_ok(s1.dim)) return hipErrorInvalidValue;  // (set_dim empties every set: not reached)
     const PairJob* djobs = plan_ptr<PairJob>(m->plan, L.jobs);
-    auto* const kern = s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128> : match_mfma_kernel<false, 128>)
-                                     : (mutual_best ? match_mfma_kernel<true, 64> : match_mfma_kernel<false, 64>);
+    auto* const kern =
+        dgeo ? (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, true> : match_mfma_kernel<false, 128, true>)
+                              : (mutual_best ? match_mfma_kernel<true, 64, true> : match_mfma_kernel<false, 64, true>))
+             : (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, false> : match_mfma_kernel<false, 128, false>)
+                              : (mutual_best ? match_mfma_kernel<true, 64, false> : match_mfma_kernel<false, 64, false>));
     hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs,
-                       plan_ptr<int2>(m->plan, L.work), m->mm_cpart, m->mm_rstate);
+                       plan_ptr<int2>(m->plan, L.work), m->mm_cpart, m->mm_rstate, dgeo, loc);
     hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(m->plan, L.fin),
                        m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
   }
@@ -1069,14 +1209,34 @@ hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, co
 // out_counts[p] and out_pairs[p][max_match][2] (in the pinned slot the pairs are P.mm apart).  Chunk k is enqueued into slot k & 1; its results
 // are read on the host while chunk k + 1 runs.  m->last_ms: the sum of the chunks' kernel intervals (multiply, finish,
 // compaction).  `what` names the entry point in the text of a device error, after which the stream is synchronised.
+// geo (with loc, the locations both sets' `first` index; untyped sets): the guided match, pair p gated by geo[p] -- the table
+// goes up once, before the first chunk, and chunk k's launch reads it from its first pair on.
 int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npairs, const int* pairs_ab, int max_match,
-              int* out_pairs, int* out_counts, float distmax, float ratiomax, int mutual_best, const char* what) {
+              int* out_pairs, int* out_counts, float distmax, float ratiomax, int mutual_best, const char* what,
+              const hess_guided_pair* geo = nullptr, const float2* loc = nullptr) {
   PairPlan P;
   if (!plan_pairs(s1.layout(), s2.layout(), npairs, pairs_ab, max_match, mutual_best, P)) {
     m->err = std::string(what) + ": a pair needs more scratch than one launch can address";
     return HESS_ERR_TOO_BIG;
   }
   if (const int rc = grow_for(m, P.need)) return rc;
+  if (geo) {
+    std::vector<GuidedGeo> h((size_t)npairs);
+    for (int p = 0; p < npairs; p++) {
+      GuidedGeo& g = h[p];
+      memcpy(g.H, geo[p].H, sizeof(g.H));
+      memcpy(g.F, geo[p].F, sizeof(g.F));
+      bool finite = true;
+      for (int k = 0; k < 9; k++) finite = finite && std::isfinite(g.H[k]) && std::isfinite(g.F[k]);
+      if (!finite) { memset(g.H, 0, sizeof(g.H)); memset(g.F, 0, sizeof(g.F)); }
+      g.hdistmax = geo[p].hdistmax;
+      g.fdistmax = geo[p].fdistmax;
+      g.la = s1.first[pairs_ab[2 * p]];
+      g.lb = s2.first[pairs_ab[2 * p + 1]];
+    }
+    M_TRY(m, grow_device(m->geo, m->geo_cap, (size_t)npairs));
+    M_TRY(m, hipMemcpy(m->geo, h.data(), h.size() * sizeof(GuidedGeo), hipMemcpyHostToDevice));  // (complete on return)
+  }
   const int mm = P.mm;
   // A list of one chunk (the typed single pair) waits for the stream and records no third event: the event after the copy
   // and the wait for it cost 7 us per call, a tenth of that pair's wall time.  Behind the last of several chunks the
@@ -1106,7 +1266,8 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
     const Chunk& c = P.chunks[k];
     const PlanLayout L = plan_layout(c);
     hipEvent_t* ev = m->mp_ev[k & 1];
-    err = run_chunk(m, s1, s2, P.jobs.data(), P.orig.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax);
+    err = run_chunk(m, s1, s2, P.jobs.data(), P.orig.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax,
+                    geo ? m->geo + c.p0 : nullptr, loc);
     if (err != hipSuccess) break;
     if (P.jpp == 4)
       hipLaunchKernelGGL(match_types_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan, L.jobs),
@@ -1195,7 +1356,7 @@ void hess_matcher_destroy(hess_matcher* m) {
   for (int k = 0; k < 2; k++) { sets_clear(m->slot[k]); (void)hipFree(m->loc[k]); }
   (void)hipFree(m->cpart); (void)hipFree(m->dotm);
   (void)hipFree(m->mm_rstate); (void)hipFree(m->mm_cpart); (void)hipFree(m->plan);
-  (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out);
+  (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out); (void)hipFree(m->geo);
   hess_geom_state_destroy(m->geom);
   for (int k = 0; k < 2; k++) {
     (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]);
@@ -1461,22 +1622,36 @@ int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, s
 int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
                              int* out_counts, float distmax, float ratiomax, int mutual_best) {
   if (!m) return HESS_ERR_ARG;
-  if (npairs < 0 || max_match < 0 || (npairs > 0 && (!pairs_ab || !out_counts || (max_match > 0 && !out_pairs)))) {
-    m->err = "match_pairs: npairs or max_match < 0, or an array is NULL";
-    return HESS_ERR_ARG;
-  }
-  const int nsets = (int)m->bank.num.size();
-  for (int p = 0; p < npairs; p++)
-    if (pairs_ab[2 * p] < 0 || pairs_ab[2 * p] >= nsets || pairs_ab[2 * p + 1] < 0 || pairs_ab[2 * p + 1] >= nsets) {
-      m->err = "match_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
-      return HESS_ERR_ARG;
-    }
+  if (const int rc = pair_list_args(m, npairs, pairs_ab, max_match, out_pairs, out_counts, "match_pairs")) return rc;
   m->last_ms = 0.0f;
   if (npairs == 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
   mutual_best = mutual_best ? 1 : 0;
 
   return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best, "match_pairs");
+}
+
+// GetGuidedSiftMatch for every pair of a list, each with its own H, F and bounds: match_mfma_kernel<GUIDED> on the bank and
+// its locations.  Everything is checked before anything is launched or changed.
+int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pairs_ab, const hess_guided_pair* geo, int max_match,
+                                    int* out_pairs, int* out_counts, float distmax, float ratiomax, int mutual_best) {
+  if (!m) return HESS_ERR_ARG;
+  if (const int rc = pair_list_args(m, npairs, pairs_ab, max_match, out_pairs, out_counts, "match_pairs_guided")) return rc;
+  if (npairs > 0 && !geo) { m->err = "match_pairs_guided: geo is NULL"; return HESS_ERR_ARG; }
+  if (m->bank.typed) {
+    m->err = "match_pairs_guided: guided matching with feature types is not built; remove the bank's types (bank_set_types NULL) first";
+    return HESS_ERR_UNSUPPORTED;
+  }
+  const float2* loc = nullptr;
+  if (!hess_geom_bank_locations(m->geom, &loc)) {
+    m->err = "match_pairs_guided: the bank has no locations (hess_matcher_bank_set_locations after loading the bank)";
+    return HESS_ERR_STATE;
+  }
+  m->last_ms = 0.0f;
+  if (npairs == 0) return 0;
+  M_TRY(m, hipSetDevice(m->device));
+  return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best ? 1 : 0,
+                   "match_pairs_guided", geo, loc);
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }

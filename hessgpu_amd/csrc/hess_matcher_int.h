@@ -31,6 +31,9 @@ int hess_matcher_device_range(hess_matcher* m, const void* p, size_t bytes, cons
 // hess_geom.hip, called by the matcher: the bank's descriptors were replaced (its locations go with them); the matcher dies.
 void hess_geom_drop_bank_locations(hess_geom_state* g);
 void hess_geom_state_destroy(hess_geom_state* g);
+// The bank's locations for guided pair lists: false without any (g may be NULL); else *loc = one (x, y) per kept row in the
+// caller's order, set s from DescSets::first[s] on -- NOT padded like the descriptors (NULL for a bank without rows).
+bool hess_geom_bank_locations(const hess_geom_state* g, const float2** loc);
 
 // A device buffer of at least n elements: kept when it is large enough, else replaced (its contents are not carried over).
 template <class T>

@@ -33,6 +33,8 @@ def _lib():
         L.hess_matcher_bank_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hess_matcher_match_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_float, C.c_float, C.c_int]
+        L.hess_matcher_match_pairs_guided.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_float, C.c_float, C.c_int]
         L.hess_matcher_set_types.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.hess_matcher_bank_set_types.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.hess_matcher_bank_set_types_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -84,6 +86,36 @@ GEOM_MODELS = {"H": 1, "F": 2, "homography": 1, "fundamental": 2, 1: 1, 2: 2}
 GEOM_PARAMS_DTYPE = np.dtype([("model", "<i4"), ("hypotheses", "<i4"), ("seed", "<u4"), ("bound", "<f4"), ("reserved", "<i4", 4)])
 GEOM_RESULT_DTYPE = np.dtype([("M", "<f4", 9), ("inliers", "<i4"), ("hypothesis", "<i4"), ("reserved", "<i4", 2)])
 assert GEOM_PARAMS_DTYPE.itemsize == 32 and GEOM_RESULT_DTYPE.itemsize == 52
+# hess_guided_pair: the geometry of one pair of match_pairs_guided
+GUIDED_PAIR_DTYPE = np.dtype([("H", "<f4", 9), ("F", "<f4", 9), ("hdistmax", "<f4"), ("fdistmax", "<f4")])
+assert GUIDED_PAIR_DTYPE.itemsize == 80
+GUIDED_OFF = 1.0e20  # the bound that switches a gate off (SiftMatchGPU::GetGuidedSiftMatch)
+
+
+def guided_pairs(n, H=None, F=None, hdistmax=32.0, fdistmax=16.0):
+    """-> GUIDED_PAIR_DTYPE [n] from H, F ([n, 3, 3] or None) and the bounds (scalars or [n]).  One missing matrix is the
+    identity with its bound at 1e20 (SiftMatchGPU::GetGuidedSiftMatch's rule); both missing, a wrong shape, a non-numeric
+    dtype or a count other than n: ValueError."""
+    if H is None and F is None:
+        raise ValueError("guided matching needs H or F (match_pairs is the unguided call)")
+    geo = np.zeros(int(n), dtype=GUIDED_PAIR_DTYPE)
+    for name, mat, bound in (("H", H, hdistmax), ("F", F, fdistmax)):
+        key = name.lower() + "distmax"
+        if mat is None:
+            geo[name] = np.eye(3, dtype=np.float32).reshape(9)
+            geo[key] = GUIDED_OFF
+            continue
+        a = np.asarray(mat)
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"{name} must be numbers, not {a.dtype}")
+        if a.shape != (n, 3, 3):
+            raise ValueError(f"{name} must have shape [{n}, 3, 3] (one matrix per pair), not {a.shape}")
+        b = np.asarray(bound)
+        if b.dtype.kind not in "fiu" or b.shape not in ((), (n,)):
+            raise ValueError(f"{key} must be a number or {n} numbers, not {b.dtype} {b.shape}")
+        geo[name] = a.astype(np.float32).reshape(n, 9)
+        geo[key] = b.astype(np.float32)
+    return geo
 
 
 def geom_sample(seed, t, k, n):
@@ -346,4 +378,21 @@ class Matcher:
         cnt = np.zeros(max(n, 1), dtype=np.int32)
         self._check(self.L.hess_matcher_match_pairs(self.h, n, p.ctypes.data, max_match, out.ctypes.data, cnt.ctypes.data,
                                                     distmax, ratiomax, int(mutual_best)))
+        return [out[k, :cnt[k]].copy() for k in range(n)]
+
+    def match_pairs_guided(self, pairs, H=None, F=None, hdistmax=32.0, fdistmax=16.0, max_match=4096, distmax=0.7,
+                           ratiomax=0.8, mutual_best=True):
+        """Guided match of bank[a] against bank[b] for every (a, b) in pairs, pair p gated by H[p] and F[p] ([n, 3, 3]; one
+        of them may be None: no such gate) within hdistmax and fdistmax (scalars or [n]) -> list of [k, 2] int32 arrays, each
+        what set_descriptors / set_locations of the two sets and match(max_match, H[p], F[p], ...) return.  The bank needs
+        locations (set_bank_locations*); what estimate_pairs returned goes straight in."""
+        p = check_pairs(pairs)
+        if max_match < 0:
+            raise ValueError("max_match must be >= 0")
+        n = len(p)
+        geo = guided_pairs(n, H, F, hdistmax, fdistmax)
+        out = np.zeros((n, max(max_match, 1), 2), dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.L.hess_matcher_match_pairs_guided(self.h, n, p.ctypes.data, geo.ctypes.data if n else None, max_match,
+                                                           out.ctypes.data, cnt.ctypes.data, distmax, ratiomax, int(mutual_best)))
         return [out[k, :cnt[k]].copy() for k in range(n)]

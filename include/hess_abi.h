@@ -50,7 +50,9 @@ extern "C" {
  *    hess_geom_sample, hess_matcher_estimate / _estimate_pairs, hess_matcher_bank_set_locations(_device) (H or F from
  *    matches on the device; added during version 5 without a bump: a matcher that never calls them behaves as before).
  *    hess_geom_params.refit, hess_geom_result.refits / .ransac_inliers (the least-squares refit on the inliers, words
- *    of the reserved arrays; added during version 5 without a bump: `refit` 0 behaves as before). */
+ *    of the reserved arrays; added during version 5 without a bump: `refit` 0 behaves as before).
+ *    hess_matcher_match_pairs_guided / hess_guided_pair (guided matching for bank pairs; added during version 5 without a
+ *    bump: a matcher that never calls it behaves as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -483,6 +485,23 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out);
  * negative hess_status; hess_matcher_last_ms: device time of all the call's kernels. */
 int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
                              int* out_counts, float distmax, float ratiomax, int mutual_best);
+/* GetGuidedSiftMatch for every pair p of a list, each with its own geometry geo[p] (3x3 row-major H and F and their bounds:
+ * what hess_matcher_estimate_pairs returns goes straight in).  Pair p = (a, b) returns, bit for bit, what
+ * hess_matcher_match(max_match, geo[p].H, geo[p].F, distmax, ratiomax, geo[p].hdistmax, geo[p].fdistmax, mutual_best)
+ * returns with slot 0 = bank[a] and slot 1 = bank[b], each with its locations (hess_matcher_bank_set_locations*) --
+ * the rule of the 8-row blocks, the clamp at 0, the tie order and the truncation to max_match included.  Output as for
+ * hess_matcher_match_pairs.  Pairs may repeat, be reversed or (a, a); the geometry belongs to the position p, not to
+ * (a, b).  A matrix that is all zero gives its pair no match, as in the single-pair call; so does, here, a matrix with a
+ * non-finite entry; neither disturbs another pair.  A caller with one matrix passes the identity with a bound of 1e20 for
+ * the other (SiftMatchGPU::GetGuidedSiftMatch's rule).
+ * Errors launch nothing and leave the matcher as it was: the bank has no locations: HESS_ERR_STATE; the bank has
+ * feature types: HESS_ERR_UNSUPPORTED (guided matching with types is not built); geo NULL with npairs > 0, or a set
+ * index outside the bank: HESS_ERR_ARG.  hess_matcher_last_ms: device time of all the call's kernels.
+ * Added during version 5 without a bump: a matcher that never calls it behaves as before. */
+typedef struct hess_guided_pair { float H[9], F[9]; float hdistmax, fdistmax; } hess_guided_pair;  /* 80 bytes */
+int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pairs_ab, const hess_guided_pair* geo,
+                                    int max_match, int* out_pairs, int* out_counts,
+                                    float distmax, float ratiomax, int mutual_best);
 
 /* Feature types (no reference counterpart in the matcher; the detector's README: "features of different types should
  * not be considered for a correspondence").  Class of a feature = type & 3 (hess_keypoint.type: 0 dark, 1 bright,
