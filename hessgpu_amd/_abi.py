@@ -102,6 +102,16 @@ RAWKEY_DTYPE = _np.dtype([("level_index", "<i4"), ("col", "<i4"), ("row", "<i4")
                           ("pad", "<u4")])
 assert KEYPOINT_DTYPE.itemsize == 24 and RAWKEY_DTYPE.itemsize == 32
 
+# hess_verify_params / hess_verify_result (hess_matcher_verify_pairs).  `geom` is a hess_geom_params (word 0 of its reserved[]
+# is `refit`), `putative` and `final` are hess_geom_results (words 0 and 1 of their reserved[]: `refits`, `ransac_inliers`).
+_GEOM_PARAMS = [("model", "<i4"), ("hypotheses", "<i4"), ("seed", "<u4"), ("bound", "<f4"), ("reserved", "<i4", 4)]
+_GEOM_RESULT = [("M", "<f4", 9), ("inliers", "<i4"), ("hypothesis", "<i4"), ("reserved", "<i4", 2)]
+VERIFY_PARAMS_DTYPE = _np.dtype([("geom", _GEOM_PARAMS), ("distmax", "<f4"), ("ratiomax", "<f4"), ("mutual_best", "<i4"),
+                                 ("guided_bound", "<f4"), ("final_estimate", "<i4"), ("reserved", "<i4", 3)])
+VERIFY_RESULT_DTYPE = _np.dtype([("putative", _GEOM_RESULT), ("final", _GEOM_RESULT), ("nputative", "<i4"), ("nguided", "<i4"),
+                                 ("reserved", "<i4", 4)])
+assert VERIFY_PARAMS_DTYPE.itemsize == 64 and VERIFY_RESULT_DTYPE.itemsize == 128
+
 _ctx = C.c_void_p
 _P = C.POINTER
 
@@ -162,6 +172,9 @@ PRODUCT_PROTOTYPES = {
     "matcher_set_types": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "matcher_bank_set_types": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "matcher_bank_set_types_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    # match, estimate, guided match and estimate of bank pairs in one call (added during version 5 without a bump)
+    "matcher_verify_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 

@@ -13,6 +13,8 @@
 //   geom_refit_kernel    only when params.refit > 0, one workgroup per pair after the finish kernel: up to `refit` times the
 //                        least-squares DLT on the inliers (hess_abi.h, step 6) -- moment sums over the mask, the serial
 //                        solve of hess_geom_refit.h on one lane, the candidate's mask into a second buffer, accept or stop;
+//   geom_jobs_fill_kernel   the job and work tables of a chunk from match counts that only the device knows
+//                        (hess_geom_enqueue for hess_matcher_verify_pairs: no host copy of the matches, no sync);
 //   geom_loc_gather_kernel  bank locations from strided records into the caller's row order of the kept rows.
 #include <hip/hip_runtime.h>
 
@@ -289,7 +291,7 @@ __device__ __forceinline__ unsigned long long geom_block_max(unsigned long long 
   return a > b ? a : b;
 }
 
-// work[blockIdx.x] = (job, block of hypotheses); only jobs with n >= k have work.
+// work[blockIdx.x] = (job, block of hypotheses); a table built on the host lists only jobs with n >= k.
 template <int MODEL>
 __global__ __launch_bounds__(256) void geom_score_kernel(const GeomJob* jobs, const int2* work, const int2* matches, int T,
                                                          float bound, GeomBest* best) {
@@ -298,6 +300,9 @@ __global__ __launch_bounds__(256) void geom_score_kernel(const GeomJob* jobs, co
   __shared__ unsigned long long wmax[4];
   const int2 w = work[blockIdx.x];
   const GeomJob J = jobs[w.x];
+  // (workgroup-uniform, before any barrier.)  Only a table filled on the device (geom_jobs_fill_kernel) lists such a job:
+  // geom_sample is undefined for n < k, and the finish kernel reads none of its block entries (nblk = 0)
+  if (J.n < K) return;
   const int2* const mt = matches + J.moff;
   const int tid = threadIdx.x, t = w.y * 256 + tid;
   float M[9];
@@ -575,6 +580,31 @@ __global__ __launch_bounds__(256) void geom_refit_kernel(const GeomJob* jobs, co
   }
 }
 
+// The job and work tables of a chunk whose match counts are known on the device alone (hess_matcher_verify_pairs): pair q
+// has its matches and mask bytes at q * mm, counts[q] of them, seed0 + q as its seed, its sets' locations from loc +
+// lalb[q].x and .y on, and nblk block entries from q * nblk on; the work table lists every (pair, block), and a pair with
+// fewer than K matches gets nblk = 0, which geom_score_kernel's early return and geom_finish_kernel's no-model branch honour.
+__global__ __launch_bounds__(256) void geom_jobs_fill_kernel(const int2* lalb, const int* counts, const float2* loc, int np,
+                                                             int mm, int nblk, int K, uint32_t seed0, GeomJob* jobs,
+                                                             int2* work) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < np) {
+    const int2 l = lalb[i];
+    const int n = counts[i];
+    GeomJob J;
+    J.l1 = loc + l.x;
+    J.l2 = loc + l.y;
+    J.moff = i * mm;
+    J.n = n;
+    J.seed = seed0 + (uint32_t)i;
+    J.boff = i * nblk;
+    J.nblk = n >= K ? nblk : 0;
+    J.pad = 0;
+    jobs[i] = J;
+  }
+  if (i < np * nblk) work[i] = make_int2(i / nblk, i % nblk);
+}
+
 // out[first kept row of set + i] = the (x, y) at record (first record of the set + i) of src, records `stride` bytes apart.
 // sets[s] = (first kept row, first record, rows kept) in ascending kept rows.
 __global__ __launch_bounds__(256) void geom_loc_gather_kernel(const unsigned char* src, size_t stride, const int3* sets,
@@ -697,18 +727,28 @@ int geom_matches_check(hess_matcher_view& v, const std::vector<GeomPair>& pairs,
   return 0;
 }
 
+// The launches of one chunk: jobs and work table as laid out in a plan buffer (np jobs, then nwork entries), the matches and
+// the result and mask buffers the jobs' offsets index.
+struct GeomBuffers {
+  const unsigned char* plan;
+  const int2* matches;
+  GeomBest* best;
+  hess_geom_result* results;
+  unsigned char *mask, *cand;
+};
+
 template <int MODEL>
-hipError_t geom_launch(hipStream_t st, hess_geom_state* g, int np, size_t nwork, int T, float bound, int refit) {
-  const GeomJob* djobs = reinterpret_cast<const GeomJob*>(g->plan);
-  const int2* dwork = reinterpret_cast<const int2*>(g->plan + (size_t)np * sizeof(GeomJob));
+hipError_t geom_launch(hipStream_t st, const GeomBuffers& b, int np, size_t nwork, int T, float bound, int refit) {
+  const GeomJob* djobs = reinterpret_cast<const GeomJob*>(b.plan);
+  const int2* dwork = reinterpret_cast<const int2*>(b.plan + (size_t)np * sizeof(GeomJob));
   if (nwork)
-    hipLaunchKernelGGL(geom_score_kernel<MODEL>, dim3((unsigned)nwork), dim3(256), 0, st, djobs, dwork, g->matches, T, bound,
-                       g->best);
-  hipLaunchKernelGGL(geom_finish_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, g->matches, g->best, bound,
-                     g->results, g->mask);
+    hipLaunchKernelGGL(geom_score_kernel<MODEL>, dim3((unsigned)nwork), dim3(256), 0, st, djobs, dwork, b.matches, T, bound,
+                       b.best);
+  hipLaunchKernelGGL(geom_finish_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, b.matches, b.best, bound,
+                     b.results, b.mask);
   if (refit > 0)
-    hipLaunchKernelGGL(geom_refit_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, g->matches, bound, refit, g->results,
-                       g->mask, g->cand);
+    hipLaunchKernelGGL(geom_refit_kernel<MODEL>, dim3((unsigned)np), dim3(256), 0, st, djobs, b.matches, bound, refit, b.results,
+                       b.mask, b.cand);
   return hipGetLastError();
 }
 
@@ -760,8 +800,9 @@ int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hes
     G_TRY(v, hipMemcpyAsync(g->plan, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
     if (nm) G_TRY(v, hipMemcpyAsync(g->matches, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
     (void)hipEventRecord(v.e0, v.st);
-    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, g, np, nwork, T, P.bound, P.refit)
-                                             : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, g, np, nwork, T, P.bound, P.refit));
+    const GeomBuffers B{g->plan, g->matches, g->best, g->results, g->mask, g->cand};
+    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, B, np, nwork, T, P.bound, P.refit)
+                                             : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, B, np, nwork, T, P.bound, P.refit));
     (void)hipEventRecord(v.e1, v.st);
     hres.resize((size_t)np);
     hmask.resize(std::max<size_t>(nm, 1));
@@ -833,6 +874,39 @@ int geom_bank_locations_args(hess_matcher_view& v, size_t stride, const char* wh
 }
 
 }  // namespace
+
+// ---- hess_matcher_int.h: estimates over matches that are on the device already (hess_matcher_verify_pairs) ------------
+
+int hess_geom_params_check(hess_matcher* m, const hess_geom_params* P, const char* what) {
+  hess_matcher_view v = hess_matcher_view_of(m);
+  return geom_params_check(v, P, what);
+}
+
+int hess_geom_reserve(hess_matcher* m, const hess_geom_params& P, int np, int mm) {
+  hess_matcher_view v = hess_matcher_view_of(m);
+  hess_geom_state* const g = geom_state(v);
+  if (!g) { *v.err = "verify_pairs: out of memory"; return HESS_ERR_NOMEM; }
+  const size_t nblk = (size_t)((P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T) + 255) / 256, nwork = (size_t)np * nblk;
+  G_TRY(v, grow_device(g->plan, g->plan_cap, (size_t)np * sizeof(GeomJob) + nwork * sizeof(int2)));
+  G_TRY(v, grow_device(g->best, g->best_cap, nwork));
+  if (P.refit > 0) G_TRY(v, grow_device(g->cand, g->cand_cap, std::max<size_t>((size_t)np * mm, 1)));
+  return 0;
+}
+
+hipError_t hess_geom_enqueue(hess_matcher* m, const hess_geom_params& P, const hess_geom_device_pairs& d) {
+  const hess_matcher_view v = hess_matcher_view_of(m);
+  hess_geom_state* const g = *v.geom;
+  const hipStream_t st = v.st;
+  const int K = geom_k(P.model), T = P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T, nblk = (T + 255) / 256;
+  const size_t nwork = (size_t)d.np * nblk;
+  GeomJob* const djobs = reinterpret_cast<GeomJob*>(g->plan);
+  int2* const dwork = reinterpret_cast<int2*>(g->plan + (size_t)d.np * sizeof(GeomJob));
+  hipLaunchKernelGGL(geom_jobs_fill_kernel, dim3((unsigned)((nwork + 255) / 256)), dim3(256), 0, st, d.lalb, d.counts,
+                     g->bank_loc, d.np, d.mm, nblk, K, d.seed0, djobs, dwork);
+  const GeomBuffers B{g->plan, d.matches, g->best, d.results, d.mask, g->cand};
+  return P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(st, B, d.np, nwork, T, P.bound, P.refit)
+                                         : geom_launch<HESS_GEOM_FUNDAMENTAL>(st, B, d.np, nwork, T, P.bound, P.refit);
+}
 
 extern "C" {
 

@@ -19,6 +19,9 @@
 // Guided match of a pair list (hess_matcher_match_pairs_guided, no reference counterpart): the same kernels, match_mfma_kernel
 // in its GUIDED form -- the gate of hess_guided_gate.h per pair and the per-8-row-block rule applied to the scores before the
 // folds; see the comment at the kernel.
+// Verified matches of a pair list (hess_matcher_verify_pairs, no reference counterpart): both forms above and the estimator
+// of hess_geom.hip chained per group of chunks in stream order, the matches never leaving the device in between --
+//   verify_geo_kernel      a group's guided geometry from its estimates; see run_verify.
 // Feature types (hess_matcher_set_types, _bank_set_types; no reference counterpart): a typed set is stored grouped by class
 // and a gated pair is one job of the same tables per class, the two kernels above unchanged --
 //   type_classify_kernel / type_place_kernel / bank_gather_kernel   class and stable position of every row, its place, the move;
@@ -836,6 +839,35 @@ __global__ __launch_bounds__(256) void match_pairs_compact_kernel(const PairJob*
   if (tid == 0) counts[blockIdx.x] = min(n, max_match);
 }
 
+// hess_matcher_verify_pairs: the guided geometry of a chunk's np pairs from the estimates res[q], by the rules the host path
+// (run_pairs) applies to a caller's hess_guided_pair -- the estimated matrix with `bound`, the identity with 1e20 for the
+// other gate (the one-matrix rule), zeros for a matrix with a non-finite entry -- and the first location rows lalb[q] of the
+// pair's sets.  A pair without a model has M all zero: nothing passes.
+__global__ __launch_bounds__(64) void verify_geo_kernel(const hess_geom_result* res, const int2* lalb, int np, int model_h,
+                                                        float bound, GuidedGeo* geo) {
+  const int q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= np) return;
+  GuidedGeo g;
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const float v = res[q].M[k], id = (k == 0 || k == 4 || k == 8) ? 1.0f : 0.0f;
+    finite = finite && fabsf(v) <= 3.402823466e38f;  // (false for NaN and infinity)
+    g.H[k] = model_h ? v : id;
+    g.F[k] = model_h ? id : v;
+  }
+  if (!finite) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) g.H[k] = g.F[k] = 0.0f;
+  }
+  g.hdistmax = model_h ? bound : 1e20f;
+  g.fdistmax = model_h ? 1e20f : bound;
+  const int2 l = lalb[q];
+  g.la = l.x;
+  g.lb = l.y;
+  geo[q] = g;
+}
+
 // Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.
 struct DescSets {
   int dim = 128;  // bytes per row (the matcher's dim when the sets were built)
@@ -886,6 +918,14 @@ struct hess_matcher {
   GuidedGeo* geo = nullptr;  // match_pairs_guided: the call's geometry table
   size_t geo_cap = 0;
   hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
+  // verify_pairs: the results of a group of chunks on the device (VerifyLayout) and through two pinned host slots; the
+  // plan buffers of the group's chunks, device and pinned; per pair of the call the first location rows of its two sets
+  uint8_t* vp_out = nullptr;
+  uint8_t* vp_hout[2] = {nullptr, nullptr};
+  uint8_t* vp_plan = nullptr;
+  uint8_t* vp_hplan[2] = {nullptr, nullptr};
+  int2* vp_lalb = nullptr;
+  size_t vp_out_cap = 0, vp_hout_cap = 0, vp_plan_cap = 0, vp_hplan_cap = 0, vp_lalb_cap = 0;
 };
 
 #define M_TRY(m, expr)                                                                       \
@@ -1160,6 +1200,14 @@ int pair_list_args(hess_matcher* m, int npairs, const int* pairs_ab, int max_mat
   return 0;
 }
 
+// The events of the two pinned slots of a chunked pair list.
+int slot_events(hess_matcher* m) {
+  for (int k = 0; k < 2; k++)
+    for (int q = 0; q < 3; q++)
+      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
+  return 0;
+}
+
 // Grows the matcher's buffers to what a plan needs; for compacted output (n.outn) also its device buffer, the two pinned
 // slots and their events.
 int grow_for(hess_matcher* m, const PlanNeed& n) {
@@ -1172,37 +1220,41 @@ int grow_for(hess_matcher* m, const PlanNeed& n) {
   if (!n.outn) return 0;
   M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, n.outn));
   M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, n.outn));
-  for (int k = 0; k < 2; k++)
-    for (int q = 0; q < 3; q++)
-      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
-  return 0;
+  return slot_events(m);
 }
 
-// Enqueues planned chunk c on m->st: its plan buffer (plan_fill) into the pinned slot hp and up to m->plan, then `start`,
-// the multiply and the finish.  s1, s2: the sets the jobs' a, b index.  The caller has grown every buffer to c's size.
-// dgeo (guided pair lists only, else NULL): the device geometry of job 0 of the chunk onwards, and loc the bank's locations.
-hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Entry* orig,
-                     const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
-                     const GuidedGeo* dgeo = nullptr, const float2* loc = nullptr) {
+// The multiply and the finish of chunk c, whose plan buffer is at dplan on the device (run_chunk: m->plan;
+// hess_matcher_verify_pairs launches both forms from one upload).  dgeo (guided pair lists only, else NULL): the device
+// geometry of job 0 of the chunk onwards, and loc the bank's locations.
+hipError_t launch_chunk(hess_matcher* m, const uint8_t* dplan, const DescSets& s1, const DescSets& s2, const Chunk& c,
+                        int mutual_best, float distmax, float ratiomax, const GuidedGeo* dgeo, const float2* loc) {
   const PlanLayout L = plan_layout(c);
-  plan_fill(hp, jobs, orig, c, mutual_best);
-  const hipError_t e = hipMemcpyAsync(m->plan, hp, L.bytes, hipMemcpyHostToDevice, m->st);
-  if (e != hipSuccess) return e;
-  (void)hipEventRecord(start, m->st);
   if (c.nwg) {
     if (s1.dim != s2.dim || !dim_ok(s1.dim)) return hipErrorInvalidValue;  // (set_dim empties every set: not reached)
-    const PairJob* djobs = plan_ptr<PairJob>(m->plan, L.jobs);
+    const PairJob* djobs = plan_ptr<PairJob>(dplan, L.jobs);
     auto* const kern =
         dgeo ? (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, true> : match_mfma_kernel<false, 128, true>)
                               : (mutual_best ? match_mfma_kernel<true, 64, true> : match_mfma_kernel<false, 64, true>))
              : (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, false> : match_mfma_kernel<false, 128, false>)
                               : (mutual_best ? match_mfma_kernel<true, 64, false> : match_mfma_kernel<false, 64, false>));
     hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs,
-                       plan_ptr<int2>(m->plan, L.work), m->mm_cpart, m->mm_rstate, dgeo, loc);
-    hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(m->plan, L.fin),
+                       plan_ptr<int2>(dplan, L.work), m->mm_cpart, m->mm_rstate, dgeo, loc);
+    hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(dplan, L.fin),
                        m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
   }
   return hipGetLastError();
+}
+
+// Enqueues planned chunk c on m->st: its plan buffer (plan_fill) into the pinned slot hp and up to m->plan, then `start`,
+// the multiply and the finish.  s1, s2: the sets the jobs' a, b index.  The caller has grown every buffer to c's size.
+hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, const PairJob* jobs, const Entry* orig,
+                     const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
+                     const GuidedGeo* dgeo = nullptr, const float2* loc = nullptr) {
+  plan_fill(hp, jobs, orig, c, mutual_best);
+  const hipError_t e = hipMemcpyAsync(m->plan, hp, plan_layout(c).bytes, hipMemcpyHostToDevice, m->st);
+  if (e != hipSuccess) return e;
+  (void)hipEventRecord(start, m->st);
+  return launch_chunk(m, m->plan, s1, s2, c, mutual_best, distmax, ratiomax, dgeo, loc);
 }
 
 // Plans the pair list pairs_ab of sets s1 x s2 (plan_pairs), runs it and delivers every pair's matches compacted on the device:
@@ -1295,6 +1347,178 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
   return 0;
 }
 
+// hess_matcher_verify_pairs works on GROUPS of up to VP_GROUP consecutive chunks of the pair plan: the matcher's kernels run
+// chunk by chunk (MP_PAIRS pairs: the plan's unit), the estimator's once per group.  Its refit kernel is one workgroup per
+// pair with a serial solve, 0.27 ms a launch whether it has 64 pairs or 256, and its score kernel fills the device only from
+// a few hundred pairs on (profiles/r22_verify_pairs.txt): a group is what one chunk of hess_matcher_estimate_pairs holds.
+constexpr int VP_GROUP = 4, VP_PAIRS = VP_GROUP * MP_PAIRS;
+
+// Where a group's results sit in m->vp_out and in its pinned slot.  A head of fixed size (the counts of both matches and the
+// results of both estimates, VP_PAIRS entries each), the guided matches, then the mask of the final estimate and the
+// putative matches where the caller takes them: [0, copy) is what one copy brings down.  The sections the caller does not
+// take, and the putative estimate's mask, lie behind it.  Matches and masks are mm per pair.
+struct VerifyLayout { size_t cnt1, cnt2, res1, res2, guided, mask2, put, mask1, copy, bytes; };
+VerifyLayout verify_layout(int np, int mm, bool want_mask, bool want_put) {
+  const size_t prs = (size_t)np * mm * 2 * sizeof(int), mk = ((size_t)np * mm + 15) / 16 * 16;
+  VerifyLayout L;
+  L.cnt1 = 0;
+  L.cnt2 = VP_PAIRS * sizeof(int);
+  L.res1 = 2 * VP_PAIRS * sizeof(int);
+  L.res2 = L.res1 + VP_PAIRS * sizeof(hess_geom_result);
+  size_t o = L.res2 + VP_PAIRS * sizeof(hess_geom_result);
+  static_assert((2 * VP_PAIRS * sizeof(int) + 2 * VP_PAIRS * sizeof(hess_geom_result)) % 16 == 0, "the matches are read as int2");
+  L.guided = o; o += prs;
+  if (want_mask) { L.mask2 = o; o += mk; }
+  if (want_put) { L.put = o; o += prs; }
+  L.copy = o;
+  if (!want_mask) { L.mask2 = o; o += mk; }
+  if (!want_put) { L.put = o; o += prs; }
+  L.mask1 = o;
+  L.bytes = o + mk;
+  return L;
+}
+
+// The chain of hess_abi.h at hess_matcher_verify_pairs, per group of chunks of the pair plan in stream order: the plan
+// buffers of the group's chunks up; per chunk the unguided multiply, finish and compaction; the estimate on the group's
+// matches (hess_geom_enqueue: counts and matches stay on the device); the group's guided geometry (verify_geo_kernel); per
+// chunk the guided multiply, finish and compaction from the SAME plan buffer and scratch (the first compaction has consumed
+// the decisions); optionally the estimate again; one copy into the pinned slot g & 1, read while group g + 1 runs
+// (run_pairs' double buffer).  Arguments are checked and nothing has been launched.
+int run_verify(hess_matcher* m, int npairs, const int* pairs_ab, const hess_verify_params& V, int max_match, int* out_pairs,
+               int* out_counts, hess_verify_result* out, unsigned char* inlier, int* putative_pairs, const float2* loc) {
+  const char* const what = "verify_pairs";
+  const DescSets& S = m->bank;
+  const int mutual_best = V.mutual_best ? 1 : 0;
+  const bool fin = V.final_estimate != 0, want_mask = fin && inlier, want_put = putative_pairs != nullptr;
+  PairPlan P;
+  if (!plan_pairs(S.layout(), S.layout(), npairs, pairs_ab, max_match, mutual_best, P)) {
+    m->err = std::string(what) + ": a pair needs more scratch than one launch can address";
+    return HESS_ERR_TOO_BIG;
+  }
+  const int mm = P.mm;
+  // group g: chunks [VP_GROUP g, VP_GROUP g + VP_GROUP) of the plan, pairs [first pair of its first chunk, last of its last)
+  const size_t nchunks = P.chunks.size(), ngroups = (nchunks + VP_GROUP - 1) / VP_GROUP;
+  auto group_first = [&](size_t g) { return P.chunks[g * VP_GROUP].p0; };
+  auto group_end = [&](size_t g) { return P.chunks[std::min(nchunks, (g + 1) * VP_GROUP) - 1].p1; };
+  int npmax = 0;
+  for (size_t g = 0; g < ngroups; g++) npmax = std::max(npmax, group_end(g) - group_first(g));
+  if ((size_t)npmax * mm > (size_t)INT_MAX) {  // (the estimator's jobs index a group's matches with an int)
+    m->err = std::string(what) + ": " + std::to_string(npmax) + " pairs of up to " + std::to_string(mm) + " matches are more than one launch can address";
+    return HESS_ERR_TOO_BIG;
+  }
+  const size_t pstride = (P.need.plan_bytes + 63) / 64 * 64;  // a chunk's plan buffer within the group's
+  PlanNeed need = P.need;
+  need.outn = need.plan_bytes = 0;  // (match_pairs' compacted output and its one plan buffer are not used)
+  if (const int rc = grow_for(m, need)) return rc;
+  if (const int rc = slot_events(m)) return rc;
+  const size_t bytes = verify_layout(npmax, mm, want_mask, want_put).bytes;
+  M_TRY(m, grow_device(m->vp_out, m->vp_out_cap, bytes));
+  M_TRY(m, grow_pinned(m->vp_hout, m->vp_hout_cap, bytes));
+  M_TRY(m, grow_device(m->vp_plan, m->vp_plan_cap, VP_GROUP * pstride));
+  M_TRY(m, grow_pinned(m->vp_hplan, m->vp_hplan_cap, VP_GROUP * pstride));
+  M_TRY(m, grow_device(m->geo, m->geo_cap, (size_t)VP_PAIRS));
+  M_TRY(m, grow_device(m->vp_lalb, m->vp_lalb_cap, (size_t)npairs));
+  if (const int rc = hess_geom_reserve(m, V.geom, npmax, mm)) return rc;
+  std::vector<int2> lalb((size_t)npairs);  // (alive until the stream has been waited for: every return below)
+  for (int p = 0; p < npairs; p++) lalb[p] = make_int2(S.first[pairs_ab[2 * p]], S.first[pairs_ab[2 * p + 1]]);
+  M_TRY(m, hipMemcpyAsync(m->vp_lalb, lalb.data(), lalb.size() * sizeof(int2), hipMemcpyHostToDevice, m->st));
+  if (inlier) memset(inlier, 0, (size_t)npairs * max_match);
+  const float gbound = V.guided_bound != 0.0f ? V.guided_bound : V.geom.bound;
+  hess_geom_result none;
+  memset(&none, 0, sizeof(none));
+  none.hypothesis = -1;
+  const bool one_group = ngroups == 1;  // (see run_pairs' one_chunk)
+  float total_ms = 0.0f;
+  auto collect = [&](size_t g) -> hipError_t {
+    const int p0 = group_first(g), np = group_end(g) - p0;
+    hipEvent_t* ev = m->mp_ev[g & 1];
+    hipError_t e = one_group ? hipStreamSynchronize(m->st) : hipEventSynchronize(ev[2]);
+    if (e != hipSuccess) return e;
+    float ms = 0.0f;
+    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e != hipSuccess) return e;
+    total_ms += ms;
+    const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
+    const uint8_t* h = m->vp_hout[g & 1];
+    const int* n1 = reinterpret_cast<const int*>(h + L.cnt1);
+    const int* n2 = reinterpret_cast<const int*>(h + L.cnt2);
+    for (int q = 0; q < np; q++) {
+      const size_t p = (size_t)p0 + q;
+      hess_verify_result& R = out[p];
+      memset(&R, 0, sizeof(R));
+      memcpy(&R.putative, h + L.res1 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
+      if (fin) memcpy(&R.final, h + L.res2 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
+      else R.final = none;
+      R.nputative = n1[q];
+      R.nguided = out_counts[p] = n2[q];
+      if (n2[q]) memcpy(out_pairs + p * max_match * 2, h + L.guided + (size_t)q * mm * 2 * sizeof(int), (size_t)n2[q] * 2 * sizeof(int));
+      if (want_mask && n2[q]) memcpy(inlier + p * max_match, h + L.mask2 + (size_t)q * mm, (size_t)n2[q]);
+      if (want_put && n1[q])
+        memcpy(putative_pairs + p * max_match * 2, h + L.put + (size_t)q * mm * 2 * sizeof(int), (size_t)n1[q] * 2 * sizeof(int));
+    }
+    return hipSuccess;
+  };
+  hipError_t err = hipSuccess;
+  // The two matches of the group's chunk k from its plan buffer: multiply and finish (guided with dgeo), then the compaction
+  // to the chunk's place (its first pair's offset in the group) in the count words at `cnt` and the lists at `lists`.
+  auto match_chunk = [&](size_t k, int p0, size_t cnt, size_t lists, const GuidedGeo* dgeo) -> hipError_t {
+    const Chunk& c = P.chunks[k];
+    const uint8_t* const dplan = m->vp_plan + (k % VP_GROUP) * pstride;
+    const int q0 = c.p0 - p0;
+    const hipError_t e = launch_chunk(m, dplan, S, S, c, mutual_best, V.distmax, V.ratiomax, dgeo ? dgeo + q0 : nullptr, loc);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(dplan, plan_layout(c).jobs),
+                       m->rowm, m->colm, mutual_best, mm, reinterpret_cast<int*>(m->vp_out + cnt) + q0,
+                       reinterpret_cast<int*>(m->vp_out + lists) + (size_t)q0 * mm * 2);
+    return hipGetLastError();
+  };
+  for (size_t g = 0; g < ngroups && err == hipSuccess; g++) {
+    const size_t k0 = g * VP_GROUP, k1 = std::min(nchunks, k0 + VP_GROUP);
+    const int p0 = group_first(g), np = group_end(g) - p0;
+    const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
+    hipEvent_t* ev = m->mp_ev[g & 1];
+    uint8_t* const d = m->vp_out;
+    uint8_t* const hp = m->vp_hplan[g & 1];
+    hess_geom_device_pairs E{np, mm, m->vp_lalb + p0, reinterpret_cast<const int*>(d + L.cnt1), reinterpret_cast<const int2*>(d + L.put),
+                             V.geom.seed + (uint32_t)p0, reinterpret_cast<hess_geom_result*>(d + L.res1), d + L.mask1};
+    for (size_t k = k0; k < k1; k++) plan_fill(hp + (k - k0) * pstride, P.jobs.data(), nullptr, P.chunks[k], mutual_best);
+    err = hipMemcpyAsync(m->vp_plan, hp, (k1 - k0 - 1) * pstride + plan_layout(P.chunks[k1 - 1]).bytes, hipMemcpyHostToDevice, m->st);
+    if (err != hipSuccess) break;
+    (void)hipEventRecord(ev[0], m->st);
+    for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt1, L.put, nullptr);
+    if (err != hipSuccess) break;
+    err = hess_geom_enqueue(m, V.geom, E);
+    if (err != hipSuccess) break;
+    hipLaunchKernelGGL(verify_geo_kernel, dim3((np + 63) / 64), dim3(64), 0, m->st, E.results, E.lalb, np,
+                       V.geom.model == HESS_GEOM_HOMOGRAPHY ? 1 : 0, gbound, m->geo);
+    for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt2, L.guided, m->geo);
+    if (err != hipSuccess) break;
+    if (fin) {
+      E.counts = reinterpret_cast<const int*>(d + L.cnt2);
+      E.matches = reinterpret_cast<const int2*>(d + L.guided);
+      E.results = reinterpret_cast<hess_geom_result*>(d + L.res2);
+      E.mask = d + L.mask2;
+      err = hess_geom_enqueue(m, V.geom, E);
+      if (err != hipSuccess) break;
+    }
+    (void)hipEventRecord(ev[1], m->st);
+    err = hipGetLastError();
+    if (err != hipSuccess) break;
+    err = hipMemcpyAsync(m->vp_hout[g & 1], d, L.copy, hipMemcpyDeviceToHost, m->st);
+    if (err != hipSuccess) break;
+    if (!one_group) (void)hipEventRecord(ev[2], m->st);
+    if (g > 0) err = collect(g - 1);
+  }
+  if (err == hipSuccess) err = collect(ngroups - 1);
+  if (err != hipSuccess) {
+    (void)hipStreamSynchronize(m->st);
+    m->err = std::string(what) + ": " + hipGetErrorString(err);
+    return HESS_ERR_DEVICE;
+  }
+  m->last_ms = total_ms;
+  return 0;
+}
+
 // The small unguided and the guided single pair, from m->e0 on: the score matrix (match_dot_kernel, gates per pair), the row
 // decisions and, for mutual best, the column decisions.
 int match_small(hess_matcher* m, int n1, int n2, const float* H, const float* F, float distmax, float ratiomax,
@@ -1357,9 +1581,10 @@ void hess_matcher_destroy(hess_matcher* m) {
   (void)hipFree(m->cpart); (void)hipFree(m->dotm);
   (void)hipFree(m->mm_rstate); (void)hipFree(m->mm_cpart); (void)hipFree(m->plan);
   (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out); (void)hipFree(m->geo);
+  (void)hipFree(m->vp_out); (void)hipFree(m->vp_plan); (void)hipFree(m->vp_lalb);
   hess_geom_state_destroy(m->geom);
   for (int k = 0; k < 2; k++) {
-    (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]);
+    (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]); (void)hipHostFree(m->vp_hout[k]); (void)hipHostFree(m->vp_hplan[k]);
     for (int q = 0; q < 3; q++)
       if (m->mp_ev[k][q]) (void)hipEventDestroy(m->mp_ev[k][q]);
   }
@@ -1652,6 +1877,46 @@ int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pair
   M_TRY(m, hipSetDevice(m->device));
   return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best ? 1 : 0,
                    "match_pairs_guided", geo, loc);
+}
+
+// Match, estimate, guided match and (optionally) estimate of every pair of a list, chained on the device: run_verify.
+// Everything is checked before anything is launched or changed.
+int hess_matcher_verify_pairs(hess_matcher* m, int npairs, const int* pairs_ab, const hess_verify_params* params, int max_match,
+                              int* out_pairs, int* out_counts, hess_verify_result* out, unsigned char* inlier,
+                              int* putative_pairs) {
+  static_assert(sizeof(hess_verify_params) == 64 && sizeof(hess_verify_result) == 128, "hess_verify_params / _result are ABI");
+  if (!m) return HESS_ERR_ARG;
+  if (npairs > 0) {  // (stricter than pair_list_args: out_pairs may not be NULL even with max_match 0; and by name)
+    const char* null = !pairs_ab ? "pairs_ab" : !params ? "params" : !out ? "out" : !out_pairs ? "out_pairs" : !out_counts ? "out_counts" : nullptr;
+    if (null) { m->err = std::string("verify_pairs: ") + null + " is NULL"; return HESS_ERR_ARG; }
+  }
+  if (const int rc = pair_list_args(m, npairs, pairs_ab, max_match, out_pairs, out_counts, "verify_pairs")) return rc;
+  if (params) {
+    if (const int rc = hess_geom_params_check(m, &params->geom, "verify_pairs")) return rc;
+    if (!(params->guided_bound >= 0.0f) || !std::isfinite(params->guided_bound)) {
+      m->err = "verify_pairs: params.guided_bound must be finite and not negative (0: geom.bound)";
+      return HESS_ERR_ARG;
+    }
+    if (params->final_estimate != 0 && params->final_estimate != 1) {
+      m->err = "verify_pairs: params.final_estimate must be 0 or 1, not " + std::to_string(params->final_estimate);
+      return HESS_ERR_ARG;
+    }
+    for (int k = 0; k < 3; k++)
+      if (params->reserved[k]) { m->err = "verify_pairs: params.reserved[" + std::to_string(k) + "] must be zero"; return HESS_ERR_ARG; }
+  }
+  if (m->bank.typed) {
+    m->err = "verify_pairs: guided matching with feature types is not built; remove the bank's types (bank_set_types NULL) first";
+    return HESS_ERR_UNSUPPORTED;
+  }
+  const float2* loc = nullptr;
+  if (!hess_geom_bank_locations(m->geom, &loc)) {
+    m->err = "verify_pairs: the bank has no locations (hess_matcher_bank_set_locations after loading the bank)";
+    return HESS_ERR_STATE;
+  }
+  m->last_ms = 0.0f;
+  if (npairs == 0) return 0;
+  M_TRY(m, hipSetDevice(m->device));
+  return run_verify(m, npairs, pairs_ab, *params, max_match, out_pairs, out_counts, out, inlier, putative_pairs, loc);
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hess_abi.h"
+
 struct hess_matcher;
 struct hess_geom_state;  // hess_geom.hip
 
@@ -34,6 +36,28 @@ void hess_geom_state_destroy(hess_geom_state* g);
 // The bank's locations for guided pair lists: false without any (g may be NULL); else *loc = one (x, y) per kept row in the
 // caller's order, set s from DescSets::first[s] on -- NOT padded like the descriptors (NULL for a bank without rows).
 bool hess_geom_bank_locations(const hess_geom_state* g, const float2** loc);
+
+// Estimates over matches that are on the device already (hess_matcher_verify_pairs): nothing here waits for the stream.
+// The np pairs of a chunk: pair q has counts[q] matches (row of set 1, row of set 2) at matches + q * mm and its mask bytes at
+// mask + q * mm, its sets' locations from row lalb[q].x and .y of the bank's locations on, seed0 + q as its seed; its
+// result goes to results[q].  All pointers are device memory; counts and matches are read in stream order.
+struct hess_geom_device_pairs {
+  int np, mm;
+  const int2* lalb;
+  const int* counts;
+  const int2* matches;
+  uint32_t seed0;
+  hess_geom_result* results;
+  unsigned char* mask;
+};
+// What hess_matcher_estimate_pairs refuses in its params, with `what` as the entry point's name in the error text.
+int hess_geom_params_check(hess_matcher* m, const hess_geom_params* P, const char* what);
+// Grows the estimator's own buffers (tables, block entries, the refit's candidate masks) for chunks of up to np pairs of
+// up to mm matches: 0 or a negative hess_status with the error text set.  Before the first launch of a call.
+int hess_geom_reserve(hess_matcher* m, const hess_geom_params& P, int np, int mm);
+// Enqueues the table fill and the score, finish and (P.refit > 0) refit kernels of d on the matcher's stream.  The bank has
+// locations and hess_geom_reserve covered d (the caller checked both).
+hipError_t hess_geom_enqueue(hess_matcher* m, const hess_geom_params& P, const hess_geom_device_pairs& d);
 
 // A device buffer of at least n elements: kept when it is large enough, else replaced (its contents are not carried over).
 template <class T>

@@ -44,6 +44,8 @@ def _lib():
         L.hess_matcher_bank_set_locations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.hess_matcher_estimate_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
+        L.hess_matcher_verify_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L.hess_matcher_last_ms.restype = C.c_float
         L.hess_matcher_last_ms.argtypes = [C.c_void_p]
         L.hess_matcher_last_error.restype = C.c_char_p
@@ -90,6 +92,8 @@ assert GEOM_PARAMS_DTYPE.itemsize == 32 and GEOM_RESULT_DTYPE.itemsize == 52
 GUIDED_PAIR_DTYPE = np.dtype([("H", "<f4", 9), ("F", "<f4", 9), ("hdistmax", "<f4"), ("fdistmax", "<f4")])
 assert GUIDED_PAIR_DTYPE.itemsize == 80
 GUIDED_OFF = 1.0e20  # the bound that switches a gate off (SiftMatchGPU::GetGuidedSiftMatch)
+VERIFY_PARAMS_DTYPE, VERIFY_RESULT_DTYPE = _abi.VERIFY_PARAMS_DTYPE, _abi.VERIFY_RESULT_DTYPE  # hess_matcher_verify_pairs
+assert VERIFY_PARAMS_DTYPE["geom"] == GEOM_PARAMS_DTYPE and VERIFY_RESULT_DTYPE["putative"] == GEOM_RESULT_DTYPE
 
 
 def guided_pairs(n, H=None, F=None, hdistmax=32.0, fdistmax=16.0):
@@ -396,3 +400,65 @@ class Matcher:
         self._check(self.L.hess_matcher_match_pairs_guided(self.h, n, p.ctypes.data, geo.ctypes.data if n else None, max_match,
                                                            out.ctypes.data, cnt.ctypes.data, distmax, ratiomax, int(mutual_best)))
         return [out[k, :cnt[k]].copy() for k in range(n)]
+
+    # ---- verified matches in one call (hess_matcher_verify_pairs, the rule is stated in include/hess_abi.h) ----
+    @staticmethod
+    def _verify_params(model, bound, hypotheses, seed, refit, guided_bound, final_estimate, distmax, ratiomax, mutual_best):
+        """The argument checks of verify_pairs -> VERIFY_PARAMS_DTYPE [1]; ValueError before the library is called."""
+        g = _geom_params(model, bound, hypotheses, seed, refit)
+        gb = 0.0 if guided_bound is None else guided_bound
+        for name, v in (("bound", bound), ("guided_bound", gb), ("distmax", distmax), ("ratiomax", ratiomax)):
+            if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isreal(v):
+                raise ValueError(f"{name} must be a number, not {v!r}")
+        if not np.isfinite(gb) or gb < 0:
+            raise ValueError(f"guided_bound must be finite and not negative (None or 0: bound), not {gb!r}")
+        if final_estimate not in (True, False, 0, 1):
+            raise ValueError(f"final_estimate is True or False, not {final_estimate!r}")
+        p = np.zeros(1, dtype=VERIFY_PARAMS_DTYPE)
+        p["geom"] = g
+        p["distmax"], p["ratiomax"], p["mutual_best"] = distmax, ratiomax, int(bool(mutual_best))
+        p["guided_bound"], p["final_estimate"] = gb, int(bool(final_estimate))
+        return p
+
+    def verify_pairs_raw(self, pairs, params, max_match=4096, inlier=True, putative=False):
+        """hess_matcher_verify_pairs as it stands: params a VERIFY_PARAMS_DTYPE [1] -> (matches int32 [n, max_match, 2], counts
+        int32 [n], results VERIFY_RESULT_DTYPE [n], inlier uint8 [n, max_match] or None, putative int32 [n, max_match, 2] or
+        None); the two optional outputs are passed as NULL when not asked for."""
+        ab = check_pairs(pairs)
+        if max_match < 0:
+            raise ValueError("max_match must be >= 0")
+        n, w = len(ab), max(int(max_match), 1)
+        out = np.zeros((max(n, 1), w, 2), dtype=np.int32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        res = np.zeros(max(n, 1), dtype=VERIFY_RESULT_DTYPE)
+        mask = np.zeros((max(n, 1), w), dtype=np.uint8) if inlier else None
+        put = np.zeros((max(n, 1), w, 2), dtype=np.int32) if putative else None
+        self._check(self.L.hess_matcher_verify_pairs(self.h, n, ab.ctypes.data, params.ctypes.data, int(max_match), out.ctypes.data,
+                                                     cnt.ctypes.data, res.ctypes.data, mask.ctypes.data if inlier else None,
+                                                     put.ctypes.data if putative else None))
+        return out[:n], cnt[:n], res[:n], (mask[:n] if inlier else None), (put[:n] if putative else None)
+
+    def verify_pairs(self, pairs, model, bound, hypotheses=0, seed=0, refit=0, guided_bound=None, final_estimate=True,
+                     max_match=4096, distmax=0.7, ratiomax=0.8, mutual_best=True, putative=False):
+        """Geometrically verified matches of bank[a] against bank[b] for every (a, b) in pairs, in one call: what match_pairs,
+        estimate_pairs (model, bound, hypotheses, seed + position, refit), match_pairs_guided with each pair's estimate
+        within guided_bound (None: bound) and, with final_estimate, estimate_pairs again on the guided matches return when
+        chained -- without their host round trips.  -> a list of dicts: matches [k, 2] (the guided matches); M [3, 3],
+        hypothesis, inliers (the estimate on the unguided matches; no model: zeros, -1, 0 and no matches); with
+        final_estimate M_final [3, 3], mask bool [k] and info (inliers, refits, ransac_inliers of the final estimate); with
+        putative=True putative [n, 2] (the unguided matches).  The bank needs locations (set_bank_locations*)."""
+        p = self._verify_params(model, bound, hypotheses, seed, refit, guided_bound, final_estimate, distmax, ratiomax, mutual_best)
+        fin = bool(final_estimate)
+        out, cnt, res, mask, put = self.verify_pairs_raw(pairs, p, max_match, inlier=fin, putative=bool(putative))
+        ret = []
+        for k in range(len(cnt)):
+            d = {"matches": out[k, :cnt[k]].copy(), "M": res["putative"]["M"][k].reshape(3, 3).copy(),
+                 "hypothesis": int(res["putative"]["hypothesis"][k]), "inliers": int(res["putative"]["inliers"][k])}
+            if fin:
+                d["M_final"] = res["final"]["M"][k].reshape(3, 3).copy()
+                d["mask"] = mask[k, :cnt[k]].astype(bool)
+                d["info"] = _geom_info(res["final"], k)
+            if putative:
+                d["putative"] = put[k, :res["nputative"][k]].copy()
+            ret.append(d)
+        return ret

@@ -52,7 +52,9 @@ extern "C" {
  *    hess_geom_params.refit, hess_geom_result.refits / .ransac_inliers (the least-squares refit on the inliers, words
  *    of the reserved arrays; added during version 5 without a bump: `refit` 0 behaves as before).
  *    hess_matcher_match_pairs_guided / hess_guided_pair (guided matching for bank pairs; added during version 5 without a
- *    bump: a matcher that never calls it behaves as before). */
+ *    bump: a matcher that never calls it behaves as before).
+ *    hess_matcher_verify_pairs / hess_verify_params / hess_verify_result (match, estimate, guided match and estimate for
+ *    bank pairs in one call; added during version 5 without a bump: a matcher that never calls it behaves as before). */
 #define HESS_ABI_VERSION 5
 
 /* Detectors (hess_params.detector).  The reference picks one at compile time (#define GPU_HESSIAN, config.h:36):
@@ -632,6 +634,55 @@ int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc,
 int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* matches,
                                 const int* counts, const hess_geom_params* params, hess_geom_result* out,
                                 unsigned char* inlier);
+
+/* Geometrically verified matches for a list of bank pairs in one call: the unguided match, the estimate, the guided match
+ * with each pair's own estimate and, optionally, the estimate on the guided matches -- per group of up to 256 pairs in
+ * stream order on the device, with no host wait in between; only the results the caller asks for cross the host link.
+ * THE RULE: for pair p = (a, b) the call returns, byte for byte, what this sequence of calls returns on the same matcher
+ * state -- truncation to max_match, tie order, the rule of the 8-row blocks, seed + p and "never fewer inliers after a
+ * refit" included:
+ *   1. hess_matcher_match_pairs(pairs_ab, max_match, distmax, ratiomax, mutual_best): P_p with n_p matches
+ *      (putative_pairs[p][0 .. n_p), out[p].nputative);
+ *   2. hess_matcher_estimate_pairs(pairs_ab, max_match, P, n, &params->geom): out[p].putative;
+ *   3. geo[p] from out[p].putative.M, the one-matrix rule of hess_matcher_match_pairs_guided: model HOMOGRAPHY H = M,
+ *      hdistmax = guided_bound, F = identity, fdistmax = 1e20; model FUNDAMENTAL F = M, fdistmax = guided_bound,
+ *      H = identity, hdistmax = 1e20 (guided_bound 0 stands for geom.bound).  A pair without a model has M all zero and
+ *      therefore no guided match;
+ *   4. hess_matcher_match_pairs_guided(pairs_ab, geo, max_match, distmax, ratiomax, mutual_best): out_pairs[p],
+ *      out_counts[p] (= out[p].nguided);
+ *   5. final_estimate 1: hess_matcher_estimate_pairs(pairs_ab, max_match, out_pairs, out_counts, &params->geom):
+ *      out[p].final and inlier[p][0 .. out_counts[p]), the rest of inlier[p] zero.  final_estimate 0: out[p].final is the
+ *      no-model result (M zero, inliers 0, hypothesis -1) and inlier is all zero.
+ * inlier ([npairs][max_match] bytes) and putative_pairs ([npairs][max_match][2] ints) may be NULL: they are then not copied
+ * and nothing else changes.  Pairs may repeat, be reversed or (a, a); p is the position in the list.
+ * Errors launch nothing and leave the matcher as it was; hess_matcher_last_error names the argument:
+ *   HESS_ERR_STATE        the bank has no locations
+ *   HESS_ERR_UNSUPPORTED  the bank has feature types (guided matching with types is not built)
+ *   HESS_ERR_ARG          NULL params, out, out_pairs or out_counts with npairs > 0; anything hess_matcher_estimate_pairs
+ *                         refuses in params->geom; guided_bound negative or not finite; final_estimate not 0 or 1;
+ *                         non-zero reserved words; a set index outside the bank; npairs or max_match < 0
+ *   HESS_ERR_TOO_BIG      the scratch of one pair overflows, as in hess_matcher_match_pairs
+ * npairs == 0 returns 0.  hess_matcher_last_ms: the sum of the kernel intervals of all chunks.
+ * Added during version 5 without a bump: a matcher that never calls it behaves as before. */
+typedef struct hess_verify_params {
+  hess_geom_params geom;   /* model, hypotheses, seed, bound, refit: exactly as hess_matcher_estimate_pairs takes them */
+  float distmax, ratiomax; /* both matches */
+  int32_t mutual_best;
+  float guided_bound;      /* bound of the guided gate for the estimated matrix; 0 = geom.bound */
+  int32_t final_estimate;  /* 1: estimate again (same geom params, same seed + p) on the guided matches */
+  int32_t reserved[3];     /* must be zero */
+} hess_verify_params;      /* 64 bytes */
+typedef struct hess_verify_result {
+  hess_geom_result putative;  /* the estimate on the unguided matches */
+  hess_geom_result final;     /* final_estimate = 1: the estimate on the returned matches; else all zero, hypothesis -1 */
+  int32_t nputative;          /* matches of the unguided step (after the truncation to max_match) */
+  int32_t nguided;            /* == out_counts[p] */
+  int32_t reserved[4];
+} hess_verify_result;         /* 128 bytes */
+int hess_matcher_verify_pairs(hess_matcher* m, int npairs, const int* pairs_ab, const hess_verify_params* params,
+                              int max_match, int* out_pairs, int* out_counts, hess_verify_result* out,
+                              unsigned char* inlier /* [npairs][max_match] or NULL */,
+                              int* putative_pairs /* [npairs][max_match][2] or NULL */);
 float hess_matcher_last_ms(hess_matcher* m);   /* device time of the last match's kernels */
 const char* hess_matcher_last_error(hess_matcher* m);
 
