@@ -14,8 +14,7 @@
 //                        least-squares DLT on the inliers (hess_abi.h, step 6) -- moment sums over the mask, the serial
 //                        solve of hess_geom_refit.h on one lane, the candidate's mask into a second buffer, accept or stop;
 //   geom_jobs_fill_kernel   the job and work tables of a chunk from match counts that only the device knows
-//                        (hess_geom_enqueue for hess_matcher_verify_pairs: no host copy of the matches, no sync);
-//   geom_loc_gather_kernel  bank locations from strided records into the caller's row order of the kept rows.
+//                        (hess_geom_enqueue for hess_matcher_verify_pairs: no host copy of the matches, no sync).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -605,77 +604,24 @@ __global__ __launch_bounds__(256) void geom_jobs_fill_kernel(const int2* lalb, c
   if (i < np * nblk) work[i] = make_int2(i / nblk, i % nblk);
 }
 
-// out[first kept row of set + i] = the (x, y) at record (first record of the set + i) of src, records `stride` bytes apart.
-// sets[s] = (first kept row, first record, rows kept) in ascending kept rows.
-__global__ __launch_bounds__(256) void geom_loc_gather_kernel(const unsigned char* src, size_t stride, const int3* sets,
-                                                              int nsets, int total, float2* out) {
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= total) return;
-  int lo = 0, hi = nsets - 1;  // the last set starting at or before g (empty sets share their successor's start)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (sets[mid].x <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  const int3 S = sets[lo];
-  const float* p = reinterpret_cast<const float*>(src + ((size_t)S.y + (size_t)(g - S.x)) * stride);
-  out[g] = make_float2(p[0], p[1]);
-}
-
 }  // namespace
 
+// The estimator's scratch: one chunk's plan (jobs, work table), matches, block entries, results and masks.
 struct hess_geom_state {
-  float2* bank_loc = nullptr;  // [kept rows of the bank] in the caller's order (DescSets::first)
-  bool have_bank_loc = false;
-  // one chunk's plan (jobs, work table), matches, block entries, results and masks
-  unsigned char* plan = nullptr;
-  int2* matches = nullptr;
-  GeomBest* best = nullptr;
-  hess_geom_result* results = nullptr;
-  unsigned char* mask = nullptr;
-  unsigned char* cand = nullptr;  // the refit's candidate masks (only with params.refit > 0)
-  size_t plan_cap = 0, matches_cap = 0, best_cap = 0, results_cap = 0, mask_cap = 0, cand_cap = 0;
+  DeviceBuf<unsigned char> plan, mask;
+  DeviceBuf<int2> matches;
+  DeviceBuf<GeomBest> best;
+  DeviceBuf<hess_geom_result> results;
+  DeviceBuf<unsigned char> cand;  // the refit's candidate masks (only with params.refit > 0)
 };
 
-void hess_geom_drop_bank_locations(hess_geom_state* g) {
-  if (!g) return;
-  (void)hipFree(g->bank_loc);
-  g->bank_loc = nullptr;
-  g->have_bank_loc = false;
-}
-
-bool hess_geom_bank_locations(const hess_geom_state* g, const float2** loc) {
-  if (!g || !g->have_bank_loc) return false;
-  *loc = g->bank_loc;
-  return true;
-}
-
-void hess_geom_state_destroy(hess_geom_state* g) {
-  if (!g) return;
-  (void)hipFree(g->bank_loc);
-  (void)hipFree(g->plan);
-  (void)hipFree(g->matches);
-  (void)hipFree(g->best);
-  (void)hipFree(g->results);
-  (void)hipFree(g->mask);
-  (void)hipFree(g->cand);
-  delete g;
-}
-
-#define G_TRY(v, expr)                                                                       \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      *(v).err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                   \
-      return HESS_ERR_DEVICE;                                                                \
-    }                                                                                        \
-  } while (0)
+void hess_geom_state_destroy(hess_geom_state* g) { delete g; }
 
 namespace {
 
 hess_geom_state* geom_state(hess_matcher_view& v) {
-  if (!*v.geom) *v.geom = new (std::nothrow) hess_geom_state();
-  return *v.geom;
+  if (!*v.geom) v.geom->reset(new (std::nothrow) hess_geom_state());
+  return v.geom->get();
 }
 
 // One pair as the caller gave it: the locations and sizes of its two sets, its n matches (i of set 1, j of set 2).
@@ -689,23 +635,23 @@ struct GeomPair {
 
 int geom_params_check(hess_matcher_view& v, const hess_geom_params* P, const char* what) {
   const std::string w = what;
-  if (!P) { *v.err = w + ": params is NULL"; return HESS_ERR_ARG; }
+  if (!P) { v.err = w + ": params is NULL"; return HESS_ERR_ARG; }
   if (P->model != HESS_GEOM_HOMOGRAPHY && P->model != HESS_GEOM_FUNDAMENTAL) {
-    *v.err = w + ": params.model must be HESS_GEOM_HOMOGRAPHY (1) or HESS_GEOM_FUNDAMENTAL (2), not " + std::to_string(P->model);
+    v.err = w + ": params.model must be HESS_GEOM_HOMOGRAPHY (1) or HESS_GEOM_FUNDAMENTAL (2), not " + std::to_string(P->model);
     return HESS_ERR_ARG;
   }
   if (P->hypotheses < 0 || P->hypotheses > GEOM_MAX_T) {
-    *v.err = w + ": params.hypotheses must lie in 0..65536, not " + std::to_string(P->hypotheses);
+    v.err = w + ": params.hypotheses must lie in 0..65536, not " + std::to_string(P->hypotheses);
     return HESS_ERR_ARG;
   }
   if (P->refit < 0 || P->refit > GEOM_MAX_REFIT) {
-    *v.err = w + ": params.refit must lie in 0..8, not " + std::to_string(P->refit);
+    v.err = w + ": params.refit must lie in 0..8, not " + std::to_string(P->refit);
     return HESS_ERR_ARG;
   }
   for (int k = 1; k < 4; k++)
-    if (P->reserved[k]) { *v.err = w + ": params.reserved[" + std::to_string(k) + "] must be zero"; return HESS_ERR_ARG; }
+    if (P->reserved[k]) { v.err = w + ": params.reserved[" + std::to_string(k) + "] must be zero"; return HESS_ERR_ARG; }
   if (!(P->bound > 0.0f) || !std::isfinite(P->bound)) {
-    *v.err = w + ": params.bound must be finite and greater than 0";
+    v.err = w + ": params.bound must be finite and greater than 0";
     return HESS_ERR_ARG;
   }
   return 0;
@@ -718,7 +664,7 @@ int geom_matches_check(hess_matcher_view& v, const std::vector<GeomPair>& pairs,
     for (int i = 0; i < G.n; i++) {
       const int a = G.matches[2 * i], b = G.matches[2 * i + 1];
       if (a < 0 || a >= G.n1 || b < 0 || b >= G.n2) {
-        *v.err = std::string(what) + ": match " + std::to_string(i) + " of pair " + std::to_string(p) + " is (" + std::to_string(a) +
+        v.err = std::string(what) + ": match " + std::to_string(i) + " of pair " + std::to_string(p) + " is (" + std::to_string(a) +
                  ", " + std::to_string(b) + "), outside its sets of " + std::to_string(G.n1) + " and " + std::to_string(G.n2);
         return HESS_ERR_ARG;
       }
@@ -757,7 +703,7 @@ hipError_t geom_launch(hipStream_t st, const GeomBuffers& b, int np, size_t nwor
 int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hess_geom_params& P, hess_geom_result* out,
              unsigned char* inlier, size_t pitch) {
   hess_geom_state* const g = geom_state(v);
-  if (!g) { *v.err = "estimate: out of memory"; return HESS_ERR_NOMEM; }
+  if (!g) { v.err = "estimate: out of memory"; return HESS_ERR_NOMEM; }
   const int K = geom_k(P.model), T = P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T, nblk = (T + 255) / 256;
   *v.last_ms = 0.0f;
   float total_ms = 0.0f;
@@ -791,24 +737,24 @@ int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hes
       moff += (size_t)G.n;
       boff += (size_t)J.nblk;
     }
-    G_TRY(v, grow_device(g->plan, g->plan_cap, hplan.size()));
-    G_TRY(v, grow_device(g->matches, g->matches_cap, std::max<size_t>(nm, 1)));
-    G_TRY(v, grow_device(g->best, g->best_cap, std::max<size_t>(nwork, 1)));
-    G_TRY(v, grow_device(g->results, g->results_cap, (size_t)np));
-    G_TRY(v, grow_device(g->mask, g->mask_cap, std::max<size_t>(nm, 1)));
-    if (P.refit > 0) G_TRY(v, grow_device(g->cand, g->cand_cap, std::max<size_t>(nm, 1)));
-    G_TRY(v, hipMemcpyAsync(g->plan, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
-    if (nm) G_TRY(v, hipMemcpyAsync(g->matches, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
+    M_TRY(&v, g->plan.grow(hplan.size()));
+    M_TRY(&v, g->matches.grow(std::max<size_t>(nm, 1)));
+    M_TRY(&v, g->best.grow(std::max<size_t>(nwork, 1)));
+    M_TRY(&v, g->results.grow((size_t)np));
+    M_TRY(&v, g->mask.grow(std::max<size_t>(nm, 1)));
+    if (P.refit > 0) M_TRY(&v, g->cand.grow(std::max<size_t>(nm, 1)));
+    M_TRY(&v, hipMemcpyAsync(g->plan.p, hplan.data(), hplan.size(), hipMemcpyHostToDevice, v.st));
+    if (nm) M_TRY(&v, hipMemcpyAsync(g->matches.p, hmatch.data(), nm * 2 * sizeof(int), hipMemcpyHostToDevice, v.st));
     (void)hipEventRecord(v.e0, v.st);
-    const GeomBuffers B{g->plan, g->matches, g->best, g->results, g->mask, g->cand};
-    G_TRY(v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, B, np, nwork, T, P.bound, P.refit)
+    const GeomBuffers B{g->plan.p, g->matches.p, g->best.p, g->results.p, g->mask.p, g->cand.p};
+    M_TRY(&v, P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(v.st, B, np, nwork, T, P.bound, P.refit)
                                              : geom_launch<HESS_GEOM_FUNDAMENTAL>(v.st, B, np, nwork, T, P.bound, P.refit));
     (void)hipEventRecord(v.e1, v.st);
     hres.resize((size_t)np);
     hmask.resize(std::max<size_t>(nm, 1));
-    G_TRY(v, hipMemcpyAsync(hres.data(), g->results, (size_t)np * sizeof(hess_geom_result), hipMemcpyDeviceToHost, v.st));
-    if (nm && inlier) G_TRY(v, hipMemcpyAsync(hmask.data(), g->mask, nm, hipMemcpyDeviceToHost, v.st));
-    G_TRY(v, hipStreamSynchronize(v.st));
+    M_TRY(&v, hipMemcpyAsync(hres.data(), g->results.p, (size_t)np * sizeof(hess_geom_result), hipMemcpyDeviceToHost, v.st));
+    if (nm && inlier) M_TRY(&v, hipMemcpyAsync(hmask.data(), g->mask.p, nm, hipMemcpyDeviceToHost, v.st));
+    M_TRY(&v, hipStreamSynchronize(v.st));
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, v.e0, v.e1);
     total_ms += ms;
@@ -819,57 +765,6 @@ int geom_run(hess_matcher_view& v, const std::vector<GeomPair>& pairs, const hes
     p0 = p1;
   }
   *v.last_ms = total_ms;
-  return 0;
-}
-
-// The bank's locations from `rows` records in device memory (checked), `stride` bytes apart.
-int geom_bank_locations(hess_matcher_view& v, const void* dev, size_t stride) {
-  hess_geom_state* const g = geom_state(v);
-  if (!g) { *v.err = "bank_set_locations: out of memory"; return HESS_ERR_NOMEM; }
-  const int nsets = (int)v.bank_num->size();
-  std::vector<int3> sets((size_t)nsets);
-  size_t srow = 0, total = 0;
-  for (int k = 0; k < nsets; k++) {
-    sets[k] = make_int3((*v.bank_first)[k], (int)srow, (*v.bank_num)[k]);
-    srow += (size_t)(*v.bank_cnt)[k];
-    total = (size_t)(*v.bank_first)[k] + (size_t)(*v.bank_num)[k];
-  }
-  float2* loc = nullptr;
-  if (total) {
-    int3* dsets = nullptr;
-    G_TRY(v, hipMalloc(&loc, total * sizeof(float2)));
-    hipError_t e = hipMalloc(&dsets, sets.size() * sizeof(int3));
-    if (e == hipSuccess) e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, v.st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(geom_loc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v.st,
-                         static_cast<const unsigned char*>(dev), stride, dsets, nsets, (int)total, loc);
-      e = hipGetLastError();
-    }
-    const hipError_t es = hipStreamSynchronize(v.st);
-    (void)hipFree(dsets);
-    if (e != hipSuccess || es != hipSuccess) (void)hipFree(loc);
-    G_TRY(v, e);
-    G_TRY(v, es);
-  }
-  (void)hipFree(g->bank_loc);
-  g->bank_loc = loc;
-  g->have_bank_loc = true;
-  return 0;
-}
-
-// What both bank_set_locations forms refuse.  rows: the records the caller counted.
-int geom_bank_locations_args(hess_matcher_view& v, size_t stride, const char* what, size_t* rows) {
-  if (!v.bank_built) {
-    *v.err = std::string(what) + ": load the bank's descriptors before their locations";
-    return HESS_ERR_STATE;
-  }
-  if (stride < 8 || stride % 4) {
-    *v.err = std::string(what) + ": stride_bytes must be a multiple of 4 and at least 8, not " + std::to_string(stride);
-    return HESS_ERR_ARG;
-  }
-  size_t n = 0;
-  for (int c : *v.bank_cnt) n += (size_t)c;
-  *rows = n;
   return 0;
 }
 
@@ -885,25 +780,25 @@ int hess_geom_params_check(hess_matcher* m, const hess_geom_params* P, const cha
 int hess_geom_reserve(hess_matcher* m, const hess_geom_params& P, int np, int mm) {
   hess_matcher_view v = hess_matcher_view_of(m);
   hess_geom_state* const g = geom_state(v);
-  if (!g) { *v.err = "verify_pairs: out of memory"; return HESS_ERR_NOMEM; }
+  if (!g) { v.err = "verify_pairs: out of memory"; return HESS_ERR_NOMEM; }
   const size_t nblk = (size_t)((P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T) + 255) / 256, nwork = (size_t)np * nblk;
-  G_TRY(v, grow_device(g->plan, g->plan_cap, (size_t)np * sizeof(GeomJob) + nwork * sizeof(int2)));
-  G_TRY(v, grow_device(g->best, g->best_cap, nwork));
-  if (P.refit > 0) G_TRY(v, grow_device(g->cand, g->cand_cap, std::max<size_t>((size_t)np * mm, 1)));
+  M_TRY(&v, g->plan.grow((size_t)np * sizeof(GeomJob) + nwork * sizeof(int2)));
+  M_TRY(&v, g->best.grow(nwork));
+  if (P.refit > 0) M_TRY(&v, g->cand.grow(std::max<size_t>((size_t)np * mm, 1)));
   return 0;
 }
 
 hipError_t hess_geom_enqueue(hess_matcher* m, const hess_geom_params& P, const hess_geom_device_pairs& d) {
   const hess_matcher_view v = hess_matcher_view_of(m);
-  hess_geom_state* const g = *v.geom;
+  hess_geom_state* const g = v.geom->get();
   const hipStream_t st = v.st;
   const int K = geom_k(P.model), T = P.hypotheses ? P.hypotheses : GEOM_DEFAULT_T, nblk = (T + 255) / 256;
   const size_t nwork = (size_t)d.np * nblk;
-  GeomJob* const djobs = reinterpret_cast<GeomJob*>(g->plan);
-  int2* const dwork = reinterpret_cast<int2*>(g->plan + (size_t)d.np * sizeof(GeomJob));
+  GeomJob* const djobs = reinterpret_cast<GeomJob*>(g->plan.p);
+  int2* const dwork = reinterpret_cast<int2*>(g->plan.p + (size_t)d.np * sizeof(GeomJob));
   hipLaunchKernelGGL(geom_jobs_fill_kernel, dim3((unsigned)((nwork + 255) / 256)), dim3(256), 0, st, d.lalb, d.counts,
-                     g->bank_loc, d.np, d.mm, nblk, K, d.seed0, djobs, dwork);
-  const GeomBuffers B{g->plan, d.matches, g->best, d.results, d.mask, g->cand};
+                     v.bank_loc, d.np, d.mm, nblk, K, d.seed0, djobs, dwork);
+  const GeomBuffers B{g->plan.p, d.matches, g->best.p, d.results, d.mask, g->cand.p};
   return P.model == HESS_GEOM_HOMOGRAPHY ? geom_launch<HESS_GEOM_HOMOGRAPHY>(st, B, d.np, nwork, T, P.bound, P.refit)
                                          : geom_launch<HESS_GEOM_FUNDAMENTAL>(st, B, d.np, nwork, T, P.bound, P.refit);
 }
@@ -923,52 +818,18 @@ int hess_matcher_estimate(hess_matcher* m, int nmatch, const int* pairs, const h
   if (!m) return HESS_ERR_ARG;
   hess_matcher_view v = hess_matcher_view_of(m);
   if (const int rc = geom_params_check(v, params, "estimate")) return rc;
-  if (!out) { *v.err = "estimate: out is NULL"; return HESS_ERR_ARG; }
-  if (nmatch < 0 || (nmatch > 0 && !pairs)) { *v.err = "estimate: nmatch < 0 or pairs NULL"; return HESS_ERR_ARG; }
+  if (!out) { v.err = "estimate: out is NULL"; return HESS_ERR_ARG; }
+  if (nmatch < 0 || (nmatch > 0 && !pairs)) { v.err = "estimate: nmatch < 0 or pairs NULL"; return HESS_ERR_ARG; }
   for (int k = 0; k < 2; k++)
     if (v.nloc[k] < 0) {
-      *v.err = "estimate: slot " + std::to_string(k) + " has no locations (hess_matcher_set_locations after its descriptors)";
+      v.err = "estimate: slot " + std::to_string(k) + " has no locations (hess_matcher_set_locations after its descriptors)";
       return HESS_ERR_STATE;
     }
   std::vector<GeomPair> one(1);
   one[0] = GeomPair{v.loc[0], v.loc[1], v.nloc[0], v.nloc[1], pairs, nmatch, params->seed};
   if (const int rc = geom_matches_check(v, one, "estimate")) return rc;
-  G_TRY(v, hipSetDevice(v.device));
+  M_TRY(&v, hipSetDevice(v.device));
   return geom_run(v, one, *params, out, inlier, 0);
-}
-
-int hess_matcher_bank_set_locations(hess_matcher* m, const float* loc, size_t stride_bytes) {
-  if (!m) return HESS_ERR_ARG;
-  hess_matcher_view v = hess_matcher_view_of(m);
-  if (!loc) { hess_geom_drop_bank_locations(*v.geom); return 0; }
-  size_t rows = 0;
-  if (const int rc = geom_bank_locations_args(v, stride_bytes, "bank_set_locations", &rows)) return rc;
-  G_TRY(v, hipSetDevice(v.device));
-  // the (x, y) pairs packed on the host, staged on the device, then the device form's gather
-  std::vector<float2> h(rows ? rows : 1);
-  for (size_t i = 0; i < rows; i++) memcpy(&h[i], reinterpret_cast<const char*>(loc) + i * stride_bytes, sizeof(float2));
-  float2* d = nullptr;
-  G_TRY(v, hipMalloc(&d, h.size() * sizeof(float2)));
-  const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
-  const int rc = e == hipSuccess ? geom_bank_locations(v, d, sizeof(float2)) : 0;
-  (void)hipFree(d);
-  G_TRY(v, e);
-  return rc;
-}
-
-int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc, size_t stride_bytes) {
-  if (!m) return HESS_ERR_ARG;
-  hess_matcher_view v = hess_matcher_view_of(m);
-  if (!dev_loc) { hess_geom_drop_bank_locations(*v.geom); return 0; }
-  size_t rows = 0;
-  if (const int rc = geom_bank_locations_args(v, stride_bytes, "bank_set_locations_device", &rows)) return rc;
-  G_TRY(v, hipSetDevice(v.device));
-  if (rows) {
-    if ((uintptr_t)dev_loc % 4) { *v.err = "bank_set_locations_device: dev_loc must be 4-byte aligned"; return HESS_ERR_ARG; }
-    if (const int rc = hess_matcher_device_range(m, dev_loc, (rows - 1) * stride_bytes + 8, "bank_set_locations_device", "locations"))
-      return rc;
-  }
-  return geom_bank_locations(v, dev_loc, stride_bytes);
 }
 
 int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, const int* matches,
@@ -978,12 +839,11 @@ int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab
   hess_matcher_view v = hess_matcher_view_of(m);
   if (const int rc = geom_params_check(v, params, "estimate_pairs")) return rc;
   if (npairs < 0 || max_match < 0 || (npairs > 0 && (!pairs_ab || !counts || !out))) {
-    *v.err = "estimate_pairs: npairs or max_match < 0, or pairs_ab, counts or out is NULL";
+    v.err = "estimate_pairs: npairs or max_match < 0, or pairs_ab, counts or out is NULL";
     return HESS_ERR_ARG;
   }
-  const hess_geom_state* const g = *v.geom;
-  if (!g || !g->have_bank_loc) {
-    *v.err = "estimate_pairs: the bank has no locations (hess_matcher_bank_set_locations after its descriptors)";
+  if (!v.bank_have_loc) {
+    v.err = "estimate_pairs: the bank has no locations (hess_matcher_bank_set_locations after its descriptors)";
     return HESS_ERR_STATE;
   }
   const int nsets = (int)v.bank_num->size();
@@ -991,21 +851,21 @@ int hess_matcher_estimate_pairs(hess_matcher* m, int npairs, const int* pairs_ab
   for (int p = 0; p < npairs; p++) {
     const int a = pairs_ab[2 * p], b = pairs_ab[2 * p + 1];
     if (a < 0 || a >= nsets || b < 0 || b >= nsets) {
-      *v.err = "estimate_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
+      v.err = "estimate_pairs: pair " + std::to_string(p) + " names a set outside the bank of " + std::to_string(nsets);
       return HESS_ERR_ARG;
     }
     if (counts[p] < 0 || counts[p] > max_match) {
-      *v.err = "estimate_pairs: counts[" + std::to_string(p) + "] = " + std::to_string(counts[p]) + " lies outside 0..max_match";
+      v.err = "estimate_pairs: counts[" + std::to_string(p) + "] = " + std::to_string(counts[p]) + " lies outside 0..max_match";
       return HESS_ERR_ARG;
     }
-    if (counts[p] > 0 && !matches) { *v.err = "estimate_pairs: matches is NULL"; return HESS_ERR_ARG; }
-    pairs[p] = GeomPair{g->bank_loc + (*v.bank_first)[a], g->bank_loc + (*v.bank_first)[b], (*v.bank_num)[a], (*v.bank_num)[b],
+    if (counts[p] > 0 && !matches) { v.err = "estimate_pairs: matches is NULL"; return HESS_ERR_ARG; }
+    pairs[p] = GeomPair{v.bank_loc + (*v.bank_first)[a], v.bank_loc + (*v.bank_first)[b], (*v.bank_num)[a], (*v.bank_num)[b],
                         matches ? matches + (size_t)p * max_match * 2 : nullptr, counts[p], params->seed + (uint32_t)p};
   }
   if (const int rc = geom_matches_check(v, pairs, "estimate_pairs")) return rc;
   *v.last_ms = 0.0f;
   if (npairs == 0) return 0;
-  G_TRY(v, hipSetDevice(v.device));
+  M_TRY(&v, hipSetDevice(v.device));
   if (inlier) memset(inlier, 0, (size_t)npairs * max_match);
   return geom_run(v, pairs, *params, out, inlier, (size_t)max_match);
 }

@@ -4,7 +4,8 @@
 // RowMatch_Kernel, ColMatch_Kernel (ProgramCU.cu:3455-3843).  Integer work: results are bit-exact.
 //
 // Descriptor sets (the user's bank, the two single-pair slots) --
-//   bank_build_kernel      sets padded to 256-row blocks, float sources quantised, score offsets from the byte sums.
+//   bank_build_kernel      sets padded to 256-row blocks, float sources quantised, score offsets from the byte sums;
+//   bank_loc_gather_kernel the bank's locations from strided records into the caller's row order of the kept rows.
 // Unguided match (GetSiftMatch), one pair or many pairs of a bank per call (hess_matcher_match_pairs, no reference
 // counterpart): matrix cores, no score matrix in memory --
 //   match_mfma_kernel      one workgroup per (pair, 256-row block, column segment) of a work table: the segment's
@@ -34,7 +35,8 @@
 // Host side.  What the kernels are launched on is decided in hess_match_plan.h / .cpp, without HIP: the layout of the sets,
 // the segments of a pair (two rules: single_sps for the untyped single pair, chunk_sps for a pair list), the chunks of a
 // list, the scratch offsets and the tables of the plan buffer.  Here: grow_for (the buffers of a plan), run_chunk (upload,
-// multiply, finish) and run_pairs (a pair list planned, its chunks run double buffered and compacted on the device), which serves
+// multiply, finish), run_slots (the double buffer of every pair list: hess_slot_pipeline.h with the events, the copy down, the
+// wait and the error text) and run_pairs (a pair list planned, its chunks run through it and compacted on the device), which serves
 // hess_matcher_match_pairs with (bank, bank) and the typed single pair with (slot 0, slot 1) and a list of one;
 // hess_matcher_match otherwise plans one job and compacts on the host, or takes match_small.
 #include <hip/hip_runtime.h>
@@ -55,6 +57,7 @@
 #include "hess_guided_gate.h"
 #include "hess_match_plan.h"
 #include "hess_matcher_int.h"
+#include "hess_slot_pipeline.h"
 
 using namespace hess::match_plan;  // the constants MM_*, MP_*, PairJob, the plan of a pair list and of the plan buffer
 static_assert(sizeof(Entry) == sizeof(int2) && alignof(Entry) == alignof(int2), "the kernels read the plan's tables as int2");
@@ -868,6 +871,23 @@ __global__ __launch_bounds__(64) void verify_geo_kernel(const hess_geom_result* 
   geo[q] = g;
 }
 
+// out[first kept row of set + i] = the (x, y) at record (first record of the set + i) of src, records `stride` bytes apart.
+// sets[s] = (first kept row, first record, rows kept) in ascending kept rows.
+__global__ __launch_bounds__(256) void bank_loc_gather_kernel(const unsigned char* src, size_t stride, const int3* sets,
+                                                              int nsets, int total, float2* out) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  int lo = 0, hi = nsets - 1;  // the last set starting at or before g (empty sets share their successor's start)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sets[mid].x <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  const int3 S = sets[lo];
+  const float* p = reinterpret_cast<const float*>(src + ((size_t)S.y + (size_t)(g - S.x)) * stride);
+  out[g] = make_float2(p[0], p[1]);
+}
+
 // Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.
 struct DescSets {
   int dim = 128;  // bytes per row (the matcher's dim when the sets were built)
@@ -880,76 +900,59 @@ struct DescSets {
   bool typed = false;
   std::vector<int> goff, gnum;           // [set][class]: first stored row and rows of the class group
   int *fwd = nullptr, *inv = nullptr;    // original row (first[s] + i) -> stored row; stored row -> i, -1 for padding
+  // locations (hess_matcher_set_locations, _bank_set_locations): one (x, y) per kept row in the caller's order, set s from
+  // first[s] on -- NOT padded like the descriptors, and not moved by the types.  A set without rows has them with loc NULL.
+  float2* loc = nullptr;
+  bool have_loc = false;
+  DescSets() = default;
+  DescSets(const DescSets&) = delete;
+  DescSets& operator=(const DescSets&) = delete;
+  ~DescSets();
   int count(int s) const { return s < (int)num.size() ? num[s] : 0; }
   SetsLayout layout() const { return {off.data(), num.data(), first.data(), typed ? goff.data() : nullptr, typed ? gnum.data() : nullptr}; }
 };
 
 }  // namespace
 
+// Every buffer frees itself (DescSets, DeviceBuf, PinnedSlots); the stream and the events go in hess_matcher_destroy, after them.
+// Calls on one matcher are serialised by the caller and every entry point returns with the stream idle, so the pair-list
+// entry points share one plan buffer and one output buffer.
 struct hess_matcher {
   int device = 0, max_sift = 4096;
   int dim = 128;  // descriptor length of every set and argument: hess_matcher_set_dim
   hipStream_t st = nullptr;
-  DescSets bank, slot[2];  // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
-  float2* loc[2] = {nullptr, nullptr};
-  int have_loc[2] = {0, 0};
-  hess_geom_state* geom = nullptr;  // hess_geom.hip: the bank's locations and the estimator's buffers
-  // small / guided path: score matrix and column partials per 64-row tile
-  int3* cpart = nullptr;
-  int* dotm = nullptr;
-  size_t mat_cap = 0;
-  // matrix-core path: row states, column partials per 256-row block, the plan (jobs, work tables) on the device and in two
-  // pinned host slots
-  int3 *mm_rstate = nullptr, *mm_cpart = nullptr;
-  uint8_t* plan = nullptr;
-  uint8_t* hplan[2] = {nullptr, nullptr};
-  size_t mm_rs_cap = 0, mm_cp_cap = 0, plan_cap = 0, hplan_cap = 0;
+  DescSets bank, slot[2];    // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
+  hess_geom_state_ptr geom;  // hess_geom.hip: the estimator's buffers
+  // small / guided path: score matrix and column partials per 64-row tile (sized together: match_small)
+  DeviceBuf<int3> cpart;
+  DeviceBuf<int> dotm;
+  // matrix-core path: row states, column partials per 256-row block
+  DeviceBuf<int3> mm_rstate, mm_cpart;
   // row and column decisions of both paths
-  int *rowm = nullptr, *colm = nullptr;
-  size_t rowm_cap = 0, colm_cap = 0;
+  DeviceBuf<int> rowm, colm;
   std::vector<int> hrow, hcol;
   std::string err;
   float last_ms = 0.0f;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // match_pairs: compacted results on the device and through two pinned host slots
-  int* mp_out = nullptr;
-  int* mp_hout[2] = {nullptr, nullptr};
-  size_t mp_out_cap = 0, mp_hout_cap = 0;
-  GuidedGeo* geo = nullptr;  // match_pairs_guided: the call's geometry table
-  size_t geo_cap = 0;
+  // pair lists and the single pair on the matrix cores: the plan (jobs, work tables; for verify_pairs those of a group's
+  // chunks) on the device and in two pinned host slots
+  DeviceBuf<uint8_t> plan;
+  PinnedSlots<uint8_t> hplan;
+  // pair lists: a unit's results on the device (match_pairs: counts, then compacted matches; verify_pairs: VerifyLayout) and
+  // through two pinned host slots, in bytes
+  DeviceBuf<uint8_t> out;
+  PinnedSlots<uint8_t> hout;
   hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
-  // verify_pairs: the results of a group of chunks on the device (VerifyLayout) and through two pinned host slots; the
-  // plan buffers of the group's chunks, device and pinned; per pair of the call the first location rows of its two sets
-  uint8_t* vp_out = nullptr;
-  uint8_t* vp_hout[2] = {nullptr, nullptr};
-  uint8_t* vp_plan = nullptr;
-  uint8_t* vp_hplan[2] = {nullptr, nullptr};
-  int2* vp_lalb = nullptr;
-  size_t vp_out_cap = 0, vp_hout_cap = 0, vp_plan_cap = 0, vp_hplan_cap = 0, vp_lalb_cap = 0;
+  DeviceBuf<GuidedGeo> geo;  // match_pairs_guided: the call's geometry table; verify_pairs: a group's
+  DeviceBuf<int2> vp_lalb;   // verify_pairs: per pair of the call the first location rows of its two sets
 };
-
-#define M_TRY(m, expr)                                                                       \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      (m)->err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                   \
-      return HESS_ERR_DEVICE;                                                                \
-    }                                                                                        \
-  } while (0)
 
 namespace {
 
-template <class T>
-hipError_t grow_pinned(T* (&p)[2], size_t& cap, size_t n) {
-  if (n <= cap) return hipSuccess;
-  for (int k = 0; k < 2; k++) { (void)hipHostFree(p[k]); p[k] = nullptr; }
-  cap = 0;
-  for (int k = 0; k < 2; k++) {
-    const hipError_t e = hipHostMalloc(&p[k], n * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) return e;
-  }
-  cap = n;
-  return hipSuccess;
+void sets_drop_locations(DescSets& s) {
+  (void)hipFree(s.loc);
+  s.loc = nullptr;
+  s.have_loc = false;
 }
 
 void sets_clear(DescSets& s) {
@@ -968,7 +971,10 @@ void sets_clear(DescSets& s) {
   s.typed = false;
   s.goff.clear();
   s.gnum.clear();
+  sets_drop_locations(s);
 }
+
+DescSets::~DescSets() { sets_clear(*this); }
 
 template <int KD>
 void launch_bank_build(hipStream_t st, size_t padded, bool f32, const void* src, const int3* dsets, int nsets, uint8_t* rows,
@@ -1156,6 +1162,56 @@ int types_args(hess_matcher* m, const DescSets& s, const void* types, size_t str
   return 0;
 }
 
+// The bank's locations from records in device memory (checked), `stride` bytes apart.
+int bank_locations(hess_matcher* m, const void* dev, size_t stride) {
+  DescSets& b = m->bank;
+  const int nsets = (int)b.num.size();
+  std::vector<int3> sets((size_t)nsets);
+  size_t srow = 0, total = 0;
+  for (int k = 0; k < nsets; k++) {
+    sets[k] = make_int3(b.first[k], (int)srow, b.num[k]);
+    srow += (size_t)b.cnt[k];
+    total = (size_t)b.first[k] + (size_t)b.num[k];
+  }
+  float2* loc = nullptr;
+  if (total) {
+    int3* dsets = nullptr;
+    M_TRY(m, hipMalloc(&loc, total * sizeof(float2)));
+    hipError_t e = hipMalloc(&dsets, sets.size() * sizeof(int3));
+    if (e == hipSuccess) e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(bank_loc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st,
+                         static_cast<const unsigned char*>(dev), stride, dsets, nsets, (int)total, loc);
+      e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(m->st);
+    (void)hipFree(dsets);
+    if (e != hipSuccess || es != hipSuccess) (void)hipFree(loc);
+    M_TRY(m, e);
+    M_TRY(m, es);
+  }
+  (void)hipFree(b.loc);
+  b.loc = loc;
+  b.have_loc = true;
+  return 0;
+}
+
+// What both bank_set_locations forms refuse.  rows: the records the caller counted.
+int bank_locations_args(hess_matcher* m, size_t stride, const char* what, size_t* rows) {
+  if (!m->bank.built) {
+    m->err = std::string(what) + ": load the bank's descriptors before their locations";
+    return HESS_ERR_STATE;
+  }
+  if (stride < 8 || stride % 4) {
+    m->err = std::string(what) + ": stride_bytes must be a multiple of 4 and at least 8, not " + std::to_string(stride);
+    return HESS_ERR_ARG;
+  }
+  size_t n = 0;
+  for (int c : m->bank.cnt) n += (size_t)c;
+  *rows = n;
+  return 0;
+}
+
 // Host floats quantised as the reference does, int(512*d + 0.5) into a byte (SiftMatchCU.cpp:88-100): set k is counts[k]
 // rows of KD floats, of which the first max_sift (kept[k]) are kept.
 std::vector<unsigned char> quantise(const float* des, size_t KD, int nsets, const int* counts, int max_sift, int* kept) {
@@ -1208,18 +1264,18 @@ int slot_events(hess_matcher* m) {
   return 0;
 }
 
-// Grows the matcher's buffers to what a plan needs; for compacted output (n.outn) also its device buffer, the two pinned
-// slots and their events.
-int grow_for(hess_matcher* m, const PlanNeed& n) {
-  M_TRY(m, grow_device(m->mm_rstate, m->mm_rs_cap, n.rs));
-  M_TRY(m, grow_device(m->mm_cpart, m->mm_cp_cap, n.cp));
-  M_TRY(m, grow_device(m->rowm, m->rowm_cap, n.rm));
-  M_TRY(m, grow_device(m->colm, m->colm_cap, n.cm));
-  M_TRY(m, grow_device(m->plan, m->plan_cap, n.plan_bytes));
-  M_TRY(m, grow_pinned(m->hplan, m->hplan_cap, n.plan_bytes));
-  if (!n.outn) return 0;
-  M_TRY(m, grow_device(m->mp_out, m->mp_out_cap, n.outn));
-  M_TRY(m, grow_pinned(m->mp_hout, m->mp_hout_cap, n.outn));
+// Grows the matcher's buffers to the scratch of a plan, plan_bytes of plan buffer and, for a pair list (out_bytes > 0), the
+// output buffer with its two pinned slots and their events.
+int grow_for(hess_matcher* m, const PlanNeed& n, size_t plan_bytes, size_t out_bytes) {
+  M_TRY(m, m->mm_rstate.grow(n.rs));
+  M_TRY(m, m->mm_cpart.grow(n.cp));
+  M_TRY(m, m->rowm.grow(n.rm));
+  M_TRY(m, m->colm.grow(n.cm));
+  M_TRY(m, m->plan.grow(plan_bytes));
+  M_TRY(m, m->hplan.grow(plan_bytes));
+  if (!out_bytes) return 0;
+  M_TRY(m, m->out.grow(out_bytes));
+  M_TRY(m, m->hout.grow(out_bytes));
   return slot_events(m);
 }
 
@@ -1238,9 +1294,9 @@ hipError_t launch_chunk(hess_matcher* m, const uint8_t* dplan, const DescSets& s
              : (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, false> : match_mfma_kernel<false, 128, false>)
                               : (mutual_best ? match_mfma_kernel<true, 64, false> : match_mfma_kernel<false, 64, false>));
     hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs,
-                       plan_ptr<int2>(dplan, L.work), m->mm_cpart, m->mm_rstate, dgeo, loc);
+                       plan_ptr<int2>(dplan, L.work), m->mm_cpart.p, m->mm_rstate.p, dgeo, loc);
     hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(dplan, L.fin),
-                       m->mm_rstate, m->mm_cpart, distmax, ratiomax, m->rowm, m->colm);
+                       m->mm_rstate.p, m->mm_cpart.p, distmax, ratiomax, m->rowm.p, m->colm.p);
   }
   return hipGetLastError();
 }
@@ -1251,16 +1307,60 @@ hipError_t run_chunk(hess_matcher* m, const DescSets& s1, const DescSets& s2, co
                      const Chunk& c, uint8_t* hp, hipEvent_t start, int mutual_best, float distmax, float ratiomax,
                      const GuidedGeo* dgeo = nullptr, const float2* loc = nullptr) {
   plan_fill(hp, jobs, orig, c, mutual_best);
-  const hipError_t e = hipMemcpyAsync(m->plan, hp, plan_layout(c).bytes, hipMemcpyHostToDevice, m->st);
+  const hipError_t e = hipMemcpyAsync(m->plan.p, hp, plan_layout(c).bytes, hipMemcpyHostToDevice, m->st);
   if (e != hipSuccess) return e;
   (void)hipEventRecord(start, m->st);
-  return launch_chunk(m, m->plan, s1, s2, c, mutual_best, distmax, ratiomax, dgeo, loc);
+  return launch_chunk(m, m->plan.p, s1, s2, c, mutual_best, distmax, ratiomax, dgeo, loc);
 }
 
-// Plans the pair list pairs_ab of sets s1 x s2 (plan_pairs), runs it and delivers every pair's matches compacted on the device:
-// out_counts[p] and out_pairs[p][max_match][2] (in the pinned slot the pairs are P.mm apart).  Chunk k is enqueued into slot k & 1; its results
-// are read on the host while chunk k + 1 runs.  m->last_ms: the sum of the chunks' kernel intervals (multiply, finish,
-// compaction).  `what` names the entry point in the text of a device error, after which the stream is synchronised.
+// One pair-list call of n units through the two pinned slots (hess_slot_pipeline.h: unit k is enqueued into slot k & 1 and its
+// results are read on the host while unit k + 1 runs).  enqueue(k, slot, &bytes) puts unit k's upload and launches on m->st,
+// records the slot's first event behind the upload and says how many bytes of m->out are its results; deliver(k, h) hands
+// unit k to the caller from its pinned copy h.  Here: the second event and the copy down behind every unit, the wait before
+// its delivery, m->last_ms as the sum of the units' kernel intervals (first to second event) and, after a device error, the
+// stream synchronised and `what`, the entry point's name, in front of the error's text.
+template <class Enqueue, class Deliver>
+int run_slots(hess_matcher* m, size_t n, const char* what, Enqueue&& enqueue, Deliver&& deliver) {
+  // A list of one unit (the typed single pair) waits for the stream and records no third event: the event after the copy
+  // and the wait for it cost 7 us per call, a tenth of that pair's wall time.  Behind the last of several units the
+  // stream wait is the slower one (profiles/r19_matcher_plan.txt).
+  const bool one_unit = n == 1;
+  float total_ms = 0.0f;
+  const hipError_t err = hess::slot_pipeline(
+      n, hipSuccess,
+      [&](size_t k, int slot) -> hipError_t {
+        size_t bytes = 0;
+        hipError_t e = enqueue(k, slot, &bytes);
+        if (e != hipSuccess) return e;
+        (void)hipEventRecord(m->mp_ev[slot][1], m->st);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(m->hout.p[slot], m->out.p, bytes, hipMemcpyDeviceToHost, m->st);
+        if (e == hipSuccess && !one_unit) (void)hipEventRecord(m->mp_ev[slot][2], m->st);
+        return e;
+      },
+      [&](size_t k, int slot) -> hipError_t {
+        hipError_t e = one_unit ? hipStreamSynchronize(m->st) : hipEventSynchronize(m->mp_ev[slot][2]);
+        if (e != hipSuccess) return e;
+        float ms = 0.0f;
+        e = hipEventElapsedTime(&ms, m->mp_ev[slot][0], m->mp_ev[slot][1]);
+        if (e != hipSuccess) return e;
+        total_ms += ms;
+        deliver(k, m->hout.p[slot]);
+        return hipSuccess;
+      });
+  if (err != hipSuccess) {
+    (void)hipStreamSynchronize(m->st);
+    m->err = std::string(what) + ": " + hipGetErrorString(err);
+    return HESS_ERR_DEVICE;
+  }
+  m->last_ms = total_ms;
+  return 0;
+}
+
+// Plans the pair list pairs_ab of sets s1 x s2 (plan_pairs), runs it chunk by chunk (run_slots) and delivers every pair's
+// matches compacted on the device: out_counts[p] and out_pairs[p][max_match][2] (in the pinned slot the pairs are P.mm
+// apart).  m->last_ms covers multiply, finish and compaction.  `what` names the entry point in the text of an error.
 // geo (with loc, the locations both sets' `first` index; untyped sets): the guided match, pair p gated by geo[p] -- the table
 // goes up once, before the first chunk, and chunk k's launch reads it from its first pair on.
 int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npairs, const int* pairs_ab, int max_match,
@@ -1271,7 +1371,7 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
     m->err = std::string(what) + ": a pair needs more scratch than one launch can address";
     return HESS_ERR_TOO_BIG;
   }
-  if (const int rc = grow_for(m, P.need)) return rc;
+  if (const int rc = grow_for(m, P.need, P.need.plan_bytes, P.need.outn * sizeof(int))) return rc;
   if (geo) {
     std::vector<GuidedGeo> h((size_t)npairs);
     for (int p = 0; p < npairs; p++) {
@@ -1286,65 +1386,39 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
       g.la = s1.first[pairs_ab[2 * p]];
       g.lb = s2.first[pairs_ab[2 * p + 1]];
     }
-    M_TRY(m, grow_device(m->geo, m->geo_cap, (size_t)npairs));
-    M_TRY(m, hipMemcpy(m->geo, h.data(), h.size() * sizeof(GuidedGeo), hipMemcpyHostToDevice));  // (complete on return)
+    M_TRY(m, m->geo.grow((size_t)npairs));
+    M_TRY(m, hipMemcpy(m->geo.p, h.data(), h.size() * sizeof(GuidedGeo), hipMemcpyHostToDevice));  // (complete on return)
   }
   const int mm = P.mm;
-  // A list of one chunk (the typed single pair) waits for the stream and records no third event: the event after the copy
-  // and the wait for it cost 7 us per call, a tenth of that pair's wall time.  Behind the last of several chunks the
-  // stream wait is the slower one (profiles/r19_matcher_plan.txt).
-  const bool one_chunk = P.chunks.size() == 1;
-  float total_ms = 0.0f;
-  auto collect = [&](size_t k) -> hipError_t {
-    const Chunk& c = P.chunks[k];
-    hipEvent_t* ev = m->mp_ev[k & 1];
-    hipError_t e = one_chunk ? hipStreamSynchronize(m->st) : hipEventSynchronize(ev[2]);
-    if (e != hipSuccess) return e;
-    float ms = 0.0f;
-    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e != hipSuccess) return e;
-    total_ms += ms;
-    const int* h = m->mp_hout[k & 1];
-    const int q0 = c.p0 / c.jpp, q1 = c.p1 / c.jpp;
-    for (int p = q0; p < q1; p++) {
-      const int n = h[p - q0];
-      out_counts[p] = n;
-      if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - q0) * mm * 2, (size_t)n * 2 * sizeof(int));
-    }
-    return hipSuccess;
-  };
-  hipError_t err = hipSuccess;
-  for (size_t k = 0; k < P.chunks.size() && err == hipSuccess; k++) {
-    const Chunk& c = P.chunks[k];
-    const PlanLayout L = plan_layout(c);
-    hipEvent_t* ev = m->mp_ev[k & 1];
-    err = run_chunk(m, s1, s2, P.jobs.data(), P.orig.data(), c, m->hplan[k & 1], ev[0], mutual_best, distmax, ratiomax,
-                    geo ? m->geo + c.p0 : nullptr, loc);
-    if (err != hipSuccess) break;
-    if (P.jpp == 4)
-      hipLaunchKernelGGL(match_types_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan, L.jobs),
-                         plan_ptr<int2>(m->plan, L.orig), s1.fwd, s2.inv, m->rowm, m->colm, mutual_best, mm, m->mp_out,
-                         m->mp_out + MP_PAIRS);
-    else
-      hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan, L.jobs),
-                         m->rowm, m->colm, mutual_best, mm, m->mp_out, m->mp_out + MP_PAIRS);
-    (void)hipEventRecord(ev[1], m->st);
-    err = hipGetLastError();
-    if (err != hipSuccess) break;
-    err = hipMemcpyAsync(m->mp_hout[k & 1], m->mp_out, (MP_PAIRS + (size_t)c.pairs() * mm * 2) * sizeof(int),
-                         hipMemcpyDeviceToHost, m->st);
-    if (err != hipSuccess) break;
-    if (!one_chunk) (void)hipEventRecord(ev[2], m->st);
-    if (k > 0) err = collect(k - 1);
-  }
-  if (err == hipSuccess) err = collect(P.chunks.size() - 1);
-  if (err != hipSuccess) {
-    (void)hipStreamSynchronize(m->st);
-    m->err = std::string(what) + ": " + hipGetErrorString(err);
-    return HESS_ERR_DEVICE;
-  }
-  m->last_ms = total_ms;
-  return 0;
+  int* const dout = reinterpret_cast<int*>(m->out.p);
+  return run_slots(
+      m, P.chunks.size(), what,
+      [&](size_t k, int slot, size_t* bytes) -> hipError_t {
+        const Chunk& c = P.chunks[k];
+        const PlanLayout L = plan_layout(c);
+        const hipError_t e = run_chunk(m, s1, s2, P.jobs.data(), P.orig.data(), c, m->hplan.p[slot], m->mp_ev[slot][0], mutual_best,
+                                       distmax, ratiomax, geo ? m->geo.p + c.p0 : nullptr, loc);
+        if (e != hipSuccess) return e;
+        if (P.jpp == 4)
+          hipLaunchKernelGGL(match_types_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan.p, L.jobs),
+                             plan_ptr<int2>(m->plan.p, L.orig), s1.fwd, s2.inv, m->rowm.p, m->colm.p, mutual_best, mm, dout,
+                             dout + MP_PAIRS);
+        else
+          hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan.p, L.jobs),
+                             m->rowm.p, m->colm.p, mutual_best, mm, dout, dout + MP_PAIRS);
+        *bytes = (MP_PAIRS + (size_t)c.pairs() * mm * 2) * sizeof(int);
+        return hipSuccess;
+      },
+      [&](size_t k, const uint8_t* slot_bytes) {
+        const Chunk& c = P.chunks[k];
+        const int* h = reinterpret_cast<const int*>(slot_bytes);
+        const int q0 = c.p0 / c.jpp, q1 = c.p1 / c.jpp;
+        for (int p = q0; p < q1; p++) {
+          const int n = h[p - q0];
+          out_counts[p] = n;
+          if (n) memcpy(out_pairs + (size_t)p * max_match * 2, h + MP_PAIRS + (size_t)(p - q0) * mm * 2, (size_t)n * 2 * sizeof(int));
+        }
+      });
 }
 
 // hess_matcher_verify_pairs works on GROUPS of up to VP_GROUP consecutive chunks of the pair plan: the matcher's kernels run
@@ -1353,7 +1427,7 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
 // a few hundred pairs on (profiles/r22_verify_pairs.txt): a group is what one chunk of hess_matcher_estimate_pairs holds.
 constexpr int VP_GROUP = 4, VP_PAIRS = VP_GROUP * MP_PAIRS;
 
-// Where a group's results sit in m->vp_out and in its pinned slot.  A head of fixed size (the counts of both matches and the
+// Where a group's results sit in m->out and in its pinned slot.  A head of fixed size (the counts of both matches and the
 // results of both estimates, VP_PAIRS entries each), the guided matches, then the mask of the final estimate and the
 // putative matches where the caller takes them: [0, copy) is what one copy brings down.  The sections the caller does not
 // take, and the putative estimate's mask, lie behind it.  Matches and masks are mm per pair.
@@ -1383,7 +1457,7 @@ VerifyLayout verify_layout(int np, int mm, bool want_mask, bool want_put) {
 // matches (hess_geom_enqueue: counts and matches stay on the device); the group's guided geometry (verify_geo_kernel); per
 // chunk the guided multiply, finish and compaction from the SAME plan buffer and scratch (the first compaction has consumed
 // the decisions); optionally the estimate again; one copy into the pinned slot g & 1, read while group g + 1 runs
-// (run_pairs' double buffer).  Arguments are checked and nothing has been launched.
+// (run_slots).  Arguments are checked and nothing has been launched.
 int run_verify(hess_matcher* m, int npairs, const int* pairs_ab, const hess_verify_params& V, int max_match, int* out_pairs,
                int* out_counts, hess_verify_result* out, unsigned char* inlier, int* putative_pairs, const float2* loc) {
   const char* const what = "verify_pairs";
@@ -1407,132 +1481,97 @@ int run_verify(hess_matcher* m, int npairs, const int* pairs_ab, const hess_veri
     return HESS_ERR_TOO_BIG;
   }
   const size_t pstride = (P.need.plan_bytes + 63) / 64 * 64;  // a chunk's plan buffer within the group's
-  PlanNeed need = P.need;
-  need.outn = need.plan_bytes = 0;  // (match_pairs' compacted output and its one plan buffer are not used)
-  if (const int rc = grow_for(m, need)) return rc;
-  if (const int rc = slot_events(m)) return rc;
-  const size_t bytes = verify_layout(npmax, mm, want_mask, want_put).bytes;
-  M_TRY(m, grow_device(m->vp_out, m->vp_out_cap, bytes));
-  M_TRY(m, grow_pinned(m->vp_hout, m->vp_hout_cap, bytes));
-  M_TRY(m, grow_device(m->vp_plan, m->vp_plan_cap, VP_GROUP * pstride));
-  M_TRY(m, grow_pinned(m->vp_hplan, m->vp_hplan_cap, VP_GROUP * pstride));
-  M_TRY(m, grow_device(m->geo, m->geo_cap, (size_t)VP_PAIRS));
-  M_TRY(m, grow_device(m->vp_lalb, m->vp_lalb_cap, (size_t)npairs));
+  if (const int rc = grow_for(m, P.need, VP_GROUP * pstride, verify_layout(npmax, mm, want_mask, want_put).bytes)) return rc;
+  M_TRY(m, m->geo.grow((size_t)VP_PAIRS));
+  M_TRY(m, m->vp_lalb.grow((size_t)npairs));
   if (const int rc = hess_geom_reserve(m, V.geom, npmax, mm)) return rc;
   std::vector<int2> lalb((size_t)npairs);  // (alive until the stream has been waited for: every return below)
   for (int p = 0; p < npairs; p++) lalb[p] = make_int2(S.first[pairs_ab[2 * p]], S.first[pairs_ab[2 * p + 1]]);
-  M_TRY(m, hipMemcpyAsync(m->vp_lalb, lalb.data(), lalb.size() * sizeof(int2), hipMemcpyHostToDevice, m->st));
+  M_TRY(m, hipMemcpyAsync(m->vp_lalb.p, lalb.data(), lalb.size() * sizeof(int2), hipMemcpyHostToDevice, m->st));
   if (inlier) memset(inlier, 0, (size_t)npairs * max_match);
   const float gbound = V.guided_bound != 0.0f ? V.guided_bound : V.geom.bound;
   hess_geom_result none;
   memset(&none, 0, sizeof(none));
   none.hypothesis = -1;
-  const bool one_group = ngroups == 1;  // (see run_pairs' one_chunk)
-  float total_ms = 0.0f;
-  auto collect = [&](size_t g) -> hipError_t {
-    const int p0 = group_first(g), np = group_end(g) - p0;
-    hipEvent_t* ev = m->mp_ev[g & 1];
-    hipError_t e = one_group ? hipStreamSynchronize(m->st) : hipEventSynchronize(ev[2]);
-    if (e != hipSuccess) return e;
-    float ms = 0.0f;
-    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e != hipSuccess) return e;
-    total_ms += ms;
-    const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
-    const uint8_t* h = m->vp_hout[g & 1];
-    const int* n1 = reinterpret_cast<const int*>(h + L.cnt1);
-    const int* n2 = reinterpret_cast<const int*>(h + L.cnt2);
-    for (int q = 0; q < np; q++) {
-      const size_t p = (size_t)p0 + q;
-      hess_verify_result& R = out[p];
-      memset(&R, 0, sizeof(R));
-      memcpy(&R.putative, h + L.res1 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
-      if (fin) memcpy(&R.final, h + L.res2 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
-      else R.final = none;
-      R.nputative = n1[q];
-      R.nguided = out_counts[p] = n2[q];
-      if (n2[q]) memcpy(out_pairs + p * max_match * 2, h + L.guided + (size_t)q * mm * 2 * sizeof(int), (size_t)n2[q] * 2 * sizeof(int));
-      if (want_mask && n2[q]) memcpy(inlier + p * max_match, h + L.mask2 + (size_t)q * mm, (size_t)n2[q]);
-      if (want_put && n1[q])
-        memcpy(putative_pairs + p * max_match * 2, h + L.put + (size_t)q * mm * 2 * sizeof(int), (size_t)n1[q] * 2 * sizeof(int));
-    }
-    return hipSuccess;
-  };
-  hipError_t err = hipSuccess;
+  uint8_t* const d = m->out.p;
   // The two matches of the group's chunk k from its plan buffer: multiply and finish (guided with dgeo), then the compaction
   // to the chunk's place (its first pair's offset in the group) in the count words at `cnt` and the lists at `lists`.
   auto match_chunk = [&](size_t k, int p0, size_t cnt, size_t lists, const GuidedGeo* dgeo) -> hipError_t {
     const Chunk& c = P.chunks[k];
-    const uint8_t* const dplan = m->vp_plan + (k % VP_GROUP) * pstride;
+    const uint8_t* const dplan = m->plan.p + (k % VP_GROUP) * pstride;
     const int q0 = c.p0 - p0;
     const hipError_t e = launch_chunk(m, dplan, S, S, c, mutual_best, V.distmax, V.ratiomax, dgeo ? dgeo + q0 : nullptr, loc);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(dplan, plan_layout(c).jobs),
-                       m->rowm, m->colm, mutual_best, mm, reinterpret_cast<int*>(m->vp_out + cnt) + q0,
-                       reinterpret_cast<int*>(m->vp_out + lists) + (size_t)q0 * mm * 2);
+                       m->rowm.p, m->colm.p, mutual_best, mm, reinterpret_cast<int*>(d + cnt) + q0,
+                       reinterpret_cast<int*>(d + lists) + (size_t)q0 * mm * 2);
     return hipGetLastError();
   };
-  for (size_t g = 0; g < ngroups && err == hipSuccess; g++) {
-    const size_t k0 = g * VP_GROUP, k1 = std::min(nchunks, k0 + VP_GROUP);
-    const int p0 = group_first(g), np = group_end(g) - p0;
-    const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
-    hipEvent_t* ev = m->mp_ev[g & 1];
-    uint8_t* const d = m->vp_out;
-    uint8_t* const hp = m->vp_hplan[g & 1];
-    hess_geom_device_pairs E{np, mm, m->vp_lalb + p0, reinterpret_cast<const int*>(d + L.cnt1), reinterpret_cast<const int2*>(d + L.put),
-                             V.geom.seed + (uint32_t)p0, reinterpret_cast<hess_geom_result*>(d + L.res1), d + L.mask1};
-    for (size_t k = k0; k < k1; k++) plan_fill(hp + (k - k0) * pstride, P.jobs.data(), nullptr, P.chunks[k], mutual_best);
-    err = hipMemcpyAsync(m->vp_plan, hp, (k1 - k0 - 1) * pstride + plan_layout(P.chunks[k1 - 1]).bytes, hipMemcpyHostToDevice, m->st);
-    if (err != hipSuccess) break;
-    (void)hipEventRecord(ev[0], m->st);
-    for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt1, L.put, nullptr);
-    if (err != hipSuccess) break;
-    err = hess_geom_enqueue(m, V.geom, E);
-    if (err != hipSuccess) break;
-    hipLaunchKernelGGL(verify_geo_kernel, dim3((np + 63) / 64), dim3(64), 0, m->st, E.results, E.lalb, np,
-                       V.geom.model == HESS_GEOM_HOMOGRAPHY ? 1 : 0, gbound, m->geo);
-    for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt2, L.guided, m->geo);
-    if (err != hipSuccess) break;
-    if (fin) {
-      E.counts = reinterpret_cast<const int*>(d + L.cnt2);
-      E.matches = reinterpret_cast<const int2*>(d + L.guided);
-      E.results = reinterpret_cast<hess_geom_result*>(d + L.res2);
-      E.mask = d + L.mask2;
-      err = hess_geom_enqueue(m, V.geom, E);
-      if (err != hipSuccess) break;
-    }
-    (void)hipEventRecord(ev[1], m->st);
-    err = hipGetLastError();
-    if (err != hipSuccess) break;
-    err = hipMemcpyAsync(m->vp_hout[g & 1], d, L.copy, hipMemcpyDeviceToHost, m->st);
-    if (err != hipSuccess) break;
-    if (!one_group) (void)hipEventRecord(ev[2], m->st);
-    if (g > 0) err = collect(g - 1);
-  }
-  if (err == hipSuccess) err = collect(ngroups - 1);
-  if (err != hipSuccess) {
-    (void)hipStreamSynchronize(m->st);
-    m->err = std::string(what) + ": " + hipGetErrorString(err);
-    return HESS_ERR_DEVICE;
-  }
-  m->last_ms = total_ms;
-  return 0;
+  return run_slots(
+      m, ngroups, what,
+      [&](size_t g, int slot, size_t* bytes) -> hipError_t {
+        const size_t k0 = g * VP_GROUP, k1 = std::min(nchunks, k0 + VP_GROUP);
+        const int p0 = group_first(g), np = group_end(g) - p0;
+        const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
+        uint8_t* const hp = m->hplan.p[slot];
+        hess_geom_device_pairs E{np, mm, m->vp_lalb.p + p0, reinterpret_cast<const int*>(d + L.cnt1), reinterpret_cast<const int2*>(d + L.put),
+                                 V.geom.seed + (uint32_t)p0, reinterpret_cast<hess_geom_result*>(d + L.res1), d + L.mask1};
+        for (size_t k = k0; k < k1; k++) plan_fill(hp + (k - k0) * pstride, P.jobs.data(), nullptr, P.chunks[k], mutual_best);
+        hipError_t err = hipMemcpyAsync(m->plan.p, hp, (k1 - k0 - 1) * pstride + plan_layout(P.chunks[k1 - 1]).bytes, hipMemcpyHostToDevice, m->st);
+        if (err != hipSuccess) return err;
+        (void)hipEventRecord(m->mp_ev[slot][0], m->st);
+        for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt1, L.put, nullptr);
+        if (err != hipSuccess) return err;
+        err = hess_geom_enqueue(m, V.geom, E);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL(verify_geo_kernel, dim3((np + 63) / 64), dim3(64), 0, m->st, E.results, E.lalb, np,
+                           V.geom.model == HESS_GEOM_HOMOGRAPHY ? 1 : 0, gbound, m->geo.p);
+        for (size_t k = k0; k < k1 && err == hipSuccess; k++) err = match_chunk(k, p0, L.cnt2, L.guided, m->geo.p);
+        if (err != hipSuccess) return err;
+        if (fin) {
+          E.counts = reinterpret_cast<const int*>(d + L.cnt2);
+          E.matches = reinterpret_cast<const int2*>(d + L.guided);
+          E.results = reinterpret_cast<hess_geom_result*>(d + L.res2);
+          E.mask = d + L.mask2;
+          err = hess_geom_enqueue(m, V.geom, E);
+        }
+        *bytes = L.copy;
+        return err;
+      },
+      [&](size_t g, const uint8_t* h) {
+        const int p0 = group_first(g), np = group_end(g) - p0;
+        const VerifyLayout L = verify_layout(np, mm, want_mask, want_put);
+        const int* n1 = reinterpret_cast<const int*>(h + L.cnt1);
+        const int* n2 = reinterpret_cast<const int*>(h + L.cnt2);
+        for (int q = 0; q < np; q++) {
+          const size_t p = (size_t)p0 + q;
+          hess_verify_result& R = out[p];
+          memset(&R, 0, sizeof(R));
+          memcpy(&R.putative, h + L.res1 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
+          if (fin) memcpy(&R.final, h + L.res2 + q * sizeof(hess_geom_result), sizeof(hess_geom_result));
+          else R.final = none;
+          R.nputative = n1[q];
+          R.nguided = out_counts[p] = n2[q];
+          if (n2[q]) memcpy(out_pairs + p * max_match * 2, h + L.guided + (size_t)q * mm * 2 * sizeof(int), (size_t)n2[q] * 2 * sizeof(int));
+          if (want_mask && n2[q]) memcpy(inlier + p * max_match, h + L.mask2 + (size_t)q * mm, (size_t)n2[q]);
+          if (want_put && n1[q])
+            memcpy(putative_pairs + p * max_match * 2, h + L.put + (size_t)q * mm * 2 * sizeof(int), (size_t)n1[q] * 2 * sizeof(int));
+        }
+      });
 }
 
 // The small unguided and the guided single pair, from m->e0 on: the score matrix (match_dot_kernel, gates per pair), the row
 // decisions and, for mutual best, the column decisions.
 int match_small(hess_matcher* m, int n1, int n2, const float* H, const float* F, float distmax, float ratiomax,
                 float hdistmax, float fdistmax, int mutual_best) {
-  M_TRY(m, grow_device(m->rowm, m->rowm_cap, (size_t)n1));
-  M_TRY(m, grow_device(m->colm, m->colm_cap, (size_t)n2));
+  M_TRY(m, m->rowm.grow((size_t)n1));
+  M_TRY(m, m->colm.grow((size_t)n2));
   const size_t need = (size_t)n1 * n2;
-  if (need > m->mat_cap) {
-    (void)hipFree(m->cpart); (void)hipFree(m->dotm);
-    m->cpart = nullptr;
-    m->dotm = nullptr;
-    M_TRY(m, hipMalloc(&m->cpart, (size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift * sizeof(int3)));
-    M_TRY(m, hipMalloc(&m->dotm, need * sizeof(int)));
-    m->mat_cap = need;
+  if (need > m->dotm.cap) {  // the column partials go with the matrix: for max_sift rows and columns, whatever the pair has
+    m->cpart.reset();
+    m->dotm.reset();
+    M_TRY(m, m->cpart.grow((size_t)((m->max_sift + TM - 1) / TM + 1) * m->max_sift));
+    M_TRY(m, m->dotm.grow(need));
   }
   GeoParams gp;
   memset(&gp, 0, sizeof(gp));
@@ -1540,13 +1579,13 @@ int match_small(hess_matcher* m, int n1, int n2, const float* H, const float* F,
   if (gp.guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
   (void)hipEventRecord(m->e0, m->st);
   hipLaunchKernelGGL(m->dim == 128 ? match_dot_kernel<128> : match_dot_kernel<64>, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM),
-                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->loc[0], m->loc[1], gp,
-                     mutual_best ? m->cpart : nullptr, m->dotm);
-  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm, n1, n2, distmax, ratiomax,
-                     m->rowm);
+                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->slot[0].loc, m->slot[1].loc, gp,
+                     mutual_best ? m->cpart.p : nullptr, m->dotm.p);
+  hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm.p, n1, n2, distmax, ratiomax,
+                     m->rowm.p);
   if (mutual_best)
-    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart, (n1 + TM - 1) / TM, n2,
-                       distmax, ratiomax, m->colm);
+    hipLaunchKernelGGL(match_col_kernel, dim3((n2 + 31) / 32), dim3(256), 0, m->st, m->cpart.p, (n1 + TM - 1) / TM, n2,
+                       distmax, ratiomax, m->colm.p);
   return 0;
 }
 
@@ -1576,22 +1615,13 @@ hess_matcher* hess_matcher_create(int device, int max_sift) {
 void hess_matcher_destroy(hess_matcher* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  sets_clear(m->bank);
-  for (int k = 0; k < 2; k++) { sets_clear(m->slot[k]); (void)hipFree(m->loc[k]); }
-  (void)hipFree(m->cpart); (void)hipFree(m->dotm);
-  (void)hipFree(m->mm_rstate); (void)hipFree(m->mm_cpart); (void)hipFree(m->plan);
-  (void)hipFree(m->rowm); (void)hipFree(m->colm); (void)hipFree(m->mp_out); (void)hipFree(m->geo);
-  (void)hipFree(m->vp_out); (void)hipFree(m->vp_plan); (void)hipFree(m->vp_lalb);
-  hess_geom_state_destroy(m->geom);
-  for (int k = 0; k < 2; k++) {
-    (void)hipHostFree(m->hplan[k]); (void)hipHostFree(m->mp_hout[k]); (void)hipHostFree(m->vp_hout[k]); (void)hipHostFree(m->vp_hplan[k]);
-    for (int q = 0; q < 3; q++)
-      if (m->mp_ev[k][q]) (void)hipEventDestroy(m->mp_ev[k][q]);
-  }
-  if (m->e0) (void)hipEventDestroy(m->e0);
-  if (m->e1) (void)hipEventDestroy(m->e1);
-  if (m->st) (void)hipStreamDestroy(m->st);
-  delete m;
+  const hipStream_t st = m->st;
+  hipEvent_t ev[8] = {m->e0, m->e1};
+  memcpy(ev + 2, m->mp_ev, sizeof(m->mp_ev));
+  delete m;  // (the sets and every buffer)
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  if (st) (void)hipStreamDestroy(st);
 }
 
 int hess_matcher_set_max(hess_matcher* m, int max_sift) {
@@ -1612,13 +1642,7 @@ int hess_matcher_set_dim(hess_matcher* m, int dim) {
   M_TRY(m, hipSetDevice(m->device));
   M_TRY(m, hipStreamSynchronize(m->st));
   sets_clear(m->bank);
-  hess_geom_drop_bank_locations(m->geom);
-  for (int k = 0; k < 2; k++) {
-    sets_clear(m->slot[k]);
-    (void)hipFree(m->loc[k]);
-    m->loc[k] = nullptr;
-    m->have_loc[k] = 0;
-  }
+  for (int k = 0; k < 2; k++) sets_clear(m->slot[k]);
   m->dim = dim;
   return 0;
 }
@@ -1631,7 +1655,6 @@ int hess_matcher_set_descriptors(hess_matcher* m, int index, int num, const unsi
   index = index > 1 ? 1 : (index < 0 ? 0 : index);
   M_TRY(m, hipSetDevice(m->device));
   if (num > m->max_sift) num = m->max_sift;
-  m->have_loc[index] = 0;
   return sets_load(m, m->slot[index], 1, &num, des, (size_t)num);
 }
 
@@ -1646,15 +1669,16 @@ int hess_matcher_set_descriptors_f32(hess_matcher* m, int index, int num, const 
 // SiftMatchCU::SetFeautreLocation, SiftMatchCU.cpp:103-123: (x, y) pairs, `gap` floats skipped after each.
 int hess_matcher_set_locations(hess_matcher* m, int index, const float* locations, int gap) {
   if (!m || !locations || index < 0 || index > 1) return HESS_ERR_ARG;
-  const int n = m->slot[index].count(0);
+  DescSets& s = m->slot[index];
+  const int n = s.count(0);
   if (n <= 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
   std::vector<float2> h((size_t)n);
   for (int i = 0; i < n; i++) { h[i].x = locations[0]; h[i].y = locations[1]; locations += 2 + gap; }
-  (void)hipFree(m->loc[index]);
-  M_TRY(m, hipMalloc(&m->loc[index], (size_t)n * sizeof(float2)));
-  M_TRY(m, hipMemcpy(m->loc[index], h.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
-  m->have_loc[index] = 1;
+  sets_drop_locations(s);
+  M_TRY(m, hipMalloc(&s.loc, (size_t)n * sizeof(float2)));
+  M_TRY(m, hipMemcpy(s.loc, h.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
+  s.have_loc = true;
   return 0;
 }
 
@@ -1677,7 +1701,7 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
   }
   if (n1 <= 0 || n2 <= 0) return 0;
   if (guided && (!H || !F)) { m->err = "guided matching needs both H and F"; return HESS_ERR_ARG; }
-  if (guided && (!m->have_loc[0] || !m->have_loc[1])) return 0;  // SiftMatchCU.cpp:131
+  if (guided && (!m->slot[0].have_loc || !m->slot[1].have_loc)) return 0;  // SiftMatchCU.cpp:131
   M_TRY(m, hipSetDevice(m->device));
   if (typed) {
     // the gated pair: a list of one through the job tables at any size (bank pairs take them below the switch too), compacted
@@ -1692,16 +1716,16 @@ int hess_matcher_match(hess_matcher* m, int max_match, int* pairs, const float* 
     PairJob job{0, 0, n1, n2};
     Chunk c{0, 1, single_sps(n1, n2), 0, 0, 0, 0, 0, 0, 1};
     plan_chunk(&job, c, mutual_best);
-    if (const int rc = grow_for(m, PlanNeed{c.rs, c.cp, c.rm, c.cm, plan_layout(c).bytes, 0})) return rc;  // (0: compacted on the host, below)
-    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], &job, nullptr, c, m->hplan[0], m->e0, mutual_best, distmax, ratiomax));
+    if (const int rc = grow_for(m, PlanNeed{c.rs, c.cp, c.rm, c.cm, 0, 0}, plan_layout(c).bytes, 0)) return rc;  // (0: compacted on the host, below)
+    M_TRY(m, run_chunk(m, m->slot[0], m->slot[1], &job, nullptr, c, m->hplan.p[0], m->e0, mutual_best, distmax, ratiomax));
   } else if (const int rc = match_small(m, n1, n2, H, F, distmax, ratiomax, hdistmax, fdistmax, mutual_best)) {
     return rc;
   }
   (void)hipEventRecord(m->e1, m->st);
   m->hrow.resize(n1);
   m->hcol.resize(n2);
-  M_TRY(m, hipMemcpyAsync(m->hrow.data(), m->rowm, (size_t)n1 * 4, hipMemcpyDeviceToHost, m->st));
-  if (mutual_best) M_TRY(m, hipMemcpyAsync(m->hcol.data(), m->colm, (size_t)n2 * 4, hipMemcpyDeviceToHost, m->st));
+  M_TRY(m, hipMemcpyAsync(m->hrow.data(), m->rowm.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, m->st));
+  if (mutual_best) M_TRY(m, hipMemcpyAsync(m->hcol.data(), m->colm.p, (size_t)n2 * 4, hipMemcpyDeviceToHost, m->st));
   M_TRY(m, hipStreamSynchronize(m->st));
   (void)hipEventElapsedTime(&m->last_ms, m->e0, m->e1);
   int nmatch = 0;
@@ -1722,7 +1746,6 @@ int hess_matcher_bank_set(hess_matcher* m, int nsets, const int* counts, const u
   size_t rows = 0;
   if (const int rc = bank_args(m, nsets, counts, des, &rows)) return rc;
   M_TRY(m, hipSetDevice(m->device));
-  hess_geom_drop_bank_locations(m->geom);
   return sets_load(m, m->bank, nsets, counts, des, rows);
 }
 
@@ -1774,7 +1797,6 @@ static int bank_set_device(hess_matcher* m, int nsets, const int* counts, const 
     if (const int rc = device_range(m, dev_desc, rows * (size_t)m->dim * esz, "bank_set_device", "descriptors")) return rc;
   }
   sets_clear(m->bank);
-  hess_geom_drop_bank_locations(m->geom);
   const int rc = sets_build(m, m->bank, nsets, counts, dev_desc, f32);
   if (rc) sets_clear(m->bank);
   return rc;
@@ -1844,6 +1866,40 @@ int hess_matcher_bank_set_types_device(hess_matcher* m, const void* dev_types, s
   return sets_regroup(m, m->bank, dev_types, stride_bytes);
 }
 
+// ---- the bank's locations, for guided pair lists and the estimator: they stay with the bank's descriptors -------------
+
+int hess_matcher_bank_set_locations(hess_matcher* m, const float* loc, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  if (!loc) { sets_drop_locations(m->bank); return 0; }
+  size_t rows = 0;
+  if (const int rc = bank_locations_args(m, stride_bytes, "bank_set_locations", &rows)) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  // the (x, y) pairs packed on the host, staged on the device, then the device form's gather
+  std::vector<float2> h(rows ? rows : 1);
+  for (size_t i = 0; i < rows; i++) memcpy(&h[i], reinterpret_cast<const char*>(loc) + i * stride_bytes, sizeof(float2));
+  float2* d = nullptr;
+  M_TRY(m, hipMalloc(&d, h.size() * sizeof(float2)));
+  const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
+  const int rc = e == hipSuccess ? bank_locations(m, d, sizeof(float2)) : 0;
+  (void)hipFree(d);
+  M_TRY(m, e);
+  return rc;
+}
+
+int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc, size_t stride_bytes) {
+  if (!m) return HESS_ERR_ARG;
+  if (!dev_loc) { sets_drop_locations(m->bank); return 0; }
+  size_t rows = 0;
+  if (const int rc = bank_locations_args(m, stride_bytes, "bank_set_locations_device", &rows)) return rc;
+  M_TRY(m, hipSetDevice(m->device));
+  if (rows) {
+    if ((uintptr_t)dev_loc % 4) { m->err = "bank_set_locations_device: dev_loc must be 4-byte aligned"; return HESS_ERR_ARG; }
+    if (const int rc = device_range(m, dev_loc, (rows - 1) * stride_bytes + 8, "bank_set_locations_device", "locations"))
+      return rc;
+  }
+  return bank_locations(m, dev_loc, stride_bytes);
+}
+
 int hess_matcher_match_pairs(hess_matcher* m, int npairs, const int* pairs_ab, int max_match, int* out_pairs,
                              int* out_counts, float distmax, float ratiomax, int mutual_best) {
   if (!m) return HESS_ERR_ARG;
@@ -1867,8 +1923,7 @@ int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pair
     m->err = "match_pairs_guided: guided matching with feature types is not built; remove the bank's types (bank_set_types NULL) first";
     return HESS_ERR_UNSUPPORTED;
   }
-  const float2* loc = nullptr;
-  if (!hess_geom_bank_locations(m->geom, &loc)) {
+  if (!m->bank.have_loc) {
     m->err = "match_pairs_guided: the bank has no locations (hess_matcher_bank_set_locations after loading the bank)";
     return HESS_ERR_STATE;
   }
@@ -1876,7 +1931,7 @@ int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pair
   if (npairs == 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
   return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best ? 1 : 0,
-                   "match_pairs_guided", geo, loc);
+                   "match_pairs_guided", geo, m->bank.loc);
 }
 
 // Match, estimate, guided match and (optionally) estimate of every pair of a list, chained on the device: run_verify.
@@ -1908,15 +1963,14 @@ int hess_matcher_verify_pairs(hess_matcher* m, int npairs, const int* pairs_ab, 
     m->err = "verify_pairs: guided matching with feature types is not built; remove the bank's types (bank_set_types NULL) first";
     return HESS_ERR_UNSUPPORTED;
   }
-  const float2* loc = nullptr;
-  if (!hess_geom_bank_locations(m->geom, &loc)) {
+  if (!m->bank.have_loc) {
     m->err = "verify_pairs: the bank has no locations (hess_matcher_bank_set_locations after loading the bank)";
     return HESS_ERR_STATE;
   }
   m->last_ms = 0.0f;
   if (npairs == 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
-  return run_verify(m, npairs, pairs_ab, *params, max_match, out_pairs, out_counts, out, inlier, putative_pairs, loc);
+  return run_verify(m, npairs, pairs_ab, *params, max_match, out_pairs, out_counts, out, inlier, putative_pairs, m->bank.loc);
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }
@@ -1926,26 +1980,9 @@ const char* hess_matcher_last_error(hess_matcher* m) { return m ? m->err.c_str()
 
 // ---- hess_matcher_int.h: the estimator's (hess_geom.hip) access to a matcher ------------------------------------------
 
-int hess_matcher_device_range(hess_matcher* m, const void* p, size_t bytes, const char* what, const char* noun) {
-  return device_range(m, p, bytes, what, noun);
-}
-
 hess_matcher_view hess_matcher_view_of(hess_matcher* m) {
-  hess_matcher_view v;
-  v.device = m->device;
-  v.st = m->st;
-  v.e0 = m->e0;
-  v.e1 = m->e1;
-  v.err = &m->err;
-  v.last_ms = &m->last_ms;
-  for (int k = 0; k < 2; k++) {
-    v.loc[k] = m->loc[k];
-    v.nloc[k] = m->have_loc[k] ? m->slot[k].count(0) : -1;
-  }
-  v.bank_built = m->bank.built;
-  v.bank_num = &m->bank.num;
-  v.bank_cnt = &m->bank.cnt;
-  v.bank_first = &m->bank.first;
-  v.geom = &m->geom;
-  return v;
+  const DescSets *s = m->slot, &b = m->bank;
+  return {m->device, m->st, m->e0, m->e1, m->err, &m->last_ms, {s[0].loc, s[1].loc},
+          {s[0].have_loc ? s[0].count(0) : -1, s[1].have_loc ? s[1].count(0) : -1},
+          b.built, &b.num, &b.cnt, &b.first, b.loc, b.have_loc, &m->geom};
 }

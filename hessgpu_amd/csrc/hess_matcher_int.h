@@ -1,41 +1,39 @@
-// hess_matcher_int.h -- what hess_geom.hip needs of a matcher.  struct hess_matcher stays in hess_match.hip; the estimator
-// reads it through this view and keeps its own state (bank locations, buffers) behind one pointer the matcher owns.
+// hess_matcher_int.h -- what hess_match.hip and hess_geom.hip share.  struct hess_matcher stays in hess_match.hip; the estimator
+// reads it through this view and keeps its own scratch buffers behind one pointer the matcher owns.  The buffer types of both.
 #ifndef HESS_MATCHER_INT_H
 #define HESS_MATCHER_INT_H
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/hess_abi.h"
 
 struct hess_matcher;
-struct hess_geom_state;  // hess_geom.hip
+struct hess_geom_state;  // hess_geom.hip: created there on first use, destroyed with the matcher
+void hess_geom_state_destroy(hess_geom_state* g);
+struct hess_geom_state_delete { void operator()(hess_geom_state* g) const { hess_geom_state_destroy(g); } };
+using hess_geom_state_ptr = std::unique_ptr<hess_geom_state, hess_geom_state_delete>;
 
 struct hess_matcher_view {
   int device;
   hipStream_t st;
   hipEvent_t e0, e1;
-  std::string* err;
+  std::string& err;
   float* last_ms;
   const float2* loc[2];  // hess_matcher_set_locations of the two single-pair slots
   int nloc[2];           // their rows (the slot's descriptors), -1: the slot has no locations
   bool bank_built;       // descriptors were loaded into the bank (possibly none)
   const std::vector<int>*bank_num, *bank_cnt, *bank_first;  // per set: rows kept, rows the caller counted, first kept row
-  hess_geom_state** geom;  // created by hess_geom.hip on first use
+  // hess_matcher_bank_set_locations: one (x, y) per kept row in the caller's order, set s from bank_first[s] on -- NOT padded
+  // like the descriptors.  NULL with bank_have_loc false when there are none (and NULL with true for a bank without rows).
+  const float2* bank_loc;
+  bool bank_have_loc;
+  hess_geom_state_ptr* geom;
 };
 
 hess_matcher_view hess_matcher_view_of(hess_matcher* m);
-// The pointer check of hess_matcher_bank_set_device: `bytes` from p on are device memory of the matcher's device within one
-// allocation, or HESS_ERR_ARG with the error text set.
-int hess_matcher_device_range(hess_matcher* m, const void* p, size_t bytes, const char* what, const char* noun);
-
-// hess_geom.hip, called by the matcher: the bank's descriptors were replaced (its locations go with them); the matcher dies.
-void hess_geom_drop_bank_locations(hess_geom_state* g);
-void hess_geom_state_destroy(hess_geom_state* g);
-// The bank's locations for guided pair lists: false without any (g may be NULL); else *loc = one (x, y) per kept row in the
-// caller's order, set s from DescSets::first[s] on -- NOT padded like the descriptors (NULL for a bank without rows).
-bool hess_geom_bank_locations(const hess_geom_state* g, const float2** loc);
 
 // Estimates over matches that are on the device already (hess_matcher_verify_pairs): nothing here waits for the stream.
 // The np pairs of a chunk: pair q has counts[q] matches (row of set 1, row of set 2) at matches + q * mm and its mask bytes at
@@ -59,16 +57,63 @@ int hess_geom_reserve(hess_matcher* m, const hess_geom_params& P, int np, int mm
 // locations and hess_geom_reserve covered d (the caller checked both).
 hipError_t hess_geom_enqueue(hess_matcher* m, const hess_geom_params& P, const hess_geom_device_pairs& d);
 
-// A device buffer of at least n elements: kept when it is large enough, else replaced (its contents are not carried over).
+// A failed HIP call ends the function with HESS_ERR_DEVICE and the call's text in m->err (m: a matcher or a pointer to its view).
+#define M_TRY(m, expr)                                                                       \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      (m)->err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                   \
+      return HESS_ERR_DEVICE;                                                                \
+    }                                                                                        \
+  } while (0)
+
+// A device buffer of at least n elements after grow(n): kept when it is large enough, else replaced (its contents are not
+// carried over).  Freed with its owner.
 template <class T>
-hipError_t grow_device(T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return hipSuccess;
-  (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const hipError_t e = hipMalloc(&p, n * sizeof(T));
-  if (e == hipSuccess) cap = n;
-  return e;
-}
+struct DeviceBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { reset(); }
+  void reset() {
+    (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  hipError_t grow(size_t n) {
+    if (n <= cap) return hipSuccess;
+    reset();
+    const hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+};
+
+// Two pinned host buffers of at least n elements each, by the same rule.
+template <class T>
+struct PinnedSlots {
+  T* p[2] = {nullptr, nullptr};
+  size_t cap = 0;
+  PinnedSlots() = default;
+  PinnedSlots(const PinnedSlots&) = delete;
+  PinnedSlots& operator=(const PinnedSlots&) = delete;
+  ~PinnedSlots() { reset(); }
+  void reset() {
+    for (int k = 0; k < 2; k++) { (void)hipHostFree(p[k]); p[k] = nullptr; }
+    cap = 0;
+  }
+  hipError_t grow(size_t n) {
+    if (n <= cap) return hipSuccess;
+    reset();
+    for (int k = 0; k < 2; k++) {
+      const hipError_t e = hipHostMalloc(&p[k], n * sizeof(T), hipHostMallocDefault);
+      if (e != hipSuccess) return e;
+    }
+    cap = n;
+    return hipSuccess;
+  }
+};
 
 #endif  // HESS_MATCHER_INT_H

@@ -8,8 +8,11 @@ not.  Both forms call the C entry points on the same matcher with output arrays 
 calls' own (for the chain plus the numpy lines that build the geometry table).  The chain and the one call alternate `--reps`
 times after one warm-up round; medians and ranges are reported: device time (the sum of last_ms over the calls: hipEvents
 around each call's kernels) and wall time (time.perf_counter around the calls), and for the chain the wall time of every step.
-The two forms' results are compared byte for byte in every round.  Prints a text table; --out also writes it."""
+The two forms' results are compared byte for byte in every round.  --parent-lib PATH also times both forms of another build of
+libhessgpu.so (the parent commit's) on a matcher of its own in the same run, alternating with this build's, and compares its
+results with this build's.  Prints a text table; --out also writes it."""
 import argparse
+import ctypes as C
 import os
 import sys
 import time
@@ -24,6 +27,41 @@ from hessgpu_amd import matcher as hm
 
 T = 2048
 STEPS = ("match", "estimate", "geometry (host)", "guided match", "final estimate")
+
+
+class OtherBuild:
+    """A matcher of another libhessgpu.so with the bank and its locations, loaded beside this build's (the libraries bind their
+    own symbols): what Forms needs of a Matcher."""
+
+    def __init__(self, path, sets, locs, max_sift):
+        L = self.L = C.CDLL(os.path.abspath(path))
+        P = C.c_void_p
+        L.hess_matcher_create.restype = P
+        L.hess_matcher_create.argtypes = [C.c_int, C.c_int]
+        L.hess_matcher_destroy.argtypes = [P]
+        L.hess_matcher_bank_set.argtypes = [P, C.c_int, P, P]
+        L.hess_matcher_bank_set_locations.argtypes = [P, P, C.c_size_t]
+        L.hess_matcher_match_pairs.argtypes = [P, C.c_int, P, C.c_int, P, P, C.c_float, C.c_float, C.c_int]
+        L.hess_matcher_match_pairs_guided.argtypes = [P, C.c_int, P, P, C.c_int, P, P, C.c_float, C.c_float, C.c_int]
+        L.hess_matcher_estimate_pairs.argtypes = [P, C.c_int, P, C.c_int, P, P, P, P, P]
+        L.hess_matcher_verify_pairs.argtypes = [P, C.c_int, P, P, C.c_int, P, P, P, P, P]
+        L.hess_matcher_last_ms.restype = C.c_float
+        L.hess_matcher_last_ms.argtypes = [P]
+        L.hess_matcher_last_error.restype = C.c_char_p
+        L.hess_matcher_last_error.argtypes = [P]
+        self.h = L.hess_matcher_create(0, max_sift)
+        counts = np.array([len(s) for s in sets], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(sets))
+        xy = np.ascontiguousarray(np.concatenate(locs), dtype=np.float32)
+        if (not self.h or L.hess_matcher_bank_set(self.h, len(counts), counts.ctypes.data, flat.ctypes.data) < 0
+                or L.hess_matcher_bank_set_locations(self.h, xy.ctypes.data, 8) < 0):
+            raise RuntimeError(f"{path}: no matcher, no bank or no locations")
+
+    def last_ms(self):
+        return float(self.L.hess_matcher_last_ms(self.h))
+
+    def close(self):
+        self.L.hess_matcher_destroy(self.h)
 
 
 class Forms:
@@ -86,53 +124,61 @@ def _fmt(x):
     return f"{np.median(x):9.5f} [{min(x):.5f}, {max(x):.5f}]"
 
 
-def run(name, reps, lines):
+def run(name, reps, lines, parent_lib=None):
     nsets, n, w = WORKLOADS[name]
     sets, locs = make_bank(nsets, n, seed=nsets)
     pairs = hm.all_pairs(nsets) if w is None else hm.window_pairs(nsets, w)
     m = hm.Matcher(0, max_sift=n)
     m.set_bank(sets)
     m.set_bank_locations(locs)
+    builds = [("", m)] + ([(", the other build", OtherBuild(parent_lib, sets, locs, n))] if parent_lib else [])
     k = len(pairs)
     lines.append(f"{name}: {k} pairs of {n} x {n}, T = {T}, reps = {reps}; ms per pair, median [min, max]")
     for model in ("H", "F"):
         for refit in (0, 2):
-            f = Forms(m, pairs, n, model, refit)
-            dev = {"chain": [], "verify_pairs": []}
-            wall = {"chain": [], "verify_pairs": []}
-            steps = [[] for _ in STEPS]
+            fs = [Forms(b, pairs, n, model, refit) for _, b in builds]
+            f = fs[0]
+            labels = [form + tag for tag, _ in builds for form in ("chain", "verify_pairs")]
+            dev = {label: [] for label in labels}
+            wall = {label: [] for label in labels}
+            steps = [[[] for _ in STEPS] for _ in builds]
             for rep in range(reps + 1):                  # the first round warms up
-                d, ts = f.chain()
-                vd, vw = f.verify()
-                f.compare()
-                if rep:
-                    dev["chain"].append(d / k)
-                    wall["chain"].append(sum(ts) / k)
-                    dev["verify_pairs"].append(vd / k)
-                    wall["verify_pairs"].append(vw / k)
-                    for s, x in zip(steps, ts):
-                        s.append(x / k)
+                for (tag, _), g, st in zip(builds, fs, steps):
+                    d, ts = g.chain()
+                    vd, vw = g.verify()
+                    g.compare()
+                    assert all(g.v[x].tobytes() == f.v[x].tobytes() for x in f.v), "the two builds' results differ"
+                    if rep:
+                        dev["chain" + tag].append(d / k)
+                        wall["chain" + tag].append(sum(ts) / k)
+                        dev["verify_pairs" + tag].append(vd / k)
+                        wall["verify_pairs" + tag].append(vw / k)
+                        for s_, x in zip(st, ts):
+                            s_.append(x / k)
             lines.append(f"  model {model}, refit {refit}: {float(np.mean(f.c['nput'])):.0f} putative, {float(np.mean(f.c['cnt'])):.0f} guided "
                          f"matches per pair, {int((f.c['res1']['hypothesis'] >= 0).sum())} of {k} pairs with a model")
-            lines.append(f"    {'form':34s} {'device':>31s}   {'wall':>31s}")
-            for label in ("chain", "verify_pairs"):
-                lines.append(f"    {label:34s} {_fmt(dev[label])}   {_fmt(wall[label])}")
-            for label, s in zip(STEPS, steps):
-                lines.append(f"    {'chain: ' + label:34s} {'':31s}   {_fmt(s)}")
+            lines.append(f"    {'form':50s} {'device':>31s}   {'wall':>31s}")
+            for label in labels:
+                lines.append(f"    {label:50s} {_fmt(dev[label])}   {_fmt(wall[label])}")
+            for (tag, _), st in zip(builds, steps):
+                for label, s_ in zip(STEPS, st):
+                    lines.append(f"    {'chain: ' + label + tag:50s} {'':31s}   {_fmt(s_)}")
             lines.append(f"    wall, chain / verify_pairs: {np.median(wall['chain']) / np.median(wall['verify_pairs']):.2f}; "
                          f"device, verify_pairs / chain: {np.median(dev['verify_pairs']) / np.median(dev['chain']):.3f}")
-    m.close()
+    for _, b in builds:
+        b.close()
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["all"], default="all")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--parent-lib", help="another build of libhessgpu.so whose two forms are timed alternately with this build's")
     ap.add_argument("--out", help="also write the table here")
     args = ap.parse_args()
     lines = ["tools/bench_verify_pairs.py: time per pair, device (hipEvents around each call's kernels) and wall (the calls themselves)"]
     for nm in (sorted(WORKLOADS) if args.workload == "all" else [args.workload]):
-        run(nm, args.reps, lines)
+        run(nm, args.reps, lines, args.parent_lib)
     text = "\n".join(lines)
     print(text)
     if args.out:
