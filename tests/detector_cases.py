@@ -23,6 +23,10 @@ The mode comes from session.params.detector.  In the difference-of-Gaussians mod
 checker); list level l is scanned in the planes l, l + 1, l + 2 and described from Gaussian level l; where the two-peak
 orientation branch ran the quantum is that of its 16-bit angles.
 
+A case may carry `amp`, the amplitude of its float pixels (tests/float_range_cases.py; 1 otherwise): the absolute bounds
+above are stated for luminance in [0, 1] and scale with it, and the response is compared as the half-precision number the
+record packs, inf and subnormal steps included.
+
 A case with batch_at = (n, i) runs as image i of a stack of n; the other images are seeded noise of the same size and
 type (or the case's own `stack`), and image i is checked exactly as a single image would be.
 
@@ -43,11 +47,11 @@ from hessgpu_amd import _abi
 
 # dense planes: the bounds of tests/test_oracle_vs_numpy.py
 TOL_GAUSS = 2e-6
-TOL_DETH = 1e-5          # x max(1, max |det-H|)
+TOL_DETH = 1e-5          # x max(1, max |det-H|) (1: the square of the case's amplitude)
 TOL_GRAD = 1e-6
-TOL_THETA = 1e-5         # where the gradient is > 1e-6
+TOL_THETA = 1e-5         # where the gradient is > 1e-6 (x the case's amplitude)
 TOL_OFFSET = 2e-3
-TOL_RESP = 1e-3          # relative
+TOL_RESP = 1e-3          # relative; stated through the half the record packs (check_against_model)
 QUANTUM = 2 * R.PI / 255.0
 QUANTUM_16 = 2 * R.PI / 65535.0     # the two-peak branch of the difference-of-Gaussians mode
 # Over one quantum (the floor of the code) an angle may differ by the binary32 error of what is floored.  The slack was set
@@ -490,6 +494,11 @@ def check_against_model(session, case, model=None, dense=True, log=None):
     largest deviation per stage.  Raises Mismatch."""
     m = model or R.DetectorModel(session.params)
     img = np.asarray(case.image)
+    # The amplitude of a float case's pixels (float_range_cases sets case.amp; 1 otherwise): every ABSOLUTE gate of the
+    # checker is stated for luminance in [0, 1] and scales with it -- the planes and the gradient by amp, det-H and its
+    # response by amp^2, an unnormalised descriptor by amp.  The reference's own absolute constants (the 1e-10 pivots) do not.
+    amp = float(getattr(case, "amp", 1.0))
+    tol_desc = TOL_DESC if m.normalize else TOL_DESC * amp
     h, w = img.shape[:2]
     st = dict(candidates=0, uncertain=0, orient_uncertain=0, gauss=0.0, deth=0.0, grad=0.0, theta=0.0, desc=0.0,
               angle=0.0, three_peaks=0)
@@ -513,7 +522,8 @@ def check_against_model(session, case, model=None, dense=True, log=None):
         base, taps0 = m.base_plane(img, case.fmt)
         # binary32 rounds relative to the magnitude: float pixels are taken as they come (0 .. 255, say), and the absolute
         # bounds of the planes, stated for luminance in [0, 1], grow with the largest pixel (1 for every 8- and 16-bit case)
-        mag = max(1.0, float(np.abs(base).max()))
+        # and shrink with a case's stated amplitude below 1 (float_range_cases; 1 for every other case)
+        mag = max(amp, float(np.abs(base).max()))
         for oc, (wa, hh) in enumerate(geo):
             for l in range(nlev):
                 a = G[oc][l].astype(np.float64)
@@ -535,7 +545,7 @@ def check_against_model(session, case, model=None, dense=True, log=None):
                         bad = int((D[oc][l] != want).sum())
                         _need(bad == 0, "response", lambda: f"octave {oc} level {l}: {bad} pixels are not G_l - G_(l-1)")
                 else:
-                    d = float(np.abs(D[oc][l] - deth).max()) / max(1.0, float(np.abs(deth).max()))
+                    d = float(np.abs(D[oc][l] - deth).max()) / max(amp * amp, float(np.abs(deth).max()))
                     st["deth"] = max(st["deth"], d)
                     _need(d < TOL_DETH, "det-H", lambda: f"octave {oc} level {l}: {d:.3g} of the plane's maximum")
                 if 1 <= l <= dog:
@@ -550,7 +560,7 @@ def check_against_model(session, case, model=None, dense=True, log=None):
                     _need(d < TOL_THETA, "theta", lambda: f"octave {oc} level {l}: {d:.3g}")
 
     if case.keys is not None:
-        _check_keypoint_list(session, case, m, GOT, scales, st)
+        _check_keypoint_list(session, case, m, GOT, scales, st, tol_desc)
         return st
 
     # ---- detection from the session's response planes
@@ -573,12 +583,12 @@ def check_against_model(session, case, model=None, dense=True, log=None):
         resp = [found[li][pos][0] for li, pos in flat]
         keep = m.topk(resp)
         if len(keep) < len(flat):
-            key = sorted((abs(R.f2h(r)) for r in resp), reverse=True)
+            key = sorted((abs(m.packed_half(r)) for r in resp), reverse=True)
             cut_in, cut_out = key[m.fct - 1], key[m.fct]
             st["topk_tie_at_cut"] = int(cut_in == cut_out)
             # a response at a rounding boundary of binary16 next to the cut would make the cut depend on float32 rounding
             for r in resp:
-                lo, hi = abs(R.f2h(abs(r) * (1 - 32 * R.U))), abs(R.f2h(abs(r) * (1 + 32 * R.U)))
+                lo, hi = abs(m.packed_half(abs(r) * (1 - 32 * R.U))), abs(m.packed_half(abs(r) * (1 + 32 * R.U)))
                 _need(lo == hi or hi < cut_out or lo > cut_in, "detect", f"response {r!r} decides the top-K cut by rounding")
         expect = [[] for _ in expect]
         for i in keep:
@@ -599,7 +609,12 @@ def check_against_model(session, case, model=None, dense=True, log=None):
             resp, typ, dx, dy, dsc = found[li][pos]
             pk = int(k["packed"])
             _need(pk & 4 and (pk & 3 == typ or pos in unsure[li]), "detect", f"level {li} {pos}: type {pk & 3}, model {typ}")
-            _need(abs(_half(pk) - resp) <= abs(resp) * TOL_RESP + 1e-7, "detect", f"level {li} {pos}: response {_half(pk)} model {resp}")
+            # The packed response is half(r') of the binary32 r'; the model has r' in float64.  Every binary32 value within
+            # TOL_RESP / 2 of the model's must pack to a half between the halves of the interval's ends -- inf above 65504,
+            # steps of 2^-24 below 2^-14, 0 below 2^-25.  On normal halves that is |half - r'| <= (TOL_RESP / 2 + 2^-11)
+            # |r'| < TOL_RESP |r'|, inside the bound this line had before, whose absolute term stood for the subnormal step.
+            lo, hi = sorted((m.packed_half(resp * (1 - TOL_RESP / 2)), m.packed_half(resp * (1 + TOL_RESP / 2))))
+            _need(lo <= _half(pk) <= hi, "detect", f"level {li} {pos}: response {_half(pk)} model half({resp}) = {m.packed_half(resp)}")
             _need(max(abs(k["dx"] - dx), abs(k["dy"] - dy), abs(k["ds"] - dsc)) < TOL_OFFSET, "detect",
                   f"level {li} {pos}: offsets {(k['dx'], k['dy'], k['ds'])} model {(dx, dy, dsc)}")
     _need(len(raw) == sum(len(raw[raw["level_index"] == li]) for li in range(len(expect))), "detect", "level index out of range")
@@ -673,7 +688,7 @@ def check_against_model(session, case, model=None, dense=True, log=None):
                              float(k["s"]) / sc, ang)
             dev = float(np.abs(d - desc[j]).max())
             st["desc"] = max(st["desc"], dev)
-            _need(dev < TOL_DESC, "descriptor", f"feature {j} level {int(k['level'])}: max |d| {dev:.3g}")
+            _need(dev < tol_desc, "descriptor", f"feature {j} level {int(k['level'])}: max |d| {dev:.3g}")
         st["descriptors"] = len(pick)
         st["clipped"] = len([j for j in pick if any(j == t[0] for t in clipped)])
     return st
@@ -700,7 +715,7 @@ def _clipped(k, sc, dwf, geo, off):
     return x - r < 1.5 or y - r < 1.5 or x + r > geo[0] - 1.5 or y + r > geo[1] - 1.5
 
 
-def _check_keypoint_list(session, case, m, GOT, scales, st):
+def _check_keypoint_list(session, case, m, GOT, scales, st, tol_desc=TOL_DESC):
     """RunSIFT(num, keys, flag) on the current image: level binning, fixed-point position and scale, the strongest
     orientation only or the caller's own, descriptors -- all of it shows in the descriptor (which level's planes, where, at
     which angle) and, without given orientations, in the returned angle."""
@@ -749,6 +764,6 @@ def _check_keypoint_list(session, case, m, GOT, scales, st):
         st["empty_windows"] = st.get("empty_windows", 0) + int(float(np.ptp(d)) == 0.0)
         dev = float(np.abs(d - desc[i]).max())
         worst = max(worst, dev)
-        _need(dev < TOL_DESC, "keylist", f"key {i} (level {hits[0]}, scale {k['s']}): descriptor max |d| {dev:.3g}")
+        _need(dev < tol_desc, "keylist", f"key {i} (level {hits[0]}, scale {k['s']}): descriptor max |d| {dev:.3g}")
     st["desc"] = worst
     st["features"] = st["descriptors"] = len(keys)

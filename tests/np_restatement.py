@@ -203,12 +203,24 @@ WRONG_RULES = {
     # planes below one tile (detector_cases.small_cases)
     "empty window gives NaN": dict(empty_nan=True),
     "det-H neighbours clamp at the row ends": dict(deth_clamp=True),
+    # float pixels of any range (float_range_cases.cases)
+    "float pixels clamped to [0, 1]": dict(float_clamp=True),
+    "float pixels above 1 divided by 255": dict(float_div255=True),
+    "pivot test relative to the matrix": dict(pivot_relative=True),
+    "half response saturates to 65504": dict(half_saturates=True),
+    "threshold applied to the unscaled response": dict(threshold_unscaled=True),
 }
 
 
-def f2h(v):
-    """binary32 -> binary16 -> float, round to nearest even (__float2half_rn / half2float, GlobalUtil.cpp:588-621)."""
-    return float(np.float32(v).astype(np.float16))
+def f2h(v, saturate=False):
+    """binary32 -> binary16 -> float, round to nearest even (__float2half_rn / half2float, GlobalUtil.cpp:588-621): a value
+    of 65520 or more becomes inf, one below 2^-14 is rounded to a multiple of 2^-24, one of 2^-25 or less to 0.
+    saturate: the WRONG rule, the largest finite half instead of inf."""
+    with np.errstate(over="ignore"):
+        h = float(np.float32(v).astype(np.float16))
+    if saturate and math.isinf(h):
+        return math.copysign(65504.0, h)
+    return h
 
 
 def fixed(v, bits):
@@ -217,11 +229,17 @@ def fixed(v, bits):
 
 
 # ---- input conversion with decimation, GLTexImage.cpp:802-916 (DownSamplePixelDataI2F / F) ------------------------
-def input_plane(img, fmt=None, ds=0, no_wrap=False):
+def input_plane(img, fmt=None, ds=0, no_wrap=False, float_clamp=False, float_div255=False):
     """-> float64 [H >> ds, (W >> ds) & ~3]: every 2^ds-th pixel of every 2^ds-th row (ws = width/ds - skip with skip the
     columns TruncateWidthCU drops, :998-1016).  Integer types: the numerator 19595 R + 38470 G + 7471 B is an `int`
-    expression (:842), so it wraps modulo 2^32 for bright 16-bit pixels."""
+    expression (:842), so it wraps modulo 2^32 for bright 16-bit pixels.  Float pixels are taken as they are (:866-912:
+    `*po++ = *p`, no scale, no clamp), whatever their range and sign.  float_clamp, float_div255: the WRONG rules -- a clamp
+    to [0, 1], and a division by 255 of an image that has a value above 1 (the guess that such an image holds byte values)."""
     a = np.asarray(img)
+    if a.dtype == np.float32 and float_clamp:
+        a = np.clip(a, 0.0, 1.0)
+    if a.dtype == np.float32 and float_div255 and a.size and float(a.max()) > 1.0:
+        a = a / np.float32(255.0)
     step = 1 << ds
     h, w = a.shape[0] >> ds, (a.shape[1] >> ds) & ~3
     a = a[:h * step:step, :w * step:step]
@@ -268,7 +286,7 @@ def upsample(src, k, clamp=False):
 
 # ---- ComputeKEY_Kernel with rounding margins ------------------------------------------------------------------------
 def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False, dog=False, dog_sign_tests=False,
-                dog_type_lxx=False):
+                dog_type_lxx=False, pivot_relative=False):
     """ComputeKEY_Kernel, ProgramCU.cu:702-882 (pure Python, one pixel) -> (result, uncertain); result is None or
     (response, type, dx, dy, ds).  uncertain: a gate value lies within 8 x a first-order bound of the
     binary32 evaluation's error of its threshold, so the float32 implementation may decide either way (the comparisons
@@ -277,7 +295,12 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False,
     be negative and a minimum positive -- and the type is BRIGHT where `response > nmax` and DARK otherwise (:853-854),
     with the response AFTER the sub-pixel step and nmax as the neighbour tests left it: the largest of all 26 neighbours
     at a maximum, of the left and right neighbour only at a minimum (the else branch never touches nmax).  There is no
-    saddle type.  dog_sign_tests, dog_type_lxx: the WRONG rules that keep the Hessian lines."""
+    saddle type.  dog_sign_tests, dog_type_lxx: the WRONG rules that keep the Hessian lines.
+    THE PIVOT GUARDS of the sub-pixel solve are ABSOLUTE: maxa >= 1e-10 and the two abs(..) >= 1e-10 (:790, 808, 813), on
+    second differences of the response, which scale with the square of the pixels' amplitude (with the amplitude in the
+    DoG build).  Below an amplitude of about 2^-13 no candidate has a pivot of 1e-10: "no solution", offsets 0, the
+    response that of the pixel, and none of the tests on the refined values.  pivot_relative: the WRONG rule, the guards
+    taken relative to the largest entry of the system."""
     signs = not dog or dog_sign_tests
     T = float(T)
     thr0 = (0.8 if (subpixel or keep08) else 1.0) * T
@@ -333,7 +356,8 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False,
         maxa = max(rw[0] for rw in rows)
         solved = False
         piv = [maxa]
-        if maxa >= 1e-10:
+        guard = 1e-10 * max(abs(v) for rw in rows for v in rw[:3]) if pivot_relative else 1e-10
+        if maxa >= guard:
             if maxa == rows[1][0]:
                 rows[0], rows[1] = rows[1], rows[0]
             elif maxa == rows[2][0]:
@@ -344,11 +368,11 @@ def key_test_ex(C, P, N, G, row, col, T, edge=10.0, subpixel=True, keep08=False,
             if abs(a2[1]) > abs(a1[1]):
                 a1, a2 = a2, a1
             piv.append(abs(a1[1]))
-            if abs(a1[1]) >= 1e-10:
+            if abs(a1[1]) >= guard:
                 a1 = a1[:2] + [a1[2] / a1[1], a1[3] / a1[1]]
                 a2 = a2[:2] + [a2[2] - a2[1] * a1[2], a2[3] - a2[1] * a1[3]]
                 piv.append(abs(a2[2]))
-                if abs(a2[2]) >= 1e-10:
+                if abs(a2[2]) >= guard:
                     solved = True
                     ds = a2[3] / a2[2]
                     dy = a1[3] - ds * a1[2]
@@ -594,7 +618,9 @@ class DetectorModel:
                           no_skip=False, no_clamp33=False, fold_refresh=False, single_last=False, keep08=False,
                           no_wrap=False, whole_step=False, lowe_before_scale=False, dog_sign_tests=False,
                           dog_plane_lower=False, dog_type_lxx=False, dog_angle8=False, dog_four_peaks=False,
-                          dog_ds_above=False, dog_sigma_off=False, empty_nan=False, deth_clamp=False)
+                          dog_ds_above=False, dog_sigma_off=False, empty_nan=False, deth_clamp=False,
+                          float_clamp=False, float_div255=False, pivot_relative=False, half_saturates=False,
+                          threshold_unscaled=False)
         assert set(wrong) <= set(self.wrong), wrong
         self.wrong.update(wrong)
         self.detector = int(get("detector", 0))
@@ -719,7 +745,8 @@ class DetectorModel:
         """-> (level 0 of the first octave BEFORE the first blur, taps of the first blur or None)."""
         a = np.asarray(img)
         ds, omin, _, _ = self.plan(a.shape[1], a.shape[0])
-        lum = input_plane(a, fmt, ds, no_wrap=self.wrong["no_wrap"])
+        lum = input_plane(a, fmt, ds, no_wrap=self.wrong["no_wrap"], float_clamp=self.wrong["float_clamp"],
+                          float_div255=self.wrong["float_div255"])
         if omin < 0:
             lum = upsample(lum, -omin, clamp=self.wrong["upsample_clamp"])           # PyramidCU.cpp:1523-1524
         return lum, self.level_taps(0, omin + ds)
@@ -741,9 +768,20 @@ class DetectorModel:
         return c, c - 1, c + 1
 
     def scan(self, C, P, N, G):
-        return scan_level(C, P, N, G, np.float32(self.T), self.edge, self.subpixel, keep08=self.wrong["keep08"],
+        """The threshold is compared with the response as it is: a caller whose pixels have the amplitude A scales it by
+        A^2 (by A in the DoG mode).  threshold_unscaled: the WRONG rule of a detector that brought 0 .. 255 responses to
+        [0, 1] first, |r| / 255^2 (/ 255) against T -- stated here as T times that factor."""
+        T = np.float32(self.T)
+        if self.wrong["threshold_unscaled"]:
+            T = np.float32(T * np.float32(255.0 if self.is_dog else 255.0 * 255.0))
+        return scan_level(C, P, N, G, T, self.edge, self.subpixel, keep08=self.wrong["keep08"],
                           dog=self.is_dog, dog_sign_tests=self.wrong["dog_sign_tests"],
-                          dog_type_lxx=self.wrong["dog_type_lxx"])
+                          dog_type_lxx=self.wrong["dog_type_lxx"], pivot_relative=self.wrong["pivot_relative"])
+
+    def packed_half(self, r):
+        """The response as the list record packs it: binary16 of the binary32 r', inf beyond 65504 + half a step, subnormal
+        steps of 2^-24 below 2^-14 (ProgramCU.cu:1574-1596, GlobalUtil.cpp:588-621).  half_saturates: the WRONG rule."""
+        return f2h(r, saturate=self.wrong["half_saturates"])
 
     def reduce_first(self, counts):
         """Per-level counts (octave-major, ascending) -> counts kept after list generation and the first LimitFeatureCount.
@@ -793,7 +831,7 @@ class DetectorModel:
         n, K = len(responses), self.fct
         if self.method != TRUNC_TOPK or K <= 0 or n < K:
             return list(range(n))
-        key = [abs(float(r)) if self.wrong["topk_float_key"] else abs(f2h(r)) for r in responses]
+        key = [abs(float(r)) if self.wrong["topk_float_key"] else abs(self.packed_half(r)) for r in responses]
         order = sorted(range(n), key=lambda i: (-key[i], -i if self.wrong["topk_tie_high"] else i))
         return sorted(order[:K])
 
