@@ -20,6 +20,27 @@ int hess_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 
+// The environment of this moment into a context's switches (struct Switches says what each one means).
+static void read_switches(Switches& sw) {
+  if (const char* d = getenv("HESS_DELIVERY")) {
+    if (!strcmp(d, "mirror")) sw.delivery_pref = kDeliverMirror;
+    else if (!strcmp(d, "dma")) sw.delivery_pref = kDeliverDma;
+    else if (!strcmp(d, "blit")) sw.delivery_pref = kDeliverBlit;
+  }
+  if (const char* m = dev_env("HESS_MIRROR_MAX_BATCH")) sw.mirror_max_batch = atoi(m);
+  if (const char* e = dev_env("HESS_MIRROR_MAX_MB")) sw.mirror_max_bytes = (size_t)std::max(0, atoi(e)) << 20;
+  if (const char* ci = dev_env("HESS_INITIAL_CAP")) sw.cap_init = atoi(ci) > 0 ? atoi(ci) : 0;
+  sw.no_pair = dev_env("HESS_NO_PAIR") != nullptr;
+  sw.no_top_fusion = dev_env("HESS_NO_TOP_FUSION") != nullptr;
+  sw.no_first_fusion = dev_env("HESS_NO_FIRST_FUSION") != nullptr;
+  if (const char* cf = dev_env("HESS_CHAIN_FROM")) sw.chain_from = atoi(cf);
+  sw.no_host_upload = dev_env("HESS_NO_SIDE_UPLOAD") != nullptr;
+  if (const char* dpn = dev_env("HESS_DESC_PARTS")) sw.desc_parts = atoi(dpn);
+  if (const char* sr = dev_env("HESS_STREAM_ROWS")) sw.stream_rows = atoi(sr) > 0 ? (atoi(sr) / 3) * 3 : 0;
+  if (const char* pb = dev_env("HESS_PX_BAND")) sw.desc_px_band = std::min(4096, std::max(64, atoi(pb)));
+  if (const char* dx = dev_env("HESS_DESC_XCD")) sw.desc_xcd_block = atoi(dx) > 0 ? atoi(dx) : 0;
+}
+
 hess_ctx* hess_create(int device, const hess_params* params) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
@@ -29,61 +50,30 @@ hess_ctx* hess_create(int device, const hess_params* params) {
   hess_ctx* c = new (std::nothrow) hess_ctx();
   if (!c) return nullptr;
   if (params) c->p = *params; else default_params(&c->p);
-  bool reserved_nonzero = false;
-  for (int r : c->p.reserved_tail) reserved_nonzero = reserved_nonzero || r != 0;
-  // version-2 / -3 structs: same layout; 0 in the order word is what they ask for (the interleaved order, their default);
-  // version-2 .. -4 structs leave the detector word (then reserved[0]) zero: the Hessian detector
-  if (c->p.detector == HESS_DETECTOR_HESSIAN &&
-      ((c->p.abi_version == 2 && c->p.descriptor_order == 0) || (c->p.abi_version == 3 && c->p.descriptor_order <= HESS_DESC_ORDER_SEQUENTIAL) ||
-       c->p.abi_version == 4))
-    c->p.abi_version = HESS_ABI_VERSION;
-  if (c->p.abi_version != HESS_ABI_VERSION || c->p.dog_level_num < 0 || c->p.dog_level_num > kMaxDog ||
-      c->p.descriptor_order < 0 || c->p.descriptor_order > HESS_DESC_ORDER_PIXEL || reserved_nonzero ||  // words 1..5 must be zero
-      (c->p.detector != HESS_DETECTOR_HESSIAN && c->p.detector != HESS_DETECTOR_DOG)) {
-    fprintf(stderr, "hessgpu: bad hess_params (abi_version %d)\n", c->p.abi_version);
-    delete c;
-    return nullptr;
-  }
-  if (c->p.first_octave < -3) c->p.first_octave = -3;  // "can't upsample by more than 8": clamped, PyramidCU.cpp:131-132
   c->device = device;
-  resolve(c);
-  memset(c->timing, 0, sizeof(c->timing));
-  memset(c->k_ms, 0, sizeof(c->k_ms));
-  memset(c->k_n, 0, sizeof(c->k_n));
-  memset(c->k_bytes, 0, sizeof(c->k_bytes));
-  memset(c->k_in_lds, 0, sizeof(c->k_in_lds));
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
+  bool ok = accept_params(&c->p);
+  if (!ok) fprintf(stderr, "hessgpu: bad hess_params (abi_version %d)\n", c->p.abi_version);
+  if (ok && !(ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&c->st.h, hipStreamNonBlocking) == hipSuccess))
     fprintf(stderr, "hessgpu: cannot create stream on device %d\n", device);
+  if (ok) {
+    for (Event& e : c->ev) ok = ok && hipEventCreate(&e.h) == hipSuccess;
+    for (Event& e : c->ev_load) ok = ok && hipEventCreate(&e.h) == hipSuccess;
+    if (!ok) fprintf(stderr, "hessgpu: cannot create events on device %d\n", device);
+  }
+  if (!ok) {  // the one way out: whatever exists by now frees itself
     delete c;
     return nullptr;
   }
-  bool ev_ok = true;
-  for (int i = 0; i < 8; i++) { c->ev[i] = nullptr; ev_ok = ev_ok && hipEventCreate(&c->ev[i]) == hipSuccess; }
-  for (int i = 0; i < 2; i++) { c->ev_load[i] = nullptr; ev_ok = ev_ok && hipEventCreate(&c->ev_load[i]) == hipSuccess; }
-  c->have_ev = true;
-  if (!ev_ok) {
-    fprintf(stderr, "hessgpu: cannot create events on device %d\n", device);
-    hess_destroy(c);
-    return nullptr;
-  }
-  if (const char* d = getenv("HESS_DELIVERY")) {
-    if (!strcmp(d, "mirror")) c->delivery_pref = kDeliverMirror;
-    else if (!strcmp(d, "dma")) c->delivery_pref = kDeliverDma;
-    else if (!strcmp(d, "blit")) c->delivery_pref = kDeliverBlit;
-  }
-  if (const char* m = dev_env("HESS_MIRROR_MAX_BATCH")) c->mirror_max_batch = atoi(m);
-  if (const char* ci = dev_env("HESS_INITIAL_CAP")) c->cap_init = atoi(ci) > 0 ? atoi(ci) : 0;
-  c->no_pair = dev_env("HESS_NO_PAIR") != nullptr;
-  c->no_top_fusion = dev_env("HESS_NO_TOP_FUSION") != nullptr;
-  c->no_first_fusion = dev_env("HESS_NO_FIRST_FUSION") != nullptr;
-  if (const char* e = dev_env("HESS_MIRROR_MAX_MB")) c->mirror_max_bytes = (size_t)std::max(0, atoi(e)) << 20;
-  if (const char* cf = dev_env("HESS_CHAIN_FROM")) c->chain_from = atoi(cf);
-  c->no_host_upload = dev_env("HESS_NO_SIDE_UPLOAD") != nullptr;
-  if (const char* dpn = dev_env("HESS_DESC_PARTS")) c->desc_parts = atoi(dpn);
-  if (const char* sr = dev_env("HESS_STREAM_ROWS")) c->stream_rows = atoi(sr) > 0 ? (atoi(sr) / 3) * 3 : 0;
-  if (const char* pb = dev_env("HESS_PX_BAND")) c->desc_px_band = std::min(4096, std::max(64, atoi(pb)));
-  if (const char* dx = dev_env("HESS_DESC_XCD")) c->desc_xcd_block = atoi(dx) > 0 ? atoi(dx) : 0;
+  resolve(c);
+  read_switches(c->sw);
   return c;
+}
+
+// A poisoned context (a DMA copy that was lost may still be in flight or land late) deliberately leaks the copy's
+// sources and targets -- result buffers on both sides and the pixel staging area -- rather than hand memory that may
+// still be written back to the allocator; a shared result buffer stays mapped for the same reason.
+static void abandon_lost_copy_targets(hess_ctx* c) {
+  for (DevBuf* b : {&c->keys, &c->desc, &c->stage, (DevBuf*)&c->h_keys, (DevBuf*)&c->h_desc, (DevBuf*)&c->h_kmap}) b->forget();
 }
 
 void hess_destroy(hess_ctx* c) {
@@ -92,39 +82,14 @@ void hess_destroy(hess_ctx* c) {
   if (c->st) (void)hipStreamSynchronize(c->st);
   copier_stop(c);
   stager_stop(c->sg);
-  DevBuf* bufs[] = {&c->gauss, &c->deth, &c->got, &c->input_f32, &c->upsampled, &c->stage, &c->zeroed, &c->rowoff,
-                    &c->level_count, &c->raw_total, &c->found, &c->task_count, &c->raw, &c->sel, &c->sel_total,
-                    &c->recs, &c->ocount, &c->foffset, &c->fsrc, &c->feat_total, &c->feat_first, &c->img_base,
-                    &c->keys, &c->desc, &c->prime_px, &c->d_user, &c->kmember, &c->kmap};
-  // A poisoned context (a DMA copy that was lost may still be in flight or land late) deliberately leaks the copy's
-  // sources and targets -- result buffers on both sides and the pixel staging area -- rather than hand memory that may
-  // still be written back to the allocator; a shared result buffer stays mapped for the same reason.
-  const bool leak = c->poisoned.load();
-  for (DevBuf* b : bufs)
-    if (!(leak && (b == &c->keys || b == &c->desc || b == &c->stage))) release(*b);
-  if (!leak) {
-    release(c->h_keys, true);
-    release(c->h_desc, true);
-    release(c->h_kmap, true);
-  }
-  release(c->h_user, true);
-  release(c->h_small, true);
+  if (c->poisoned.load()) abandon_lost_copy_targets(c);
   if (c->share_dir) {
     (void)munmap(c->share_dir, 4096);
     char dir[256];
     snprintf(dir, sizeof(dir), "/%s.h", c->share.c_str());
     (void)shm_unlink(dir);
-    c->share_dir = nullptr;
   }
-  release(c->h_stage, true);
-  if (c->have_ev) {
-    for (int i = 0; i < 8; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 2; i++) if (c->ev_load[i]) (void)hipEventDestroy(c->ev_load[i]);
-  }
-  for (auto& ep : c->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-  for (auto e : c->pool) (void)hipEventDestroy(e);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;
+  delete c;  // every buffer, event, signal and stream goes with its member (hess_ctx says in which order)
 }
 
 static int refuse_pending(hess_ctx* c) {
@@ -364,7 +329,7 @@ static int store_user_keys(hess_ctx* c, const hess_keypoint* keys, const int* co
   clear_user_list(c);
   if (total == 0) return 0;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = ensure(c, c->h_user, user_block_bytes((int)total, nimg), true)) return rc;
+  if (int rc = ensure(c, c->h_user, user_block_bytes((int)total, nimg))) return rc;
   try {
     c->user_counts.assign(counts, counts + nimg);
   } catch (...) { c->user_counts.clear(); set_err(c, "out of host memory"); return HESS_ERR_NOMEM; }
@@ -543,7 +508,7 @@ int hess_debug_level(hess_ctx* c, int img, int octave, int level, int what, floa
   HIP_TRY(c, hipSetDevice(c->device));
   const OctGeom& og = c->g.o[octave];
   if (what == HESS_DBG_GAUSS && !c->keep_levels &&
-      ((level == c->sch.level_max && !c->no_top_fusion) || (level == 0 && octave == 0 && c->level0_in_lds))) {
+      ((level == c->sch.level_max && !c->sw.no_top_fusion) || (level == 0 && octave == 0 && c->level0_in_lds))) {
     set_err(c, "this Gaussian level is not materialised (the octave's top level; level 0 of octave 0): call hess_debug_keep_levels before the run");
     return HESS_ERR_STATE;
   }
@@ -602,10 +567,12 @@ int hess_share_results(hess_ctx* c, const char* name) {
   memset(m, 0, 4096);
   c->share_dir = static_cast<hess_ctx::ShareDir*>(m);
   c->share_dir->magic = 0x48455353u;  // "HESS"
+  c->h_keys.shared = 'k';  // from now on the two result buffers grow in shared memory (ensure -> ensure_shared)
+  c->h_desc.shared = 'd';
   // results of an earlier run stay readable through hess_fetch only until the next run: the buffers move now
   if (c->st) HIP_TRY(c, hipStreamSynchronize(c->st));
-  release(c->h_keys, true);
-  release(c->h_desc, true);
+  release(c->h_keys);
+  release(c->h_desc);
   c->planned = false;
   c->batch = 0;
   return 0;
@@ -662,16 +629,13 @@ int hess_profile_get_in_lds(hess_ctx* c, int kernel, double* bytes) {
 int hess_math_probe(hess_ctx* c, int which, const float* a, const float* b, float* out, int n) {
   if (!c || !a || !out || n <= 0) return HESS_ERR_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
-  float *da = nullptr, *db = nullptr, *dout = nullptr;
-  HIP_TRY(c, hipMalloc(&da, (size_t)n * 4));
-  HIP_TRY(c, hipMalloc(&db, (size_t)n * 4));
-  HIP_TRY(c, hipMalloc(&dout, (size_t)n * 4));
-  HIP_TRY(c, hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(db, b ? b : a, (size_t)n * 4, hipMemcpyHostToDevice));
-  launch_math_probe(c->st, which, da, db, dout, n);
+  DevBuf da, db, dout;  // (freed on every way out)
+  for (DevBuf* d : {&da, &db, &dout}) if (int rc = ensure(c, *d, (size_t)n * 4)) return rc;
+  HIP_TRY(c, hipMemcpy(da.p, a, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(db.p, b ? b : a, (size_t)n * 4, hipMemcpyHostToDevice));
+  launch_math_probe(c->st, which, (float*)da.p, (float*)db.p, (float*)dout.p, n);
   HIP_TRY(c, hipStreamSynchronize(c->st));
-  HIP_TRY(c, hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+  HIP_TRY(c, hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -28,8 +28,8 @@ static bool copier_hsa_setup(hess_ctx* c) {
   // are registered shared memory, whose owner ROCr reports differently)
   if (hsa_amd_pointer_info(c->h_small.p, &pi, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS || pi.type == HSA_EXT_POINTER_TYPE_UNKNOWN) return false;
   cp.cpu_agent = pi.agentOwner;
-  if (hsa_signal_create(0, 0, nullptr, &cp.sig) != HSA_STATUS_SUCCESS) return false;
-  if (hsa_signal_create(0, 0, nullptr, &cp.sig2) != HSA_STATUS_SUCCESS) { (void)hsa_signal_destroy(cp.sig); return false; }
+  if (hsa_signal_create(0, 0, nullptr, &cp.sig.h) != HSA_STATUS_SUCCESS) return false;
+  if (hsa_signal_create(0, 0, nullptr, &cp.sig2.h) != HSA_STATUS_SUCCESS) return false;
   uint32_t pref = 0;
   if (hsa_amd_memory_get_preferred_copy_engine(cp.cpu_agent, cp.gpu_agent, &pref) == HSA_STATUS_SUCCESS && pref) {
     const int n = __builtin_popcount(pref), k = g_copier_count.fetch_add(1) % n;
@@ -160,7 +160,8 @@ static Step bring_to_host(hess_ctx* c, const HostBlock* b, int n, uint32_t engin
     int lost = sdma_finish(c, cp.sig, what, injectable, s.msg, detail);
     if (second && sdma_finish(c, cp.sig2, what, false, lost ? nullptr : s.msg, detail)) lost = 2;
     if (lost) {
-      cp.hsa_ready = false; cp.hsa_failed = true;  // later batches take the stream copy; the signals are not reused
+      cp.hsa_ready = false; cp.hsa_failed = true;  // later batches take the stream copy; the signals are not reused,
+      cp.sig.forget(); cp.sig2.forget();           // nor destroyed: a late copy may still write them
       s.rc = HESS_ERR_DEVICE;
     }
     if (lost || n == 1 || second) return s;  // failed, or the blocks are in host memory
@@ -182,6 +183,7 @@ void copier_warm_up(hess_ctx* c) {
   auto tiny = [&](hsa_signal_t sig, void* dst, const void* src) {
     if (sdma_start(cp.engine, dst, cp.cpu_agent, src, cp.gpu_agent, 64, sig) && sdma_finish(c, sig, "", false, nullptr)) {
       cp.hsa_ready = false; cp.hsa_failed = true;
+      cp.sig.forget(); cp.sig2.forget();
     }
   };
   tiny(cp.sig, c->h_keys.p, c->keys.p);
@@ -200,6 +202,7 @@ static Step await_upload_and_enqueue(hess_ctx* c) {
     snprintf(s.msg + strlen(s.msg), sizeof(s.msg) - strlen(s.msg), " (copier)");
     s.rc = HESS_ERR_DEVICE;
     cp.have_sig_in = false;  // (a signal that may still be written is left alone, not reused)
+    cp.sig_in.forget();
   }
   PendingRun& r = *cp.run;
   r.t_load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -220,7 +223,7 @@ static Step make_room(hess_ctx* c, size_t total, size_t db) {
   Step s;
   DevBuf &hk = c->h_keys, &hd = c->h_desc;
   if (hk.bytes >= total * sizeof(HostKeypoint) && (!c->dim || hd.bytes >= total * db)) return s;
-  if (ensure(c, hk, total * sizeof(HostKeypoint), true) || (c->dim && ensure(c, hd, total * db, true))) {
+  if (ensure(c, hk, total * sizeof(HostKeypoint)) || (c->dim && ensure(c, hd, total * db))) {
     snprintf(s.msg, sizeof(s.msg), "pinned result buffers: %s (copier)", c->err.empty() ? "allocation failed" : c->err.c_str());
     s.rc = HESS_ERR_NOMEM;
   }
@@ -301,38 +304,29 @@ static void copier_main(hess_ctx* c) {
 
 int copier_start(hess_ctx* c) {
   Copier& cp = c->cp;
-  if (cp.started) return 0;
-  HIP_TRY(c, hipStreamCreateWithFlags(&cp.cs, hipStreamNonBlocking));
-  HIP_TRY(c, hipEventCreateWithFlags(&cp.ev_done, hipEventDisableTiming));
-  for (hipEvent_t& ev : cp.ev_part) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (cp.th.joinable()) return 0;
+  HIP_TRY(c, hipStreamCreateWithFlags(&cp.cs.h, hipStreamNonBlocking));
+  HIP_TRY(c, hipEventCreateWithFlags(&cp.ev_done.h, hipEventDisableTiming));
+  for (Event& ev : cp.ev_part) HIP_TRY(c, hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
   try {
     cp.th = std::thread(copier_main, c);
   } catch (...) {
     set_err(c, "cannot start the copier thread");
     return HESS_ERR_NOMEM;
   }
-  cp.started = true;
   return 0;
 }
 
 void copier_stop(hess_ctx* c) {
   Copier& cp = c->cp;
-  if (cp.started) {
-    {
-      std::unique_lock<std::mutex> lk(cp.mu);
-      cp.cv.wait(lk, [&] { return cp.done; });
-      cp.stop = true;
-      cp.cv.notify_all();
-    }
-    cp.th.join();
-    cp.started = false;
+  if (!cp.th.joinable()) return;
+  {
+    std::unique_lock<std::mutex> lk(cp.mu);
+    cp.cv.wait(lk, [&] { return cp.done; });
+    cp.stop = true;
+    cp.cv.notify_all();
   }
-  // (a poisoned context's signals may still be written by a late copy: left alone, like the buffers)
-  if (cp.hsa_ready) { (void)hsa_signal_destroy(cp.sig); (void)hsa_signal_destroy(cp.sig2); cp.hsa_ready = false; }
-  if (cp.have_sig_in && !c->poisoned.load()) { (void)hsa_signal_destroy(cp.sig_in); cp.have_sig_in = false; }
-  if (cp.cs) { (void)hipStreamDestroy(cp.cs); cp.cs = nullptr; }
-  if (cp.ev_done) { (void)hipEventDestroy(cp.ev_done); cp.ev_done = nullptr; }
-  for (hipEvent_t& ev : cp.ev_part) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+  cp.th.join();
 }
 
 // How the results of a batch of `batch` images reach the host (see the kDeliver* comment): small batches through the
@@ -348,8 +342,8 @@ void choose_delivery(hess_ctx* c, int batch) {
   // what the context's last batch of this size delivered (the capacity is a worst case many times the typical count): the
   // first batch of a context uses the mirror.  HESS_MIRROR_MAX_MB (16) is the limit.
   const size_t expect = (c->last_result_batch == batch && !c->caller_waits) ? c->last_result_bytes : 0;
-  const bool small = batch <= c->mirror_max_batch && !(batch >= 2 && !c->caller_waits);  // (a submitted pair: see enqueue())
-  int d = c->delivery_pref >= 0 ? c->delivery_pref : (small && expect <= c->mirror_max_bytes ? kDeliverMirror : kDeliverDma);
+  const bool small = batch <= c->sw.mirror_max_batch && !(batch >= 2 && !c->caller_waits);  // (a submitted pair: see enqueue())
+  int d = c->sw.delivery_pref >= 0 ? c->sw.delivery_pref : (small && expect <= c->sw.mirror_max_bytes ? kDeliverMirror : kDeliverDma);
   if (d == kDeliverMirror && !c->host_fits) d = kDeliverDma;  // the mirror needs the worst case pinned up front
   if (d == kDeliverDma && copier_start(c) != 0) d = kDeliverBlit;
   c->delivery = d;
@@ -376,7 +370,7 @@ static void copier_post(hess_ctx* c, PendingRun* run, bool upload_first) {
 // cost nothing (tools/r03/r03_h2d_bg.py).  *taken: the batch is submitted; else nothing is in flight, take the stream.
 int upload_beside_queues(hess_ctx* c, const void* pixels, size_t bytes, bool* taken) {
   *taken = false;
-  if (c->no_host_upload) return 0;
+  if (c->sw.no_host_upload) return 0;
   if (int rc = plan(c, c->run.width, c->run.height, c->run.batch)) return rc;
   choose_delivery(c, c->run.batch);
   Copier& cp = c->cp;
@@ -386,7 +380,7 @@ int upload_beside_queues(hess_ctx* c, const void* pixels, size_t bytes, bool* ta
   if (c->delivery != kDeliverDma || !copier_hsa_setup(c) ||
       hsa_amd_pointer_info(const_cast<void*>(pixels), &pi, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS ||
       pi.type == HSA_EXT_POINTER_TYPE_UNKNOWN ||
-      !(cp.have_sig_in || hsa_signal_create(1, 0, nullptr, &cp.sig_in) == HSA_STATUS_SUCCESS))
+      !(cp.have_sig_in || hsa_signal_create(1, 0, nullptr, &cp.sig_in.h) == HSA_STATUS_SUCCESS))
     return 0;
   cp.have_sig_in = true;
   if (!sdma_start(cp.engine_in, c->stage.p, cp.gpu_agent, pixels, pi.agentOwner, bytes, cp.sig_in)) return 0;
@@ -405,7 +399,7 @@ int upload_beside_queues(hess_ctx* c, const void* pixels, size_t bytes, bool* ta
 // image: 0.544 ms per call alone, 0.58 ms with helpers; profiles/r03_host_path.json).
 // Nothing here allocates or throws once the helpers exist (nothing thrown crosses the C ABI).
 static int upload_staged(hess_ctx* c, const void* pixels, size_t bytes) {
-  if (int rc = ensure(c, c->h_stage, bytes, true)) return rc;
+  if (int rc = ensure(c, c->h_stage, bytes)) return rc;
   const size_t chunk = std::min<size_t>((size_t)4 << 20, std::max<size_t>((size_t)256 << 10, ((bytes / 4 + 65535) >> 16) << 16));
   hipError_t cerr = hipSuccess;  // the first one
   const bool ran = stager_run(c->sg, pixels, c->h_stage.p, bytes, chunk, bytes >= policy::kStagerHelpFrom, [&](size_t off, size_t len) {
@@ -518,8 +512,8 @@ int wait_inner(hess_ctx* c, PendingRun& r) {
   const size_t db = run_desc_bytes(c, r.desc_format);
   c->last_result_bytes = total * (sizeof(HostKeypoint) + db);
   c->last_result_batch = batch;
-  if ((rc = ensure(c, c->h_keys, (total ? total : 1) * sizeof(HostKeypoint), true))) return rc;
-  if (c->dim && (rc = ensure(c, c->h_desc, (total ? total : 1) * db, true))) return rc;
+  if ((rc = ensure(c, c->h_keys, (total ? total : 1) * sizeof(HostKeypoint)))) return rc;
+  if (c->dim && (rc = ensure(c, c->h_desc, (total ? total : 1) * db))) return rc;
   if (total && c->delivery == kDeliverBlit) {
     HIP_TRY(c, hipMemcpyAsync(c->h_keys.p, c->keys.p, total * sizeof(HostKeypoint), hipMemcpyDeviceToHost, c->st));
     if (c->dim)
@@ -588,6 +582,5 @@ int wait_impl(hess_ctx* c, PendingRun& r) {
     return HESS_ERR_NOMEM;
   }
 }
-
 
 }  // namespace hess

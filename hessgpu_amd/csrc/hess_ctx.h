@@ -44,7 +44,6 @@
 
 namespace hess {
 
-
 struct Schedule {
   int detector;                // HESS_DETECTOR_*: levels 0..dog+1 (Hessian) or 0..dog+2 (DoG) per octave
   int dog, level_max, level_num, level_ds;
@@ -55,12 +54,39 @@ struct Schedule {
   Taps taps[kMaxLev];          // taps[l] produces level l from level l-1 (l >= 1)
 };
 
+// A grow-only allocation that knows its kind and frees itself (ensure / release, hess_plan.hip).  Not the matcher's
+// DeviceBuf<T>: that one frees before it allocates and has one kind; here the new allocation is made before the old one is
+// freed, so that a context survives a refused hess_reserve, and the kinds differ in how they are freed.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  const bool pinned;  // hipHostMalloc / hipHostFree, else hipMalloc / hipFree
+  char shared = 0;    // 'k' / 'd': a pinned result buffer that grows in node-shared memory (set by hess_share_results; ensure_shared)
   std::string shm;  // non-empty: p is a registered mapping of this POSIX shared memory object ("/name") or, when /dev/shm
                     // had no room, of this file (an absolute path: it has further slashes) -- hess_share_results
+  explicit DevBuf(bool pinned_host = false) : pinned(pinned_host) {}
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf();  // release()
+  void forget() { p = nullptr; bytes = 0; shm.clear(); }  // the memory is given up without being freed (a lost copy may still write it)
 };
+struct PinnedBuf : DevBuf { PinnedBuf() : DevBuf(true) {} };
+
+// A runtime handle destroyed with its owner: a stream, an event, a completion signal.  A null handle owns nothing.
+template <class H, class R, R (*destroy)(H)>
+struct Owned {
+  H h{};
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { if (*this) (void)destroy(h); }
+  operator H() const { return h; }
+  explicit operator bool() const { H none{}; return memcmp(&h, &none, sizeof(H)) != 0; }
+  void forget() { h = H{}; }  // given up without being destroyed (a signal that a lost copy may still write)
+};
+using Stream = Owned<hipStream_t, hipError_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipError_t, hipEventDestroy>;
+using Signal = Owned<hsa_signal_t, hsa_status_t, hsa_signal_destroy>;
 
 struct EventPair {
   hipEvent_t a, b;
@@ -70,7 +96,6 @@ struct EventPair {
   double in_lds = 0.0;  // bytes of the reference's array layout this launch neither writes nor reads: the array lives in LDS only
   int count = 1;     // launches between the two events (ProfRun: a run of consecutive launches of one kernel family)
 };
-
 
 // The schedule's thresholds, in one place.  Each was set by a same-call A/B on MI355X; the measurement is named beside it
 // (files under profiles/, sections of DESIGN.md).  The developer build can override the ones marked (dev).
@@ -108,7 +133,6 @@ constexpr size_t kStagerHelpFrom = (size_t)8 << 20;
 
 using namespace hess;
 
-
 // One batch's pixels and their layout, built with designated initialisers (what is not named is zero).
 struct PendingRun {
   const void* dev = nullptr;
@@ -142,22 +166,24 @@ struct Copier {
   std::thread th;
   std::mutex mu;
   std::condition_variable cv;
-  bool started = false, stop = false, has_job = false, done = true;
+  bool stop = false, has_job = false, done = true;
   int rc = 0;            // result of the last job (hess_status)
   bool overflow = false; // the batch overflowed its feature storage: nothing was copied
   char err[320] = "";    // message of the last failed job (a fixed array: the copier thread must not throw)
-  hipStream_t cs = nullptr;     // copy-only stream (fallback path)
-  hipEvent_t ev_done = nullptr; // recorded on the context's stream behind the last kernel of a batch
+  Stream cs;             // copy-only stream (fallback path)
+  Event ev_done;         // recorded on the context's stream behind the last kernel of a batch
   // A batch's descriptors may come from up to kMaxParts launches (hess_ctx::parts); ev_part[k] is recorded behind launch k, ev_done behind the last.
   static constexpr int kMaxParts = 4;
-  hipEvent_t ev_part[kMaxParts - 1] = {nullptr, nullptr, nullptr};
+  Event ev_part[kMaxParts - 1];
   // ROCr side (SDMA): agents owning the device / pinned host buffers, engine, completion signal
   bool hsa_ready = false, hsa_failed = false;
   hsa_agent_t gpu_agent{}, cpu_agent{};
   uint32_t engine = 0;          // hsa_amd_sdma_engine_id_t bit, 0 = let ROCr choose
   uint32_t engine_in = 0;       // the same for the host->device upload of pinned pixels
-  hsa_signal_t sig{}, sig2{};   // one completion signal per copy in flight (keypoints, descriptors), each armed with 1: tools that
+  Signal sig, sig2;             // one completion signal per copy in flight (keypoints, descriptors), each armed with 1: tools that
                                 // interpose on ROCr (rocprofv3 --memory-copy-trace) expect exactly that of a copy's signal
+  // hsa_ready and have_sig_in say whether the signals may be USED.  Where a copy is lost its signal is forgotten on the spot
+  // (Signal::forget: a late copy may still write it), so what the Copier still owns at its end is safe to destroy.
   // The job (copier_post): the run to deliver and whether it begins with the batch's pixels still on their way
   // (hess_submit_host, pinned input).  Then the upload is an SDMA copy started by the submitting thread with sig_in as
   // its completion signal; the copier thread waits for it ON THE HOST and only then enqueues the kernels -- no command
@@ -165,7 +191,7 @@ struct Copier {
   PendingRun* run = nullptr;
   bool upload_first = false;
   bool have_sig_in = false;
-  hsa_signal_t sig_in{};
+  Signal sig_in;
 };
 
 // The descriptor launches of the batch being enqueued (choose_parts, hess_schedule.hip): n groups of images, end[k] = first
@@ -175,18 +201,50 @@ struct Parts {
   bool features = false;
 };
 
+// The developer switches of one context, as read_switches() (hess_abi.hip) found them in the environment when hess_create ran:
+// per context, since tests set and clear them between contexts of one process.  HESS_DELIVERY is read with getenv (the shipped
+// library has it), the rest with dev_env().  Read once per process or at first use, where they act: HESS_NO_PRIME_BATCH, HESS_COPIER,
+// HESS_COPIER_ENGINE, HESS_UPLOAD_ENGINE, HESS_COPIER_FAULT, HESS_CHAIN_STAMPS, HESS_SHARE_FORCE_FILE; HESS_COPY_TIMEOUT_S (shipped).
+struct Switches {
+  int delivery_pref = -1;          // HESS_DELIVERY=mirror|dma|blit: a kDeliver* value (-1: by batch size, choose_delivery)
+  int mirror_max_batch = policy::kLatencyBatch;       // HESS_MIRROR_MAX_BATCH: largest batch that takes the latency settings
+  size_t mirror_max_bytes = policy::kMirrorMaxBytes;  // HESS_MIRROR_MAX_MB: largest results the descriptor kernel mirrors (floored at 0)
+  int cap_init = 0;                // HESS_INITIAL_CAP: initial raw / feature capacity, so that the grow path runs (0: by image size)
+  bool no_pair = false;            // HESS_NO_PAIR: one launch per pyramid level
+  bool no_top_fusion = false;      // HESS_NO_TOP_FUSION: the top level is stored and its det-H made by a launch of its own
+  bool no_first_fusion = false;    // HESS_NO_FIRST_FUSION: level 0 of octave 0 from a launch of its own, written to HBM
+  int chain_from = 0;              // HESS_CHAIN_FROM: first octave produced by one level-chain launch (0: by batch size; 99: none)
+  bool no_host_upload = false;     // HESS_NO_SIDE_UPLOAD: pinned input is uploaded by a copy on the context's stream
+  int desc_parts = 0;              // HESS_DESC_PARTS: descriptor launches / result transfers per batch (0: by batch size)
+  int stream_rows = 0;             // HESS_STREAM_ROWS: rows per wavefront segment of the extrema scan, a multiple of 3 (0: by batch size)
+  int desc_px_band = 4096;         // HESS_PX_BAND: pixels per raster band of descriptor_pixel_kernel, 64 .. 4096 (small bands at ordinary footprints)
+  int desc_xcd_block = 64;         // HESS_DESC_XCD: features per XCD block of the descriptor launch (0: plain order)
+};
+
+struct ProfEvents {  // the profiling events of a context
+  std::vector<EventPair> pending;  // pairs recorded and not yet read (drain_profile)
+  std::vector<hipEvent_t> pool;    // events free for reuse
+  ~ProfEvents() { for (auto& ep : pending) pool.insert(pool.end(), {ep.a, ep.b}); for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
+};
+
+// Members are destroyed in reverse order (hess_destroy ends in `delete c`): the buffers first, then the copier's stream, events
+// and signals, the context's events, and the stream last.  A member that owns a runtime object needs no line anywhere else.
 struct hess_ctx {
   int device = 0;
-  hipStream_t st = nullptr;
-  hess_params p;
-  Schedule sch;
+  Stream st;
+  Event ev[8], ev_load[2];         // between the stages of a batch; around the host->device transfer of the pixels
+  ProfEvents prof_ev;
+  Copier cp;
+  Switches sw;
+  hess_params p{};
+  Schedule sch{};
   // geometry of the current plan
   bool planned = false;
   int in_w = 0, in_h = 0;   // caller's image size
   int ds = 0;               // input decimation (first_octave / auto down-scaling)
   int img_w = 0, img_h = 0; // after decimation and width truncation
-  Geom g;
-  Taps taps0;               // initial smoothing
+  Geom g{};
+  Taps taps0{};              // initial smoothing
   bool has_taps0 = false;
   int cap_raw = 0, cap_sel = 0, cap_feat = 0;
   bool use_topk = false, multi = false;
@@ -213,7 +271,7 @@ struct hess_ctx {
   int pyramid_batch = 0;  // images whose pyramid is resident (hess_run_keypoints on the current image)
   std::vector<int> counts;
   std::vector<size_t> offs;
-  DevBuf h_keys, h_desc, h_small;  // pinned
+  PinnedBuf h_keys, h_desc, h_small;
   // hess_share_results: the two result buffers live in shared memory objects "/<share>.k<n>" / "/<share>.d<n>" that
   // another process of the node can map; a 4 KB directory object "/<share>.h" says which ones are current
   std::string share;
@@ -225,11 +283,10 @@ struct hess_ctx {
     char keys_path[1024], desc_path[1024];
   }* share_dir = nullptr;
   bool share_by_need = false;      // the shared result buffers are sized by the batches seen, not for the worst case
-  DevBuf h_stage;                  // pinned staging of pageable input pixels (hess_submit_host)
+  PinnedBuf h_stage;               // pinned staging of pageable input pixels (hess_submit_host)
   double stamp_submit0 = 0.0, stamp_submit1 = 0.0;  // HESS_CHAIN_STAMPS
   bool level0_in_lds = false;      // the last run's level 0 of octave 0 was not written to HBM (FIRST tiles)
   size_t last_input_bytes = 0;     // bytes of the last batch handed over by hess_submit_host (still in `stage`)
-  hipEvent_t ev_load[2];           // around the host->device transfer of the pixels
   // results written by the descriptor kernel straight into the pinned host buffers (no D2H pass after it)
   bool host_direct = false;        // delivery == kDeliverMirror for the submitted batch
   bool host_fits = false;          // the pinned result buffers hold the worst case of the current plan
@@ -239,30 +296,16 @@ struct hess_ctx {
   // while a job is posted: every entry that enqueues refuses while run.active, hess_reserve's dry batch returns early then,
   // and wait_inner's regrow loop resubmits only after it has seen cp.done under cp.mu.
   Parts parts;
-  size_t mirror_max_bytes = policy::kMirrorMaxBytes;   // (dev: HESS_MIRROR_MAX_MB)
   size_t last_result_bytes = 0;    // keypoints + descriptors the last batch delivered, and its size
   int last_result_batch = 0;
   std::atomic<bool> caller_waits{false};  // inside hess_run_* (submit + wait in one call; read by the copier thread, too)
-  int delivery_pref = -1;          // HESS_DELIVERY=mirror|dma|blit (-1 = by batch size, see plan())
-  int mirror_max_batch = policy::kLatencyBatch;        // (dev: HESS_MIRROR_MAX_BATCH)
   int regrown = 0;                 // times the feature storage was grown after an overflow (hess_debug_regrown)
   int seen_features = 0;           // largest per-image feature count of the last finished batch (0: none yet): sizes the descriptor grid
-  int cap_init = 0;                // HESS_INITIAL_CAP: initial raw/feature capacity (developer switch for the grow path)
-  bool no_pair = false;            // HESS_NO_PAIR: one launch per pyramid level (A/B switch)
-  bool no_first_fusion = false;    // HESS_NO_FIRST_FUSION: level 0 of octave 0 from a launch of its own, written to HBM (A/B switch)
-  bool no_top_fusion = false;      // HESS_NO_TOP_FUSION: the top level is stored and its det-H made by a launch of its own (A/B switch)
   bool keep_levels = false;        // hess_debug_keep_levels: the top Gaussian level of every octave is written to HBM as well
-  int chain_from = 0;              // HESS_CHAIN_FROM: first octave produced by one level-chain launch (0: by batch size; 99: none)
-  bool no_host_upload = false;     // HESS_NO_SIDE_UPLOAD: pinned input is uploaded by a copy on the context's stream (A/B switch)
-  int desc_parts = 0;              // HESS_DESC_PARTS: descriptor launches / result transfers per batch (0: default)
-  int stream_rows = 0;             // HESS_STREAM_ROWS: rows per wavefront segment of the extrema scan (0: by batch size; A/B switch)
-  int desc_px_band = 4096;         // HESS_PX_BAND: pixels per raster band of descriptor_pixel_kernel (test hook: small bands at ordinary footprints)
-  int desc_xcd_block = 64;         // HESS_DESC_XCD: features per XCD block of the descriptor launch (0: plain order; A/B switch)
-  Copier cp;
   Stager sg;                       // hess_stager.h
   // A DMA copy that did not complete in time (or that ROCr reported as failed) may still be in flight, or land later:
   // its targets -- the pinned result buffers, the pixel staging area -- must neither be reused nor freed.  The context
-  // refuses every further run (HESS_ERR_DEVICE) and hess_destroy leaves those buffers and the signals alone.
+  // refuses every further run (HESS_ERR_DEVICE) and hess_destroy leaves those buffers alone (abandon_lost_copy_targets).
   std::atomic<bool> poisoned{false};
   long long primed_shapes[4] = {-1, -1, -1, -1};  // shapes (width, height, batch) hess_reserve has run a dry batch for
   unsigned primed_next = 0;
@@ -272,7 +315,8 @@ struct hess_ctx {
   // user-supplied keypoint lists (SiftPyramid::SetKeypointList), one per image of the next run: used by it, then cleared.
   // The keys of all images lie back to back at the start of the pinned block h_user since the set call; enqueue_user
   // appends what else key_bin_kernel reads (UserBlock) and uploads the block to d_user with one copy.
-  DevBuf h_user, d_user;
+  PinnedBuf h_user;
+  DevBuf d_user;
   std::vector<int> user_counts;     // keys per image; empty: no list is pending
   int user_total = 0, user_max = 0; // their sum (> 0 while a list is pending) and the largest of them
   bool user_have_orientation = false;
@@ -280,8 +324,8 @@ struct hess_ctx {
   bool user_on_current = false;     // RunSIFT(num, keys, flag): skip filtering, reuse the resident pyramid
   std::vector<int> user_levels;     // parity hook: explicit level index per user keypoint (hess_debug_key_levels; one image)
   DevBuf kmember;                   // key_bin_kernel's scratch: [B][user_max] levels of every key
-  DevBuf kmap, h_kmap;              // [B][cap_list] list position -> input index (_keypoint_index); h_kmap: pinned, filled by
-                                    // the route the results take (the kernel's own stores, the copier thread, hess_wait's copy)
+  DevBuf kmap;                      // [B][cap_list] list position -> input index (_keypoint_index); h_kmap: pinned, filled by
+  PinnedBuf h_kmap;                 // the route the results take (the kernel's own stores, the copier thread, hess_wait's copy)
   bool user_result = false;         // last results are in u_keys / u_desc (input order, the images back to back)
   std::vector<hess_keypoint> u_keys;
   std::vector<unsigned char> u_desc;  // [sum of counts][run_desc_bytes]: floats or bytes, as the run's format says
@@ -291,24 +335,19 @@ struct hess_ctx {
   const RawKey* d_list = nullptr;  // list fed to the orientation stage in the last run
   const int* d_list_total = nullptr;
   int cap_list = 0;
-  float timing[HESS_T_COUNT];
-  hipEvent_t ev[8];
+  float timing[HESS_T_COUNT] = {};
   bool stage_events = false;  // events between the stages of the running batch (each costs a ~6 us bubble on the stream)
-  bool have_ev = false;
   std::string err;
   // profiling
   bool prof = false;
-  std::vector<EventPair> pending;
-  std::vector<hipEvent_t> pool;
-  double k_ms[HESS_K_COUNT];
-  long long k_n[HESS_K_COUNT];
-  double k_bytes[HESS_K_COUNT];
-  double k_in_lds[HESS_K_COUNT];   // hess_profile_get_in_lds
+  double k_ms[HESS_K_COUNT] = {};
+  long long k_n[HESS_K_COUNT] = {};
+  double k_bytes[HESS_K_COUNT] = {};
+  double k_in_lds[HESS_K_COUNT] = {};   // hess_profile_get_in_lds
 };
 
 // ---- shared by the host-side files (namespace hess) ----
 namespace hess {
-
 
 void set_err(hess_ctx* c, const char* fmt, ...);
 
@@ -328,13 +367,9 @@ inline void clear_user_list(hess_ctx* c) {
 
 // Environment switches.  The shipped library reads four: HESS_SHARE_DIR (and TMPDIR) -- where node-shared result buffers go
 // when /dev/shm has no room --, HESS_COPY_TIMEOUT_S -- how long a result copy may take before the context is poisoned --
-// and HESS_DELIVERY (mirror | dma | blit: how results reach the host, hess_copier.hip).  Everything else -- schedule A/B
-// switches (HESS_NO_PAIR, HESS_NO_TOP_FUSION, HESS_NO_FIRST_FUSION, HESS_CHAIN_FROM, HESS_STREAM_ROWS, HESS_DESC_PARTS,
-// HESS_DESC_XCD, HESS_MIRROR_MAX_BATCH, HESS_MIRROR_MAX_MB, HESS_NO_SIDE_UPLOAD, HESS_NO_PRIME_BATCH), test hooks
-// (HESS_INITIAL_CAP, HESS_COPIER_FAULT, HESS_SHARE_FORCE_FILE), engine choices (HESS_COPIER, HESS_COPIER_ENGINE,
-// HESS_UPLOAD_ENGINE) and HESS_CHAIN_STAMPS -- exists only in the DEVELOPER build (-DHESS_DEV_SWITCHES:
-// hessgpu_amd/dev/libhessgpu.so, built beside the product by hessgpu_amd/build.py; hess_dev_switches() tells which one
-// is loaded).  The tests that need a switch and tools/robustness.sh load that build.
+// and HESS_DELIVERY (how results reach the host).  Everything else (struct Switches and the list above it) exists only in the
+// DEVELOPER build (-DHESS_DEV_SWITCHES: hessgpu_amd/dev/libhessgpu.so, built beside the product by hessgpu_amd/build.py;
+// hess_dev_switches() tells which one is loaded).  The tests that need a switch and tools/robustness.sh load that build.
 #ifdef HESS_DEV_SWITCHES
 inline const char* dev_env(const char* name) { return getenv(name); }
 #else
@@ -350,17 +385,17 @@ inline const char* dev_env(const char*) { return nullptr; }
     }                                                                                     \
   } while (0)
 
-
 // hess_plan.hip
-int ensure(hess_ctx* c, DevBuf& b, size_t bytes, bool pinned_host = false);
-void release(DevBuf& b, bool pinned_host = false);
+int ensure(hess_ctx* c, DevBuf& b, size_t bytes);
+void release(DevBuf& b);
 void default_params(hess_params* p);
+bool accept_params(hess_params* p);
 void make_taps(const hess_params& p, float sigma, Taps* t);
 void resolve(hess_ctx* c);
 int fmt_channels(int format);
 int plan(hess_ctx* c, int width, int height, int batch);
 // hess_shared.hip
-int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which);
+int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes);
 // hess_schedule.hip
 void drain_profile(hess_ctx* c);
 int enqueue(hess_ctx* c, const PendingRun& r);

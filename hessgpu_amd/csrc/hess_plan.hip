@@ -13,35 +13,34 @@ void set_err(hess_ctx* c, const char* fmt, ...) {
   if (c->p.verbose & 1) fprintf(stderr, "hessgpu: %s\n", buf);
 }
 
-
-int ensure(hess_ctx* c, DevBuf& b, size_t bytes, bool pinned_host) {
+int ensure(hess_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.bytes) return 0;
-  if (pinned_host && c->share_dir && (&b == &c->h_keys || &b == &c->h_desc)) return ensure_shared(c, b, bytes, &b == &c->h_keys ? 'k' : 'd');
+  if (b.shared) return ensure_shared(c, b, bytes);
   // the new buffer first: when the allocation fails the old one is still there (a context survives a refused
   // hess_reserve)
   const size_t want = bytes + bytes / 8;  // slack so slightly larger inputs do not reallocate
   void* np = nullptr;
-  if (pinned_host) HIP_TRY(c, hipHostMalloc(&np, want, hipHostMallocDefault));
+  if (b.pinned) HIP_TRY(c, hipHostMalloc(&np, want, hipHostMallocDefault));
   else HIP_TRY(c, hipMalloc(&np, want));
-  if (b.p) { if (pinned_host) (void)hipHostFree(b.p); else (void)hipFree(b.p); }
+  release(b);
   b.p = np;
   b.bytes = want;
   return 0;
 }
 
-void release(DevBuf& b, bool pinned_host) {
+void release(DevBuf& b) {
   if (b.p && !b.shm.empty()) {
     (void)hipHostUnregister(b.p);
     (void)munmap(b.p, b.bytes);
     if (strchr(b.shm.c_str() + 1, '/')) (void)unlink(b.shm.c_str());  // a file (the fallback), else a shared memory object
     else (void)shm_unlink(b.shm.c_str());
-    b.shm.clear();
   } else if (b.p) {
-    if (pinned_host) (void)hipHostFree(b.p); else (void)hipFree(b.p);
+    if (b.pinned) (void)hipHostFree(b.p); else (void)hipFree(b.p);
   }
-  b.p = nullptr;
-  b.bytes = 0;
+  b.forget();
 }
+
+DevBuf::~DevBuf() { release(*this); }
 
 // ---- parameters: GlobalUtil.cpp:51-144 defaults, SiftParam::ParseSiftParam SiftGPU.cpp:491-563 ----
 
@@ -67,6 +66,24 @@ void default_params(hess_params* p) {
   p->feature_count_threshold = -1;
   p->tex_max_dim = 3200;
   p->descriptor_order = HESS_DESC_ORDER_PIXEL;
+}
+
+// What hess_create accepts: a struct of this version, or an older one upgraded in place; false refuses it.
+bool accept_params(hess_params* p) {
+  bool reserved_nonzero = false;
+  for (int r : p->reserved_tail) reserved_nonzero = reserved_nonzero || r != 0;
+  // version-2 / -3 structs: same layout; 0 in the order word is what they ask for (the interleaved order, their default);
+  // version-2 .. -4 structs leave the detector word (then reserved[0]) zero: the Hessian detector
+  if (p->detector == HESS_DETECTOR_HESSIAN &&
+      ((p->abi_version == 2 && p->descriptor_order == 0) || (p->abi_version == 3 && p->descriptor_order <= HESS_DESC_ORDER_SEQUENTIAL) ||
+       p->abi_version == 4))
+    p->abi_version = HESS_ABI_VERSION;
+  if (p->abi_version != HESS_ABI_VERSION || p->dog_level_num < 0 || p->dog_level_num > kMaxDog ||
+      p->descriptor_order < 0 || p->descriptor_order > HESS_DESC_ORDER_PIXEL || reserved_nonzero ||  // words 1..5 must be zero
+      (p->detector != HESS_DETECTOR_HESSIAN && p->detector != HESS_DETECTOR_DOG))
+    return false;
+  if (p->first_octave < -3) p->first_octave = -3;  // "can't upsample by more than 8": clamped, PyramidCU.cpp:131-132
+  return true;
 }
 
 // ProgramCU::CreateFilterKernel, ProgramCU.cu:423-453 (host arithmetic, libm expf).
@@ -185,8 +202,7 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
     int rc;
     if ((rc = ensure(c, c->d_user, c->h_user.bytes))) return rc;
     if ((rc = ensure(c, c->kmember, (size_t)B * c->user_max * 4))) return rc;
-    if ((rc = ensure(c, c->kmap, (size_t)B * need * 4))) return rc;
-    if ((rc = ensure(c, c->h_kmap, (size_t)B * need * 4, true))) return rc;
+    for (DevBuf* b : {&c->kmap, (DevBuf*)&c->h_kmap}) if ((rc = ensure(c, *b, (size_t)B * need * 4))) return rc;
   }
   if (same) return 0;
 
@@ -233,7 +249,7 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   c->dim = p.compute_descriptors ? (p.half_sift ? 64 : 128) : 0;
   long long det_px = gt / B;  // detection pixels per image
   int cap_raw = (int)(det_px / 32 < 16384 ? 16384 : det_px / 32);
-  if (c->cap_init > 0) cap_raw = c->cap_init;  // developer switch: start small so that the grow-and-re-run path is taken
+  if (c->sw.cap_init > 0) cap_raw = c->sw.cap_init;  // developer switch: start small so that the grow-and-re-run path is taken
   if (cap_raw < c->cap_raw) cap_raw = c->cap_raw;
   if (cap_raw < need) cap_raw = need;
   int cap_sel = c->use_topk ? p.feature_count_threshold : cap_raw;
@@ -245,8 +261,7 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   if (cap_feat < need) cap_feat = need;
 
   int rc;
-  if ((rc = ensure(c, c->gauss, (size_t)lvl * 4))) return rc;
-  if ((rc = ensure(c, c->deth, (size_t)lvl * 4))) return rc;
+  for (DevBuf* b : {&c->gauss, &c->deth}) if ((rc = ensure(c, *b, (size_t)lvl * 4))) return rc;
   if ((rc = ensure(c, c->got, (size_t)gt * 8))) return rc;
   {
     const int up = ds < 0 ? -ds : 0;  // the converted input is held at its own size; the up-sampled copy in `upsampled`
@@ -266,16 +281,13 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
   }
   if ((rc = ensure(c, c->rowoff, (size_t)B * g.NR * 4))) return rc;
   if ((rc = ensure(c, c->level_count, (size_t)B * g.nlev * 4))) return rc;
-  if ((rc = ensure(c, c->raw_total, (size_t)B * 4))) return rc;
-  if ((rc = ensure(c, c->sel_total, (size_t)B * 4))) return rc;
-  if ((rc = ensure(c, c->feat_total, (size_t)B * 4))) return rc;
-  if ((rc = ensure(c, c->feat_first, (size_t)B * 4))) return rc;
+  for (DevBuf* b : {&c->raw_total, &c->sel_total, &c->feat_total, &c->feat_first}) if ((rc = ensure(c, *b, (size_t)B * 4))) return rc;
   if ((rc = ensure(c, c->img_base, (size_t)(B + 1) * 4))) return rc;
   if ((rc = ensure(c, c->raw, (size_t)B * cap_raw * sizeof(RawKey)))) return rc;
   {  // the scan's unordered detections: every scan task's slots + the image's spill list (hess_dev.h, DetectStore);
      // tasks for the shortest segments a batch may be scanned with (enqueue(): batches of one or two images, HESS_STREAM_ROWS)
     int ntask = extrema_tasks(g);
-    for (int rows : {kStreamRows / policy::kLatencyStreamRowsDiv, c->stream_rows}) {
+    for (int rows : {kStreamRows / policy::kLatencyStreamRowsDiv, c->sw.stream_rows}) {
       if (rows <= 0) continue;
       Geom gr = g;
       set_stream_rows(gr, rows);
@@ -289,13 +301,12 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
     if ((rc = ensure(c, c->sel, (size_t)B * cap_sel * sizeof(RawKey)))) return rc;
   }
   if ((rc = ensure(c, c->recs, (size_t)B * cap_sel * sizeof(FRec)))) return rc;
-  if ((rc = ensure(c, c->ocount, (size_t)B * cap_sel * 4))) return rc;
-  if ((rc = ensure(c, c->foffset, (size_t)B * cap_sel * 4))) return rc;
+  for (DevBuf* b : {&c->ocount, &c->foffset}) if ((rc = ensure(c, *b, (size_t)B * cap_sel * 4))) return rc;
   if ((rc = ensure(c, c->fsrc, (size_t)B * cap_feat * 4))) return rc;
   if ((rc = ensure(c, c->keys, (size_t)B * cap_feat * sizeof(HostKeypoint)))) return rc;
   const size_t dbytes = run_desc_bytes(c, c->desc_format);  // (grow-only in BYTES: a buffer that held floats holds the bytes of the same plan)
   if (c->dim && (rc = ensure(c, c->desc, (size_t)B * cap_feat * dbytes))) return rc;
-  if ((rc = ensure(c, c->h_small, (size_t)(3 * B + 8) * 4, true))) return rc;
+  if ((rc = ensure(c, c->h_small, (size_t)(3 * B + 8) * 4))) return rc;
   {
     // The pinned result buffers hold the worst case B * cap_feat records up front while that stays moderate; beyond
     // it they grow on demand once the counts are known (wait_impl / the copier), and the in-kernel mirror is not used.
@@ -303,11 +314,11 @@ int plan_inner(hess_ctx* c, int width, int height, int batch) {
     // Node-shared result buffers of a batch the copier delivers are sized by the batches seen (+ 25 %), not for the
     // worst case B * cap_feat: 79 MB per context, 3.8 - 4.4 GB of /dev/shm for a node's six or seven contexts x eight
     // ranks, where the results are 24 MB per context; the copier (or hess_wait) grows them under a new generation when a batch needs more.
-    c->share_by_need = c->share_dir && B > c->mirror_max_batch && c->delivery_pref != kDeliverMirror;
+    c->share_by_need = c->share_dir && B > c->sw.mirror_max_batch && c->sw.delivery_pref != kDeliverMirror;
     c->host_fits = !c->share_by_need && host_bytes <= policy::kHostWorstCaseMax;
     if (c->host_fits) {
-      if ((rc = ensure(c, c->h_keys, (size_t)B * cap_feat * sizeof(HostKeypoint), true))) return rc;
-      if (c->dim && (rc = ensure(c, c->h_desc, (size_t)B * cap_feat * dbytes, true))) return rc;
+      if ((rc = ensure(c, c->h_keys, (size_t)B * cap_feat * sizeof(HostKeypoint)))) return rc;
+      if (c->dim && (rc = ensure(c, c->h_desc, (size_t)B * cap_feat * dbytes))) return rc;
     }
   }
 
@@ -338,6 +349,5 @@ int plan(hess_ctx* c, int width, int height, int batch) {
   }
   return rc;
 }
-
 
 }  // namespace hess

@@ -5,7 +5,7 @@ namespace hess {
 
 // ---- profiling helpers ----
 hipEvent_t get_event(hess_ctx* c) {
-  if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
+  if (!c->prof_ev.pool.empty()) { hipEvent_t e = c->prof_ev.pool.back(); c->prof_ev.pool.pop_back(); return e; }
   hipEvent_t e = nullptr;
   if (hipEventCreate(&e) != hipSuccess) { set_err(c, "hipEventCreate failed: profiling disabled"); c->prof = false; return nullptr; }
   return e;
@@ -27,8 +27,8 @@ struct ProfRun {
     if (!open) {
       ep.a = get_event(c); ep.b = get_event(c); ep.bytes = 0.0; ep.in_lds = 0.0; ep.count = 0;
       if (!ep.a || !ep.b || hipEventRecord(ep.a, c->st) != hipSuccess) {
-        if (ep.a) c->pool.push_back(ep.a);
-        if (ep.b) c->pool.push_back(ep.b);
+        if (ep.a) c->prof_ev.pool.push_back(ep.a);
+        if (ep.b) c->prof_ev.pool.push_back(ep.b);
         return;
       }
       open = true;
@@ -38,8 +38,8 @@ struct ProfRun {
   void close() {
     if (!open) return;
     open = false;
-    if (hipEventRecord(ep.b, c->st) != hipSuccess) { c->pool.push_back(ep.a); c->pool.push_back(ep.b); return; }
-    c->pending.push_back(ep);
+    if (hipEventRecord(ep.b, c->st) != hipSuccess) { c->prof_ev.pool.push_back(ep.a); c->prof_ev.pool.push_back(ep.b); return; }
+    c->prof_ev.pending.push_back(ep);
   }
   ~ProfRun() { close(); }
 };
@@ -59,7 +59,7 @@ static ProfScope book_pyramid(ProfRun& run, bool octave0, double bytes, double i
   return ProfScope(run.c, HESS_K_GAUSS, bytes, HESS_K_GAUSS_OCT0, in_lds, octave0);
 }
 void drain_profile(hess_ctx* c) {
-  for (auto& ep : c->pending) {
+  for (auto& ep : c->prof_ev.pending) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, ep.a, ep.b) == hipSuccess) {
       c->k_ms[ep.kernel] += ms;
@@ -70,10 +70,10 @@ void drain_profile(hess_ctx* c) {
         c->k_ms[ep.kernel2] += ms; c->k_n[ep.kernel2] += ep.count; c->k_bytes[ep.kernel2] += ep.bytes; c->k_in_lds[ep.kernel2] += ep.in_lds;
       }
     }
-    c->pool.push_back(ep.a);
-    c->pool.push_back(ep.b);
+    c->prof_ev.pool.push_back(ep.a);
+    c->prof_ev.pool.push_back(ep.b);
   }
-  c->pending.clear();
+  c->prof_ev.pending.clear();
 }
 
 // 2^_octave_min: scale of the first octave relative to the input (PyramidCU.cpp:566-569,746-748,1054-1057).
@@ -115,7 +115,7 @@ static DescParams desc_params(const hess_ctx* c, int pixtype, int desc_format, b
   dsp.hdesc = (c->host_direct && c->dim) ? c->h_desc.p : nullptr;
   dsp.u8 = desc_format == HESS_DESC_FORMAT_U8;
   dsp.first_image = 0; dsp.part = 0; dsp.part_den = 1;  // (one launch over the whole list)
-  dsp.xcd_block = c->desc_xcd_block; dsp.px_band = c->desc_px_band;
+  dsp.xcd_block = c->sw.desc_xcd_block; dsp.px_band = c->sw.desc_px_band;
   dsp.sequential = p.descriptor_order == HESS_DESC_ORDER_SEQUENTIAL;
   // the pixel order's fixed point assumes luminance in [0, 1] (8- and 16-bit inputs); float pixels are taken as they are
   // and keep the interleaved order (the test oracle applies the same rule)
@@ -138,7 +138,7 @@ static void choose_parts(hess_ctx* c, int batch) {
   pt.features = false;
   static_assert(policy::kLargeImageParts <= Copier::kMaxParts, "parts of one image");
   if (batch == 1 && c->delivery == kDeliverDma) { want = policy::kLargeImageParts; pt.features = true; }
-  if (c->desc_parts > 0) want = std::max(1, std::min<int>(Copier::kMaxParts, pt.features ? c->desc_parts : std::min(batch, c->desc_parts)));
+  if (c->sw.desc_parts > 0) want = std::max(1, std::min<int>(Copier::kMaxParts, pt.features ? c->sw.desc_parts : std::min(batch, c->sw.desc_parts)));
   if (c->delivery != kDeliverDma || !c->cp.ev_part[0]) want = 1;
   if (want == 1) pt.features = false;
   pt.n = want;
@@ -177,7 +177,7 @@ static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
   // modes: resolve()) also writes level 0 of the next octave (its even rows and columns): no decimation launches.
   // det-H of the top level by the launch that produces it (k_gauss.hip, TOP tiles); HESS_NO_TOP_FUSION=1: the round-4
   // form (the level is stored, hessian_rows4_kernel reads it back) for A/B runs
-  const bool top_fused = s.level_max == g.dog + 1 && !c->no_top_fusion;
+  const bool top_fused = s.level_max == g.dog + 1 && !c->sw.no_top_fusion;
   c->zero_filled = false;
   // Level l of octave o from level l-1; the same launch emits det-H (+ gradient/theta) of level l-1 from the source
   // window it stages: 8 B R+W for the blur, 4 B (+8 B) W for the fused planes (+ 4 B per pixel of the next octave's
@@ -221,7 +221,7 @@ static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
   // T(o, l) = 3o + l is the earliest step of level l of octave o (level 0 of octave o+1 is the decimated level_ds of
   // octave o): the top level of an octave and level 1 of the next are due together and independent, so they share a
   // launch (launch_gauss_pair) -- one launch fewer per octave in the dependent chain.
-  const bool pair_levels = !c->no_pair;
+  const bool pair_levels = !c->sw.no_pair;
   // A single image (or two): octaves from 1 on get levels 1..level_ds -- what the next octave waits for -- from ONE
   // launch each (gauss_chain_kernel: 32x32 tiles computed in LDS on a shrinking halo): below 960x540 a level launch is a
   // few dozen workgroups that mostly wait, and the eighteen of them for octaves 1-6 of a 1080p image were two thirds of
@@ -235,7 +235,7 @@ static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
   // HESS_CHAIN_FROM=n forces the first chained octave (99: never).
   int chain_from = g.noct;
   if (s.level_max == s.level_ds + 1 && gauss_chain_available(s.taps, s.level_ds)) {
-    chain_from = c->chain_from;
+    chain_from = c->sw.chain_from;
     if (chain_from <= 0) {  // by size: the first octave (>= 1) whose planes of the whole batch are at most two 960x540 planes
       chain_from = g.noct;
       // (a PAIR of images handed over by hess_submit_* -- a caller who pipelines -- gets the level-by-level launches and
@@ -279,7 +279,7 @@ static int enqueue_pyramid(hess_ctx* c, const PendingRun& r) {
       l = s.level_max;
     } else if (o == 0) {
       bool first_fused = false;  // levels 0 and 1 come out of one launch (level 0 never written)
-      if (direct_u8 && !c->no_first_fusion && s.level_ds != 1 && gauss_first_available(c->taps0, s.taps[1])) {
+      if (direct_u8 && !c->sw.no_first_fusion && s.level_ds != 1 && gauss_first_available(c->taps0, s.taps[1])) {
         // Decided BEFORE the profile scope: a refused launch must not book bytes.  The tap counts are the one refusal of
         // launch_gauss_first that can still fire here: its alignment clauses (pitch % 4, img_stride % 4) repeat what
         // direct_u8 already requires, and level(0, 1) has the plane pointers it asks for.  An unaligned pitch, image
@@ -383,7 +383,7 @@ static int enqueue_detection(hess_ctx* c, int batch, const LimitParams& lp) {
   dp.edge = (p.edge_threshold + 1) * (p.edge_threshold + 1) / p.edge_threshold;      // ProgramCU.cu:913
   dp.subpixel = p.subpixel;
   Geom gx = g;  // the extrema scan's segment length
-  if (c->stream_rows > 0) set_stream_rows(gx, c->stream_rows);      // HESS_STREAM_ROWS (A/B switch; a multiple of 3)
+  if (c->sw.stream_rows > 0) set_stream_rows(gx, c->sw.stream_rows);      // HESS_STREAM_ROWS (A/B switch; a multiple of 3)
   else if (batch <= policy::kLatencyBatch) set_stream_rows(gx, kStreamRows / policy::kLatencyStreamRowsDiv);  // shorter segments, twice the wavefronts
   if (!c->zero_filled)  // overflow flags, row counts, histogram, masks (normally cleared by octave 0's top-level launch)
     HIP_TRY(c, hipMemsetAsync(c->zeroed.p, 0, c->zeroed_used, st));
@@ -567,6 +567,5 @@ int enqueue_user(hess_ctx* c, int batch, int desc_format) {
   lp.threshold = -1;  // LimitFeatureCount returns at once for existing keypoints (SiftPyramid.cpp:203)
   return enqueue_features(c, lp, batch, HESS_PIX_U8, desc_format, true, !c->user_have_orientation);
 }
-
 
 }  // namespace hess

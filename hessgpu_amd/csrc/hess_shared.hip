@@ -6,18 +6,17 @@ namespace hess {
 // A pinned result buffer of a context whose results are shared with other processes of the node (hess_share_results):
 // a POSIX shared memory object, mapped and registered with the runtime, so that the copier's DMA copy (or the
 // descriptor kernel's own stores) lands in memory the consumer process has mapped as well -- every GPU of a node
-// delivers over its own host link and nothing is funnelled through one rank's.  `which` is 'k' or 'd'.
+// delivers over its own host link and nothing is funnelled through one rank's.  DevBuf::shared is 'k' or 'd'.
 // Where /dev/shm has no room (containers often give it 64 MB) the buffer becomes a file under HESS_SHARE_DIR / TMPDIR /
 // /tmp instead, mapped MAP_SHARED and registered the same way: page-cache pages, pinned by the registration -- the
 // consumer maps the same pages.  Slower to set up, the same to use.  HESS_SHARE_FORCE_FILE=1 skips /dev/shm (tests).
-int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which) {
-  if (bytes <= b.bytes) return 0;
+int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes) {
   const long page = sysconf(_SC_PAGESIZE);
   size_t want = bytes + bytes / 4;  // grown by need: a quarter of slack so that batches of similar size do not reallocate
   want = (want + (size_t)page - 1) / (size_t)page * (size_t)page;
-  uint32_t& gen = which == 'k' ? c->share_dir->gen_keys : c->share_dir->gen_desc;
+  uint32_t& gen = b.shared == 'k' ? c->share_dir->gen_keys : c->share_dir->gen_desc;
   char name[256], path[1024];
-  snprintf(name, sizeof(name), "/%s.%c%u", c->share.c_str(), which, gen + 1);
+  snprintf(name, sizeof(name), "/%s.%c%u", c->share.c_str(), b.shared, gen + 1);
   // (posix_fallocate, not ftruncate: a full file system must fail here, not as a bus error at the first store)
   auto size_fd = [&](int fd) {
     int fe = posix_fallocate(fd, 0, (off_t)want);
@@ -73,7 +72,7 @@ int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which) {
     munmap(np, want); drop();
     return e == hipErrorOutOfMemory ? HESS_ERR_NOMEM : HESS_ERR_DEVICE;
   }
-  release(b, true);
+  release(b);
   try {
     b.shm = is_file ? path : name;
   } catch (...) {  // (nothing thrown crosses the C ABI)
@@ -84,13 +83,12 @@ int ensure_shared(hess_ctx* c, DevBuf& b, size_t bytes, char which) {
   }
   b.p = np; b.bytes = want;
   // size and path first, the generation number last: a reader that sees the new generation sees its buffer
-  (which == 'k' ? c->share_dir->keys_bytes : c->share_dir->desc_bytes) = want;
-  snprintf(which == 'k' ? c->share_dir->keys_path : c->share_dir->desc_path, sizeof(c->share_dir->keys_path), "%s", path);
+  (b.shared == 'k' ? c->share_dir->keys_bytes : c->share_dir->desc_bytes) = want;
+  snprintf(b.shared == 'k' ? c->share_dir->keys_path : c->share_dir->desc_path, sizeof(c->share_dir->keys_path), "%s", path);
   __sync_synchronize();
   gen++;
   __sync_synchronize();
   return 0;
 }
-
 
 }  // namespace hess
