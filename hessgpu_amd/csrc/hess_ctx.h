@@ -40,6 +40,7 @@
 
 #include "../../include/hess_abi.h"
 #include "hess_dev.h"
+#include "hess_owned.h"
 #include "hess_stager.h"
 
 namespace hess {
@@ -55,8 +56,9 @@ struct Schedule {
 };
 
 // A grow-only allocation that knows its kind and frees itself (ensure / release, hess_plan.hip).  Not the matcher's
-// DeviceBuf<T>: that one frees before it allocates and has one kind; here the new allocation is made before the old one is
-// freed, so that a context survives a refused hess_reserve, and the kinds differ in how they are freed.
+// DeviceBuf<T>: that one has one kind and frees before it allocates (what must survive there, a descriptor set, is built in a
+// second DeviceBuf and swapped in); here the new allocation is made before the old one is freed, so that a context survives a
+// refused hess_reserve, and the kinds differ in how they are freed.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -72,20 +74,7 @@ struct DevBuf {
 };
 struct PinnedBuf : DevBuf { PinnedBuf() : DevBuf(true) {} };
 
-// A runtime handle destroyed with its owner: a stream, an event, a completion signal.  A null handle owns nothing.
-template <class H, class R, R (*destroy)(H)>
-struct Owned {
-  H h{};
-  Owned() = default;
-  Owned(const Owned&) = delete;
-  Owned& operator=(const Owned&) = delete;
-  ~Owned() { if (*this) (void)destroy(h); }
-  operator H() const { return h; }
-  explicit operator bool() const { H none{}; return memcmp(&h, &none, sizeof(H)) != 0; }
-  void forget() { h = H{}; }  // given up without being destroyed (a signal that a lost copy may still write)
-};
-using Stream = Owned<hipStream_t, hipError_t, hipStreamDestroy>;
-using Event = Owned<hipEvent_t, hipError_t, hipEventDestroy>;
+// Owned<>, Stream and Event: hess_owned.h (the matcher has them too).  The completion signal needs the ROCr headers.
 using Signal = Owned<hsa_signal_t, hsa_status_t, hsa_signal_destroy>;
 
 struct EventPair {

@@ -39,6 +39,9 @@
 // wait and the error text) and run_pairs (a pair list planned, its chunks run through it and compacted on the device), which serves
 // hess_matcher_match_pairs with (bank, bank) and the typed single pair with (slot 0, slot 1) and a list of one;
 // hess_matcher_match otherwise plans one job and compacts on the host, or takes match_small.
+// Lifetimes are written in types: the stream and the events are hess_owned.h's, every device allocation is a DeviceBuf -- the
+// members of DescSets and of the matcher, and the temporaries of a load, which `stage` fills from a host array.  A set that must
+// survive a failed change (sets_regroup, bank_locations) is built in local buffers and swapped in after the last call that can fail.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +60,7 @@
 #include "hess_guided_gate.h"
 #include "hess_match_plan.h"
 #include "hess_matcher_int.h"
+#include "hess_owned.h"
 #include "hess_slot_pipeline.h"
 
 using namespace hess::match_plan;  // the constants MM_*, MP_*, PairJob, the plan of a pair list and of the plan buffer
@@ -888,39 +892,40 @@ __global__ __launch_bounds__(256) void bank_loc_gather_kernel(const unsigned cha
   out[g] = make_float2(p[0], p[1]);
 }
 
-// Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.
+// Descriptor sets on the device (bank_build_kernel's layout); a zero-padded set serves as either side of a match.  Every
+// buffer frees itself: not copyable, and what empties a set (sets_clear, sets_drop_locations) resets members.
 struct DescSets {
   int dim = 128;  // bytes per row (the matcher's dim when the sets were built)
-  uint8_t* rows = nullptr;
-  int *rfix = nullptr, *cfix = nullptr;  // one allocation: cfix = rfix + padded rows
+  DeviceBuf<uint8_t> rows;
+  DeviceBuf<int> rfix;                   // 2 x padded rows, allocated to the element: the row offsets, then the column offsets
   std::vector<int> off, num;             // first padded row and stored descriptors of each set (in the caller's order)
   std::vector<int> cnt, first;           // descriptors the caller counted per set (before max_sift); first original row
   bool built = false;                    // descriptors were loaded (possibly none)
   // feature types (hess_matcher_set_types, _bank_set_types): the rows are stored by class instead
   bool typed = false;
   std::vector<int> goff, gnum;           // [set][class]: first stored row and rows of the class group
-  int *fwd = nullptr, *inv = nullptr;    // original row (first[s] + i) -> stored row; stored row -> i, -1 for padding
+  DeviceBuf<int> fwd, inv;               // original row (first[s] + i) -> stored row; stored row -> i, -1 for padding
   // locations (hess_matcher_set_locations, _bank_set_locations): one (x, y) per kept row in the caller's order, set s from
-  // first[s] on -- NOT padded like the descriptors, and not moved by the types.  A set without rows has them with loc NULL.
-  float2* loc = nullptr;
+  // first[s] on -- NOT padded like the descriptors, and not moved by the types.  A set without rows has them with loc.p NULL.
+  DeviceBuf<float2> loc;
   bool have_loc = false;
-  DescSets() = default;
-  DescSets(const DescSets&) = delete;
-  DescSets& operator=(const DescSets&) = delete;
-  ~DescSets();
+  int* cfix() const { return rfix.p + rfix.cap / 2; }
   int count(int s) const { return s < (int)num.size() ? num[s] : 0; }
   SetsLayout layout() const { return {off.data(), num.data(), first.data(), typed ? goff.data() : nullptr, typed ? gnum.data() : nullptr}; }
 };
 
 }  // namespace
 
-// Every buffer frees itself (DescSets, DeviceBuf, PinnedSlots); the stream and the events go in hess_matcher_destroy, after them.
+// Every member frees itself (hess_owned.h, DescSets, DeviceBuf, PinnedSlots), so hess_matcher_destroy is `delete`.  The stream
+// and the events stand BEFORE everything that holds memory: members go in reverse order, the buffers first, the handles last.
 // Calls on one matcher are serialised by the caller and every entry point returns with the stream idle, so the pair-list
 // entry points share one plan buffer and one output buffer.
 struct hess_matcher {
   int device = 0, max_sift = 4096;
   int dim = 128;  // descriptor length of every set and argument: hess_matcher_set_dim
-  hipStream_t st = nullptr;
+  hess::Stream st;
+  hess::Event e0, e1;        // around the kernels of a single pair
+  hess::Event mp_ev[2][3];   // per pinned slot of a pair list: start, kernels done, copy done; created by slot_events
   DescSets bank, slot[2];    // hess_matcher_bank_*; the one-set slots of set_descriptors(0|1)
   hess_geom_state_ptr geom;  // hess_geom.hip: the estimator's buffers
   // small / guided path: score matrix and column partials per 64-row tile (sized together: match_small)
@@ -933,7 +938,6 @@ struct hess_matcher {
   std::vector<int> hrow, hcol;
   std::string err;
   float last_ms = 0.0f;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   // pair lists and the single pair on the matrix cores: the plan (jobs, work tables; for verify_pairs those of a group's
   // chunks) on the device and in two pinned host slots
   DeviceBuf<uint8_t> plan;
@@ -942,7 +946,6 @@ struct hess_matcher {
   // through two pinned host slots, in bytes
   DeviceBuf<uint8_t> out;
   PinnedSlots<uint8_t> hout;
-  hipEvent_t mp_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: start, kernels done, copy done
   DeviceBuf<GuidedGeo> geo;  // match_pairs_guided: the call's geometry table; verify_pairs: a group's
   DeviceBuf<int2> vp_lalb;   // verify_pairs: per pair of the call the first location rows of its two sets
 };
@@ -950,31 +953,29 @@ struct hess_matcher {
 namespace {
 
 void sets_drop_locations(DescSets& s) {
-  (void)hipFree(s.loc);
-  s.loc = nullptr;
+  s.loc.reset();
   s.have_loc = false;
 }
 
 void sets_clear(DescSets& s) {
-  (void)hipFree(s.rows);
-  (void)hipFree(s.rfix);
-  s.rows = nullptr;
-  s.rfix = s.cfix = nullptr;
-  s.off.clear();
-  s.num.clear();
-  s.cnt.clear();
-  s.first.clear();
-  s.built = false;
-  (void)hipFree(s.fwd);
-  (void)hipFree(s.inv);
-  s.fwd = s.inv = nullptr;
-  s.typed = false;
-  s.goff.clear();
-  s.gnum.clear();
+  s.rows.reset();
+  s.rfix.reset();
+  s.fwd.reset();
+  s.inv.reset();
+  for (std::vector<int>* v : {&s.off, &s.num, &s.cnt, &s.first, &s.goff, &s.gnum}) v->clear();
+  s.built = s.typed = false;
   sets_drop_locations(s);
 }
 
-DescSets::~DescSets() { sets_clear(*this); }
+// d = the n elements at h, in an allocation of at least one element: copied on stream st or, without one, before the return.
+// Every host array that a kernel reads goes up through here, into a buffer that frees itself.
+template <class T>
+hipError_t stage(DeviceBuf<T>& d, const T* h, size_t n, hipStream_t st = nullptr) {
+  const hipError_t e = d.grow(n ? n : 1);
+  if (e != hipSuccess) return e;
+  if (st) return hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st);
+  return hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice);
+}
 
 template <int KD>
 void launch_bank_build(hipStream_t st, size_t padded, bool f32, const void* src, const int3* dsets, int nsets, uint8_t* rows,
@@ -1000,19 +1001,13 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
   }
   for (int k = 0; k < nsets; k++) sets[k] = make_int3(off[k], srow[k], num[k]);
   if (padded) {
-    M_TRY(m, hipMalloc(&s.rows, padded * KD));
-    M_TRY(m, hipMalloc(&s.rfix, 2 * padded * sizeof(int)));
-    s.cfix = s.rfix + padded;
-    int3* dsets = nullptr;
-    M_TRY(m, hipMalloc(&dsets, sets.size() * sizeof(int3)));
-    hipError_t e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
-    if (e == hipSuccess) {
-      if (m->dim == 128) launch_bank_build<128>(m->st, padded, f32, src, dsets, nsets, s.rows, s.rfix, s.cfix);
-      else launch_bank_build<64>(m->st, padded, f32, src, dsets, nsets, s.rows, s.rfix, s.cfix);
-      e = hipGetLastError();
-    }
-    const hipError_t es = hipStreamSynchronize(m->st);
-    (void)hipFree(dsets);
+    DeviceBuf<int3> dsets;
+    M_TRY(m, s.rows.grow(padded * KD));
+    M_TRY(m, s.rfix.grow(2 * padded));
+    M_TRY(m, stage(dsets, sets.data(), sets.size(), m->st));
+    if (m->dim == 128) launch_bank_build<128>(m->st, padded, f32, src, dsets.p, nsets, s.rows.p, s.rfix.p, s.cfix());
+    else launch_bank_build<64>(m->st, padded, f32, src, dsets.p, nsets, s.rows.p, s.rfix.p, s.cfix());
+    const hipError_t e = hipGetLastError(), es = hipStreamSynchronize(m->st);
     M_TRY(m, e);
     M_TRY(m, es);
   }
@@ -1027,16 +1022,9 @@ int sets_build(hess_matcher* m, DescSets& s, int nsets, const int* counts, const
 // `s` from host bytes: `rows` (the sum of counts) staged on the device, then sets_build.  On failure `s` is empty.
 int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const unsigned char* des, size_t rows) {
   sets_clear(s);
-  const size_t KD = (size_t)m->dim;
-  uint8_t* staging = nullptr;
-  if (rows) {
-    M_TRY(m, hipMalloc(&staging, rows * KD));
-    const hipError_t e = hipMemcpy(staging, des, rows * KD, hipMemcpyHostToDevice);
-    if (e != hipSuccess) (void)hipFree(staging);
-    M_TRY(m, e);
-  }
-  const int rc = sets_build(m, s, nsets, counts, staging, false);
-  (void)hipFree(staging);
+  DeviceBuf<uint8_t> staging;  // (stays empty for a bank without rows)
+  if (rows) M_TRY(m, stage(staging, des, rows * (size_t)m->dim));
+  const int rc = sets_build(m, s, nsets, counts, staging.p, false);
   if (rc) sets_clear(s);
   return rc;
 }
@@ -1044,21 +1032,8 @@ int sets_load(hess_matcher* m, DescSets& s, int nsets, const int* counts, const 
 template <int KD>
 void launch_bank_gather(hipStream_t st, size_t padded, const DescSets& o, const int* src, uint8_t* rows, int* rfix, int* cfix) {
   const dim3 grid((unsigned)((padded + 4096 / KD - 1) / (4096 / KD)));
-  hipLaunchKernelGGL(bank_gather_kernel<KD>, grid, dim3(256), 0, st, o.rows, o.rfix, o.cfix, src, (int)padded, rows, rfix, cfix);
+  hipLaunchKernelGGL(bank_gather_kernel<KD>, grid, dim3(256), 0, st, o.rows.p, o.rfix.p, o.cfix(), src, (int)padded, rows, rfix, cfix);
 }
-
-// Device buffers of one sets_regroup, freed when it returns.
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() { for (void* q : p) (void)hipFree(q); }
-  template <class T> hipError_t get(T*& out, size_t n) {
-    out = nullptr;
-    const hipError_t e = hipMalloc(&out, (n ? n : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(out);
-    return e;
-  }
-  void keep(void* q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
-};
 
 // Stores the rows of `s` grouped by the class of dev_types (device memory: one u16 per descriptor the caller counted,
 // `stride` bytes apart), or back in the caller's order for dev_types == NULL.  The rows move from the present storage,
@@ -1069,12 +1044,15 @@ int sets_regroup(hess_matcher* m, DescSets& s, const void* dev_types, size_t str
   const size_t KD = (size_t)s.dim;
   const size_t total = nsets ? (size_t)s.first[nsets - 1] + s.num[nsets - 1] : 0;
   std::vector<int> goff, gnum;
-  Scratch tmp;
-  int *pos = nullptr, *fwd = nullptr, *inv = nullptr, *src = nullptr, *rfix = nullptr;
-  uint8_t* rows = nullptr;
   size_t padded = 0;
   std::vector<TypeSet> tab((size_t)nsets);
   for (int k = 0; k < nsets; k++) tab[k] = TypeSet{s.first[k], s.off[k], {0, 0, 0, 0}};
+  // what `s` will hold, built aside (fwd and inv stay empty without types), and what only this call needs: all of it is
+  // freed on every way out, after the commit below the former with the buffers `s` held before
+  DeviceBuf<uint8_t> rows;
+  DeviceBuf<int> rfix, fwd, inv, pos, src, dcounts;
+  DeviceBuf<int3> dsets;
+  DeviceBuf<TypeSet> dtab;
   if (dev_types) {
     goff.assign((size_t)nsets * 4, 0);
     gnum.assign((size_t)nsets * 4, 0);
@@ -1085,16 +1063,13 @@ int sets_regroup(hess_matcher* m, DescSets& s, const void* dev_types, size_t str
         sets[k] = make_int3((int)srow, s.num[k], s.first[k]);
         srow += (size_t)s.cnt[k];
       }
-      int3* dsets = nullptr;
-      int* dcounts = nullptr;
-      M_TRY(m, tmp.get(pos, total));
-      M_TRY(m, tmp.get(dsets, (size_t)nsets));
-      M_TRY(m, tmp.get(dcounts, (size_t)nsets * 4));
-      M_TRY(m, hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st));
+      M_TRY(m, pos.grow(total));
+      M_TRY(m, dcounts.grow((size_t)nsets * 4));
+      M_TRY(m, stage(dsets, sets.data(), sets.size(), m->st));
       hipLaunchKernelGGL(type_classify_kernel, dim3(nsets), dim3(256), 0, m->st, static_cast<const uint8_t*>(dev_types), stride,
-                         dsets, pos, dcounts);
+                         dsets.p, pos.p, dcounts.p);
       M_TRY(m, hipGetLastError());
-      M_TRY(m, hipMemcpyAsync(gnum.data(), dcounts, gnum.size() * sizeof(int), hipMemcpyDeviceToHost, m->st));
+      M_TRY(m, hipMemcpyAsync(gnum.data(), dcounts.p, gnum.size() * sizeof(int), hipMemcpyDeviceToHost, m->st));
       M_TRY(m, hipStreamSynchronize(m->st));
     }
     if (!group_layout(4 * nsets, gnum.data(), KD, goff.data(), &padded)) { m->err = "set_types: bank too large"; return HESS_ERR_TOO_BIG; }
@@ -1102,34 +1077,28 @@ int sets_regroup(hess_matcher* m, DescSets& s, const void* dev_types, size_t str
   } else if (nsets) {
     padded = (size_t)s.off[nsets - 1] + pad_rows((size_t)s.num[nsets - 1]);
   }
-  if (total) {
-    TypeSet* dtab = nullptr;
-    M_TRY(m, tmp.get(rows, padded * KD));
-    M_TRY(m, tmp.get(rfix, 2 * padded));
-    M_TRY(m, tmp.get(src, padded));
-    M_TRY(m, tmp.get(dtab, (size_t)nsets));
-    M_TRY(m, hipMemsetAsync(src, 0xff, padded * sizeof(int), m->st));
+  if (total) {  // (so there are sets and padded rows: no size below is zero)
+    M_TRY(m, rows.grow(padded * KD));
+    M_TRY(m, rfix.grow(2 * padded));
+    M_TRY(m, src.grow(padded));
+    M_TRY(m, hipMemsetAsync(src.p, 0xff, padded * sizeof(int), m->st));
     if (dev_types) {
-      M_TRY(m, tmp.get(fwd, total));
-      M_TRY(m, tmp.get(inv, padded));
-      M_TRY(m, hipMemsetAsync(inv, 0xff, padded * sizeof(int), m->st));
+      M_TRY(m, fwd.grow(total));
+      M_TRY(m, inv.grow(padded));
+      M_TRY(m, hipMemsetAsync(inv.p, 0xff, padded * sizeof(int), m->st));
     }
-    M_TRY(m, hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(TypeSet), hipMemcpyHostToDevice, m->st));
-    hipLaunchKernelGGL(type_place_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st, dtab, nsets, (int)total,
-                       pos, s.typed ? s.fwd : nullptr, fwd, inv, src);
-    if (s.dim == 128) launch_bank_gather<128>(m->st, padded, s, src, rows, rfix, rfix + padded);
-    else launch_bank_gather<64>(m->st, padded, s, src, rows, rfix, rfix + padded);
+    M_TRY(m, stage(dtab, tab.data(), tab.size(), m->st));
+    hipLaunchKernelGGL(type_place_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st, dtab.p, nsets, (int)total,
+                       pos.p, s.typed ? s.fwd.p : nullptr, fwd.p, inv.p, src.p);
+    if (s.dim == 128) launch_bank_gather<128>(m->st, padded, s, src.p, rows.p, rfix.p, rfix.p + padded);
+    else launch_bank_gather<64>(m->st, padded, s, src.p, rows.p, rfix.p, rfix.p + padded);
     M_TRY(m, hipGetLastError());
     M_TRY(m, hipStreamSynchronize(m->st));
-    tmp.keep(rows); tmp.keep(rfix); tmp.keep(fwd); tmp.keep(inv);
-    (void)hipFree(s.rows); (void)hipFree(s.rfix);
-    s.rows = rows;
-    s.rfix = rfix;
-    s.cfix = rfix + padded;
+    s.rows.swap(rows);  // the commit: nothing fails from here on
+    s.rfix.swap(rfix);
   }
-  (void)hipFree(s.fwd); (void)hipFree(s.inv);
-  s.fwd = fwd;
-  s.inv = inv;
+  s.fwd.swap(fwd);
+  s.inv.swap(inv);
   s.typed = dev_types != nullptr;
   s.goff.swap(goff);
   s.gnum.swap(gnum);
@@ -1143,13 +1112,9 @@ int sets_types_host(hess_matcher* m, DescSets& s, const uint16_t* types, size_t 
   for (int c : s.cnt) n += (size_t)c;
   std::vector<uint16_t> h(n ? n : 1);
   for (size_t i = 0; i < n; i++) memcpy(&h[i], reinterpret_cast<const char*>(types) + i * stride, 2);
-  uint16_t* d = nullptr;
-  M_TRY(m, hipMalloc(&d, h.size() * 2));
-  hipError_t e = hipMemcpy(d, h.data(), h.size() * 2, hipMemcpyHostToDevice);
-  const int rc = e == hipSuccess ? sets_regroup(m, s, d, 2) : 0;
-  (void)hipFree(d);
-  M_TRY(m, e);
-  return rc;
+  DeviceBuf<uint16_t> d;
+  M_TRY(m, stage(d, h.data(), h.size()));
+  return sets_regroup(m, s, d.p, 2);
 }
 
 // What every types setter refuses: `what` names the entry point in the error text.
@@ -1173,25 +1138,18 @@ int bank_locations(hess_matcher* m, const void* dev, size_t stride) {
     srow += (size_t)b.cnt[k];
     total = (size_t)b.first[k] + (size_t)b.num[k];
   }
-  float2* loc = nullptr;
+  DeviceBuf<float2> loc;  // built aside: a failure leaves the bank's present locations in place
+  DeviceBuf<int3> dsets;
   if (total) {
-    int3* dsets = nullptr;
-    M_TRY(m, hipMalloc(&loc, total * sizeof(float2)));
-    hipError_t e = hipMalloc(&dsets, sets.size() * sizeof(int3));
-    if (e == hipSuccess) e = hipMemcpyAsync(dsets, sets.data(), sets.size() * sizeof(int3), hipMemcpyHostToDevice, m->st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(bank_loc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st,
-                         static_cast<const unsigned char*>(dev), stride, dsets, nsets, (int)total, loc);
-      e = hipGetLastError();
-    }
-    const hipError_t es = hipStreamSynchronize(m->st);
-    (void)hipFree(dsets);
-    if (e != hipSuccess || es != hipSuccess) (void)hipFree(loc);
+    M_TRY(m, loc.grow(total));
+    M_TRY(m, stage(dsets, sets.data(), sets.size(), m->st));
+    hipLaunchKernelGGL(bank_loc_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->st,
+                       static_cast<const unsigned char*>(dev), stride, dsets.p, nsets, (int)total, loc.p);
+    const hipError_t e = hipGetLastError(), es = hipStreamSynchronize(m->st);
     M_TRY(m, e);
     M_TRY(m, es);
   }
-  (void)hipFree(b.loc);
-  b.loc = loc;
+  b.loc.swap(loc);
   b.have_loc = true;
   return 0;
 }
@@ -1260,7 +1218,7 @@ int pair_list_args(hess_matcher* m, int npairs, const int* pairs_ab, int max_mat
 int slot_events(hess_matcher* m) {
   for (int k = 0; k < 2; k++)
     for (int q = 0; q < 3; q++)
-      if (!m->mp_ev[k][q]) M_TRY(m, hipEventCreate(&m->mp_ev[k][q]));
+      M_TRY(m, hess::ensure(m->mp_ev[k][q]));
   return 0;
 }
 
@@ -1293,7 +1251,7 @@ hipError_t launch_chunk(hess_matcher* m, const uint8_t* dplan, const DescSets& s
                               : (mutual_best ? match_mfma_kernel<true, 64, true> : match_mfma_kernel<false, 64, true>))
              : (s1.dim == 128 ? (mutual_best ? match_mfma_kernel<true, 128, false> : match_mfma_kernel<false, 128, false>)
                               : (mutual_best ? match_mfma_kernel<true, 64, false> : match_mfma_kernel<false, 64, false>));
-    hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows, s1.rfix, s2.rows, s2.cfix, djobs,
+    hipLaunchKernelGGL(kern, dim3((unsigned)c.nwg), dim3(256), 0, m->st, s1.rows.p, s1.rfix.p, s2.rows.p, s2.cfix(), djobs,
                        plan_ptr<int2>(dplan, L.work), m->mm_cpart.p, m->mm_rstate.p, dgeo, loc);
     hipLaunchKernelGGL(match_finish_kernel, dim3((unsigned)c.nfin), dim3(256), 0, m->st, djobs, plan_ptr<int2>(dplan, L.fin),
                        m->mm_rstate.p, m->mm_cpart.p, distmax, ratiomax, m->rowm.p, m->colm.p);
@@ -1401,7 +1359,7 @@ int run_pairs(hess_matcher* m, const DescSets& s1, const DescSets& s2, int npair
         if (e != hipSuccess) return e;
         if (P.jpp == 4)
           hipLaunchKernelGGL(match_types_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan.p, L.jobs),
-                             plan_ptr<int2>(m->plan.p, L.orig), s1.fwd, s2.inv, m->rowm.p, m->colm.p, mutual_best, mm, dout,
+                             plan_ptr<int2>(m->plan.p, L.orig), s1.fwd.p, s2.inv.p, m->rowm.p, m->colm.p, mutual_best, mm, dout,
                              dout + MP_PAIRS);
         else
           hipLaunchKernelGGL(match_pairs_compact_kernel, dim3(c.pairs()), dim3(256), 0, m->st, plan_ptr<PairJob>(m->plan.p, L.jobs),
@@ -1579,7 +1537,7 @@ int match_small(hess_matcher* m, int n1, int n2, const float* H, const float* F,
   if (gp.guided) { memcpy(gp.H, H, 36); memcpy(gp.F, F, 36); gp.hdistmax = hdistmax; gp.fdistmax = fdistmax; }
   (void)hipEventRecord(m->e0, m->st);
   hipLaunchKernelGGL(m->dim == 128 ? match_dot_kernel<128> : match_dot_kernel<64>, dim3((n2 + TN - 1) / TN, (n1 + TM - 1) / TM),
-                     dim3(256), 0, m->st, m->slot[0].rows, n1, m->slot[1].rows, n2, m->slot[0].loc, m->slot[1].loc, gp,
+                     dim3(256), 0, m->st, m->slot[0].rows.p, n1, m->slot[1].rows.p, n2, m->slot[0].loc.p, m->slot[1].loc.p, gp,
                      mutual_best ? m->cpart.p : nullptr, m->dotm.p);
   hipLaunchKernelGGL(match_row_kernel, dim3((n1 + 3) / 4), dim3(256), 0, m->st, m->dotm.p, n1, n2, distmax, ratiomax,
                      m->rowm.p);
@@ -1599,29 +1557,22 @@ hess_matcher* hess_matcher_create(int device, int max_sift) {
     fprintf(stderr, "hessgpu: no usable HIP device %d (found %d)\n", device, ndev);
     return nullptr;
   }
-  hess_matcher* m = new (std::nothrow) hess_matcher();
-  if (!m) return nullptr;
-  m->device = device;
-  m->max_sift = max_sift > 0 ? max_sift : 4096;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess) {
-    delete m;
-    return nullptr;
+  std::unique_ptr<hess_matcher> m(new (std::nothrow) hess_matcher());
+  if (m && hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&m->st.h, hipStreamNonBlocking) == hipSuccess) {
+    m->device = device;
+    m->max_sift = max_sift > 0 ? max_sift : 4096;
+    (void)hess::ensure(m->e0);
+    (void)hess::ensure(m->e1);
+  } else {
+    m.reset();
   }
-  (void)hipEventCreate(&m->e0);
-  (void)hipEventCreate(&m->e1);
-  return m;
+  return m.release();
 }
 
 void hess_matcher_destroy(hess_matcher* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  const hipStream_t st = m->st;
-  hipEvent_t ev[8] = {m->e0, m->e1};
-  memcpy(ev + 2, m->mp_ev, sizeof(m->mp_ev));
-  delete m;  // (the sets and every buffer)
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (st) (void)hipStreamDestroy(st);
+  delete m;  // (members in reverse order: every buffer, then the events and the stream)
 }
 
 int hess_matcher_set_max(hess_matcher* m, int max_sift) {
@@ -1676,8 +1627,7 @@ int hess_matcher_set_locations(hess_matcher* m, int index, const float* location
   std::vector<float2> h((size_t)n);
   for (int i = 0; i < n; i++) { h[i].x = locations[0]; h[i].y = locations[1]; locations += 2 + gap; }
   sets_drop_locations(s);
-  M_TRY(m, hipMalloc(&s.loc, (size_t)n * sizeof(float2)));
-  M_TRY(m, hipMemcpy(s.loc, h.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
+  M_TRY(m, stage(s.loc, h.data(), h.size()));
   s.have_loc = true;
   return 0;
 }
@@ -1826,11 +1776,11 @@ int hess_matcher_bank_read(hess_matcher* m, int set, unsigned char* out) {
       for (int c = 0; c < 4; c++) ext += pad_rows((size_t)m->bank.gnum[4 * set + c]);
       std::vector<unsigned char> grp(ext * KD);
       std::vector<int> fwd((size_t)n);
-      M_TRY(m, hipMemcpy(grp.data(), m->bank.rows + (size_t)g0 * KD, ext * KD, hipMemcpyDeviceToHost));
-      M_TRY(m, hipMemcpy(fwd.data(), m->bank.fwd + m->bank.first[set], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+      M_TRY(m, hipMemcpy(grp.data(), m->bank.rows.p + (size_t)g0 * KD, ext * KD, hipMemcpyDeviceToHost));
+      M_TRY(m, hipMemcpy(fwd.data(), m->bank.fwd.p + m->bank.first[set], (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
       for (int i = 0; i < n; i++) memcpy(out + (size_t)i * KD, grp.data() + (size_t)(fwd[i] - g0) * KD, KD);
     } else {
-      M_TRY(m, hipMemcpy(out, m->bank.rows + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
+      M_TRY(m, hipMemcpy(out, m->bank.rows.p + (size_t)m->bank.off[set] * KD, (size_t)n * KD, hipMemcpyDeviceToHost));
     }
   }
   return n;
@@ -1877,13 +1827,9 @@ int hess_matcher_bank_set_locations(hess_matcher* m, const float* loc, size_t st
   // the (x, y) pairs packed on the host, staged on the device, then the device form's gather
   std::vector<float2> h(rows ? rows : 1);
   for (size_t i = 0; i < rows; i++) memcpy(&h[i], reinterpret_cast<const char*>(loc) + i * stride_bytes, sizeof(float2));
-  float2* d = nullptr;
-  M_TRY(m, hipMalloc(&d, h.size() * sizeof(float2)));
-  const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
-  const int rc = e == hipSuccess ? bank_locations(m, d, sizeof(float2)) : 0;
-  (void)hipFree(d);
-  M_TRY(m, e);
-  return rc;
+  DeviceBuf<float2> d;
+  M_TRY(m, stage(d, h.data(), h.size()));
+  return bank_locations(m, d.p, sizeof(float2));
 }
 
 int hess_matcher_bank_set_locations_device(hess_matcher* m, const void* dev_loc, size_t stride_bytes) {
@@ -1931,7 +1877,7 @@ int hess_matcher_match_pairs_guided(hess_matcher* m, int npairs, const int* pair
   if (npairs == 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
   return run_pairs(m, m->bank, m->bank, npairs, pairs_ab, max_match, out_pairs, out_counts, distmax, ratiomax, mutual_best ? 1 : 0,
-                   "match_pairs_guided", geo, m->bank.loc);
+                   "match_pairs_guided", geo, m->bank.loc.p);
 }
 
 // Match, estimate, guided match and (optionally) estimate of every pair of a list, chained on the device: run_verify.
@@ -1970,7 +1916,7 @@ int hess_matcher_verify_pairs(hess_matcher* m, int npairs, const int* pairs_ab, 
   m->last_ms = 0.0f;
   if (npairs == 0) return 0;
   M_TRY(m, hipSetDevice(m->device));
-  return run_verify(m, npairs, pairs_ab, *params, max_match, out_pairs, out_counts, out, inlier, putative_pairs, m->bank.loc);
+  return run_verify(m, npairs, pairs_ab, *params, max_match, out_pairs, out_counts, out, inlier, putative_pairs, m->bank.loc.p);
 }
 
 float hess_matcher_last_ms(hess_matcher* m) { return m ? m->last_ms : 0.0f; }
@@ -1982,7 +1928,7 @@ const char* hess_matcher_last_error(hess_matcher* m) { return m ? m->err.c_str()
 
 hess_matcher_view hess_matcher_view_of(hess_matcher* m) {
   const DescSets *s = m->slot, &b = m->bank;
-  return {m->device, m->st, m->e0, m->e1, m->err, &m->last_ms, {s[0].loc, s[1].loc},
+  return {m->device, m->st, m->e0, m->e1, m->err, &m->last_ms, {s[0].loc.p, s[1].loc.p},
           {s[0].have_loc ? s[0].count(0) : -1, s[1].have_loc ? s[1].count(0) : -1},
-          b.built, &b.num, &b.cnt, &b.first, b.loc, b.have_loc, &m->geom};
+          b.built, &b.num, &b.cnt, &b.first, b.loc.p, b.have_loc, &m->geom};
 }

@@ -6,6 +6,7 @@
 
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/hess_abi.h"
@@ -68,7 +69,7 @@ hipError_t hess_geom_enqueue(hess_matcher* m, const hess_geom_params& P, const h
   } while (0)
 
 // A device buffer of at least n elements after grow(n): kept when it is large enough, else replaced (its contents are not
-// carried over).  Freed with its owner.
+// carried over).  Freed with its owner.  What must outlive a failed replacement is built in a buffer of its own and swapped in.
 template <class T>
 struct DeviceBuf {
   T* p = nullptr;
@@ -81,6 +82,10 @@ struct DeviceBuf {
     (void)hipFree(p);
     p = nullptr;
     cap = 0;
+  }
+  void swap(DeviceBuf& o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
   }
   hipError_t grow(size_t n) {
     if (n <= cap) return hipSuccess;
